@@ -12,7 +12,10 @@ descriptor with scale normalisation (SURVEY.md §8(d) "pure kernel benchmark" fo
 --gpus N>1 every rank holds its own N trajectories (weak scaling) and the fit / k-means
 exchange Gram matrices and exact per-cluster sums over RCCL.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline line (with
+the per-stage split and the roofline block those steps record); --full adds everything measured beside it (the step in the
+reference's k-means orders, the S = 20 model form, scene latencies, the other sizes, the scaling model, the CPU baselines).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -41,14 +44,22 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--trajectories", dest="n", type=float, default=1e7, help="trajectories per GPU")
     ap.add_argument("--max-iter", type=int, default=100)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also run the measurements beside them (reference-order step, extra "
+                         "stages, other sizes, scaling model, CPU baselines); a plain run does the headline steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra stage measurements (S=20 model form, N=1e5/1e6 end-to-end, scene latency)")
+                    help="with --full: skip the extra stage measurements (S=20 model form, N=1e5/1e6 end-to-end, scene latency)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (a fixed sample of the trajectories)")
     ap.add_argument("--cpu-budget", type=float, default=45.0,
                     help="seconds of host time the PyTorch-CPU baseline may use for its N=1e6 run")
     ap.add_argument("--c-port-sample", type=int, default=300_000,
                     help="trajectories of the scalar C oracle's sample (second CPU figure, ~5 s on one core)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 class Stage:
@@ -87,10 +98,12 @@ class Stage:
         return [a.elapsed_time(b) for a, b in self.t.get(name, [])]
 
 
-def one_step(ops, obs, pred, K, max_iter, first_index, sw, km=None, timing=None, comm=None, reference_order=False):
+def one_step(ops, obs, pred, K, max_iter, first_index, sw, km=None, timing=None, comm=None, reference_order=False,
+             keep=None):
     """The hot path once.  Returns (n_iter of the Lloyd loop).  `reference_order`: the k-means (farthest-first and Lloyd
     loop) in ATen's own fp32 summation orders (BatchKMeans(sums="reference-order"): the reference's labels bit for bit)
-    instead of the exact partition-independent sums."""
+    instead of the exact partition-independent sums.  `keep`: a dict that receives every array the step hands its caller
+    (--dump-outputs); the step itself is the same."""
     n = obs.shape[0]
     mode = ops.MODE_MOVING
     sw.start("fit")
@@ -106,6 +119,8 @@ def one_step(ops, obs, pred, K, max_iter, first_index, sw, km=None, timing=None,
     sw.start("reconstruct")
     rec = ops.anchor_reconstruct(c_pred.view(6, n, 1), None, None, U_pred, None, mode, nrm=nrm)
     sw.stop("reconstruct")
+    if keep is not None:
+        keep.update(U_obs=U_obs, U_pred=U_pred, c_obs=c_obs, c_pred=c_pred, nrm=nrm, reconstruct=rec)
     del rec, c_obs
     if km is None and reference_order:
         sw.start("kmeans_init")
@@ -134,7 +149,31 @@ def one_step(ops, obs, pred, K, max_iter, first_index, sw, km=None, timing=None,
         sw.start("kmeans_lloyd")
         res = skm.fit(c0, max_iter, 1e-4)
         sw.stop("kmeans_lloyd")
+    if keep is not None:
+        keep.update(kmeans_init=c0, centroids=res["centroids"], labels=res["labels"], n_iter=res["n_iter"])
     return res["n_iter"]
+
+
+DUMP_SAMPLE = 1 << 18  # trajectories --dump-outputs writes of each per-trajectory array (all of them below that)
+
+
+def dump_outputs(out_dir, kept, n):
+    """--dump-outputs: the arrays the last timed step handed its caller, one DIR/<name>.npy each, float32 as computed
+    (float64 for the integer labels and indices).  The per-trajectory arrays are cut to a fixed sample of DUMP_SAMPLE
+    trajectories drawn from a seeded generator (the same indices for the same N on every run: sample_index.npy), which
+    keeps the whole dump under 50 MB; the fitted bases and the centroids are written whole."""
+    os.makedirs(out_dir, exist_ok=True)
+    idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else np.arange(n)
+    sel = torch.from_numpy(idx).to(kept["c_pred"].device)
+    arrays = dict(sample_index=torch.from_numpy(idx.astype(np.float64)),
+                  U_obs=kept["U_obs"], U_pred=kept["U_pred"],  # (2 T_obs, 6), (2 T_pred, 6)
+                  c_obs=kept["c_obs"][:, sel], c_pred=kept["c_pred"][:, sel], nrm=kept["nrm"][:, sel],  # (6|4, sample)
+                  reconstruct=kept["reconstruct"][:, sel],  # (1, sample, T_pred, 2)
+                  kmeans_init=kept["kmeans_init"], centroids=kept["centroids"],  # (6, K)
+                  labels=kept["labels"][sel].to(torch.float64),  # (sample,)
+                  n_iter=torch.tensor([float(kept["n_iter"])], dtype=torch.float64))
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().cpu().numpy())
 
 
 # the dominant kernel of the step: one launch per Lloyd iteration for shards above 32768 points (the chained kernel),
@@ -684,8 +723,10 @@ def main():
     barrier()
     t0 = time.perf_counter()
     iters, step_ends = [], []
-    for _ in range(args.steps):
-        iters.append(one_step(ops, obs, pred, K, args.max_iter, first_index, sw, km, timing, comm))
+    last = {} if args.dump_outputs and rank == 0 else None  # (rank 0's shard of the last step's outputs)
+    for i in range(args.steps):
+        iters.append(one_step(ops, obs, pred, K, args.max_iter, first_index, sw, km, timing, comm,
+                              keep=last if i == args.steps - 1 else None))
         step_ends.append(time.perf_counter())  # (a step ends synchronised: the k-means fit hands its iteration count to the host)
     barrier()
     elapsed = time.perf_counter() - t0
@@ -705,6 +746,9 @@ def main():
             dist.destroy_process_group()
             sys.exit(3)
     step_ms = np.diff(np.asarray([t0] + step_ends)) * 1e3
+    if last is not None:
+        dump_outputs(args.dump_outputs, last, n)
+        del last
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -770,7 +814,7 @@ def main():
                                rccl_ranks=(native_ranks if comm is not None else
                                            (dist.get_world_size() if dist.is_initialized() else 0)), dist_path=dist_path),
                    roofline=roofline, stages=stages)
-        if world == 1 and not force_dist and not args.no_extras:
+        if args.full and world == 1 and not force_dist and not args.no_extras:
             # the same step with the k-means in the REFERENCE's summation orders (the mode that ends with the imported
             # reference's labels bit for bit: tests/golden g7, g7c, g7d) -- `value` times the exact-sum default
             sw_ro = Stage()
@@ -798,7 +842,7 @@ def main():
                                                        ms_per_step=out["ms_per_step"], lloyd_iterations=float(np.mean(iters)),
                                                        **step_roofline(n, ms_per_step, float(np.mean(iters)), K))
             out["sizes"] = sizes
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             del obs, pred
             torch.cuda.empty_cache()
             out["cpu_baseline"] = cpu_baseline(args.max_iter, args.cpu_budget, args.c_port_sample)

@@ -18,7 +18,7 @@ def pytest_sessionstart(session):
     lib = os.path.join(ROOT, "eigentrajectory_amd", "libetamd.so")
     if not os.path.exists(lib):
         import subprocess
-        subprocess.call(["make", "-C", os.path.join(ROOT, "eigentrajectory_amd", "csrc"), "-j", str(os.cpu_count() or 4)])
+        subprocess.call(["make", "-C", os.path.join(ROOT, "eigentrajectory_amd", "csrc"), "-j", str(min(16, os.cpu_count() or 4))])
 
 
 @pytest.fixture(scope="session")
