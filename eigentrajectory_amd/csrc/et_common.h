@@ -71,6 +71,26 @@ __device__ __forceinline__ RowNorm row_norm(float ox, float oy, float dx, float 
     return p;
 }
 
+// Normaliser state of trajectory n from the cached nrm (4,N) or, failing that, from obs.
+__device__ __forceinline__ RowNorm load_row_norm(const float *__restrict__ nrm, const float *__restrict__ obs,
+                                                 int64_t N, int64_t n, int T_obs, int mode, float static_dist) {
+    float ox = 0.f, oy = 0.f, dx = 0.f, dy = 0.f;
+    if (mode == ET_MODE_IDENTITY) {
+    } else if (nrm) {
+        ox = nrm[n];
+        oy = nrm[N + n];
+        dx = nrm[2 * N + n];
+        dy = nrm[3 * N + n];
+    } else {
+        const float *row = obs + n * 2 * T_obs;
+        ox = row[2 * (T_obs - 1)];
+        oy = row[2 * (T_obs - 1) + 1];
+        dx = ox - row[2 * (T_obs - 3)];
+        dy = oy - row[2 * (T_obs - 3) + 1];
+    }
+    return row_norm(ox, oy, dx, dy, mode, static_dist);
+}
+
 // normalizer.py:42-51: ((p - ori) @ R) * sca with R = [[c,-s],[s,c]]
 __device__ __forceinline__ void normalize_point(const RowNorm &p, float x, float y, float &xn, float &yn) {
     const float tx = x - p.ox, ty = y - p.oy;

@@ -239,6 +239,30 @@ class EigenTrajectory(nn.Module):
         return ops.anchor_reconstruct_metrics(C_pred_refine.contiguous(), pred_traj, A_m, A_s, U_pred_m, U_pred_s,
                                               ops.MODE_SPLIT, sd, nrm=nrm, t_obs=obs_traj.shape[1])
 
+    @torch.no_grad()
+    def evaluate_metrics(self, obs_traj, pred_traj, addl_info=None):
+        r"""The reference's four test metrics per pedestrian (utils/metrics.py:30-155 on :meth:`forward`'s
+        ``recon_traj``, utils/trainer.py:183-190) without materialising it: one fused launch reconstructs every sample in
+        registers.  The call's pedestrians form one scene (COL counts pairs among them), as in the reference's test loop.
+
+        Returns:
+            dict of (num_ped,) tensors: ADE, FDE, TCC, COL
+        """
+        sd = self.static_dist
+        if self._scene_ok(obs_traj):
+            C_obs, obs_ori, nrm = self._scene_project(obs_traj)
+        else:
+            U_obs_m, _, U_obs_s, _ = self._U()
+            C_obs, _, nrm, _ = ops.norm_project(obs_traj, None, U_obs_m, None, U_obs_s, None, ops.MODE_SPLIT, sd,
+                                                want_flag=False)
+            obs_ori = nrm[:2] - nrm[:2].mean(dim=1, keepdim=True)
+        C_pred_refine = self._predict(C_obs, obs_ori, addl_info)
+        _, U_pred_m, _, U_pred_s = self._U()
+        A_m, A_s = self.ET_m_anchor.C_anchor.detach(), self.ET_s_anchor.C_anchor.detach()
+        return ops.anchor_reconstruct_metrics_scenes(C_pred_refine.contiguous(), pred_traj, A_m, A_s, U_pred_m, U_pred_s,
+                                                     ops.MODE_SPLIT, sd, nrm=nrm, t_obs=obs_traj.shape[1],
+                                                     metrics=("ADE", "FDE", "TCC", "COL"))
+
     # ---- replayed scene calls ---------------------------------------------------------------------------------------
     # A scene call is four to five small launches and ~35 us of host work around them.  For loops that visit the SAME
     # device-resident scenes again and again (the reference's test loop walks the same ~70 scenes per split every epoch,

@@ -207,6 +207,85 @@ def anchor_reconstruct_metrics(Cc, gt, A_m, A_s, U_m, U_s, mode, static_dist=0.0
     return ade, fde
 
 
+
+# ------------------------------------------------------------------------------------ test metrics (TCC / COL)
+METRIC_KEYS = ("ADE", "FDE", "TCC", "COL", "best")
+
+
+def scene_offsets(sizes, n, device):
+    """Scene sizes (pedestrians per scene, in row order) -> int32 offsets (n_scenes + 1,) on ``device``; None -> None
+    (the whole batch is one scene).  Checked on the host: non-negative, summing to ``n``."""
+    if sizes is None:
+        return None
+    if torch.is_tensor(sizes):
+        sizes = sizes.detach().cpu().tolist()
+    sizes = [int(v) for v in sizes]
+    if not sizes or min(sizes) < 0 or sum(sizes) != n:
+        raise ValueError(f"scene_sizes must be non-negative and sum to the {n} rows (got {len(sizes)} sizes summing to "
+                         f"{sum(sizes)})")
+    if n > 2**31 - 1:
+        raise ValueError("scene_sizes: more than 2^31 - 1 rows")
+    off = [0]
+    for v in sizes:
+        off.append(off[-1] + v)
+    return torch.tensor(off, dtype=torch.int32).to(device, non_blocking=True)
+
+
+def _metric_outputs(n, dev, metrics):
+    unknown = set(metrics) - set(METRIC_KEYS)
+    if unknown:
+        raise ValueError(f"unknown metrics {sorted(unknown)}; choose from {METRIC_KEYS}")
+    return {key: torch.empty((n,), device=dev, dtype=torch.int32 if key == "best" else torch.float32)
+            for key in METRIC_KEYS if key in metrics}
+
+
+def _gt3(gt):
+    return gt.squeeze(0) if gt.dim() == 4 else gt
+
+
+def traj_metrics(pred, gt, scene_sizes=None, metrics=METRIC_KEYS):
+    """utils/metrics.py:30-155 per pedestrian in one launch: pred (S,N,T,2), gt (N,T,2) or (1,N,T,2) ->
+    dict of (N,) tensors: ADE, FDE, TCC, COL (float32) and best (int32, the arg-min sample of the final error).
+
+    ``scene_sizes``: pedestrians per scene in row order (COL compares pairs within a scene only, as the reference's test
+    loop calls the metric once per scene); None = one scene of N.  ``metrics`` selects the outputs (leaving out COL skips
+    the pair pass)."""
+    dev = L.require_device(pred)
+    pred, gt = _dev_args(dev, pred, _gt3(gt))
+    s, n, t, _ = pred.shape
+    if gt.shape != (n, t, 2):
+        raise ValueError(f"gt {tuple(gt.shape)} does not match pred {tuple(pred.shape)}")
+    off = scene_offsets(scene_sizes, n, dev)
+    out = _metric_outputs(n, dev, metrics)
+    L.check(L.lib().et_traj_metrics(L.ptr(pred), L.i64(n), s, t, L.ptr(gt), L.ptr(off), 0 if off is None else off.numel() - 1,
+                                    L.ptr(out.get("ADE")), L.ptr(out.get("FDE")), L.ptr(out.get("TCC")),
+                                    L.ptr(out.get("COL")), L.ptr(out.get("best")), L.stream(dev)), "et_traj_metrics")
+    return out
+
+
+def anchor_reconstruct_metrics_scenes(Cc, gt, A_m, A_s, U_m, U_s, mode, static_dist=0.0, *, obs=None, nrm=None, pose=None,
+                                      t_obs=8, scene_sizes=None, metrics=METRIC_KEYS):
+    """:func:`traj_metrics` of :func:`anchor_reconstruct`'s output without writing it: C (k,N,S), gt (N,T_pred,2) ->
+    dict of (N,) tensors (ADE, FDE, TCC, COL, best), every sample reconstructed in registers with the reconstruction's
+    own arithmetic.  The normaliser comes from ``nrm`` or ``obs``, else from ``pose`` (within an ulp or two for moving
+    rows)."""
+    dev = L.require_device(Cc)
+    Cc, gt, obs, nrm, A_m, A_s, U_m, U_s, pose = _dev_args(dev, Cc, _gt3(gt), obs, nrm, A_m, A_s, U_m, U_s, pose)
+    k, n, s = Cc.shape
+    if obs is not None:
+        t_obs = obs.shape[1]
+    t_pred = gt.shape[1]
+    if gt.shape != (n, t_pred, 2):
+        raise ValueError(f"gt {tuple(gt.shape)} does not match C {tuple(Cc.shape)}")
+    off = scene_offsets(scene_sizes, n, dev)
+    out = _metric_outputs(n, dev, metrics)
+    L.check(L.lib().et_anchor_reconstruct_metrics_scenes(
+        L.ptr(Cc), L.i64(n), s, k, int(t_obs), t_pred, L.ptr(obs), L.ptr(nrm), L.ptr(pose), L.ptr(A_m), L.ptr(A_s), L.ptr(U_m),
+        L.ptr(U_s), int(mode), L.f32(static_dist), L.ptr(gt), L.ptr(off), 0 if off is None else off.numel() - 1,
+        L.ptr(out.get("ADE")), L.ptr(out.get("FDE")), L.ptr(out.get("TCC")), L.ptr(out.get("COL")), L.ptr(out.get("best")),
+        L.stream(dev)), "et_anchor_reconstruct_metrics_scenes")
+    return out
+
 # ------------------------------------------------------------------------------------ fit
 def fit_gram(obs, pred, mode, static_dist=0.0, which=1):
     """Gram matrices (fp64) of the normalised rows routed to descriptor ``which`` + their count (int64, device)."""

@@ -15,7 +15,8 @@ written against :class:`eigentrajectory_amd.EigenTrajectory`:
                         ``batch_size`` (also for the shorter last group), one step per group;
 * ``valid``             pedestrian-weighted ``loss_euclidean_fde`` (:156-170, :233-247) -- the number that selects
                         the best checkpoint (:74-75);
-* ``test``              best-of-S ADE / FDE over the test scenes (:173-195) through the fused epilogue.
+* ``test``              best-of-S ADE / FDE over the test scenes (:173-195) through the fused epilogue; with
+                        ``metrics="all"`` also TCC and COL (:89-91), through the fused scene-metrics kernel.
 
 Data parallelism: with ``torch.distributed`` initialised (one process per GPU, backend "nccl" = RCCL), the
 predictor is wrapped in DistributedDataParallel and rank r takes batches r, r + world, ... of every epoch.
@@ -192,19 +193,40 @@ class ETTrainer:
         return {k.replace("baseline_model.module.", "baseline_model."): v for k, v in self.model.state_dict().items()}
 
     @torch.no_grad()
-    def test(self, data=None):
-        """-> dict(ADE, FDE) over all pedestrians of the test scenes (scene by scene, like utils/trainer.py:173-195)."""
+    def test(self, data=None, metrics=("ADE", "FDE")):
+        """-> dict(ADE, FDE) over all pedestrians of the test scenes (scene by scene, like utils/trainer.py:173-195).
+
+        ``metrics="all"`` (or any subset of ADE, FDE, TCC, COL) -> those keys, each averaged over the pedestrians like
+        the reference's four meters (utils/trainer.py:89-91), through :meth:`EigenTrajectory.evaluate_metrics`."""
         data = data or self.test_data
+        if metrics == "all":
+            metrics = ("ADE", "FDE", "TCC", "COL")
+        metrics = tuple(metrics)
+        unknown = set(metrics) - {"ADE", "FDE", "TCC", "COL"}
+        if unknown or not metrics:
+            raise ValueError(f"test(metrics=...): choose from ADE, FDE, TCC, COL or 'all' (got {metrics})")
         self.model.eval()
-        ade_sum = torch.zeros((), device=self.device, dtype=torch.float64)
-        fde_sum = torch.zeros((), device=self.device, dtype=torch.float64)
+        if set(metrics) <= {"ADE", "FDE"}:
+            ade_sum = torch.zeros((), device=self.device, dtype=torch.float64)
+            fde_sum = torch.zeros((), device=self.device, dtype=torch.float64)
+            n_ped = 0
+            with self._bare_predictor(self):
+                for idx in range(len(data))[self.rank::self.world]:
+                    obs, pred, addl = self._scene(data, idx)
+                    a, f = self.model.evaluate(obs.to(self.device), pred.to(self.device), addl)
+                    ade_sum += a.double().sum()
+                    fde_sum += f.double().sum()
+                    n_ped += a.numel()
+            a, f, n = self._reduce(float(ade_sum), float(fde_sum), n_ped)
+            res = {"ADE": a / max(n, 1.0), "FDE": f / max(n, 1.0)}
+            return {key: res[key] for key in metrics}
+        sums = torch.zeros((len(metrics),), device=self.device, dtype=torch.float64)
         n_ped = 0
         with self._bare_predictor(self):
             for idx in range(len(data))[self.rank::self.world]:
                 obs, pred, addl = self._scene(data, idx)
-                a, f = self.model.evaluate(obs.to(self.device), pred.to(self.device), addl)
-                ade_sum += a.double().sum()
-                fde_sum += f.double().sum()
-                n_ped += a.numel()
-        a, f, n = self._reduce(float(ade_sum), float(fde_sum), n_ped)
-        return {"ADE": a / max(n, 1.0), "FDE": f / max(n, 1.0)}
+                out = self.model.evaluate_metrics(obs.to(self.device), pred.to(self.device), addl)
+                sums += torch.stack([out[key].double().sum() for key in metrics])
+                n_ped += out["ADE"].numel()
+        *totals, n = self._reduce(*sums.tolist(), n_ped)
+        return {key: v / max(n, 1.0) for key, v in zip(metrics, totals)}

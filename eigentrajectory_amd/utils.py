@@ -3,7 +3,8 @@
 Only what the hot-path boundary needs: the attribute-style config dict the
 wrapper is constructed with (utils/utils.py:32-39), the flip augmentation that
 shapes the fit input (utils/utils.py:69-86) and ADE/FDE, the parity instrument
-(utils/metrics.py:73-102).
+(utils/metrics.py:73-102), and the test loop's other two metrics, TCC and COL (utils/metrics.py:30-70, 105-155), through
+the scene-batched HIP kernel (ops.traj_metrics).
 """
 from __future__ import annotations
 
@@ -51,3 +52,26 @@ def compute_batch_fde(pred, gt):
     r"""FDE per pedestrian (utils/metrics.py:89-102)"""
     temp = (pred - gt).norm(p=2, dim=-1)
     return temp[:, :, -1].min(dim=0)[0]
+
+
+def compute_batch_tcc(pred, gt, *, scene_sizes=None):
+    r"""TCC per pedestrian (utils/metrics.py:105-130): the best sample's temporal correlation with gt, pred (S,N,T,2),
+    gt (N,T,2) or (1,N,T,2) -> (N,).  ``scene_sizes`` is accepted for symmetry with :func:`compute_batch_col` (TCC does
+    not couple pedestrians)."""
+    from . import ops
+    return ops.traj_metrics(pred, gt, scene_sizes, metrics=("TCC",))["TCC"]
+
+
+def compute_batch_col(pred, gt, *, scene_sizes=None):
+    r"""COL per pedestrian (utils/metrics.py:133-155): percent of samples in which the pedestrian collides with another
+    of its scene.  ``scene_sizes`` (pedestrians per scene, in row order) evaluates many scenes in one launch; None = the
+    whole batch is one scene, as in the reference's call."""
+    from . import ops
+    return ops.traj_metrics(pred, gt, scene_sizes, metrics=("COL",))["COL"]
+
+
+def compute_batch_metric(pred, gt, *, scene_sizes=None):
+    r"""ADE, FDE, COL, TCC per pedestrian in that order (utils/metrics.py:30-70), one launch.  gt may be 3-D or 4-D."""
+    from . import ops
+    out = ops.traj_metrics(pred, gt, scene_sizes, metrics=("ADE", "FDE", "TCC", "COL"))
+    return out["ADE"], out["FDE"], out["COL"], out["TCC"]

@@ -208,6 +208,32 @@ int et_anchor_reconstruct_metrics_pose(const float *C, int64_t N, int S, int k, 
                                        int mode, float static_dist, const float *gt, float *ade, float *fde,
                                        et_stream_t stream);
 
+/* ---- the reference's test metrics (utils/metrics.py:30-155; utils/trainer.py:173-195) --------------------------------
+ * Per pedestrian of pred (S,N,T,2) against gt (N,T,2), 2 <= T <= ET_MAX_T:
+ *   ade, fde  best-of-S displacement errors (as et_anchor_reconstruct_metrics)
+ *   best      int32 arg-min over samples of the final displacement (first index on ties, the first NaN wins)
+ *   tcc       temporal correlation coefficient of the best sample (:105-130): per coordinate the Pearson correlation over
+ *             the T steps (covariance factor 1/(T-1)), clamped to [-1, 1], NaN -> 0, mean of the two coordinates
+ *   col       collision rate in percent (:133-155): 100 * (samples in which the pedestrian comes closer than 0.2 to another
+ *             pedestrian of its scene at one of the first min(14, 1 + 4 (T-1)) instants of the path densified 4x) / S
+ * Scenes: scene_offsets (n_scenes + 1) int32 device array, 0 = off[0] <= ... <= off[n_scenes] = N (N <= INT32_MAX);
+ * NULL = one scene of N rows (the reference called on the whole tensor).  Only pairs within a scene are compared; a whole
+ * split is one launch.  Any output may be NULL; col == NULL skips the pair pass.  pred, gt: 8-byte aligned. */
+int et_traj_metrics(const float *pred, int64_t N, int S, int T, const float *gt,
+                    const int32_t *scene_offsets, int n_scenes,
+                    float *ade, float *fde, float *tcc, float *col, int32_t *best, et_stream_t stream);
+/* The same from the coefficients (fused: nothing of size (S,N,T_pred,2) is written): every (sample, pedestrian) is
+ * reconstructed in registers with et_anchor_reconstruct_fwd's arithmetic, so the results equal et_traj_metrics applied to
+ * that call's output.  The normaliser comes from nrm or obs when given, else from pose (5,N) of et_norm_project_pose (its
+ * rotation is then recovered as (c sca) / sca: within an ulp or two of the nrm form for moving rows). */
+int et_anchor_reconstruct_metrics_scenes(const float *C, int64_t N, int S, int k, int T_obs, int T_pred,
+                                         const float *obs, const float *nrm, const float *pose,
+                                         const float *A_m, const float *A_s, const float *U_pred_m, const float *U_pred_s,
+                                         int mode, float static_dist, const float *gt,
+                                         const int32_t *scene_offsets, int n_scenes,
+                                         float *ade, float *fde, float *tcc, float *col, int32_t *best,
+                                         et_stream_t stream);
+
 /* dC[j][n][s] = sum_f U_pred[f][j] * ((dtraj[s][n] @ R_n) / sca_n)[f]          (k,N,S) */
 int et_anchor_reconstruct_bwd(const float *dtraj, int64_t N, int S, int k, int T_obs, int T_pred,
                               const float *obs, const float *nrm,
