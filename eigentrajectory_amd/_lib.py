@@ -22,6 +22,7 @@ ABI_VERSION = 3  # include/eigentraj.h ET_ABI_VERSION: the struct mirrors below 
 MODE_STATIC, MODE_MOVING, MODE_SPLIT, MODE_IDENTITY = 0, 1, 2, 3
 MAX_T, MAX_K, KMEANS_MAX_D, KMEANS_MAX_CLUSTERS = 32, 32, 32, 255
 SCENE_MAX_N = 16384  # ET_SCENE_MAX_N
+CURVE_MAX_FITS = 64  # ET_CURVE_MAX_FITS
 
 #: every symbol include/eigentraj.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -30,6 +31,7 @@ SYMBOLS = [
     "et_norm_project", "et_norm_project_pose", "et_scene_project", "et_scene_project_train", "et_wrapper_losses_fwd", "et_wrapper_losses_bwd",
     "et_anchor_reconstruct_fwd", "et_anchor_reconstruct_bwd", "et_anchor_reconstruct_metrics",
     "et_anchor_reconstruct_metrics_pose", "et_traj_metrics", "et_anchor_reconstruct_metrics_scenes",
+    "et_curve_fit_batch_workspace_bytes", "et_curve_fit_batch",
     "et_fit_gram_workspace_bytes", "et_fit_gram", "et_eigh_topk", "et_eigh_topk_batch",
     "et_fit_descriptor_workspace_bytes", "et_fit_descriptor",
     "et_euc_sim", "et_euc_sim_batch", "et_kmeans_partials_len", "et_kmeans_workspace_bytes", "et_kmeans_scan", "et_kmeans_begin",
@@ -84,7 +86,8 @@ def lib():
         for name in ("et_fit_gram_workspace_bytes", "et_fit_descriptor_workspace_bytes", "et_kmeans_partials_len", "et_kmeans_workspace_bytes",
                      "et_kmeanspp_workspace_bytes", "et_kmeans_sharded_workspace_bytes", "et_kmeans_batch_workspace_bytes",
                      "et_kmeanspp_batch_workspace_bytes", "et_kmeans_reforder_workspace_bytes",
-                     "et_kmeans_reforder_batch_workspace_bytes", "et_kmeans_reforder_sharded_workspace_bytes"):
+                     "et_kmeans_reforder_batch_workspace_bytes", "et_kmeans_reforder_sharded_workspace_bytes",
+                     "et_curve_fit_batch_workspace_bytes"):
             getattr(l, name).restype = C.c_size_t
         l.et_kmeans_reforder_shard_block.restype = C.c_int64
         _lib = l

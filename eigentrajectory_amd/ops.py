@@ -286,6 +286,56 @@ def anchor_reconstruct_metrics_scenes(Cc, gt, A_m, A_s, U_m, U_s, mode, static_d
         L.stream(dev)), "et_anchor_reconstruct_metrics_scenes")
     return out
 
+# ----------------------------------------------------------------------- curve fitting
+def curve_fit_batch(trajs, bases, steps=100000, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, want_cp=False, want_loss=False):
+    """CurveModel/curve_fitting.py for a batch of fits: fit f fits basis ``bases[f]`` (T_f, ncp_f) to every trajectory of
+    ``trajs[f]`` (N_f, T_f, 2) (already normalised) by ``steps`` Adam steps on the mean L2 error.  All fits of up to
+    ET_CURVE_MAX_FITS (64) run in one launch per pass; longer lists are split.  Returns a dict:
+    ``recon`` list of (N_f, T_f, 2) float32, the recon of each fit's best step; ``best`` (B,) int64 best steps;
+    ``cp`` list of (N_f, ncp_f, 2) control points (want_cp); ``loss`` (B, steps) float64 per-step mean loss (want_loss)."""
+    if len(trajs) != len(bases) or not trajs:
+        raise ValueError("curve_fit_batch: trajs and bases must be non-empty lists of the same length")
+    dev = L.require_device(*trajs, *bases)
+    trajs = [t.to(dev, torch.float32).contiguous() for t in trajs]
+    bases = [b.to(dev, torch.float32).contiguous() for b in bases]
+    out = {"recon": [], "best": [], "cp": [] if want_cp else None, "loss": [] if want_loss else None}
+    for c0 in range(0, len(trajs), L.CURVE_MAX_FITS):
+        tr, bs = trajs[c0:c0 + L.CURVE_MAX_FITS], bases[c0:c0 + L.CURVE_MAX_FITS]
+        fits, t_off, b_off, c_off = [], 0, 0, 0
+        for t, b in zip(tr, bs):
+            if t.dim() != 3 or t.shape[2] != 2 or b.dim() != 2 or b.shape[0] != t.shape[1]:
+                raise ValueError(f"curve_fit_batch: traj {tuple(t.shape)} and basis {tuple(b.shape)} do not match")
+            n, T, ncp = t.shape[0], t.shape[1], b.shape[1]
+            fits.append([n, T, ncp, t_off, b_off, c_off])
+            t_off, b_off, c_off = t_off + n * T * 2, b_off + T * ncp, c_off + n * ncp * 2
+        nf = len(fits)
+        table = (C.c_int64 * (6 * nf))(*[v for row in fits for v in row])
+        traj = torch.cat([t.reshape(-1) for t in tr])
+        basis = torch.cat([b.reshape(-1) for b in bs])
+        recon = torch.empty_like(traj)
+        cp = torch.empty((c_off,), device=dev, dtype=torch.float32) if want_cp else None
+        loss = torch.empty((nf, int(steps)), device=dev, dtype=torch.float64) if want_loss else None
+        best = torch.empty((nf,), device=dev, dtype=torch.int32)
+        nbytes = L.lib().et_curve_fit_batch_workspace_bytes(nf, L.i64(steps))
+        if nbytes == 0:
+            raise ValueError(f"curve_fit_batch: steps={steps} not taken")
+        ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+        L.check(L.lib().et_curve_fit_batch(
+            L.ptr(traj), L.ptr(basis), table, nf, L.i64(steps), C.c_double(lr), C.c_double(betas[0]),
+            C.c_double(betas[1]), C.c_double(eps), L.ptr(recon), L.ptr(cp), L.ptr(loss), L.ptr(best), L.ptr(ws),
+            C.c_size_t(nbytes), L.stream(dev)), "et_curve_fit_batch")
+        for (n, T, ncp, to, _, co) in fits:
+            out["recon"].append(recon[to:to + n * T * 2].view(n, T, 2))
+            if want_cp:
+                out["cp"].append(cp[co:co + n * ncp * 2].view(n, ncp, 2))
+        out["best"].append(best.long())
+        if want_loss:
+            out["loss"].append(loss)
+    out["best"] = torch.cat(out["best"])
+    if want_loss:
+        out["loss"] = torch.cat(out["loss"])
+    return out
+
 # ------------------------------------------------------------------------------------ fit
 def fit_gram(obs, pred, mode, static_dist=0.0, which=1):
     """Gram matrices (fp64) of the normalised rows routed to descriptor ``which`` + their count (int64, device)."""

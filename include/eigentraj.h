@@ -240,6 +240,31 @@ int et_anchor_reconstruct_bwd(const float *dtraj, int64_t N, int S, int k, int T
                               const float *U_pred_m, const float *U_pred_s,
                               int mode, float static_dist, float *dC, et_stream_t stream);
 
+/* ---- curve-fitting baselines (CurveModel/curve_fitting.py; script/descriptor_evaluation.py:38-85) -----------------------
+ * A batch of n_fits independent fits, one launch per pass.  Fit f is a row of fits_host (HOST array, n_fits x 6 int64):
+ *   (N, T, ncp, traj_off, basis_off, cp_off)   1 <= N <= INT32_MAX, 2 <= T <= 32, 2 <= ncp <= 8
+ * its trajectories are traj[traj_off ..] (N,T,2) (already normalised), its basis basis[basis_off ..] (T,ncp), its recon goes
+ * to recon[traj_off ..] (N,T,2) and its control points to cp[cp_off ..] (N,ncp,2) (offsets in floats).  Per pedestrian:
+ *   cp[0] = traj[0], cp[i] = cp[i-1] + (traj[T-1] - traj[0]) / (ncp-1);  recon[t] = sum_i basis[t][i] cp[i]
+ *   loss = mean over the fit's N T points of ||recon - traj||_2, minimised by Adam(lr, (beta1, beta2), eps) for n_steps
+ * (fp32, torch.optim.Adam's single-tensor order, the norm's gradient 0 at a zero residual; as in the reference, which never
+ * zeroes .grad, Adam is fed the running sum of the step gradients).  The loss of a step is summed
+ * in fixed point (per pedestrian the fp64 sum of its T norms rounded to a multiple of 2^-28, clamped to 2^26), so it and
+ * the best step do not depend on the launch geometry.  Outputs:
+ *   recon      the recon of the fit's best step = the first step of minimum loss (the parameters BEFORE that step's
+ *              update: step 0 is the initial guess)
+ *   cp         (may be NULL) the control points of that step
+ *   loss       (may be NULL) n_fits x n_steps fp64: the per-step mean loss (fixed-point sum * 2^-28 / (N T))
+ *   best_step  (may be NULL) n_fits int32
+ * 1 <= n_steps <= INT32_MAX; 0 < lr; 0 <= beta1, beta2 < 1; 0 <= eps.  The sum of a fit's T N norms must stay below 2^35
+ * (far beyond trajectories in metres).  Pass 2 replays every pedestrian to its best step, so a call costs up to 2 n_steps
+ * steps.  Bad shapes / arguments: ET_ERR_INVALID_ARG before any work is enqueued. */
+#define ET_CURVE_MAX_FITS 64
+size_t et_curve_fit_batch_workspace_bytes(int n_fits, int64_t n_steps); /* 0: arguments not taken */
+int et_curve_fit_batch(const float *traj, const float *basis, const int64_t *fits_host, int n_fits, int64_t n_steps,
+                       double lr, double beta1, double beta2, double eps, float *recon, float *cp, double *loss,
+                       int32_t *best_step, void *workspace, size_t workspace_bytes, et_stream_t stream);
+
 /* ---- fit ----------------------------------------------------------------------------
  * Gram matrices of the normalised trajectories routed to descriptor `which`
  * (1 moving / 0 static) under `mode`:  G_obs (2T_obs,2T_obs), G_pred (2T_pred,2T_pred)
