@@ -32,6 +32,9 @@ SYMBOLS = [
     "et_anchor_reconstruct_fwd", "et_anchor_reconstruct_bwd", "et_anchor_reconstruct_metrics",
     "et_anchor_reconstruct_metrics_pose", "et_traj_metrics", "et_anchor_reconstruct_metrics_scenes",
     "et_curve_fit_batch_workspace_bytes", "et_curve_fit_batch",
+    "et_tsne_neighbors", "et_tsne_affinities_workspace_bytes", "et_tsne_affinities", "et_tsne_kl_grad_workspace_bytes",
+    "et_tsne_kl_grad", "et_tsne_update", "et_tsne_optimize_workspace_bytes", "et_tsne_optimize",
+    "et_tsne_pca_init_workspace_bytes", "et_tsne_pca_init",
     "et_fit_gram_workspace_bytes", "et_fit_gram", "et_eigh_topk", "et_eigh_topk_batch",
     "et_fit_descriptor_workspace_bytes", "et_fit_descriptor",
     "et_euc_sim", "et_euc_sim_batch", "et_kmeans_partials_len", "et_kmeans_workspace_bytes", "et_kmeans_scan", "et_kmeans_begin",
@@ -87,7 +90,9 @@ def lib():
                      "et_kmeanspp_workspace_bytes", "et_kmeans_sharded_workspace_bytes", "et_kmeans_batch_workspace_bytes",
                      "et_kmeanspp_batch_workspace_bytes", "et_kmeans_reforder_workspace_bytes",
                      "et_kmeans_reforder_batch_workspace_bytes", "et_kmeans_reforder_sharded_workspace_bytes",
-                     "et_curve_fit_batch_workspace_bytes"):
+                     "et_curve_fit_batch_workspace_bytes", "et_tsne_affinities_workspace_bytes",
+                     "et_tsne_kl_grad_workspace_bytes", "et_tsne_optimize_workspace_bytes",
+                     "et_tsne_pca_init_workspace_bytes"):
             getattr(l, name).restype = C.c_size_t
         l.et_kmeans_reforder_shard_block.restype = C.c_int64
         _lib = l

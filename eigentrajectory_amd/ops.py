@@ -336,6 +336,100 @@ def curve_fit_batch(trajs, bases, steps=100000, lr=1e-4, betas=(0.9, 0.999), eps
         out["loss"] = torch.cat(out["loss"])
     return out
 
+# ------------------------------------------------------------------------------------ t-SNE
+def _tsne_ws(nbytes, dev):
+    if nbytes == 0:
+        raise ValueError("t-SNE: arguments not taken")
+    return torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+
+
+def tsne_affinities(X, perplexity=30.0):
+    """sklearn's kNN + perplexity search + symmetrised P (et_tsne_affinities) for X (N,d) fp32, d <= 32.  -> dict:
+    ``knn_idx`` (N,k) int32 and ``knn_dist`` (N,k) fp32 squared distances in column order, ``p_cond`` (N,k) fp64,
+    ``indptr`` (N+1) int32, ``indices`` (nnz) int32, ``P`` (nnz) fp64 (canonical CSR, normalised), ``total`` (1) fp64."""
+    dev = L.require_device(X)
+    X = L.on_device(X, dev)
+    if X.dim() != 2:
+        raise ValueError("tsne_affinities: X must be (N, d)")
+    n, d = X.shape
+    k = L.lib().et_tsne_neighbors(L.i64(n), C.c_double(perplexity))
+    if k < 1:
+        raise ValueError(f"tsne_affinities: N={n}, perplexity={perplexity} not taken")
+    ws = _tsne_ws(L.lib().et_tsne_affinities_workspace_bytes(L.i64(n), d, k), dev)
+    out = {"knn_idx": torch.empty((n, k), device=dev, dtype=torch.int32),
+           "knn_dist": torch.empty((n, k), device=dev),
+           "p_cond": torch.empty((n, k), device=dev, dtype=torch.float64),
+           "indptr": torch.empty((n + 1,), device=dev, dtype=torch.int32),
+           "indices": torch.empty((2 * n * k,), device=dev, dtype=torch.int32),
+           "P": torch.empty((2 * n * k,), device=dev, dtype=torch.float64),
+           "total": torch.empty((1,), device=dev, dtype=torch.float64)}
+    L.check(L.lib().et_tsne_affinities(
+        L.ptr(X), L.i64(n), d, C.c_double(perplexity), k, L.ptr(out["knn_idx"]), L.ptr(out["knn_dist"]),
+        L.ptr(out["p_cond"]), L.ptr(out["indptr"]), L.ptr(out["indices"]), L.ptr(out["P"]), L.ptr(out["total"]),
+        L.ptr(ws), C.c_size_t(ws.numel()), L.stream(dev)), "et_tsne_affinities")
+    nnz = int(out["indptr"][n].item())
+    out["indices"], out["P"] = out["indices"][:nnz], out["P"][:nnz]
+    return out
+
+
+def tsne_kl_grad(Y, indptr, indices, P, want_kl=True):
+    """KL divergence and gradient at Y (N,2) with exact repulsion (et_tsne_kl_grad); P fp32 (fp64 is rounded to fp32,
+    as sklearn's _kl_divergence_bh does).  -> (kl fp64 device scalar | None, grad (N,2) fp32)."""
+    dev = L.require_device(Y)
+    Y = L.on_device(Y, dev)
+    if Y.dim() != 2 or Y.shape[1] != 2:
+        raise ValueError("tsne_kl_grad: Y must be (N, 2)")
+    n = Y.shape[0]
+    indptr, indices = L.on_device(indptr, dev, torch.int32), L.on_device(indices, dev, torch.int32)
+    P = L.on_device(P, dev, torch.float32)
+    grad = torch.empty_like(Y)
+    kl = torch.empty((1,), device=dev, dtype=torch.float64) if want_kl else None
+    ws = _tsne_ws(L.lib().et_tsne_kl_grad_workspace_bytes(L.i64(n)), dev)
+    L.check(L.lib().et_tsne_kl_grad(L.ptr(Y), L.i64(n), L.ptr(indptr), L.ptr(indices), L.ptr(P), L.ptr(grad), L.ptr(kl),
+                                    L.ptr(ws), C.c_size_t(ws.numel()), L.stream(dev)), "et_tsne_kl_grad")
+    return (kl[0] if want_kl else None), grad
+
+
+def tsne_update(p, update, gains, grad, momentum, learning_rate):
+    """One step of sklearn's _gradient_descent in place (et_tsne_update): p fp32, update fp64, gains fp32, grad fp32
+    (scaled by the new gains)."""
+    for t, dt in ((p, torch.float32), (update, torch.float64), (gains, torch.float32), (grad, torch.float32)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != p.numel():
+            raise ValueError("tsne_update: p, gains, grad fp32 and update fp64, contiguous, of one size")
+    dev = L.require_device(p)
+    L.check(L.lib().et_tsne_update(L.ptr(p), L.ptr(update), L.ptr(gains), L.ptr(grad), L.i64(p.numel()),
+                                   C.c_double(momentum), C.c_double(learning_rate), L.stream(dev)), "et_tsne_update")
+
+
+def tsne_optimize(Y0, indptr, indices, P, early_exaggeration=12.0, learning_rate=200.0, max_iter=1000):
+    """TSNE._tsne from Y0 (N,2) with the fp64 CSR P of :func:`tsne_affinities` (et_tsne_optimize).
+    -> (Y (N,2) fp32, kl float, n_iter int)."""
+    dev = L.require_device(Y0)
+    Y = L.on_device(Y0, dev).clone()
+    n = Y.shape[0]
+    indptr, indices = L.on_device(indptr, dev, torch.int32), L.on_device(indices, dev, torch.int32)
+    P = L.on_device(P, dev, torch.float64)
+    ws = _tsne_ws(L.lib().et_tsne_optimize_workspace_bytes(L.i64(n), L.i64(P.numel())), dev)
+    kl, it = C.c_double(0.0), C.c_int(0)
+    L.check(L.lib().et_tsne_optimize(L.ptr(Y), L.i64(n), L.ptr(indptr), L.ptr(indices), L.ptr(P), L.i64(P.numel()),
+                                     C.c_double(early_exaggeration), C.c_double(learning_rate), int(max_iter),
+                                     C.byref(kl), C.byref(it), L.ptr(ws), C.c_size_t(ws.numel()), L.stream(dev)),
+            "et_tsne_optimize")
+    return Y, kl.value, it.value
+
+
+def tsne_pca_init(X):
+    """sklearn's init="pca" for t-SNE (et_tsne_pca_init): X (N,d) -> Y0 (N,2) fp32."""
+    dev = L.require_device(X)
+    X = L.on_device(X, dev)
+    n, d = X.shape
+    Y = torch.empty((n, 2), device=dev)
+    ws = _tsne_ws(L.lib().et_tsne_pca_init_workspace_bytes(L.i64(n), d), dev)
+    L.check(L.lib().et_tsne_pca_init(L.ptr(X), L.i64(n), d, L.ptr(Y), L.ptr(ws), C.c_size_t(ws.numel()), L.stream(dev)),
+            "et_tsne_pca_init")
+    return Y
+
+
 # ------------------------------------------------------------------------------------ fit
 def fit_gram(obs, pred, mode, static_dist=0.0, which=1):
     """Gram matrices (fp64) of the normalised rows routed to descriptor ``which`` + their count (int64, device)."""

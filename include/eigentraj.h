@@ -265,6 +265,49 @@ int et_curve_fit_batch(const float *traj, const float *basis, const int64_t *fit
                        double lr, double beta1, double beta2, double eps, float *recon, float *cp, double *loss,
                        int32_t *best_step, void *workspace, size_t workspace_bytes, et_stream_t stream);
 
+/* ---- t-SNE of descriptor coefficients (script/plot_coeff_tsne.py: sklearn.manifold.TSNE, Barnes-Hut) ------------------
+ * sklearn's pipeline with exact repulsion, n_components = 2.  X (N,d) fp32 row-major, 2 <= N, 1 <= d <= 32; Y (N,2) fp32.
+ * et_tsne_neighbors: k = min(N-1, floor(3 perplexity + 1)) (0: arguments not taken).
+ * et_tsne_affinities: the k nearest other rows of every row by (squared distance, index) -- the squared distance summed
+ *   in fp64 from fp32 differences, rounded through sqrt and squared again to fp32 -- written in column order:
+ *   knn_idx / knn_dist (N,k); p_cond (N,k) fp64 the perplexity search's conditional P; the symmetric
+ *   P = (P_cond + P_cond^T) / total as canonical CSR: indptr (N+1), indices / P (capacity 2 N k; nnz = indptr[N]);
+ *   p_total (device, may be NULL) the total.  Synchronises the stream once.  Non-finite X or N < 2: ET_ERR_BAD_DATA.
+ * et_tsne_kl_grad: grad (N,2) = 4 (sum_j p_ij q_ij (y_i - y_j) - sum_{j ~ i} q_ij^2 (y_i - y_j) / Z) with
+ *   q_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i ~ j} q_ij, P fp32 CSR; j ~ i: j is not within 1e-6 of i in both
+ *   coordinates (as sklearn's quadtree, which skips such points; j = i included); kl (device, may be NULL) the KL
+ *   divergence over the CSR entries.  Bit-identical from run to run (the summation order depends on N only).  The
+ *   workspace holds ceil(N / 1024) x N x 8 bytes of partial sums (grows as N^2; 7 MB at N = 3e4, 78 MB at 1e5);
+ *   N <= 65 535 x 1 024.  Synchronises the stream once.  Non-finite Y: ET_ERR_BAD_DATA.
+ * et_tsne_update: one step of sklearn's _gradient_descent on n coordinates in place (gains, update fp64, p; grad is
+ *   scaled by the new gains).
+ * et_tsne_optimize: TSNE._tsne from Y (in/out): 250 iterations with P x early_exaggeration and momentum 0.5, then up to
+ *   max_iter with momentum 0.8; KL and the gradient norm every 50 iterations, sklearn's stop rules.  P is the fp64 CSR
+ *   of et_tsne_affinities.  kl_out / n_iter_out (host) = sklearn's kl_divergence_ / n_iter_ (at max_iter = 250, as
+ *   sklearn: the second phase runs no iteration and returns 250 and DBL_MAX; max_iter < 250, not an sklearn setting,
+ *   ends the first phase early).  Workspace as et_tsne_kl_grad's plus O(N + nnz).  Synchronises the stream twice
+ *   (after each phase).  Non-finite Y: ET_ERR_BAD_DATA.
+ * et_tsne_pca_init: sklearn's init="pca": the top two eigenvectors of the centred X's covariance (et_eigh_topk), signs by
+ *   svd_flip(u_based_decision=False), Y = (X - mean) V / std(Y[:,0]) * 1e-4.  2 <= d <= 32.  Synchronises the
+ *   stream once.  Non-finite X: ET_ERR_BAD_DATA. */
+int et_tsne_neighbors(int64_t N, double perplexity);
+size_t et_tsne_affinities_workspace_bytes(int64_t N, int d, int k); /* 0: arguments not taken */
+int et_tsne_affinities(const float *X, int64_t N, int d, double perplexity, int k, int32_t *knn_idx, float *knn_dist,
+                       double *p_cond, int32_t *indptr, int32_t *indices, double *P, double *p_total, void *workspace,
+                       size_t workspace_bytes, et_stream_t stream);
+size_t et_tsne_kl_grad_workspace_bytes(int64_t N);
+int et_tsne_kl_grad(const float *Y, int64_t N, const int32_t *indptr, const int32_t *indices, const float *P,
+                    float *grad, double *kl, void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_tsne_update(float *p, double *update, float *gains, float *grad, int64_t n, double momentum,
+                   double learning_rate, et_stream_t stream);
+size_t et_tsne_optimize_workspace_bytes(int64_t N, int64_t nnz);
+int et_tsne_optimize(float *Y, int64_t N, const int32_t *indptr, const int32_t *indices, const double *P, int64_t nnz,
+                     double early_exaggeration, double learning_rate, int max_iter, double *kl_out, int *n_iter_out,
+                     void *workspace, size_t workspace_bytes, et_stream_t stream);
+size_t et_tsne_pca_init_workspace_bytes(int64_t N, int d);
+int et_tsne_pca_init(const float *X, int64_t N, int d, float *Y, void *workspace, size_t workspace_bytes,
+                     et_stream_t stream);
+
 /* ---- fit ----------------------------------------------------------------------------
  * Gram matrices of the normalised trajectories routed to descriptor `which`
  * (1 moving / 0 static) under `mode`:  G_obs (2T_obs,2T_obs), G_pred (2T_pred,2T_pred)

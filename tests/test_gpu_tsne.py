@@ -1,0 +1,227 @@
+"""t-SNE of descriptor coefficients on the GPU (csrc/et_tsne.hip): affinities against sklearn (tests/golden/g18*,
+tools/make_golden_tsne.py), gradient / KL against sklearn's theta = 0 gradient and the numpy restatement
+(tests/_tsne_np.py), the optimiser step bit for bit, whole runs against sklearn's recorded spread, and the full-size
+script pipeline (scripts/coeff_tsne.py) on eth and univ train."""
+import importlib.util
+import os
+import zlib
+
+import numpy as np
+import pytest
+import torch
+
+from . import _golden as G
+from . import _tsne_np as TN
+from ._gpu_common import *  # noqa: F401,F403 -- fixtures (dev, ops) and helpers
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+Z = G.load("g18_tsne.npz")
+
+
+def crc(a):
+    return zlib.crc32(np.ascontiguousarray(a).tobytes())
+
+
+def _check_rows(aff, rows, z, pre=""):
+    d = aff["knn_dist"].cpu().numpy()[rows]
+    i = aff["knn_idx"].cpu().numpy()[rows]
+    pc = aff["p_cond"].cpu().numpy()[rows]
+    assert [crc(np.sort(r)) for r in d] == list(z[pre + "knn_dcrc"])
+    tie = z[pre + "knn_tie"]
+    icrc = np.array([crc(np.sort(r)) for r in i], np.uint32)
+    assert np.array_equal(icrc[~tie], z[pre + "knn_icrc"][~tie])
+    return d, i, pc
+
+
+def _check_pcond(got, ref):
+    """within one fp32 ulp everywhere.  Not bit for bit: the device's fp64 exp / log (OCML) and glibc's differ in the
+    last bit on some arguments, and the binary search carries that (DESIGN §4 has the measured fraction)."""
+    assert np.all(np.abs(got - ref) <= np.spacing(ref.astype(np.float32)).astype(np.float64))
+    print(f"conditional P bit-equal to sklearn on {np.mean(got == ref):.4f} of {got.size} entries")
+
+
+@pytest.fixture(scope="module")
+def sub(dev):
+    from eigentrajectory_amd import ops
+    return ops.tsne_affinities(torch.from_numpy(Z["sub.X"]).to(dev))
+
+
+def test_affinities_subset_match_sklearn(sub):
+    n = Z["sub.X"].shape[0]
+    _check_rows(sub, np.arange(n), Z, "sub.")
+    rows = Z["sub.s_rows"]
+    assert np.array_equal(sub["knn_dist"].cpu().numpy()[rows], Z["sub.s_knn_d"])
+    _check_pcond(sub["p_cond"].cpu().numpy()[rows], Z["sub.s_pcond"])
+    indptr, indices, P = (sub[k].cpu().numpy() for k in ("indptr", "indices", "P"))
+    assert np.array_equal(indptr, Z["sub.P_indptr"])
+    assert [crc(indices[indptr[r]:indptr[r + 1]]) for r in range(n)] == list(Z["sub.P_icrc"])
+    np.testing.assert_allclose(np.add.reduceat(P, indptr[:-1]), Z["sub.P_rowsum"], rtol=1e-6)
+    off = Z["sub.s_P_off"]
+    for t, r in enumerate(rows):
+        assert np.array_equal(indices[indptr[r]:indptr[r + 1]], Z["sub.s_P_idx"][off[t]:off[t + 1]])
+        np.testing.assert_allclose(P[indptr[r]:indptr[r + 1]], Z["sub.s_P_val"][off[t]:off[t + 1]], rtol=1e-6)
+    # the CSR against the restated symmetrisation of the kernel's own conditional P: same pattern, same bits
+    ip2, ix2, P2, tot2 = TN.symmetrize(sub["knn_idx"].cpu().numpy(), sub["p_cond"].cpu().numpy())
+    assert np.array_equal(ip2, indptr) and np.array_equal(ix2, indices) and np.array_equal(P2, P)
+    assert sub["total"].item() == tot2
+
+
+def test_affinities_full_eth_sample_rows_match_sklearn(dev):
+    from eigentrajectory_amd import ops
+    zb = G.load("g18b_tsne_eth.npz")
+    aff = ops.tsne_affinities(torch.from_numpy(zb["X"]).to(dev))
+    rows = zb["rows"]
+    d, _, pc = _check_rows(aff, rows, zb)
+    assert np.array_equal(d[:128], zb["s_knn_d"])
+    _check_pcond(pc[:128], zb["s_pcond"])
+    n = zb["X"].shape[0]
+    indptr = aff["indptr"].cpu().numpy()
+    assert indptr[0] == 0 and np.all(np.diff(indptr) >= 91) and indptr[n] == aff["P"].numel()
+    assert abs(aff["P"].sum().item() - 1.0) < 1e-9
+
+
+@pytest.mark.parametrize("name", ["y50", "y400", "yrand"])
+def test_kl_grad_matches_sklearn_and_restatement(dev, sub, name):
+    from eigentrajectory_amd import ops
+    Y = torch.from_numpy(Z[f"emb.{name}"]).to(dev)
+    P32 = sub["P"].float()
+    kl, g = ops.tsne_kl_grad(Y, sub["indptr"], sub["indices"], P32)
+    kl2, g2 = ops.tsne_kl_grad(Y, sub["indptr"], sub["indices"], P32)
+    assert torch.equal(g, g2) and kl.item() == kl2.item()
+    g = g.cpu().numpy()
+    ref = Z[f"grad.{name}"]
+    assert np.abs(g - ref).max() <= 5e-5 * np.abs(ref).max()  # sklearn's fp32 force sums, as in test_tsne_cpu
+    assert abs(kl.item() - Z[f"kl.{name}"]) <= 1e-5 * abs(Z[f"kl.{name}"])
+    kln, gn = TN.kl_grad(Z[f"emb.{name}"], sub["indptr"].cpu().numpy(), sub["indices"].cpu().numpy(),
+                        P32.cpu().numpy())
+    assert np.abs(g - gn).max() <= 5e-5 * np.abs(gn).max()
+    assert abs(kl.item() - kln) <= 1e-5 * abs(kln)
+
+
+def test_update_step_bit_equal_to_restatement(dev):
+    from eigentrajectory_amd import ops
+    rng = np.random.default_rng(5)
+    n = 4000
+    p = rng.standard_normal(n).astype(np.float32) * 10
+    upd = rng.standard_normal(n) * 1e-2
+    upd[:100] = 0.0
+    gains = rng.uniform(0.005, 3, n).astype(np.float32)
+    grad = (rng.standard_normal(n) * 1e-3).astype(np.float32)
+    for mom, lr in ((0.5, np.maximum(2000 / 12.0 / 4, 50)), (0.8, np.maximum(29809 / 12.0 / 4, 50))):
+        ref = TN.update(p, upd, gains, grad, mom, lr)
+        t = [torch.from_numpy(a.copy()).to(dev) for a in (p, upd, gains, grad)]
+        ops.tsne_update(*t, mom, float(lr))
+        for a, b in zip(t, ref):
+            assert np.array_equal(a.cpu().numpy(), b)
+
+
+def test_phase_boundary_step_bit_equal(dev, sub):
+    """iteration 250, the first of the second phase, inside et_tsne_optimize equals one standalone step from the
+    positions after 250 iterations: the gradient on fp32((P x 12) / 12), update reset to 0, gains reset to 1,
+    momentum 0.8.  Also sklearn's returns at max_iter = 250 (an empty second phase: n_iter_ 250, KL = DBL_MAX)."""
+    from eigentrajectory_amd import ops
+    Y0 = torch.from_numpy(Z["sub.Y0"]).to(dev)
+    n = Y0.shape[0]
+    lr = float(np.maximum(n / 12.0 / 4, 50))
+    args = (sub["indptr"], sub["indices"], sub["P"], 12.0, lr)
+    y250, kl250, it250 = ops.tsne_optimize(Y0, *args, 250)
+    assert it250 == 250 and kl250 == np.finfo(np.float64).max
+    y251, kl251, it251 = ops.tsne_optimize(Y0, *args, 251)
+    assert it251 == 250
+    p2 = torch.from_numpy(TN.phase_p(sub["P"].cpu().numpy(), 12.0, True)).to(dev)
+    kl, g = ops.tsne_kl_grad(y250, sub["indptr"], sub["indices"], p2)
+    assert kl.item() == kl251  # the last iteration's KL: phase-2 P, positions before the step
+    p = y250.clone().reshape(-1)
+    upd = torch.zeros(2 * n, device=dev, dtype=torch.float64)
+    gains = torch.ones(2 * n, device=dev)
+    ops.tsne_update(p, upd, gains, g.reshape(-1).contiguous(), 0.8, lr)
+    assert torch.equal(p.reshape(n, 2), y251)
+    # the same step with the gains not reset differs: the check sees the reset
+    gains_kept = torch.full((2 * n,), 3.0, device=dev)
+    q = y250.clone().reshape(-1)
+    ops.tsne_update(q, torch.zeros_like(upd), gains_kept, g.reshape(-1).contiguous(), 0.8, lr)
+    assert not torch.equal(q.reshape(n, 2), y251)
+
+
+def test_non_finite_input_is_bad_data(dev, sub):
+    from eigentrajectory_amd import ops
+    Y = torch.from_numpy(Z["emb.yrand"]).to(dev)
+    Y[7, 1] = float("nan")
+    with pytest.raises(ValueError):
+        ops.tsne_kl_grad(Y, sub["indptr"], sub["indices"], sub["P"].float())
+    X = torch.from_numpy(Z["sub.X"]).to(dev)
+    X[3, 2] = float("inf")
+    with pytest.raises(ValueError):
+        ops.tsne_pca_init(X)
+    with pytest.raises(ValueError):
+        ops.tsne_affinities(X)
+
+
+def test_whole_run_subset(dev, sub):
+    from eigentrajectory_amd import ops
+    from eigentrajectory_amd.tsne import TSNE
+    X, Y0 = Z["sub.X"], Z["sub.Y0"]
+    n = X.shape[0]
+    lr = float(np.maximum(n / 12.0 / 4, 50))
+    # the first iterations against the restatement.  The exaggerated phase amplifies rounding differences (fp32 chunk
+    # sums here, fp64 there) by about 1.3x an iteration: 1.8e-7 of max |Y| after 5 iterations, 6.9e-2 after 50.  The
+    # prefix is held to 1e-4 for 5 iterations; after 50 only to a bound that catches a broken step (20 %).
+    P64, ip, ix = sub["P"].cpu().numpy(), sub["indptr"].cpu().numpy(), sub["indices"].cpu().numpy()
+    for iters, tol in ((5, 1e-4), (50, 0.2)):
+        y, _, it = ops.tsne_optimize(torch.from_numpy(Y0).to(dev), sub["indptr"], sub["indices"], sub["P"], 12.0, lr,
+                                     iters)
+        assert it == iters  # a first phase cut short: the second runs no iteration and returns i = it
+        ref = TN.optimize(Y0, ip, ix, P64, 12.0, lr, iters=iters)
+        err = np.abs(y.cpu().numpy() - ref).max() / np.abs(ref).max()
+        print(f"{iters} iterations: max difference to the restatement {err:.3g} of max |Y|")
+        assert err <= tol
+    # whole run from sklearn's init: KL and trustworthiness inside sklearn theta = 0's spread
+    ts = TSNE(n_components=2, random_state=42, init=Y0)
+    emb = ts.fit_transform(X)
+    assert ts.n_iter_ == 999 and np.all(np.isfinite(emb))
+    kls, tws = Z["run.kl"], Z["run.tw"]
+    spread = kls.max() - kls.min()
+    print(f"subset whole run: KL {ts.kl_divergence_:.6f} (sklearn theta = 0: {kls.min():.6f} .. {kls.max():.6f})")
+    # exact repulsion in another summation order is one more rounding path through the same run: within 3 x the spread
+    # of sklearn's three runs (3.2e-5) of their mean (measured: 0.601242 against 0.601209 .. 0.601241)
+    assert abs(ts.kl_divergence_ - kls.mean()) <= 3 * spread, (ts.kl_divergence_, kls)
+    tw = TN.trustworthiness(X, emb, 10)
+    print(f"subset whole run: trustworthiness@10 {tw:.5f} (sklearn theta = 0: {tws.min():.5f} .. {tws.max():.5f})")
+    assert tw >= tws.min() - 0.002, (tw, tws)
+    # bit-identical reruns
+    ts2 = TSNE(n_components=2, random_state=42, init=Y0)
+    assert np.array_equal(ts2.fit_transform(X), emb) and ts2.kl_divergence_ == ts.kl_divergence_
+    # init="pca" against sklearn's PCA init
+    y0 = ops.tsne_pca_init(torch.from_numpy(X).to(dev)).cpu().numpy()
+    err = np.abs(y0 - Y0).max() / np.abs(Y0).max()
+    print(f"init='pca': max difference to sklearn's {err:.3g} of max |Y0|")
+    assert err <= 1e-6
+
+
+def _script():
+    spec = importlib.util.spec_from_file_location("coeff_tsne", os.path.join(ROOT, "scripts", "coeff_tsne.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+@pytest.mark.parametrize("scene", ["eth", "univ"])
+def test_full_size_script_pipeline(dev, scene):
+    m = _script()
+    obs, pred = m.load_train(scene, None, dev)
+    r = m.run_scene(obs, pred)
+    n = obs.shape[0]
+    assert r["embedding"].shape == (n, 2) and np.all(np.isfinite(r["embedding"]))
+    assert r["n_iter"] == 999
+    ref = float(Z[f"default.{scene}.kl"])
+    assert int(Z[f"default.{scene}.N"]) == n
+    assert 0.95 * ref <= r["kl"] <= 1.02 * ref, (r["kl"], ref)
+    labels = m.clusters(torch.from_numpy(r["C_obs"]).to(dev)).cpu().numpy()
+    assert np.array_equal(labels, r["labels"])
+    if scene == "eth":  # the script's coefficients against the reference's (torch SVD) up to column sign and rounding
+        ref_c = G.load("g18b_tsne_eth.npz")["X"]
+        c = G.sign_align(r["C_obs"], ref_c)
+        err = np.abs(c - ref_c).max() / np.abs(ref_c).max()
+        print(f"eth C_obs: max difference to the reference's {err:.3g} of max |C_obs|")
+        assert err <= 1e-5
