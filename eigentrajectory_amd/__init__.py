@@ -10,5 +10,6 @@ from .normalizer import TrajNorm
 from .descriptor import ETDescriptor
 from .anchor import ETAnchor
 from .kmeans import BatchKMeans
+from .stgcnn import SocialSTGCNN
 
-__all__ = ["EigenTrajectory", "TrajNorm", "ETDescriptor", "ETAnchor", "BatchKMeans"]
+__all__ = ["EigenTrajectory", "TrajNorm", "ETDescriptor", "ETAnchor", "BatchKMeans", "SocialSTGCNN"]

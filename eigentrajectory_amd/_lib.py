@@ -35,6 +35,7 @@ SYMBOLS = [
     "et_tsne_neighbors", "et_tsne_affinities_workspace_bytes", "et_tsne_affinities", "et_tsne_kl_grad_workspace_bytes",
     "et_tsne_kl_grad", "et_tsne_update", "et_tsne_optimize_workspace_bytes", "et_tsne_optimize",
     "et_tsne_pca_init_workspace_bytes", "et_tsne_pca_init",
+    "et_stgcnn_workspace_bytes", "et_stgcnn_forward_scenes", "et_stgcnn_forward_graph",
     "et_fit_gram_workspace_bytes", "et_fit_gram", "et_eigh_topk", "et_eigh_topk_batch",
     "et_fit_descriptor_workspace_bytes", "et_fit_descriptor",
     "et_euc_sim", "et_euc_sim_batch", "et_kmeans_partials_len", "et_kmeans_workspace_bytes", "et_kmeans_scan", "et_kmeans_begin",
@@ -62,6 +63,25 @@ class KMeansTiming(C.Structure):
     """Mirror of ``et_kmeans_timing``."""
     _fields_ = [("assign_ms", C.c_double), ("assign_launches", C.c_int64), ("first_assign_ms", C.c_double),
                 ("iterations", C.c_int64)]
+
+
+STGCNN_MAX_LAYERS = 8  # ET_STGCNN_MAX_LAYERS
+
+
+class STGCNNLayer(C.Structure):
+    """Mirror of ``et_stgcnn_layer``: device pointers to one st_gcn block's tensors (field order: include/eigentraj.h)."""
+    _fields_ = [(name, C.c_void_p) for name in (
+        "gcn_w", "gcn_b", "bn1_w", "bn1_b", "bn1_mean", "bn1_var", "prelu1", "tcn_w", "tcn_b", "bn2_w", "bn2_b",
+        "bn2_mean", "bn2_var", "res_w", "res_b", "res_bn_w", "res_bn_b", "res_bn_mean", "res_bn_var", "prelu")]
+
+
+class STGCNNParams(C.Structure):
+    """Mirror of ``et_stgcnn_params``."""
+    _fields_ = [("n_stgcnn", C.c_int), ("n_txpcnn", C.c_int), ("input_feat", C.c_int), ("output_feat", C.c_int),
+                ("seq_len", C.c_int), ("pred_seq_len", C.c_int), ("kernel_size", C.c_int), ("bn_eps", C.c_float),
+                ("st_gcns", STGCNNLayer * STGCNN_MAX_LAYERS), ("tpcnn_w", C.c_void_p * STGCNN_MAX_LAYERS),
+                ("tpcnn_b", C.c_void_p * STGCNN_MAX_LAYERS), ("prelus", C.c_void_p * STGCNN_MAX_LAYERS),
+                ("out_w", C.c_void_p), ("out_b", C.c_void_p)]
 
 
 STATE_BYTES = C.sizeof(KMeansState)
@@ -92,7 +112,7 @@ def lib():
                      "et_kmeans_reforder_batch_workspace_bytes", "et_kmeans_reforder_sharded_workspace_bytes",
                      "et_curve_fit_batch_workspace_bytes", "et_tsne_affinities_workspace_bytes",
                      "et_tsne_kl_grad_workspace_bytes", "et_tsne_optimize_workspace_bytes",
-                     "et_tsne_pca_init_workspace_bytes"):
+                     "et_tsne_pca_init_workspace_bytes", "et_stgcnn_workspace_bytes"):
             getattr(l, name).restype = C.c_size_t
         l.et_kmeans_reforder_shard_block.restype = C.c_int64
         _lib = l

@@ -1,0 +1,120 @@
+"""Social-STGCNN, the predictor of ET-STGCNN (baseline/stgcnn/model.py: social_stgcnn), inference on HIP kernels.
+
+Same constructor signature and the same sub-module / parameter / buffer names as the reference (``st_gcns.{i}.gcn.conv``,
+``st_gcns.{i}.tcn.{0,1,2,3}``, ``st_gcns.{i}.residual.{0,1}``, ``st_gcns.{i}.prelu``, ``tpcnns.{j}``, ``tpcnn_ouput``,
+``prelus.{j}``), so a reference ET-STGCNN checkpoint's ``baseline_model.*`` keys load unchanged, and the module plugs into
+:class:`eigentrajectory_amd.EigenTrajectory` through the existing ``stgcnn`` bridge::
+
+    model = EigenTrajectory(SocialSTGCNN(n_stgcnn=1, n_txpcnn=5, input_feat=1, output_feat=hp.num_samples,
+                                         seq_len=hp.k + 2, pred_seq_len=hp.k, kernel_size=3),
+                            get_hook_func("stgcnn"), hp).eval()
+
+``forward(v, a)`` in eval mode is ONE launch of ``et_stgcnn_forward_graph`` (csrc/et_stgcnn.hip): BatchNorm uses its
+running statistics, dropout is off, the weights are read in place from this module's tensors (a ``load_state_dict``, a
+``.to()`` or an in-place edit is seen by the next call, and by a captured graph's next replay).  Training (batch
+statistics, the backward pass) is not implemented natively: a forward in training mode raises.  A whole split runs as one
+launch through :meth:`EigenTrajectory.evaluate_split` / :func:`eigentrajectory_amd.ops.stgcnn_forward_scenes`.
+Supported family: ``input_feat = 1``, ``kernel_size = 3``, ``seq_len = pred_seq_len + 2``, ``1 <= output_feat <= 64``,
+``pred_seq_len <= 32``, ``1 <= n_stgcnn, n_txpcnn <= 8``; other shapes construct, but their forward raises.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from . import _lib as L
+
+
+class _GraphConv(nn.Module):
+    """The gcn of an st_gcn block: a 1x1 convolution to out * K channels, contracted with the (K, V, V) graph."""
+
+    def __init__(self, in_channels, out_channels, kernel_size):
+        super().__init__()
+        self.kernel_size = kernel_size
+        self.conv = nn.Conv2d(in_channels, out_channels * kernel_size, kernel_size=(1, 1))
+
+
+class _STGCNBlock(nn.Module):
+    """One st_gcn block: gcn -> BN -> PReLU -> (t, 1) temporal conv -> BN (-> dropout, off), + residual, PReLU."""
+
+    def __init__(self, in_channels, out_channels, kernel_size):
+        super().__init__()
+        t_kernel, graph_kernel = kernel_size
+        self.gcn = _GraphConv(in_channels, out_channels, graph_kernel)
+        self.tcn = nn.Sequential(nn.BatchNorm2d(out_channels), nn.PReLU(),
+                                 nn.Conv2d(out_channels, out_channels, (t_kernel, 1), (1, 1), ((t_kernel - 1) // 2, 0)),
+                                 nn.BatchNorm2d(out_channels), nn.Dropout(0.0, inplace=True))
+        if in_channels != out_channels:
+            self.residual = nn.Sequential(nn.Conv2d(in_channels, out_channels, kernel_size=1, stride=(1, 1)),
+                                          nn.BatchNorm2d(out_channels))
+        else:
+            self.residual = None  # identity
+        self.prelu = nn.PReLU()
+
+
+def _p(t):
+    return t.data_ptr()
+
+
+class SocialSTGCNN(nn.Module):
+    r"""baseline/stgcnn/model.py's ``social_stgcnn`` (eval-mode inference on the GPU).  ``forward(v, a)``: v (1, 1, K, N),
+    a (K, N, N) as the stgcnn bridge's pre-hook builds them -> (1, S, k, N), the raw output the post-hook permutes."""
+
+    def __init__(self, n_stgcnn=1, n_txpcnn=1, input_feat=2, output_feat=5, seq_len=8, pred_seq_len=12, kernel_size=3):
+        super().__init__()
+        self.n_stgcnn, self.n_txpcnn = n_stgcnn, n_txpcnn
+        self.input_feat, self.output_feat = input_feat, output_feat
+        self.seq_len, self.pred_seq_len, self.kernel_size = seq_len, pred_seq_len, kernel_size
+        self.st_gcns = nn.ModuleList(
+            [_STGCNBlock(input_feat if i == 0 else output_feat, output_feat, (kernel_size, seq_len)) for i in range(n_stgcnn)])
+        self.tpcnns = nn.ModuleList(
+            [nn.Conv2d(seq_len if j == 0 else pred_seq_len, pred_seq_len, 3, padding=1) for j in range(n_txpcnn)])
+        self.tpcnn_ouput = nn.Conv2d(pred_seq_len, pred_seq_len, 3, padding=1)  # (sic: the reference's name)
+        self.prelus = nn.ModuleList([nn.PReLU() for _ in range(n_txpcnn)])
+
+    def et_params(self):
+        """-> (et_stgcnn_params, device): this module's tensors as the kernel reads them (include/eigentraj.h)."""
+        p = L.STGCNNParams()
+        p.n_stgcnn, p.n_txpcnn, p.input_feat = self.n_stgcnn, self.n_txpcnn, self.input_feat
+        p.output_feat, p.seq_len, p.pred_seq_len, p.kernel_size = (self.output_feat, self.seq_len, self.pred_seq_len,
+                                                                   self.kernel_size)
+        tensors = list(self.parameters()) + [b for b in self.buffers() if b.is_floating_point()]
+        dev = tensors[0].device
+        if dev.type != "cuda" or any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
+            raise L.ETLibraryError("SocialSTGCNN: every parameter and buffer must be a contiguous float32 tensor on ONE HIP "
+                                   "device (model.cuda()); there is no CPU path")
+        bns = [m for m in self.modules() if isinstance(m, nn.BatchNorm2d)]
+        eps = {float(m.eps) for m in bns}
+        if len(eps) != 1 or any(m.running_mean is None or m.weight is None for m in bns):
+            raise L.ETLibraryError("SocialSTGCNN: the kernel takes one BatchNorm eps and affine BatchNorms with running "
+                                   "statistics")
+        p.bn_eps = eps.pop()
+        if self.n_stgcnn > L.STGCNN_MAX_LAYERS or self.n_txpcnn > L.STGCNN_MAX_LAYERS:
+            return p, dev  # the kernel answers ET_ERR_UNSUPPORTED
+        for i, blk in enumerate(self.st_gcns):
+            s = p.st_gcns[i]
+            bn1, pr1, conv, bn2 = blk.tcn[0], blk.tcn[1], blk.tcn[2], blk.tcn[3]
+            s.gcn_w, s.gcn_b = _p(blk.gcn.conv.weight), _p(blk.gcn.conv.bias)
+            s.bn1_w, s.bn1_b, s.bn1_mean, s.bn1_var = (_p(bn1.weight), _p(bn1.bias), _p(bn1.running_mean),
+                                                       _p(bn1.running_var))
+            s.prelu1 = _p(pr1.weight)
+            s.tcn_w, s.tcn_b = _p(conv.weight), _p(conv.bias)
+            s.bn2_w, s.bn2_b, s.bn2_mean, s.bn2_var = (_p(bn2.weight), _p(bn2.bias), _p(bn2.running_mean),
+                                                       _p(bn2.running_var))
+            if blk.residual is not None:
+                rc, rb = blk.residual[0], blk.residual[1]
+                s.res_w, s.res_b = _p(rc.weight), _p(rc.bias)
+                s.res_bn_w, s.res_bn_b, s.res_bn_mean, s.res_bn_var = (_p(rb.weight), _p(rb.bias), _p(rb.running_mean),
+                                                                       _p(rb.running_var))
+            s.prelu = _p(blk.prelu.weight)
+        for j, (conv, pr) in enumerate(zip(self.tpcnns, self.prelus)):
+            p.tpcnn_w[j], p.tpcnn_b[j], p.prelus[j] = _p(conv.weight), _p(conv.bias), _p(pr.weight)
+        p.out_w, p.out_b = _p(self.tpcnn_ouput.weight), _p(self.tpcnn_ouput.bias)
+        return p, dev
+
+    def forward(self, v, a):
+        if self.training:
+            raise RuntimeError("SocialSTGCNN: only inference is native (BatchNorm running statistics, no dropout); "
+                               "training-mode forward and backward are not implemented -- call .eval() first")
+        from . import ops
+        return ops.stgcnn_forward_graph(self, v, a)

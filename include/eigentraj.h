@@ -308,6 +308,66 @@ size_t et_tsne_pca_init_workspace_bytes(int64_t N, int d);
 int et_tsne_pca_init(const float *X, int64_t N, int d, float *Y, void *workspace, size_t workspace_bytes,
                      et_stream_t stream);
 
+/* ---- Social-STGCNN predictor, inference (baseline/stgcnn: bridge.py pre-hook + social_stgcnn.forward + post-hook) ---
+ * Eval mode only: every BatchNorm2d uses its running statistics, dropout is off.  The parameters are read in place from
+ * the module's own tensors through the pointer table below (fp32, contiguous); the BatchNorm transform
+ * (x - running_mean) / sqrt(running_var + bn_eps) * weight + bias is formed inside the kernel.  Field <-> state_dict name
+ * (i = st_gcn layer, j = tpcnn index):
+ *   st_gcns[i].gcn_w / gcn_b         st_gcns.{i}.gcn.conv.weight (S K, C_in, 1, 1) / .bias (S K)
+ *   st_gcns[i].bn1_*                 st_gcns.{i}.tcn.0.weight / bias / running_mean / running_var (S)
+ *   st_gcns[i].prelu1                st_gcns.{i}.tcn.1.weight (1)
+ *   st_gcns[i].tcn_w / tcn_b         st_gcns.{i}.tcn.2.weight (S, S, 3, 1) / .bias (S)
+ *   st_gcns[i].bn2_*                 st_gcns.{i}.tcn.3.weight / bias / running_mean / running_var (S)
+ *   st_gcns[i].res_w / res_b         st_gcns.{i}.residual.0.weight (S, C_in, 1, 1) / .bias (S); NULL when C_in == S
+ *   st_gcns[i].res_bn_*              st_gcns.{i}.residual.1.weight / bias / running_mean / running_var (S)
+ *   st_gcns[i].prelu                 st_gcns.{i}.prelu.weight (1)
+ *   tpcnn_w[j] / tpcnn_b[j]          tpcnns.{j}.weight (k, j ? k : K, 3, 3) / .bias (k)
+ *   prelus[j]                        prelus.{j}.weight (1)
+ *   out_w / out_b                    tpcnn_ouput.weight (k, k, 3, 3) / .bias (k)
+ * with K = seq_len, k = pred_seq_len, S = output_feat.  tpcnns[j] / prelus[j] are read for j < max(1, n_txpcnn - 1)
+ * only (the reference's loop leaves the last pair unused); the others may be NULL.
+ * Supported: input_feat = 1, kernel_size = 3, seq_len = pred_seq_len + 2, 1 <= pred_seq_len <= ET_MAX_K,
+ * 1 <= output_feat <= 64, 1 <= n_stgcnn, n_txpcnn <= ET_STGCNN_MAX_LAYERS; anything else: ET_ERR_UNSUPPORTED.
+ *
+ * The adjacency of "time" row t of v (bridge.py:4-21): a_inv = 1 / |v[t,i] - v[t,j]| (0 where the distance is 0),
+ * a_hat = a_inv + I, D = rowsum(a_hat)^-1/2, L = I - D a_hat D.
+ *   et_stgcnn_forward_graph   one scene as the bridge hands it over: v (1,1,K,N), a = L (K,N,N) -> out (1,S,k,N), the
+ *                             network's raw output.  N <= ET_SCENE_MAX_N.
+ *   et_stgcnn_forward_scenes  a whole split: C_obs (k,N), nrm (4,N) of et_norm_project (rows 0-1: last observed position);
+ *                             per scene v = [C_obs; nrm[0:2] - their mean over the scene] (model.py:86-90), L formed on
+ *                             the fly from v, -> C_pred_refine (k,N,S) (the post-hook's layout).  scene_offsets as
+ *                             et_traj_metrics (NULL = one scene of N rows); n_scenes = 0 takes N = 0 only.  One launch.
+ * Workspace: a scene whose activations fit a workgroup's LDS arena (at S = 20, k = 6: up to 33 pedestrians) needs none;
+ * larger ones use workspace rows [off[s], off[s+1]) of et_stgcnn_workspace_bytes(p, N, max_scene_n) bytes (0 when a
+ * scene of max_scene_n pedestrians fits the arena).  A scene larger than ET_SCENE_MAX_N, or one that fits neither, is
+ * not computed: its outputs are NaN.  No host synchronisation, no allocation: the calls can be captured in a graph. */
+#define ET_STGCNN_MAX_LAYERS 8
+typedef struct et_stgcnn_layer {
+    const float *gcn_w, *gcn_b;
+    const float *bn1_w, *bn1_b, *bn1_mean, *bn1_var;
+    const float *prelu1;
+    const float *tcn_w, *tcn_b;
+    const float *bn2_w, *bn2_b, *bn2_mean, *bn2_var;
+    const float *res_w, *res_b;
+    const float *res_bn_w, *res_bn_b, *res_bn_mean, *res_bn_var;
+    const float *prelu;
+} et_stgcnn_layer;
+typedef struct et_stgcnn_params {
+    int n_stgcnn, n_txpcnn, input_feat, output_feat, seq_len, pred_seq_len, kernel_size;
+    float bn_eps;
+    et_stgcnn_layer st_gcns[ET_STGCNN_MAX_LAYERS];
+    const float *tpcnn_w[ET_STGCNN_MAX_LAYERS];
+    const float *tpcnn_b[ET_STGCNN_MAX_LAYERS];
+    const float *prelus[ET_STGCNN_MAX_LAYERS];
+    const float *out_w, *out_b;
+} et_stgcnn_params;
+size_t et_stgcnn_workspace_bytes(const et_stgcnn_params *params, int64_t N, int64_t max_scene_n);
+int et_stgcnn_forward_scenes(const et_stgcnn_params *params, const float *C_obs, const float *nrm, int64_t N,
+                             const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, void *workspace,
+                             size_t workspace_bytes, et_stream_t stream);
+int et_stgcnn_forward_graph(const et_stgcnn_params *params, const float *v, const float *a, int64_t N, float *out,
+                            void *workspace, size_t workspace_bytes, et_stream_t stream);
+
 /* ---- fit ----------------------------------------------------------------------------
  * Gram matrices of the normalised trajectories routed to descriptor `which`
  * (1 moving / 0 static) under `mode`:  G_obs (2T_obs,2T_obs), G_pred (2T_pred,2T_pred)
