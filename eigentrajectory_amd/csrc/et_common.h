@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/eigentraj.h"
 
 #define ET_HIP_TRY(expr)                         \
@@ -27,6 +29,46 @@ constexpr int kWave = 64;  // CDNA wavefront width
 
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 __host__ __device__ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// A value (or a "done once" flag) of the CURRENT device, zero / default until its first user fills it in: a process may
+// drive several GPUs, and a CU count, a function attribute or a slot counter belongs to one of them.  Declared `static`
+// where it is used.
+template <typename T>
+class PerDevice {
+  public:
+    T &current() {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+        return slot_[dev & 63];
+    }
+
+  private:
+    T slot_[64] = {};
+};
+
+// Runtime value -> template argument: f is a generic lambda and is called with a std::integral_constant, so the occupancy
+// query, the attribute list and the launch inside it all name the SAME instantiation of a kernel.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <typename F>
+static inline auto with_bool(bool b, F &&f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+// coordinates per point: the unrolled d = 6 form of a kernel, or its general form (0: d is read at run time)
+template <typename F>
+static inline auto with_dim(int d, F &&f) {
+    return d == 6 ? f(int_c<6>{}) : f(int_c<0>{});
+}
+// row-block width of the matrix-core label filter (et_mfma_filter.h): K <= 20 clusters fit 10 rows per lane, K <= 32 need 16
+template <typename F>
+static inline auto with_filter_rows(int K, F &&f) {
+    return K <= 20 ? f(int_c<10>{}) : f(int_c<16>{});
+}
+// ... or 0 for the form of a kernel that runs without the filter (the reference-order loop below its size threshold)
+template <typename F>
+static inline auto with_filter_rows(bool filtered, int K, F &&f) {
+    return filtered ? with_filter_rows(K, f) : f(int_c<0>{});
+}
 
 // Normaliser state of one trajectory (EigenTrajectory/normalizer.py:17-29).
 struct RowNorm {

@@ -36,14 +36,14 @@
 // fixed-point integer (truncation, power-of-two scale => exact) and integers are summed, so the
 // result is independent of the order: the same bits for any workgroup schedule, grid size or
 // number of GPUs, and identical to the CPU oracle (oracle/et_oracle.c).
+#include <algorithm>
 #include <atomic>
+#include <condition_variable>
 #include <cstdlib>
-#include <type_traits>
+#include <mutex>
 #include <vector>
 
 #include "et_common.h"
-#include <sched.h>
-
 #include "et_hostring.h"
 #include "et_options.h"
 #include "et_mfma_filter.h"

@@ -1,6 +1,7 @@
 // et_kmeans_chain.inl -- part of csrc/et_kmeans.hip (ONE translation unit: this file is #included there, in order, and is not
 // compiled on its own): one launch per iteration: the stand-alone filter kernel, the delta fold, update_body, kmeans_lloyd_chain_kernel and its finalize kernel.
-// clang-format off: the fragment starts and ends at namespace scope of whatever the including file has open.
+namespace et {
+
 template <int NREGS>
 __global__ __launch_bounds__(kFilterMaxThreads) void kmeans_assign_filter_kernel(
     const float *__restrict__ X, int64_t N, int K, const et_kmeans_state *__restrict__ state,
@@ -509,3 +510,5 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_chain_finalize_kernel(const
     __syncthreads();
     update_body(state, sTot, d, K, tol, cen, trace, ch.st_rd, ch.last);
 }
+
+}  // namespace et

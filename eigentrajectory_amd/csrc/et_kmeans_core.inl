@@ -1,6 +1,5 @@
 // et_kmeans_core.inl -- part of csrc/et_kmeans.hip (ONE translation unit: this file is #included there, in order, and is not
 // compiled on its own): shared definitions: threads / limits, the scalar helpers the oracle shares, centroids in LDS, the scan / begin kernels and the exact (vector-ALU) assignment scan.
-// clang-format off: the fragment starts and ends at namespace scope of whatever the including file has open.
 namespace et {
 
 constexpr int kKmThreads = 256;
@@ -660,3 +659,5 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_assign_kernel(
     if (state->done) return;
     assign_body_valu<D, VEC>(X, N, d_rt, K, state, cen, given, labels, block_partials);
 }
+
+}  // namespace et

@@ -1,6 +1,7 @@
 // et_kmeans_filter.inl -- part of csrc/et_kmeans.hip (ONE translation unit: this file is #included there, in order, and is not
 // compiled on its own): the matrix-core label filter on fp32 rows (filter_assign_body): iterations >= 1 of traced fits and of shards below the packed threshold.
-// clang-format off: the fragment starts and ends at namespace scope of whatever the including file has open.
+namespace et {
+
 // ------------------------------------------------------------------------------------------
 // Lloyd half-step for iterations >= 1: matrix-core FILTER + exact certification (d = 6, K <= 32).
 //
@@ -501,6 +502,4 @@ __device__ __forceinline__ void filter_assign_body(const float *__restrict__ X, 
     ET_BSTAMP(9);
 }
 
-// ------------------------------------------------------------------------------------------
-// Trace-less Lloyd iterations on a PACKED copy of the points (d = 6, K <= 32, big shards).
-//
+}  // namespace et

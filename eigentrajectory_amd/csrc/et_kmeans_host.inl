@@ -1,25 +1,24 @@
 // et_kmeans_host.inl -- part of csrc/et_kmeans.hip (ONE translation unit: this file is #included there, in order, and is not
 // compiled on its own): host side: grids, workspace layout, the step API (scan / begin / assign_accumulate / update / labels / predict / init_*) and et_kmeans_init_farthest.
-// clang-format off: the fragment starts and ends at namespace scope of whatever the including file has open.
+namespace et {
+
+// CU count of the CURRENT device
+static int km_cu_count() {
+    static PerDevice<int> cu_of_device;
+    int &n_cu = cu_of_device.current();
+    if (n_cu == 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            n_cu <= 0)
+            n_cu = 256;
+    }
+    return n_cu;
 }
 
 // Grid of a grid-stride kernel sized to exactly one resident wave of workgroups (CUs x workgroups
 // per CU from the occupancy query): every workgroup then gets the same number of passes (+-1) and
 // there is no sparsely filled last round (4096 workgroups at 5 resident per CU would leave the
 // chip 80 % idle for its fourth round).
-// CU count of the CURRENT device (cached per device id; a process may drive several GPUs)
-static int km_cu_count(int *dev_out = nullptr) {
-    static int cu_of_device[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (dev_out) *dev_out = dev;
-    int &n_cu = cu_of_device[dev & 63];
-    if (n_cu == 0) {
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    }
-    return n_cu;
-}
-
 template <typename Kernel>
 static int km_resident_grid(Kernel kernel, size_t lds_bytes, int64_t work_items, int threads = kKmThreads) {
     const int n_cu = km_cu_count();
@@ -147,22 +146,22 @@ static KmWorkspace km_carve(void *base, int64_t N, int d, int K) {
     return w;
 }
 
-template <int D>
+// the exact scan, four points per lane (vec4) or one; returns its grid
 static int launch_assign(const float *X, int64_t N, int d, int K, const et_kmeans_state *state, const float *cen,
                          const int64_t *given, uint8_t *labels, long long *block_partials, bool vec4, hipStream_t st) {
     const size_t plen = km_plen(d, K);
     const size_t lds = sizeof(long long) * ((plen + 1) & ~(size_t)1) + sizeof(float) * (size_t)K * ((d + 1 + 3) & ~3);
-    int grid;
-    if (vec4) {
-        grid = km_resident_grid(kmeans_assign_kernel<D, 4>, lds, N / 4);
-        hipLaunchKernelGGL((kmeans_assign_kernel<D, 4>), dim3(grid), dim3(kKmThreads), lds, st, X, N, d, K, state, cen,
-                           given, labels, block_partials);
-    } else {
-        grid = km_resident_grid(kmeans_assign_kernel<D, 1>, lds, N);
-        hipLaunchKernelGGL((kmeans_assign_kernel<D, 1>), dim3(grid), dim3(kKmThreads), lds, st, X, N, d, K, state, cen,
-                           given, labels, block_partials);
-    }
-    return grid;
+    // (an empty shard takes the general form, one point per lane: it only zeroes its partials)
+    return with_dim(N > 0 ? d : 0, [&](auto dim) {
+        constexpr int D = dim.value;
+        return with_bool(N > 0 && vec4, [&](auto quad) {
+            constexpr int kPerLane = quad.value ? 4 : 1;
+            const int grid = km_resident_grid(kmeans_assign_kernel<D, kPerLane>, lds, N / kPerLane);
+            hipLaunchKernelGGL((kmeans_assign_kernel<D, kPerLane>), dim3(grid), dim3(kKmThreads), lds, st, X, N, d, K, state,
+                               cen, given, labels, block_partials);
+            return grid;
+        });
+    });
 }
 
 }  // namespace et
@@ -208,33 +207,37 @@ static std::atomic<unsigned long long> g_test_abort_mask{0};
 extern "C" void et_testhook_kmeans_abort_mask(unsigned long long mask) { g_test_abort_mask.store(mask, std::memory_order_relaxed); }
 #endif
 
+// four points per lane: 16-byte loads of the coordinate rows, 4-byte stores of the labels
+static bool km_vec4_ok(const float *X, int64_t N, const uint8_t *labels_u8) {
+    return (N % 4 == 0) && aligned16(X) && ((reinterpret_cast<uintptr_t>(labels_u8) & 3u) == 0);
+}
+
 // matrix-core filter + exact certification (default; option kmeans_argmax = v disables it)
 static bool km_use_filter(const float *X, int64_t N, int d, int K, const uint8_t *labels_u8) {
-    const bool vec4 = (N % 4 == 0) && aligned16(X) && ((reinterpret_cast<uintptr_t>(labels_u8) & 3u) == 0);
-    return km_argmax_mode() == 'f' && vec4 && d == 6 && K >= 3 && K <= 32 && N >= 1024 && N <= 0xffffffffll;
+    return km_argmax_mode() == 'f' && km_vec4_ok(X, N, labels_u8) && d == 6 && K >= 3 && K <= 32 && N >= 1024 && N <= 0xffffffffll;
 }
 
 // 96 KB of dynamic LDS for the fat (16-wavefront) kernels: above the default 64 KB window; the attribute is per device
 static int km_fat_lds_attribute() {
-    static bool lds_set[64] = {};
-    int dev_id = 0;
-    ET_HIP_TRY(hipGetDevice(&dev_id));
-    bool &lds_ok = lds_set[dev_id & 63];
+    static PerDevice<bool> lds_set;
+    bool &lds_ok = lds_set.current();
     if (lds_ok) return ET_OK;
-#define ET_FAT4(KERNEL)                                                                                       \
-    reinterpret_cast<const void *>(KERNEL<10, true>), reinterpret_cast<const void *>(KERNEL<10, false>),           \
-        reinterpret_cast<const void *>(KERNEL<16, true>), reinterpret_cast<const void *>(KERNEL<16, false>)
-    const void *fat[] = {reinterpret_cast<const void *>(kmeans_assign_filter_kernel<10>),
-                         reinterpret_cast<const void *>(kmeans_assign_filter_kernel<16>),
-                         ET_FAT4(kmeans_lloyd_chain_kernel), ET_FAT4(kmeans_lloyd_persist_kernel),
-                         reinterpret_cast<const void *>(kmeans_lloyd_chain_kernel<10, true, true>),
-                         reinterpret_cast<const void *>(kmeans_lloyd_chain_kernel<10, false, true>),
-                         reinterpret_cast<const void *>(kmeans_lloyd_chain_kernel<16, true, true>),
-                         reinterpret_cast<const void *>(kmeans_lloyd_chain_kernel<16, false, true>)};
-#undef ET_FAT4
-    for (const void *f : fat) ET_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    lds_ok = true;
-    return ET_OK;
+    auto set_all = [](auto nr) -> int {  // every fat kernel of one row-block width
+        constexpr int NR = nr.value;
+        for (const void *f : {reinterpret_cast<const void *>(kmeans_assign_filter_kernel<NR>),
+                              reinterpret_cast<const void *>(kmeans_lloyd_chain_kernel<NR, true, false>),
+                              reinterpret_cast<const void *>(kmeans_lloyd_chain_kernel<NR, false, false>),
+                              reinterpret_cast<const void *>(kmeans_lloyd_chain_kernel<NR, true, true>),
+                              reinterpret_cast<const void *>(kmeans_lloyd_chain_kernel<NR, false, true>),
+                              reinterpret_cast<const void *>(kmeans_lloyd_persist_kernel<NR, true>),
+                              reinterpret_cast<const void *>(kmeans_lloyd_persist_kernel<NR, false>)})
+            ET_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        return ET_OK;
+    };
+    int rc = set_all(int_c<10>{});
+    if (!rc) rc = set_all(int_c<16>{});
+    lds_ok = !rc;
+    return rc;
 }
 
 static size_t km_filter_lds_bytes(int d, int K, int threads) {
@@ -250,10 +253,7 @@ static int km_filter_threads(int64_t N) {
         const int t = options().kmeans_filter_threads.load(std::memory_order_relaxed);
         if (t >= 256 && t <= kFilterMaxThreads && t % 64 == 0) return t;
     }
-    int dev = 0, n_cu = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n_cu <= 0)
-        n_cu = 256;
+    const int n_cu = km_cu_count();
     const int64_t groups = ceil_div(N, (int64_t)256);
     const int64_t p12 = ceil_div(groups, (int64_t)n_cu * (kFilterMinThreads / 64));
     const int64_t p16 = ceil_div(groups, (int64_t)n_cu * (kFilterMaxThreads / 64));
@@ -288,7 +288,6 @@ static int assign_accumulate_impl(const float *X, int64_t N, int d, int K, et_km
         return ET_ERR_INVALID_ARG;
     if (!workspace || workspace_bytes < et_kmeans_workspace_bytes(N, d, K)) return ET_ERR_WORKSPACE;
     const KmWorkspace w = km_carve(workspace, N, d, K);
-    const bool vec4 = (N % 4 == 0) && aligned16(X) && ((reinterpret_cast<uintptr_t>(labels_u8) & 3u) == 0);
     // The filter kernel itself runs the plain exact scan for the first iteration of a fit (state->iter == 0: no
     // labels to confirm yet).
     const bool use_filter = !given_labels && km_use_filter(X, N, d, K, labels_u8);
@@ -299,20 +298,14 @@ static int assign_accumulate_impl(const float *X, int64_t N, int d, int K, et_km
         if (rc_attr) return rc_attr;
         const int threads = km_filter_threads(N);
         const size_t lds = km_filter_lds_bytes(d, K, threads);
-        if (K <= 20) {
-            grid = km_resident_grid(kmeans_assign_filter_kernel<10>, lds, N / 4, threads);
-            hipLaunchKernelGGL(kmeans_assign_filter_kernel<10>, dim3(grid), dim3(threads), lds, st, X, N, K, state,
+        with_filter_rows(K, [&](auto nr) {
+            grid = km_resident_grid(kmeans_assign_filter_kernel<nr.value>, lds, N / 4, threads);
+            hipLaunchKernelGGL(kmeans_assign_filter_kernel<nr.value>, dim3(grid), dim3(threads), lds, st, X, N, K, state,
                                centroids, labels_u8, w.block_partials, (long long *)nullptr);
-        } else {
-            grid = km_resident_grid(kmeans_assign_filter_kernel<16>, lds, N / 4, threads);
-            hipLaunchKernelGGL(kmeans_assign_filter_kernel<16>, dim3(grid), dim3(threads), lds, st, X, N, K, state,
-                               centroids, labels_u8, w.block_partials, (long long *)nullptr);
-        }
-    } else if (N > 0) {
-        grid = d == 6 ? launch_assign<6>(X, N, d, K, state, centroids, given_labels, labels_u8, w.block_partials, vec4, st)
-                      : launch_assign<0>(X, N, d, K, state, centroids, given_labels, labels_u8, w.block_partials, vec4, st);
+        });
     } else {
-        grid = launch_assign<0>(X, N, d, K, state, centroids, given_labels, labels_u8, w.block_partials, false, st);
+        grid = launch_assign(X, N, d, K, state, centroids, given_labels, labels_u8, w.block_partials,
+                             km_vec4_ok(X, N, labels_u8), st);
     }
     ET_LAUNCH_CHECK();
     if (ev_end) ET_HIP_TRY(hipEventRecord(ev_end, st));
@@ -378,12 +371,10 @@ extern "C" int et_kmeans_predict_batch(const float *X, int64_t x_stride, int64_t
     const size_t lds = sizeof(float) * (size_t)K * ((d + 1 + 3) & ~3);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)km_grid(N), (unsigned)batch);
-    if (d == 6)
-        hipLaunchKernelGGL((kmeans_predict_kernel<6>), grid, dim3(kKmThreads), lds, st, X, N, d, centroids, K, labels, maxsims,
-                           x_stride);
-    else
-        hipLaunchKernelGGL((kmeans_predict_kernel<0>), grid, dim3(kKmThreads), lds, st, X, N, d, centroids, K, labels, maxsims,
-                           x_stride);
+    with_dim(d, [&](auto dim) {
+        hipLaunchKernelGGL((kmeans_predict_kernel<dim.value>), grid, dim3(kKmThreads), lds, st, X, N, d, centroids, K, labels,
+                           maxsims, x_stride);
+    });
     ET_LAUNCH_CHECK();
     return ET_OK;
 }
@@ -419,14 +410,11 @@ static int init_step_impl(const float *X, int64_t N, int d, int K, int i, const 
     const int n_prev = i > 1 ? init_step_grid(N, i - 1) : 0;
     // tile summaries: written by step 2 and every later one, used from step 3 on (K <= 32: the label set is a 32-bit mask)
     uint4 *meta = (K <= 32 && km_init_tiles_mode()) ? w.init_meta : nullptr;
-    if (d == 6)
-        hipLaunchKernelGGL((kmeans_init_step_kernel<6>), dim3(grid), dim3(kKmThreads), 0, st, X, N, d, K, i, C0, best,
+    with_dim(d, [&](auto dim) {
+        hipLaunchKernelGGL((kmeans_init_step_kernel<dim.value>), dim3(grid), dim3(kKmThreads), 0, st, X, N, d, K, i, C0, best,
                            w.labels_u8, w.init_maxabs, index_base, keys, prev, n_prev, fused, (unsigned char *)cand, meta,
                            i > 2 ? 1 : 0);
-    else
-        hipLaunchKernelGGL((kmeans_init_step_kernel<0>), dim3(grid), dim3(kKmThreads), 0, st, X, N, d, K, i, C0, best,
-                           w.labels_u8, w.init_maxabs, index_base, keys, prev, n_prev, fused, (unsigned char *)cand, meta,
-                           i > 2 ? 1 : 0);
+    });
     ET_LAUNCH_CHECK();
     if (!fused || last) {
         hipLaunchKernelGGL(kmeans_init_pick_kernel, dim3(1), dim3(kKmThreads), 0, st, X, N, d, keys, grid, index_base,

@@ -1,6 +1,10 @@
 // et_kmeans_init.inl -- part of csrc/et_kmeans.hip (ONE translation unit: this file is #included there, in order, and is not
 // compiled on its own): farthest-first initialisation kernels (kmeans.py:88-112).
-// clang-format off: the fragment starts and ends at namespace scope of whatever the including file has open.
+namespace et {
+
+// ------------------------------------------------------------------------------------------
+// farthest-first initialisation (kmeans.py:88-112): one pass per new centroid.
+// best[n] = max(best[n], sim(x_n, c_{i-1})); candidate = arg-min over n (first index on ties,
 // NaN first) encoded as a 64-bit key so that a plain unsigned min is the reduction.
 // ------------------------------------------------------------------------------------------
 //
@@ -406,3 +410,6 @@ __global__ void kmeans_state_reset_kernel(et_kmeans_state *state) {
 static int km_grid(int64_t work_items) {
     const int64_t b = ceil_div(work_items, (int64_t)kKmThreads);
     return (int)(b < 1 ? 1 : (b > kKmMaxBlocks ? kKmMaxBlocks : b));
+}
+
+}  // namespace et

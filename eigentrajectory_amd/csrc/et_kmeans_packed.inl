@@ -1,7 +1,11 @@
 // et_kmeans_packed.inl -- part of csrc/et_kmeans.hip (ONE translation unit: this file is #included there, in order, and is not
 // compiled on its own): trace-less Lloyd iterations on the packed f16 copy of the points: PackedHeader, kmeans_pack_kernel, the per-launch tables, packed_assign_body.
-// clang-format off: the fragment starts and ends at namespace scope of whatever the including file has open.
-// The filter above reads 24 B per point and iteration to certify that a label did not change, and an iteration takes as
+namespace et {
+
+// ------------------------------------------------------------------------------------------
+// Trace-less Lloyd iterations on a PACKED copy of the points (d = 6, K <= 32, big shards).
+//
+// The filter (et_kmeans_filter.inl) reads 24 B per point and iteration to certify that a label did not change, and an iteration takes as
 // long as the memory side needs to stream them (HISTORY.md 3.2).  The certification does not need the exact coordinates:
 // kmeans_pack_kernel writes, once per fit,
 //   xh   three rows of N dwords: the coordinate pairs (0,1), (2,3), (4,5) of  s (x - mu)  rounded to f16 (nearest);
@@ -506,3 +510,5 @@ __device__ __forceinline__ void packed_assign_body(const LloydPacked pk, const f
     KM_PSTAMP(8);
     KM_PSTAMP_FLUSH();
 }
+
+}  // namespace et

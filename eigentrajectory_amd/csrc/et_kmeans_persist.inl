@@ -1,6 +1,7 @@
 // et_kmeans_persist.inl -- part of csrc/et_kmeans.hip (ONE translation unit: this file is #included there, in order, and is not
 // compiled on its own): all iterations of a fit in one launch (kmeans_lloyd_persist_kernel), the inertia pass, predict.
-// clang-format off: the fragment starts and ends at namespace scope of whatever the including file has open.
+namespace et {
+
 // ------------------------------------------------------------------------------------------
 // Single-GPU fit, shards the filter takes: ALL Lloyd iterations in ONE launch (persistent workgroups).
 //
@@ -376,6 +377,4 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_predict_kernel(const float 
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// farthest-first initialisation (kmeans.py:88-112): one pass per new centroid.
-// best[n] = max(best[n], sim(x_n, c_{i-1})); candidate = arg-min over n (first index on ties,
+}  // namespace et

@@ -26,10 +26,9 @@
 // ~0.1 ms per iteration against 12 us) and it does not shard: the order of the sums is a property of the whole array.
 // Third-party arithmetic (torch 2.10.0 CPU, AVX2-width Vectorized<float>) pinned by tests/test_oracle_golden.py
 // (oracle == torch on random inputs) and tests/golden/g7c_* (whole runs of the imported reference).
+#include <algorithm>
 #include <cstdlib>
-
 #include <vector>
-#include <sched.h>
 
 #include "et_common.h"
 #include "et_hostring.h"

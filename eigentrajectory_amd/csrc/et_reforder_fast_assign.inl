@@ -1,5 +1,9 @@
 // et_reforder_fast_assign.inl -- part of csrc/et_kmeans_reforder.hip (ONE translation unit: this file is #included there, in order, and is
 // not compiled on its own): the fast form: assignment of a group by matrix-core certification, and the first half of an iteration (reforder_groups_kernel: assignment + cascade levels 0 and 1).
+namespace et {
+namespace reforder {
+namespace fast {
+
 // ---- the assignment of a group by CERTIFICATION (iterations >= 1, no NaN possible): csrc/et_kmeans.hip's matrix-core filter
 //      ("Lloyd half-step for iterations >= 1": that is where the bounds are derived) on the quads of the permuted copy.  Per
 //      point the second largest of the f16-MFMA upper bounds u_j >= Y_j + |x|^2 is compared with the exact Y_l + |x|^2 of the
@@ -452,3 +456,7 @@ __device__ __forceinline__ float inner_sum_parallel(const float *v, int size, fl
     __syncthreads();
     return r;
 }
+
+}  // namespace fast
+}  // namespace reforder
+}  // namespace et

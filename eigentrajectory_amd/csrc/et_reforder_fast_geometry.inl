@@ -1,5 +1,8 @@
 // et_reforder_fast_geometry.inl -- part of csrc/et_kmeans_reforder.hip (ONE translation unit: this file is #included there, in order, and is
 // not compiled on its own): the fast form (d = 6, K <= 32, 1024 <= N < 2^29): the cascade tree as geometry, workspace layout, the permuted copy, exact packed arg-max.
+namespace et {
+namespace reforder {  // (namespace fast opens below its overview, and all three close at the end of this file)
+
 // =====================================================================================================================
 // The FAST form of the reference-order Lloyd iteration (d = 6, K <= 32, 1024 <= N < 2^29): one launch per iteration.
 //
@@ -392,3 +395,7 @@ __device__ __forceinline__ void cascade_levels(Load load, const unsigned *sLab, 
         RF_ACC(5, tacc);
     }
 }
+
+}  // namespace fast
+}  // namespace reforder
+}  // namespace et

@@ -1,5 +1,9 @@
 // et_reforder_fast_update.inl -- part of csrc/et_kmeans_reforder.hip (ONE translation unit: this file is #included there, in order, and is
 // not compiled on its own): the fast form: second half of an iteration (levels 2 / 3, the lane combination, new centroids, joint stop of a batch).
+namespace et {
+namespace reforder {
+namespace fast {
+
 // ---- second half: level 2 (workgroup b: block b, its groups' results in group order); the workgroup that arrives last:
 //      level 3, the leftovers, the lane combination, the new centroids (kmeans.py:180-182); the last one of the batch: the
 //      error over the whole (l, d, K) tensor in ATen's order (kmeans.py:45-51, 232), the stop flag, the next launch's
@@ -289,3 +293,7 @@ __global__ __launch_bounds__(TT) void reforder_update_kernel2(const Args a, int 
     if (tid == 0) *a.batch_arrive = 0u;
     RF_STAMP(3, 4);
 }
+
+}  // namespace fast
+}  // namespace reforder
+}  // namespace et

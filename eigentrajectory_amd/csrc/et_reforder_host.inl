@@ -1,5 +1,60 @@
 // et_reforder_host.inl -- part of csrc/et_kmeans_reforder.hip (ONE translation unit: this file is #included there, in order, and is
 // not compiled on its own): host side: workspace queries, the generic loop, the sharded run, the C ABI entry points.
+namespace et {
+namespace reforder {
+namespace fast {
+
+// the kernels' argument block: `batch` problems in `workspace` (shared part first, then one block per problem)
+static Args make_args(const Geo &geo, const float *X, int64_t x_stride, int K, int64_t batch, int max_iter, float tol,
+                      float *trace, void *workspace, unsigned long long *mail) {
+    Args a;
+    a.geo = geo;
+    a.lay = make_layout(a.geo, K);
+    unsigned char *base = (unsigned char *)workspace;
+    a.batch_arrive = (unsigned *)base;
+    a.sq_all = (float *)(base + 256);
+    a.ws = base + shared_bytes(K, batch);
+    a.ws_stride = (int64_t)a.lay.bytes;
+    a.X = X;
+    a.x_stride = x_stride;
+    a.K = K;
+    a.batch = (int)batch;
+    a.tol = tol;
+    a.trace = trace;
+    a.max_iter = max_iter;
+    a.mail = mail;
+    a.tiles_per_round = fast_tiles_per_round(a.geo);
+    return a;
+}
+
+// first half of an iteration: without the matrix-core label filter, or with it at the row-block width K needs.  The
+// filter pays where the exact scan is what a launch waits for: L >= 32 (N > 4.2e6)
+using GroupsKernel = void (*)(const Args);
+static GroupsKernel groups_kernel(const Geo &geo, int K) {
+    return with_filter_rows(geo.lp >= fast_filter_min_lp() && K >= 3, K,
+                            [](auto nr) -> GroupsKernel { return reforder_groups_kernel<nr.value>; });
+}
+
+// dynamic LDS above the default 64 KB window for every kernel of the fast form that asks for it (per device, once)
+static int lds_attributes() {
+    static PerDevice<bool> lds_set;
+    bool &lds_ok = lds_set.current();
+    if (lds_ok) return ET_OK;
+    for (const void *f : {reinterpret_cast<const void *>(reforder_groups_kernel<0>), reinterpret_cast<const void *>(reforder_groups_kernel<10>),
+                          reinterpret_cast<const void *>(reforder_groups_kernel<16>)})
+        ET_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
+    for (const void *f : {reinterpret_cast<const void *>(reforder_update_kernel2<kUThreads, false>),
+                          reinterpret_cast<const void *>(reforder_update_kernel2<1024, true>),
+                          reinterpret_cast<const void *>(reforder_level2_sharded_kernel), reinterpret_cast<const void *>(reforder_finish_sharded_kernel)})
+        ET_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kUMaxLds));
+    lds_ok = true;
+    return ET_OK;
+}
+
+}  // namespace fast
+}  // namespace reforder
+}  // namespace et
+
 using namespace et::reforder;
 
 static size_t fast_workspace_bytes(int64_t N, int K, int64_t batch) {
@@ -26,45 +81,15 @@ static int fast_fit(const float *X, int64_t x_stride, int64_t N, int K, int64_t 
                     int64_t *labels, float *trace, et_kmeans_state *states_host, et_kmeans_timing *timing_host, void *workspace,
                     hipStream_t st) {
     using namespace fast;
-    Args a;
-    a.geo = make_geo(N);
-    a.lay = make_layout(a.geo, K);
-    unsigned char *base = (unsigned char *)workspace;
-    a.batch_arrive = (unsigned *)base;
-    a.sq_all = (float *)(base + 256);
-    a.ws = base + shared_bytes(K, batch);
-    a.ws_stride = (int64_t)a.lay.bytes;
-    a.X = X;
-    a.x_stride = x_stride;
-    a.K = K;
-    a.batch = (int)batch;
-    a.tol = tol;
-    a.trace = trace;
-    a.max_iter = max_iter;
-    a.mail = nullptr;
-    int rc = ET_OK;
-    et::StateRing *ring = et::StateRing::get(&rc);
-    if (!ring) return rc;
-    a.mail = ring->mailbox_device();
-    if (a.mail) ring->mailbox_reset();
-    a.tiles_per_round = fast_tiles_per_round(a.geo);
+    et::LoopPacer pacer;  // single GPU: the update kernel reports (done, iterations) into the pinned mailbox
+    int rc = pacer.begin(et::LoopPacer::kMailbox, st);
+    if (rc) return rc;
+    const Args a = make_args(make_geo(N), X, x_stride, K, batch, max_iter, tol, trace, workspace, pacer.mailbox_device());
     const size_t lds = fast_lds_bytes(a.geo, K, a.tiles_per_round);
     size_t ulds = 0;
     const int rows_cap = update_rows_cap(a.geo, K, (int)batch, &ulds);
-    {
-        static bool lds_set[64] = {};
-        int dev_id = 0;
-        ET_HIP_TRY(hipGetDevice(&dev_id));
-        if (!lds_set[dev_id & 63]) {
-            for (const void *f : {reinterpret_cast<const void *>(reforder_groups_kernel<0>), reinterpret_cast<const void *>(reforder_groups_kernel<10>),
-                                  reinterpret_cast<const void *>(reforder_groups_kernel<16>)})
-                ET_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-            for (const void *f : {reinterpret_cast<const void *>(reforder_update_kernel2<kUThreads, false>),
-                                  reinterpret_cast<const void *>(reforder_update_kernel2<1024, true>)})
-                ET_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kUMaxLds));
-            lds_set[dev_id & 63] = true;
-        }
-    }
+    rc = lds_attributes();
+    if (rc) return rc;
     for (int64_t b = 0; b < batch; ++b) {
         rc = et_kmeans_scan(X + b * x_stride, N, kD, (et_kmeans_state *)(a.ws + b * a.ws_stride + a.lay.state), (et_stream_t)st);
         if (rc) return rc;
@@ -83,9 +108,7 @@ static int fast_fit(const float *X, int64_t x_stride, int64_t N, int K, int64_t 
         ET_HIP_TRY(hipEventCreate(&ev[1]));
         ET_HIP_TRY(hipEventRecord(ev[0], st));
     }
-    // the matrix-core label filter pays where the exact scan is what a launch waits for: L >= 32 (N > 4.2e6)
-    const bool use_filter = a.geo.lp >= fast_filter_min_lp() && K >= 3;
-    constexpr int kAhead = 16, kEvery = 4;
+    const GroupsKernel groups = groups_kernel(a.geo, K);
     et_kmeans_state *state0 = (et_kmeans_state *)(a.ws + a.lay.state);
     int launched = 0;
     bool done = false;
@@ -94,32 +117,16 @@ static int fast_fit(const float *X, int64_t x_stride, int64_t N, int K, int64_t 
     const int uslot = (kD * K + kFMaxK / 4 + 63) / 64 * 64;
     const bool single_update = a.geo.n_blk <= 1024 / uslot && et::options().reforder_single_update.load(std::memory_order_relaxed) != 0;
     for (int it = 0; it < max_iter && !done; ++it) {
-        if (!use_filter) hipLaunchKernelGGL(reforder_groups_kernel<0>, grid, dim3(kFThreads), lds, st, a);
-        else if (K <= 20) hipLaunchKernelGGL(reforder_groups_kernel<10>, grid, dim3(kFThreads), lds, st, a);
-        else hipLaunchKernelGGL(reforder_groups_kernel<16>, grid, dim3(kFThreads), lds, st, a);
-        if (single_update)
-            hipLaunchKernelGGL((reforder_update_kernel2<1024, true>), dim3(1, (unsigned)batch), dim3(1024), ulds, st, a, rows_cap, uslot);
-        else
-            hipLaunchKernelGGL((reforder_update_kernel2<kUThreads, false>), ugrid, dim3(kUThreads), ulds, st, a, rows_cap, 0);
+        hipLaunchKernelGGL(groups, grid, dim3(kFThreads), lds, st, a);
+        et::with_bool(single_update, [&](auto single) {
+            constexpr int TT = single.value ? 1024 : kUThreads;
+            hipLaunchKernelGGL((reforder_update_kernel2<TT, single.value>), single.value ? dim3(1, (unsigned)batch) : ugrid, dim3(TT), ulds,
+                               st, a, rows_cap, single.value ? uslot : 0);
+        });
         ET_LAUNCH_CHECK();
         launched = it + 1;
-        if (a.mail) {  // stay at most kAhead launches ahead of the device's report; stop when it carries the flag
-            for (unsigned spins = 0;; ++spins) {
-                if (ring->mailbox_done()) {
-                    done = true;
-                    break;
-                }
-                if ((long long)launched - ring->mailbox_iter() <= kAhead) break;
-                if ((spins & 0xfffu) == 0xfffu && hipStreamQuery(st) == hipSuccess) break;
-                sched_yield();
-            }
-        } else {
-            if (launched % kEvery == 0) {
-                rc = ring->post(state0, st, &done);
-                if (rc) return rc;
-            }
-            ring->poll(&done);
-        }
+        rc = pacer.after_launch(launched, state0, &done);
+        if (rc) return rc;
     }
     if (timing_host) ET_HIP_TRY(hipEventRecord(ev[1], st));
     const int64_t fgrid = std::min<int64_t>((N + kThreads - 1) / kThreads, 2048);
@@ -223,46 +230,21 @@ extern "C" int et_internal_kmeans_reforder_sharded_run(const float *X, const int
     if (nranks > 1 && !gather) return ET_ERR_INVALID_ARG;
     if (workspace_bytes < p.bytes) return ET_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    Args a;
-    a.geo = p.geo;
-    a.lay = make_layout(a.geo, K);
+    const Args a = make_args(p.geo, X, 0, K, 1, max_iter, tol, trace, workspace, nullptr);
     unsigned char *base = (unsigned char *)workspace;
-    a.batch_arrive = (unsigned *)base;
-    a.sq_all = (float *)(base + 256);
-    a.ws = base + shared_bytes(K, 1);
-    a.ws_stride = (int64_t)a.lay.bytes;
-    a.X = X;
-    a.x_stride = 0;
-    a.K = K;
-    a.batch = 1;
-    a.tol = tol;
-    a.trace = trace;
-    a.max_iter = max_iter;
-    a.mail = nullptr;
-    a.tiles_per_round = fast_tiles_per_round(a.geo);
     float4 *send = (float4 *)(base + p.off_send), *table = (float4 *)(base + p.off_table);
     int *rows_dev = (int *)(base + p.off_rows);
-    et::StateRing *ring = et::StateRing::get(&rc);
-    if (!ring) return rc;
+    et::LoopPacer pacer;  // a gather between the launches
+    rc = pacer.begin(et::LoopPacer::kLockstep, st);
+    if (rc) return rc;
     const size_t lds = fast_lds_bytes(a.geo, K, a.tiles_per_round);
     size_t l2lds = 0;
     const int l2cap = update_rows_cap(a.geo, K, 1, &l2lds);
     const size_t rowb = sizeof(float4) * (size_t)p.rec.rowlen;
     const int fcap = (int)std::min<size_t>((size_t)p.max_rows, kUMaxLds / rowb);
     const size_t flds = std::max<size_t>((size_t)fcap * rowb, sizeof(float) * (size_t)kD * K);
-    {
-        static bool lds_set[64] = {};
-        int dev_id = 0;
-        ET_HIP_TRY(hipGetDevice(&dev_id));
-        if (!lds_set[dev_id & 63]) {
-            for (const void *f : {reinterpret_cast<const void *>(reforder_groups_kernel<0>), reinterpret_cast<const void *>(reforder_groups_kernel<10>),
-                                  reinterpret_cast<const void *>(reforder_groups_kernel<16>)})
-                ET_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-            for (const void *f : {reinterpret_cast<const void *>(reforder_level2_sharded_kernel), reinterpret_cast<const void *>(reforder_finish_sharded_kernel)})
-                ET_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kUMaxLds));
-            lds_set[dev_id & 63] = true;
-        }
-    }
+    rc = lds_attributes();
+    if (rc) return rc;
     et_kmeans_state *state = (et_kmeans_state *)(a.ws + a.lay.state);
     rc = et_kmeans_scan(X, a.geo.N, kD, state, stream);
     if (rc) return rc;
@@ -280,15 +262,12 @@ extern "C" int et_internal_kmeans_reforder_sharded_run(const float *X, const int
                            a.geo);
     }
     ET_LAUNCH_CHECK();
-    const bool use_filter = a.geo.lp >= fast_filter_min_lp() && K >= 3;
-    constexpr int kEvery = 4;
+    const GroupsKernel groups = groups_kernel(a.geo, K);
     bool done = false;
     const dim3 grid((unsigned)(a.geo.G + 1), 1), l2grid((unsigned)std::max(p.rows[rank], 1), 1);
     const size_t rec_bytes = sizeof(float4) * (size_t)p.rec.words();
     for (int it = 0; it < max_iter && !done; ++it) {
-        if (!use_filter) hipLaunchKernelGGL(reforder_groups_kernel<0>, grid, dim3(kFThreads), lds, st, a);
-        else if (K <= 20) hipLaunchKernelGGL(reforder_groups_kernel<10>, grid, dim3(kFThreads), lds, st, a);
-        else hipLaunchKernelGGL(reforder_groups_kernel<16>, grid, dim3(kFThreads), lds, st, a);
+        hipLaunchKernelGGL(groups, grid, dim3(kFThreads), lds, st, a);
         hipLaunchKernelGGL(reforder_level2_sharded_kernel, l2grid, dim3(kUThreads), l2lds, st, a, p.rec, p.rows[rank], send, l2cap);
         ET_LAUNCH_CHECK();
         if (gather) {
@@ -300,13 +279,8 @@ extern "C" int et_internal_kmeans_reforder_sharded_run(const float *X, const int
         hipLaunchKernelGGL(reforder_finish_sharded_kernel, dim3(1), dim3(kUThreads), flds, st, a, p.rec, p.P, (const int *)rows_dev,
                            p.tail_rank, p.tail_full, p.N_total, (const float4 *)table, fcap);
         ET_LAUNCH_CHECK();
-        // the stop flag is read one post late, by a blocking wait on that specific copy: which copy a rank sees must not
-        // depend on timing, or the ranks would stop enqueueing collectives at different iterations (et_sharded.hip)
-        if ((it + 1) % kEvery == 0) {
-            rc = ring->post(state, st, &done);
-            if (!rc && ring->pending() > 1) rc = ring->wait_oldest(&done);
-            if (rc) return rc;
-        }
+        rc = pacer.after_launch(it + 1, state, &done);
+        if (rc) return rc;
     }
     const int64_t fgrid = std::max<int64_t>(1, std::min<int64_t>((a.geo.N + kThreads - 1) / kThreads, 2048));
     hipLaunchKernelGGL(reforder_fast_finish_kernel, dim3((unsigned)fgrid, 1), dim3(kThreads), 0, st, a, centroids,
@@ -346,12 +320,11 @@ extern "C" int et_kmeans_init_farthest_reforder(const float *X, int64_t N, int d
         // not see this launch's records -- and picks centroid i - 1 itself; only the last centroid needs the pick launch)
         Cand *mine = w.cands + (size_t)(i & 1) * kMaxBlocks;
         const Cand *prev = i > 1 ? w.cands + (size_t)((i - 1) & 1) * kMaxBlocks : nullptr;
-        if (incremental && d == 6)
-            hipLaunchKernelGGL(reforder_init_step_inc_kernel<6>, dim3(grid), dim3(kThreads), 0, st, X, N, d, K, i, (const float *)C0,
-                               w.maxsims, w.best4, w.labels_u8, max_abs_bits, skip_ok, mine, prev, grid, C0);
-        else if (incremental)
-            hipLaunchKernelGGL(reforder_init_step_inc_kernel<0>, dim3(grid), dim3(kThreads), 0, st, X, N, d, K, i, (const float *)C0,
-                               w.maxsims, w.best4, w.labels_u8, max_abs_bits, skip_ok, mine, prev, grid, C0);
+        if (incremental)
+            et::with_dim(d, [&](auto dim) {
+                hipLaunchKernelGGL(reforder_init_step_inc_kernel<dim.value>, dim3(grid), dim3(kThreads), 0, st, X, N, d, K, i,
+                                   (const float *)C0, w.maxsims, w.best4, w.labels_u8, max_abs_bits, skip_ok, mine, prev, grid, C0);
+            });
         else
             hipLaunchKernelGGL(reforder_init_step_kernel, dim3(grid), dim3(kThreads), lds, st, X, N, d, K, i, (const float *)C0,
                                w.cands);

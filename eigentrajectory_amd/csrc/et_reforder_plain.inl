@@ -632,3 +632,6 @@ static int grid_for(int64_t items) {
     const int64_t b = (items + kThreads - 1) / kThreads;
     return (int)(b < 1 ? 1 : (b > kMaxBlocks ? kMaxBlocks : b));
 }
+
+}  // namespace reforder
+}  // namespace et

@@ -1,5 +1,9 @@
 // et_reforder_sharded.inl -- part of csrc/et_kmeans_reforder.hip (ONE translation unit: this file is #included there, in order, and is
 // not compiled on its own): the reference-order iteration over shards: level-2 rows gathered over ranks, finish kernel, fast_fit host loop.
+namespace et {
+namespace reforder {
+namespace fast {
+
 // =====================================================================================================================
 // The reference-order iteration over SHARDS (one process per GPU; not in the reference).  The order of a cascade sum is a
 // property of the whole array, but its tree is made of index ranges: with every shard boundary on a multiple of a level-2
@@ -305,6 +309,5 @@ extern "C" int et_debug_rfstamps(unsigned long long *host) {
 #endif
 
 }  // namespace fast
-
 }  // namespace reforder
 }  // namespace et

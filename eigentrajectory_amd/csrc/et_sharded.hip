@@ -239,6 +239,17 @@ int sum_over_ranks(void *ctx, long long *buf, size_t count, hipStream_t st) {  /
     const ncclResult_t r = et::g_rccl.AllReduce(buf, buf, count, ncclInt64, ncclSum, static_cast<ReduceCtx *>(ctx)->comm, st);
     return r == ncclSuccess ? ET_OK : ET_ERR_RCCL;
 }
+// what either loop form of et_kmeans_fit_sharded ends with: this rank's labels, the final state on the host
+int finish_fit(const uint8_t *labels_u8, int64_t N_local, int64_t *labels, const et_kmeans_state *state,
+               et_kmeans_state *state_host, et_stream_t stream) {
+    if (labels) {
+        const int rc = et_kmeans_labels_i64(labels_u8, N_local, labels, stream);
+        if (rc) return rc;
+    }
+    ET_HIP_TRY(hipMemcpyAsync(state_host, state, sizeof(et_kmeans_state), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    ET_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return state_host->bad_input ? ET_ERR_BAD_DATA : ET_OK;
+}
 }  // namespace
 
 extern "C" int et_kmeans_fit_sharded(const float *X, int64_t N_local, int64_t N_total, int d, int K, int max_iter,
@@ -267,26 +278,17 @@ extern "C" int et_kmeans_fit_sharded(const float *X, int64_t N_local, int64_t N_
     // (d = 6, 3 <= K <= 32).  The two loop forms enqueue different collectives, so every rank must take the same one: the
     // choice depends on (d, K) alone -- a shard whose size or alignment rules out the 16-byte loads of the filter body
     // runs the exact scan inside the same chained kernel -- and needs neither a collective nor a host round trip.
-    {
-        const bool usable = N_total <= 0xffffffffll && et_internal_kmeans_chain_usable(d, K) != 0;
-        if (usable) {
-            ReduceCtx ctx{c};
-            rc = et_internal_kmeans_chain_run(X, N_local, d, K, max_iter, tol, centroids, labels_u8, trace, state, partials,
-                                              workspace, workspace_bytes, comm ? &sum_over_ranks : nullptr, &ctx, stream);
-            if (rc) return rc;
-            if (labels) {
-                rc = et_kmeans_labels_i64(labels_u8, N_local, labels, stream);
-                if (rc) return rc;
-            }
-            ET_HIP_TRY(hipMemcpyAsync(state_host, state, sizeof(et_kmeans_state), hipMemcpyDeviceToHost, st));
-            ET_HIP_TRY(hipStreamSynchronize(st));
-            return state_host->bad_input ? ET_ERR_BAD_DATA : ET_OK;
-        }
+    if (N_total <= 0xffffffffll && et_internal_kmeans_chain_usable(d, K) != 0) {
+        ReduceCtx ctx{c};
+        rc = et_internal_kmeans_chain_run(X, N_local, d, K, max_iter, tol, centroids, labels_u8, trace, state, partials,
+                                          workspace, workspace_bytes, comm ? &sum_over_ranks : nullptr, &ctx, stream);
+        return rc ? rc : finish_fit(labels_u8, N_local, labels, state, state_host, stream);
     }
-    StateRing *ring = StateRing::get(&rc);
-    if (!ring) return rc;
+    // (in lockstep also without a communicator: one pacing for the loop, whatever the number of ranks)
+    LoopPacer pacer;
+    rc = pacer.begin(LoopPacer::kLockstep, st);
+    if (rc) return rc;
     const size_t plen = et_kmeans_partials_len(d, K);
-    constexpr int kEvery = 4;
     bool done = false;
     for (int it = 0; it < max_iter && !done; ++it) {
         rc = et_kmeans_assign_accumulate(X, N_local, d, K, state, centroids, nullptr, labels_u8, partials, workspace,
@@ -295,23 +297,10 @@ extern "C" int et_kmeans_fit_sharded(const float *X, int64_t N_local, int64_t N_
         if (comm) ET_RCCL_TRY(g_rccl.AllReduce(partials, partials, plen, ncclInt64, ncclSum, c, st));  // 1.1 KB, in place
         rc = et_kmeans_update(state, partials, d, K, tol, centroids, trace, stream);
         if (rc) return rc;
-        // The host looks at the convergence flag one post LATE and by a blocking wait on that specific copy (posted
-        // kEvery iterations ago, long since arrived): which copy a rank sees must not depend on timing, or the ranks
-        // would stop enqueueing collectives at different iterations.  The flag itself is computed from identical
-        // integers on every rank; launches after convergence are no-ops.
-        if ((it + 1) % kEvery == 0) {
-            rc = ring->post(state, st, &done);
-            if (!rc && ring->pending() > 1) rc = ring->wait_oldest(&done);
-            if (rc) return rc;
-        }
-    }
-    if (labels) {
-        rc = et_kmeans_labels_i64(labels_u8, N_local, labels, stream);
+        rc = pacer.after_launch(it + 1, state, &done);
         if (rc) return rc;
     }
-    ET_HIP_TRY(hipMemcpyAsync(state_host, state, sizeof(et_kmeans_state), hipMemcpyDeviceToHost, st));
-    ET_HIP_TRY(hipStreamSynchronize(st));
-    return state_host->bad_input ? ET_ERR_BAD_DATA : ET_OK;
+    return finish_fit(labels_u8, N_local, labels, state, state_host, stream);
 }
 
 extern "C" int et_internal_kmeans_reforder_sharded_run(const float *X, const int64_t *n_locals, int nranks, int rank, int K,
