@@ -343,9 +343,9 @@ __device__ __forceinline__ double block_sum_f64(double v, double *sh) {
     return r;
 }
 
-// per row i and column chunk c: (nx, ny) = sum q^2 (y_i - y_j) over the chunk's j that are not within 1e-6 of y_i in
-// both coordinates (j = i included) (fp32, j order); zpart[c * nrb + block] = the fp64 sum of the block's rows' fp32
-// sums of q over the chunk
+// per row i and column chunk c: (nx, ny) = sum q^2 (y_i - y_j) over the chunk's j whose position differs from y_i in
+// at least one coordinate (fp32, j order); zpart[c * nrb + block] = the fp64 sum of the block's rows' fp32 sums of q
+// over the chunk
 __global__ void __launch_bounds__(kBlock) rep_kernel(const float2 *__restrict__ Y, int64_t N, float *__restrict__ part,
                                                      double *__restrict__ zpart, const OptState *__restrict__ st) {
     if (st && st->stop) return;
@@ -364,9 +364,10 @@ __global__ void __launch_bounds__(kBlock) rep_kernel(const float2 *__restrict__ 
         for (int j = 0; j < nc; ++j) {
             const float dx = yi.x - ty[j].x, dy = yi.y - ty[j].y;
             const float d2 = fmaf(dy, dy, dx * dx);
-            // like sklearn's tree, which leaves out every point within 1e-6 of the query in each coordinate (its own
-            // "self interaction"), not only j == i: coincident points (no force, dx = dy = 0) do not inflate Z
-            const bool skip = j == self || (fabsf(dx) <= 1e-6f && fabsf(dy) <= 1e-6f);
+            // like sklearn's tree as compiled, which leaves out the points exactly coincident with the query (its own
+            // "self interaction": the 1e-6 its source names has no effect), not only j == i: coincident
+            // points (no force, dx = dy = 0) do not inflate Z; a point 1e-7 away counts like any other
+            const bool skip = j == self || (dx == 0.f && dy == 0.f);
             const float q = skip ? 0.f : 1.0f / (1.0f + d2);
             const float q2 = q * q;
             z = z + q;
@@ -414,7 +415,9 @@ __global__ void __launch_bounds__(kBlock) grad_kernel(GradArgs a) {
     // Z: the same fixed order in every block
     double zs = 0.0;
     for (int64_t e = threadIdx.x; e < a.nzp; e += kBlock) zs = zs + a.zpart[e];
-    const double Z = block_sum_f64(zs, sh);
+    // sklearn: sum_Q = max(sum_Q, DBL_EPSILON) -- all points coincident: Z = 0, every force 0, the gradient exactly 0
+    const double zsum = block_sum_f64(zs, sh);
+    const double Z = zsum > DBL_EPSILON ? zsum : DBL_EPSILON;
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const int64_t N = a.N;
     double kl = 0.0, gn = 0.0;

@@ -274,9 +274,9 @@ int et_curve_fit_batch(const float *traj, const float *basis, const int64_t *fit
  *   P = (P_cond + P_cond^T) / total as canonical CSR: indptr (N+1), indices / P (capacity 2 N k; nnz = indptr[N]);
  *   p_total (device, may be NULL) the total.  Synchronises the stream once.  Non-finite X or N < 2: ET_ERR_BAD_DATA.
  * et_tsne_kl_grad: grad (N,2) = 4 (sum_j p_ij q_ij (y_i - y_j) - sum_{j ~ i} q_ij^2 (y_i - y_j) / Z) with
- *   q_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i ~ j} q_ij, P fp32 CSR; j ~ i: j is not within 1e-6 of i in both
- *   coordinates (as sklearn's quadtree, which skips such points; j = i included); kl (device, may be NULL) the KL
- *   divergence over the CSR entries.  Bit-identical from run to run (the summation order depends on N only).  The
+ *   q_ij = 1 / (1 + |y_i - y_j|^2), Z = max(sum_{i ~ j} q_ij, DBL_EPSILON), P fp32 CSR; j ~ i: y_j differs from y_i in
+ *   a coordinate (as sklearn's quadtree as compiled, which skips exactly coincident points; j = i included; all points
+ *   coincident: grad = 0); kl (device, may be NULL) the KL divergence over the CSR entries.  Bit-identical from run to run (the summation order depends on N only).  The
  *   workspace holds ceil(N / 1024) x N x 8 bytes of partial sums (grows as N^2; 7 MB at N = 3e4, 78 MB at 1e5);
  *   N <= 65 535 x 1 024.  Synchronises the stream once.  Non-finite Y: ET_ERR_BAD_DATA.
  * et_tsne_update: one step of sklearn's _gradient_descent on n coordinates in place (gains, update fp64, p; grad is

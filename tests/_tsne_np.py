@@ -130,16 +130,16 @@ def symmetrize(idx, pc):
 
 
 def kl_grad(Y, indptr, indices, P32):
-    """KL and gradient with exact repulsion: attraction and KL over the CSR entries, repulsion over all j not within 1e-6
-    of i in both coordinates, in fp64."""
+    """KL and gradient with exact repulsion: attraction and KL over the CSR entries, repulsion over all j whose fp32
+    position differs from i's in at least one coordinate (sklearn's compiled tree leaves out exactly coincident points
+    only), in fp64; Z = max(Z, DBL_EPSILON) as sklearn clamps sum_Q."""
     Y = np.asarray(Y, np.float32)
     y = Y.astype(np.float64)
     n = Y.shape[0]
     diff = y[:, None, :] - y[None, :, :]
     q = 1.0 / (1.0 + (diff ** 2).sum(-1))
-    dd = Y[:, None, :] - Y[None, :, :]
-    q[np.all(np.abs(dd) <= np.float32(1e-6), axis=-1)] = 0.0  # j = i and points within 1e-6 (sklearn's tree skips them)
-    Z = q.sum()
+    q[np.all(diff == 0.0, axis=-1)] = 0.0  # j = i and exactly coincident points
+    Z = max(q.sum(), np.finfo(np.float64).eps)
     neg = ((q * q)[:, :, None] * diff).sum(1)
     r = np.repeat(np.arange(n), np.diff(indptr))
     b = y[r] - y[indices]
@@ -149,6 +149,34 @@ def kl_grad(Y, indptr, indices, P32):
     np.add.at(pos, r, (p * qe)[:, None] * b)
     kl = float(np.sum(p * np.log(np.maximum(p, FLT_MIN) / np.maximum(qe / Z, FLT_MIN))))
     return kl, (4.0 * (pos - neg / Z)).astype(np.float32)
+
+
+def edge_embeddings(n, seed):
+    """seeded (n,2) fp32 embeddings at the coincidence edges (n even): name -> Y.  `dup`: the second half repeats the
+    first exactly; `d1e-7`, `d9e-7`, `d2e-6`: the second half is the first moved by that much in both coordinates (std 0.5,
+    so that fp32 keeps the offsets: the tool and the tests assert what the differences are); `pca`: std 1e-4, the scale
+    of init="pca"; `eq0`, `eqc`: all points at the origin / at one other point."""
+    rng = np.random.default_rng(seed)
+    h = n // 2
+    base = (rng.standard_normal((n, 2)) * 0.5).astype(np.float32)
+    out = {}
+    y = base.copy()
+    y[h:2 * h] = y[:h]
+    out["dup"] = y
+    for name, delta in (("d1e-7", 1e-7), ("d9e-7", 9e-7), ("d2e-6", 2e-6)):
+        y = base.copy()
+        y[h:2 * h] = (y[:h].astype(np.float64) + delta).astype(np.float32)
+        out[name] = y
+    out["pca"] = (rng.standard_normal((n, 2)) * 1e-4).astype(np.float32)
+    out["eq0"] = np.zeros((n, 2), np.float32)
+    out["eqc"] = np.tile(np.float32([0.3, -0.7]), (n, 1))
+    return out
+
+
+def pair_offsets(Y):
+    """max-norm offsets |y_i - y_{i+n/2}| of the paired halves of an edge embedding (fp32 differences, as the kernel forms)"""
+    h = Y.shape[0] // 2
+    return np.abs(Y[h:2 * h] - Y[:h]).max(-1), np.abs(Y[h:2 * h] - Y[:h]).min(-1)
 
 
 def update(p, upd, gains, grad, momentum, lr):
@@ -218,3 +246,29 @@ def trustworthiness(X, Y, k=10):
 def libm_exp(a):
     """exp through the C library, element by element (sklearn's perplexity search calls libm's exp)."""
     return np.frompyfunc(math.exp, 1, 1)(a).astype(np.float64)
+
+
+# ---- the coincidence edges (tests/golden/g18c_tsne_edges.npz): case names and the bounds both test modules hold
+EDGE_NAMES = ["dup", "d1e-7", "d9e-7", "d2e-6", "pca", "eq0", "eqc"]
+N2_P = (np.int32([0, 1, 2]), np.int32([1, 0]), np.float32([0.5, 0.5]))  # the only symmetric P of two points
+
+
+def check_kl_grad(kl, g, kl_ref, g_ref, all_equal):
+    """the project's bounds: 5e-5 of max |grad|, 1e-5 relative KL.  All points equal: the gradient is exactly 0 and the KL
+    only not NaN (sklearn's own value there is finite at N = 2 and 300 and -inf at N = 2 000)."""
+    if all_equal:
+        assert not np.any(g_ref) and not np.any(g) and not np.isnan(kl)
+        return
+    assert np.abs(g - g_ref).max() <= 5e-5 * np.abs(g_ref).max(), (np.abs(g - g_ref).max(), np.abs(g_ref).max())
+    assert abs(kl - kl_ref) <= 1e-5 * abs(kl_ref), (kl, kl_ref)
+
+
+def check_n2_far(kl, g, Y):
+    """two distinct points: P = Q = 1/2 whatever the distance, so KL and gradient are 0 and what any fp32 evaluation
+    returns is the rounding of two cancelling forces of size F = 4 p q |y_0 - y_1| (sklearn's record: 2.2e-8 F).  A bound
+    relative to max |grad| is a bound relative to noise here; held instead to 2^-22 F (the forces are sums of two
+    products rounded to 2^-24 each), and |KL| to 2^-22 (sum p = 1, log of a ratio within 2^-23 of 1)."""
+    d = Y[0].astype(np.float64) - Y[1]
+    F = 4 * 0.5 / (1.0 + d @ d) * np.abs(d).max()
+    assert np.abs(g).max() <= 2.0 ** -22 * F, (np.abs(g).max(), F)
+    assert abs(kl) <= 2.0 ** -22, kl

@@ -146,3 +146,76 @@ def test_fixture_records():
     assert abs(float(Z["default.eth.kl"]) - 1.4434) < 2e-3
     for name in ("y50", "y400", "yrand"):
         assert Z[f"emb.mind.{name}"] > 1e-6
+
+
+# ------------------------------------------------------------ coincident and nearly coincident embedding points (g18c)
+ZE = G.load("g18c_tsne_edges.npz")
+@pytest.fixture(scope="module")
+def edge_csr():
+    X = ZE["X"]
+    idx, d = T.knn(X, T.n_neighbors(X.shape[0]))
+    indptr, indices, P, _ = T.symmetrize(idx, T.binary_search_perplexity(d, 30.0, exp=T.libm_exp))
+    return indptr, indices, P
+
+
+def test_edge_fixture_records(edge_csr):
+    """the recorded cases are what their names say, and the restated P is the P sklearn's records were computed on"""
+    indptr, indices, P = edge_csr
+    assert P.size == int(ZE["P_nnz"]) and crc(P) == int(ZE["P_crc"])
+    embs = T.edge_embeddings(ZE["X"].shape[0], int(ZE["seed"]) + 1)
+    for name in T.EDGE_NAMES:
+        assert np.array_equal(embs[name], ZE[f"emb.{name}"]), name
+    for name, lo_min, hi_max in (("d1e-7", 0.0, 1e-6), ("d9e-7", 0.0, 1e-6), ("d2e-6", 1e-6, 3e-6)):
+        hi, lo = T.pair_offsets(embs[name])
+        assert np.all(lo > lo_min) and np.all(hi <= hi_max), name
+    hi, _ = T.pair_offsets(embs["dup"])
+    assert not np.any(hi)
+    y = embs["pca"].astype(np.float64)
+    near = np.all(np.abs(y[:, None] - y[None]) <= 1e-6, axis=-1).sum() - len(y)
+    assert near > 0 and len(np.unique(embs["pca"], axis=0)) == len(y)  # pairs within 1e-6, none equal
+    assert ZE["zero.n_iter"] == 99 and not np.any(ZE["zero.embedding"])
+    m = G.manifest()["g18c_tsne_edges"]
+    assert m["sklearn"] == "1.7.2" and float(m["kl"]["d9e-7"]) == float(ZE["kl.d9e-7"])
+
+
+@pytest.mark.parametrize("name", T.EDGE_NAMES)
+def test_np_edge_gradient_matches_sklearn_records(edge_csr, name):
+    """sklearn as compiled leaves out exactly coincident points only (d1e-7 and d9e-7 have the KL of d2e-6, not of dup)
+    and clamps Z to DBL_EPSILON (eq0, eqc: gradient exactly 0)"""
+    indptr, indices, P = edge_csr
+    kl, g = T.kl_grad(ZE[f"emb.{name}"], indptr, indices, P.astype(np.float32))
+    T.check_kl_grad(kl, g, float(ZE[f"kl.{name}"]), ZE[f"grad.{name}"], name.startswith("eq"))
+
+
+def test_np_edge_gradient_two_points_match_sklearn_records():
+    kl, g = T.kl_grad(ZE["n2.emb.eq"], *T.N2_P)
+    T.check_kl_grad(kl, g, float(ZE["n2.kl.eq"]), ZE["n2.grad.eq"], True)
+    Y = ZE["n2.emb.far"]
+    T.check_n2_far(float(ZE["n2.kl.far"]), ZE["n2.grad.far"], Y)  # sklearn's own record
+    T.check_n2_far(*T.kl_grad(Y, *T.N2_P), Y)
+
+
+def test_np_edge_gradient_matches_live_sklearn():
+    """the same cases at another size and seed against the installed sklearn's theta = 0 gradient"""
+    _t_sne = pytest.importorskip("sklearn.manifold._t_sne")
+    from scipy.sparse import csr_matrix
+    from sklearn.neighbors import NearestNeighbors
+    n = 120
+    X = np.random.default_rng(7).standard_normal((n, 3)).astype(np.float32)
+    g = NearestNeighbors(n_neighbors=T.n_neighbors(n, 10.0)).fit(X).kneighbors_graph(mode="distance")
+    g.data **= 2
+    P = _t_sne._joint_probabilities_nn(g, 10.0, 0)
+    kw = dict(angle=0.0, skip_num_points=0, verbose=0, num_threads=1, compute_error=True)
+    for name, Y in T.edge_embeddings(n, 8).items():
+        err, grad = _t_sne._kl_divergence_bh(Y.ravel().copy(), P, 1, n, 2, **kw)
+        kl, gn = T.kl_grad(Y, P.indptr, P.indices, P.data.astype(np.float32))
+        T.check_kl_grad(kl, gn, float(err), grad.reshape(n, 2).astype(np.float32), name.startswith("eq"))
+    P2 = csr_matrix(np.array([[0.0, 0.5], [0.5, 0.0]]))
+    for key, all_equal in (("eq", True), ("far", False)):
+        Y = ZE[f"n2.emb.{key}"]
+        err, grad = _t_sne._kl_divergence_bh(Y.ravel().copy(), P2, 1, 2, 2, **kw)
+        grad = grad.reshape(2, 2).astype(np.float32)
+        if all_equal:
+            T.check_kl_grad(*T.kl_grad(Y, *T.N2_P), float(err), grad, True)
+        else:
+            T.check_n2_far(float(err), grad, Y)

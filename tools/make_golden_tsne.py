@@ -3,6 +3,7 @@
 script/plot_coeff_tsne.py, on the CPU.
 
     python tools/make_golden_tsne.py --ref /path/to/reference --out tests/golden [--threads 16] [--skip-default]
+    python tools/make_golden_tsne.py --edges --out tests/golden      (numpy and sklearn only, no reference tree)
 
 C_obs is computed with the reference's own code: TrajNorm(ori=True, rot=True, sca=False) on the train split (not
 augmented), rank-6 SVD of the normalised observed part, C_obs = (U[:, :6].T @ A).T.  Two files, each under 1 MiB:
@@ -23,15 +24,23 @@ g18_tsne.npz -- a fixed 2 000-row subset of eth train's pairwise distinct rows (
 g18b_tsne_eth.npz -- full eth train: `X` (29 809 x 6 C_obs), 1 024 seeded sample rows `rows` with the same per-row
   crc32 / tie fields as the subset, and full values for the first 128 of them (`s_knn_i`, `s_knn_d`, `s_pcond`).
 
+g18c_tsne_edges.npz (--edges) -- what sklearn's theta = 0 gradient does where embedding points coincide or nearly do, on
+  seeded inputs: `X` (300 x 6, unit normal, seed `seed`), whose P (perplexity 30, k = 91) the restatement
+  tests/_tsne_np.py reproduces bit for bit (asserted here; `P_crc`, `P_nnz`), and the embeddings of
+  tests/_tsne_np.edge_embeddings(300, seed + 1) (`emb.<name>`): for each, `_kl_divergence_bh(angle=0)`'s error and
+  gradient (`kl.<name>`, `grad.<name>` fp32).  `n2.*`: N = 2 with P = [[0, .5], [.5, 0]], the two points distinct
+  (`n2.emb.far`) and equal (`n2.emb.eq`).  `zero.embedding`, `zero.n_iter`, `zero.kl`: TSNE(angle=0,
+  init=zeros).fit on X.  MANIFEST.json gets the entry `g18c_tsne_edges` (sklearn / numpy versions, the KLs).
+
 Only data is written; nothing of the reference is copied."""
 import argparse
+import json
 import os
 import sys
 import time
 import zlib
 
 import numpy as np
-import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -44,6 +53,7 @@ SUB_SEED, SUB_N = 18, 2000
 
 
 def c_obs_ref(TrajNorm, scene):
+    import torch
     obs, _, _ = G.dataset(scene, "train")
     obs = torch.from_numpy(obs)
     n, t, d = obs.shape
@@ -77,13 +87,75 @@ def knn_rows(X, rows):
     return g, d32, idx, pc, f
 
 
+EDGE_SEED, EDGE_N = 180, 300
+
+
+def edges(out_dir, threads):
+    """g18c: sklearn's compiled behaviour at coincident and nearly coincident embedding points"""
+    import sklearn
+    from scipy.sparse import csr_matrix
+    from sklearn.manifold import TSNE
+    from sklearn.manifold._t_sne import _joint_probabilities_nn, _kl_divergence_bh
+    from sklearn.neighbors import NearestNeighbors
+    from tests import _tsne_np as T
+    n = EDGE_N
+    X = np.random.default_rng(EDGE_SEED).standard_normal((n, 6)).astype(np.float32)
+    k = T.n_neighbors(n)
+    g = NearestNeighbors(n_neighbors=k).fit(X).kneighbors_graph(mode="distance")
+    g.data **= 2
+    P = _joint_probabilities_nn(g, 30.0, 0)
+    idx, d32 = T.knn(X, k)
+    ip, ix, Pn, _ = T.symmetrize(idx, T.binary_search_perplexity(d32, 30.0, exp=T.libm_exp))
+    assert np.array_equal(ip, P.indptr) and np.array_equal(ix, P.indices) and np.array_equal(Pn, P.data)
+    out = {"seed": np.int64(EDGE_SEED), "X": X, "P_crc": np.uint32(crc(P.data)), "P_nnz": np.int64(P.nnz)}
+    kw = dict(angle=0.0, skip_num_points=0, verbose=0, num_threads=threads)
+    embs = T.edge_embeddings(n, EDGE_SEED + 1)
+    for name in ("dup", "d1e-7", "d9e-7", "d2e-6"):  # what the cases are meant to be
+        hi, lo = T.pair_offsets(embs[name])
+        want = {"dup": (0.0, 0.0), "d2e-6": (1e-6, 3e-6)}.get(name, (0.0, 1e-6))
+        assert np.all(lo >= want[0]) and np.all(hi <= want[1]) and (name == "dup" or np.all(lo > 0.0)), name
+    man = {"sklearn": sklearn.__version__, "numpy": np.__version__, "N": n, "kl": {}}
+    for name, Y in embs.items():
+        err, grad = _kl_divergence_bh(Y.ravel().copy(), P, 1, n, 2, compute_error=True, **kw)
+        out[f"emb.{name}"], out[f"kl.{name}"] = Y, np.float64(err)
+        out[f"grad.{name}"] = grad.reshape(n, 2).astype(np.float32)
+        man["kl"][name] = repr(float(err))
+        print(f"{name}: KL {err!r} max |grad| {np.abs(grad).max():.6g}", flush=True)
+    P2 = csr_matrix(np.array([[0.0, 0.5], [0.5, 0.0]]))
+    for name, Y in (("far", np.float32([[0.25, -0.5], [-1.0, 0.75]])), ("eq", np.float32([[0.3, -0.7], [0.3, -0.7]]))):
+        err, grad = _kl_divergence_bh(Y.ravel().copy(), P2, 1, 2, 2, compute_error=True, **kw)
+        out[f"n2.emb.{name}"], out[f"n2.kl.{name}"] = Y, np.float64(err)
+        out[f"n2.grad.{name}"] = grad.reshape(2, 2).astype(np.float32)
+        man["kl"]["n2." + name] = repr(float(err))
+        print(f"n2.{name}: KL {err!r} grad {grad}", flush=True)
+    ts = TSNE(n_components=2, random_state=42, angle=0.0, init=np.zeros((n, 2), np.float32))
+    out["zero.embedding"] = ts.fit_transform(X).astype(np.float32)
+    out["zero.n_iter"], out["zero.kl"] = np.int64(ts.n_iter_), np.float64(ts.kl_divergence_)
+    print(f"init=zeros: n_iter {ts.n_iter_} KL {ts.kl_divergence_!r} max |embedding| {np.abs(ts.embedding_).max()}")
+    path = os.path.join(out_dir, "g18c_tsne_edges.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path))
+    mpath = os.path.join(out_dir, "MANIFEST.json")
+    with open(mpath) as f:
+        m = json.load(f)
+    m["g18c_tsne_edges"] = man
+    with open(mpath, "w") as f:
+        json.dump(m, f, indent=1, sort_keys=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", required=True)
+    ap.add_argument("--ref")
+    ap.add_argument("--edges", action="store_true", help="write g18c_tsne_edges.npz only (numpy and sklearn, no --ref)")
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--skip-default", action="store_true", help="leave out the five default-TSNE runs (about 6 min)")
     args = ap.parse_args()
+    if args.edges:
+        return edges(args.out, args.threads)
+    if not args.ref:
+        ap.error("--ref is required without --edges")
+    import torch
     torch.set_num_threads(args.threads)
     sys.path.insert(0, os.path.abspath(args.ref))
     from EigenTrajectory.normalizer import TrajNorm
