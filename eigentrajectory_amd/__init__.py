@@ -11,5 +11,6 @@ from .descriptor import ETDescriptor
 from .anchor import ETAnchor
 from .kmeans import BatchKMeans
 from .stgcnn import SocialSTGCNN
+from .sgcn import SGCN
 
-__all__ = ["EigenTrajectory", "TrajNorm", "ETDescriptor", "ETAnchor", "BatchKMeans", "SocialSTGCNN"]
+__all__ = ["EigenTrajectory", "TrajNorm", "ETDescriptor", "ETAnchor", "BatchKMeans", "SocialSTGCNN", "SGCN"]

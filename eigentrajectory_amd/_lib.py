@@ -36,6 +36,7 @@ SYMBOLS = [
     "et_tsne_kl_grad", "et_tsne_update", "et_tsne_optimize_workspace_bytes", "et_tsne_optimize",
     "et_tsne_pca_init_workspace_bytes", "et_tsne_pca_init",
     "et_stgcnn_workspace_bytes", "et_stgcnn_forward_scenes", "et_stgcnn_forward_graph",
+    "et_sgcn_workspace_bytes", "et_sgcn_forward_scenes", "et_sgcn_forward_graph",
     "et_fit_gram_workspace_bytes", "et_fit_gram", "et_eigh_topk", "et_eigh_topk_batch",
     "et_fit_descriptor_workspace_bytes", "et_fit_descriptor",
     "et_euc_sim", "et_euc_sim_batch", "et_kmeans_partials_len", "et_kmeans_workspace_bytes", "et_kmeans_scan", "et_kmeans_begin",
@@ -84,6 +85,36 @@ class STGCNNParams(C.Structure):
                 ("out_w", C.c_void_p), ("out_b", C.c_void_p)]
 
 
+SGCN_MAX_LAYERS = 8  # ET_SGCN_MAX_LAYERS
+SGCN_MAX_N = 512     # ET_SGCN_MAX_N
+
+
+class SGCNAttention(C.Structure):
+    """Mirror of ``et_sgcn_attention`` (field order: include/eigentraj.h)."""
+    _fields_ = [(name, C.c_void_p) for name in ("emb_w", "emb_b", "q_w", "q_b", "k_w", "k_b")]
+
+
+class SGCNAsym(C.Structure):
+    """Mirror of ``et_sgcn_asym``."""
+    _fields_ = [(name, C.c_void_p) for name in ("conv1_w", "conv2_w", "conv2_b", "act")]
+
+
+class SGCNGcn(C.Structure):
+    """Mirror of ``et_sgcn_gcn``."""
+    _fields_ = [(name, C.c_void_p) for name in ("w", "act")]
+
+
+class SGCNParams(C.Structure):
+    """Mirror of ``et_sgcn_params``."""
+    _fields_ = [("n_asym", C.c_int), ("embedding_dims", C.c_int), ("n_gcn_layers", C.c_int), ("obs_len", C.c_int),
+                ("pred_len", C.c_int), ("n_tcn", C.c_int), ("in_dims", C.c_int), ("out_dims", C.c_int),
+                ("num_heads", C.c_int), ("dropout", C.c_float),
+                ("att", SGCNAttention * 2), ("fus_w", C.c_void_p), ("fus_b", C.c_void_p), ("fus_a", C.c_void_p),
+                ("asym_s", SGCNAsym * SGCN_MAX_LAYERS), ("asym_t", SGCNAsym * SGCN_MAX_LAYERS), ("gcn", SGCNGcn * 4),
+                ("fusion_w", C.c_void_p), ("tcn_w", C.c_void_p * SGCN_MAX_LAYERS), ("tcn_b", C.c_void_p * SGCN_MAX_LAYERS),
+                ("tcn_a", C.c_void_p * SGCN_MAX_LAYERS), ("out_w", C.c_void_p), ("out_b", C.c_void_p)]
+
+
 STATE_BYTES = C.sizeof(KMeansState)
 _lib = None
 
@@ -112,7 +143,7 @@ def lib():
                      "et_kmeans_reforder_batch_workspace_bytes", "et_kmeans_reforder_sharded_workspace_bytes",
                      "et_curve_fit_batch_workspace_bytes", "et_tsne_affinities_workspace_bytes",
                      "et_tsne_kl_grad_workspace_bytes", "et_tsne_optimize_workspace_bytes",
-                     "et_tsne_pca_init_workspace_bytes", "et_stgcnn_workspace_bytes"):
+                     "et_tsne_pca_init_workspace_bytes", "et_stgcnn_workspace_bytes", "et_sgcn_workspace_bytes"):
             getattr(l, name).restype = C.c_size_t
         l.et_kmeans_reforder_shard_block.restype = C.c_int64
         _lib = l

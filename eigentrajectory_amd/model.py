@@ -265,22 +265,30 @@ class EigenTrajectory(nn.Module):
 
     @torch.no_grad()
     def evaluate_split(self, obs_traj, pred_traj, seq_start_end, metrics=("ADE", "FDE")):
-        r"""A whole test split in three launches: the projection of every row, the bridge + predictor + post-hook of every
-        scene (``et_stgcnn_forward_scenes``), the reconstruction + metrics of every scene -- what the reference's test loop
+        r"""A whole test split in a fixed number of launches: the projection of every row, the bridge + predictor +
+        post-hook of every scene (``et_stgcnn_forward_scenes``: one launch; ``et_sgcn_forward_scenes``: 6 + the number of
+        asymmetric convolution layers), the reconstruction + metrics of every scene -- what the reference's test loop
         (utils/trainer.py:173-195) computes with one :meth:`evaluate` per scene.
 
         ``obs_traj`` (N, t_obs, 2), ``pred_traj`` (N, t_pred, 2): the split's rows, scene after scene; ``seq_start_end``
         (M, 2): each scene's (start, end) rows, consecutive and covering all N.  ``metrics``: any of ADE, FDE, TCC, COL.
         Returns a dict of (N,) tensors.  Only for a :class:`~eigentrajectory_amd.stgcnn.SocialSTGCNN` predictor under the
-        ``stgcnn`` hooks, in eval mode; any other predictor raises (use :meth:`evaluate` scene by scene)."""
+        ``stgcnn`` hooks or a :class:`~eigentrajectory_amd.sgcn.SGCN` predictor under the ``sgcn`` hooks, in eval mode; any
+        other predictor raises (use :meth:`evaluate` scene by scene)."""
         from .bridges import BRIDGES
+        from .sgcn import SGCN
         from .stgcnn import SocialSTGCNN
-        pre, fwd, post = BRIDGES["stgcnn"]
         hooks = self.hook_func
-        if not (isinstance(self.baseline_model, SocialSTGCNN) and hooks.model_forward_pre_hook is pre
-                and hooks.model_forward is fwd and hooks.model_forward_post_hook is post):
+        forward_scenes = None
+        for cls, name, fn in ((SocialSTGCNN, "stgcnn", ops.stgcnn_forward_scenes), (SGCN, "sgcn", ops.sgcn_forward_scenes)):
+            pre, fwd, post = BRIDGES[name]
+            if (isinstance(self.baseline_model, cls) and hooks.model_forward_pre_hook is pre
+                    and hooks.model_forward is fwd and hooks.model_forward_post_hook is post):
+                forward_scenes = fn
+        if forward_scenes is None:
             raise NotImplementedError("evaluate_split: the whole-split path is built for a SocialSTGCNN predictor under the "
-                                      "'stgcnn' hooks only; call evaluate() scene by scene for other predictors")
+                                      "'stgcnn' hooks and an SGCN predictor under the 'sgcn' hooks only; call evaluate() "
+                                      "scene by scene for other predictors")
         if self.baseline_model.training:
             raise RuntimeError("evaluate_split: the predictor is in training mode; call .eval() first")
         sse = torch.as_tensor(seq_start_end).detach().cpu().long().reshape(-1, 2)
@@ -293,7 +301,7 @@ class EigenTrajectory(nn.Module):
         A_m, A_s = self.ET_m_anchor.C_anchor.detach(), self.ET_s_anchor.C_anchor.detach()
         C_obs, _, nrm, _ = ops.norm_project(obs_traj, None, U_obs_m, None, U_obs_s, None, ops.MODE_SPLIT, sd,
                                             want_flag=False)
-        Cc = ops.stgcnn_forward_scenes(self.baseline_model, C_obs, nrm, scene_sizes=sizes)
+        Cc = forward_scenes(self.baseline_model, C_obs, nrm, scene_sizes=sizes)
         if n == 0:
             return {key: torch.empty((0,), device=Cc.device) for key in metrics}
         return ops.anchor_reconstruct_metrics_scenes(Cc, pred_traj, A_m, A_s, U_pred_m, U_pred_s, ops.MODE_SPLIT, sd,

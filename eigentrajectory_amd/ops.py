@@ -334,6 +334,84 @@ def stgcnn_forward_scenes(model, C_obs, nrm, scene_sizes=None):
                                              L.stream(dev)), "et_stgcnn_forward_scenes")
     return out
 
+
+# ------------------------------------------------------------------------------ SGCN predictor (inference)
+def _sgcn_ws(params, n, sum_n2, n_scenes, dev):
+    nbytes = L.lib().et_sgcn_workspace_bytes(C.byref(params), L.i64(n), L.i64(sum_n2), int(n_scenes))
+    return (torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None), nbytes
+
+
+def _sgcn_logits(want, T, n, sum_n2, dev):
+    if not want:
+        return None, None
+    return torch.empty((4 * T * sum_n2,), device=dev), torch.empty((n * 4 * T * T,), device=dev)
+
+
+def sgcn_forward_graph(model, v, identity, want_logits=False):
+    """``model`` (:class:`eigentrajectory_amd.sgcn.SGCN`, eval mode) on one scene as the sgcn bridge hands it over: v
+    (1, T, N, 1), identity = [spatial (1 or T, N, N), temporal (N, 1, 1) or (N, T, T)] -> (pred_len, N, out_dims); with
+    ``want_logits`` also the values that enter the interaction mask's sigmoids, logit_s (T, 4, N, N) and logit_t
+    (N, 4, T, T).  The inputs must be contiguous float32 tensors on the model's device (they are read in place)."""
+    model._check_mode()
+    params, dev = model.et_params()
+    T, k, S = params.obs_len, params.pred_len, params.out_dims
+    id_s, id_t = identity
+    n = v.shape[2] if v.dim() == 4 else -1
+    if (tuple(v.shape) != (1, T, n, 1) or tuple(id_s.shape) not in ((1, n, n), (T, n, n))
+            or tuple(id_t.shape) not in ((n, 1, 1), (n, T, T))):
+        raise ValueError(f"sgcn_forward_graph: v {tuple(v.shape)} / identity {tuple(id_s.shape)}, {tuple(id_t.shape)} are not "
+                         f"(1,{T},N,1) / (1 or {T},N,N), (N,1,1) or (N,{T},{T})")
+    for name, t in (("v", v), ("identity[0]", id_s), ("identity[1]", id_t)):
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"sgcn_forward_graph: {name} must be a contiguous float32 tensor on {dev} (got {t.dtype}, "
+                             f"{t.device}, contiguous={t.is_contiguous()})")
+    if n > L.SGCN_MAX_N:
+        raise ValueError(f"sgcn_forward_graph: N = {n} exceeds the {L.SGCN_MAX_N} pedestrians a scene may have")
+    out = torch.empty((k, n, S), device=dev)
+    ls, lt = _sgcn_logits(want_logits, T, n, n * n, dev)
+    ws, nbytes = _sgcn_ws(params, n, n * n, 1, dev)
+    L.check(L.lib().et_sgcn_forward_graph(C.byref(params), L.ptr(v.detach()), L.ptr(id_s.detach()), int(id_s.shape[0]),
+                                          L.ptr(id_t.detach()), int(id_t.shape[1]), L.i64(n), L.ptr(out), L.ptr(ls),
+                                          L.ptr(lt), L.ptr(ws), C.c_size_t(nbytes), L.stream(dev)), "et_sgcn_forward_graph")
+    if want_logits:
+        return out, ls.view(T, 4, n, n), lt.view(n, 4, T, T)
+    return out
+
+
+def sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_logits=False):
+    """The sgcn bridge + ``model`` (eval mode) + the post-hook for every scene of a split in a fixed number of launches:
+    C_obs (k, N) and nrm (4, N) of :func:`norm_project` (rows 0-1: the last observed positions, centred here per scene),
+    ``scene_sizes`` pedestrians per scene in row order (None = one scene; an empty list takes N = 0) -> C_pred_refine
+    (k, N, S).  With ``want_logits`` also the packed logits: scene s's (T, 4, n, n) block at 4 T (n_0^2 + ... + n_{s-1}^2)
+    of the first and its (n, 4, T, T) block at 4 T T (n_0 + ... + n_{s-1}) of the second."""
+    model._check_mode()
+    params, dev = model.et_params()
+    C_obs, nrm = _dev_args(dev, C_obs, nrm)
+    k, n = C_obs.shape
+    T = params.obs_len
+    if k != params.pred_len or nrm.dim() != 2 or nrm.shape[0] < 2 or nrm.shape[1] != n:
+        raise ValueError(f"sgcn_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
+                         f"k = {params.pred_len}")
+    if scene_sizes is not None:
+        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
+        if not sizes and n:
+            raise ValueError(f"sgcn_forward_scenes: no scenes for {n} rows")
+        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
+    else:
+        sizes, off = [n], None
+    if max(sizes, default=0) > L.SGCN_MAX_N:
+        raise ValueError(f"sgcn_forward_scenes: a scene of {max(sizes)} pedestrians exceeds the {L.SGCN_MAX_N} a scene may have")
+    sum_n2, max_n = sum(s * s for s in sizes), max(sizes, default=0)
+    out = torch.empty((k, n, params.out_dims), device=dev)
+    ls, lt = _sgcn_logits(want_logits, T, n, sum_n2, dev)
+    ws, nbytes = _sgcn_ws(params, n, sum_n2, len(sizes), dev)
+    L.check(L.lib().et_sgcn_forward_scenes(C.byref(params), L.ptr(C_obs), L.ptr(nrm), L.i64(n), L.ptr(off),
+                                           0 if off is None else len(sizes), L.i64(sum_n2), L.i64(max_n), L.ptr(out),
+                                           L.ptr(ls), L.ptr(lt), L.ptr(ws), C.c_size_t(nbytes), L.stream(dev)),
+            "et_sgcn_forward_scenes")
+    return (out, ls, lt) if want_logits else out
+
+
 # ----------------------------------------------------------------------- curve fitting
 def curve_fit_batch(trajs, bases, steps=100000, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, want_cp=False, want_loss=False):
     """CurveModel/curve_fitting.py for a batch of fits: fit f fits basis ``bases[f]`` (T_f, ncp_f) to every trajectory of

@@ -1,0 +1,175 @@
+"""SGCN, the predictor of ET-SGCN (baseline/sgcn/model.py: TrajectoryModel), inference on HIP kernels.
+
+Same constructor signature and the same sub-module / parameter names as the reference
+(``sparse_weighted_adjacency_matrices.{spatial,temporal}_attention.{embedding,query,key}``, ``….spa_fusion.conv.{0,1}``,
+``….interaction_mask.{spatial,temporal}_asymmetric_convolutions.{j}.{conv1,conv2,activation}``,
+``stsgcn.{spatial_temporal,temporal_spatial}_sparse_gcn.{0,1}.{embedding,activation}``, ``fusion_``, ``tcns.{j}.{0,1}``,
+``output``), so a reference ET-SGCN checkpoint's ``baseline_model.*`` keys load unchanged, and the module plugs into
+:class:`eigentrajectory_amd.EigenTrajectory` through the existing ``sgcn`` bridge::
+
+    model = EigenTrajectory(SGCN(number_asymmetric_conv_layer=7, embedding_dims=64, number_gcn_layers=1, dropout=0,
+                                 obs_len=hp.k + 2, pred_len=hp.k, n_tcn=5, in_dims=1, out_dims=hp.num_samples),
+                            get_hook_func("sgcn"), hp).eval()
+
+``forward(graph, identity)`` in eval mode is ``et_sgcn_forward_graph`` (csrc/et_sgcn.hip): graph (1, T, N, 1), identity a
+list of the spatial (1 or T, N, N) and the temporal (N, 1, 1) or (N, T, T) one -> (pred_len, N, out_dims).  The identities
+are read as given: the bridge's temporal one is all ones, not ``eye(T)``.  The weights are read in place from this module's
+tensors (a ``load_state_dict``, a ``.to()`` or an in-place edit is seen by the next call, and by a captured graph's next
+replay).  Training (the backward pass, the reference's always-active ``F.dropout``) is not implemented natively: a forward
+in training mode, or with ``dropout != 0``, raises.  A whole split runs in a fixed number of launches through
+:meth:`EigenTrajectory.evaluate_split` / :func:`eigentrajectory_amd.ops.sgcn_forward_scenes`.
+Supported family: ``in_dims = 1``, ``num_heads = 4``, ``embedding_dims = 64``, ``1 <= number_asymmetric_conv_layer, n_tcn <=
+8``, ``pred_len <= 32``, ``obs_len = pred_len + 2``, ``1 <= out_dims <= 64``, ``N <= 512``; other shapes construct, but their
+forward raises.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+import torch.nn as nn
+
+from . import _lib as L
+
+
+class _AsymmetricConvolution(nn.Module):
+    """PReLU(conv(1x3) + conv(3x1)) + shortcut; conv1 (3x1) carries no bias."""
+
+    def __init__(self, in_cha, out_cha):
+        super().__init__()
+        self.conv1 = nn.Conv2d(in_cha, out_cha, kernel_size=(3, 1), padding=(1, 0), bias=False)
+        self.conv2 = nn.Conv2d(in_cha, out_cha, kernel_size=(1, 3), padding=(0, 1))
+        self.activation = nn.PReLU()
+
+
+class _InteractionMask(nn.Module):
+    def __init__(self, number_asymmetric_conv_layer=7, spatial_channels=4, temporal_channels=4):
+        super().__init__()
+        self.number_asymmetric_conv_layer = number_asymmetric_conv_layer
+        self.spatial_asymmetric_convolutions = nn.ModuleList()
+        self.temporal_asymmetric_convolutions = nn.ModuleList()
+        for _ in range(number_asymmetric_conv_layer):
+            self.spatial_asymmetric_convolutions.append(_AsymmetricConvolution(spatial_channels, spatial_channels))
+            self.temporal_asymmetric_convolutions.append(_AsymmetricConvolution(temporal_channels, temporal_channels))
+
+
+class _SelfAttention(nn.Module):
+    def __init__(self, in_dims=2, d_model=64, num_heads=4):
+        super().__init__()
+        self.embedding = nn.Linear(in_dims, d_model)
+        self.query = nn.Linear(d_model, d_model)
+        self.key = nn.Linear(d_model, d_model)
+        self.scaled_factor = math.sqrt(d_model)  # a plain attribute, as in the reference: not in the state dict
+        self.num_heads = num_heads
+
+
+class _SpatialTemporalFusion(nn.Module):
+    def __init__(self, obs_len=8):
+        super().__init__()
+        self.conv = nn.Sequential(nn.Conv2d(obs_len, obs_len, 1), nn.PReLU())
+
+
+class _SparseWeightedAdjacency(nn.Module):
+    def __init__(self, spa_in_dims=2, tem_in_dims=3, embedding_dims=64, obs_len=8, dropout=0,
+                 number_asymmetric_conv_layer=7):
+        super().__init__()
+        self.spatial_attention = _SelfAttention(spa_in_dims, embedding_dims)
+        self.temporal_attention = _SelfAttention(tem_in_dims, embedding_dims)
+        self.spa_fusion = _SpatialTemporalFusion(obs_len=obs_len)
+        self.interaction_mask = _InteractionMask(number_asymmetric_conv_layer=number_asymmetric_conv_layer)
+        self.dropout = dropout
+
+
+class _GraphConvolution(nn.Module):
+    def __init__(self, in_dims=2, embedding_dims=16, dropout=0):
+        super().__init__()
+        self.embedding = nn.Linear(in_dims, embedding_dims, bias=False)
+        self.activation = nn.PReLU()
+        self.dropout = dropout
+
+
+class _SparseGraphConvolution(nn.Module):
+    def __init__(self, in_dims=16, embedding_dims=16, dropout=0):
+        super().__init__()
+        self.dropout = dropout
+        self.spatial_temporal_sparse_gcn = nn.ModuleList()
+        self.temporal_spatial_sparse_gcn = nn.ModuleList()
+        self.spatial_temporal_sparse_gcn.append(_GraphConvolution(in_dims, embedding_dims))
+        self.spatial_temporal_sparse_gcn.append(_GraphConvolution(embedding_dims, embedding_dims))
+        self.temporal_spatial_sparse_gcn.append(_GraphConvolution(in_dims, embedding_dims))
+        self.temporal_spatial_sparse_gcn.append(_GraphConvolution(embedding_dims, embedding_dims))
+
+
+def _p(t):
+    return t.data_ptr()
+
+
+class SGCN(nn.Module):
+    r"""baseline/sgcn/model.py's ``TrajectoryModel`` (eval-mode inference on the GPU).  ``forward(graph, identity)``: graph
+    (1, T, N, 1) and the two identities as the sgcn bridge's pre-hook builds them -> (pred_len, N, out_dims)."""
+
+    def __init__(self, number_asymmetric_conv_layer=7, embedding_dims=64, number_gcn_layers=1, dropout=0, obs_len=8,
+                 pred_len=12, n_tcn=5, in_dims=2, out_dims=5, num_heads=4):
+        super().__init__()
+        self.number_asymmetric_conv_layer = number_asymmetric_conv_layer
+        self.embedding_dims, self.number_gcn_layers, self.n_tcn, self.dropout = embedding_dims, number_gcn_layers, n_tcn, dropout
+        self.obs_len, self.pred_len, self.in_dims, self.out_dims, self.num_heads = obs_len, pred_len, in_dims, out_dims, num_heads
+        # (the reference leaves the adjacency's embedding_dims and the attention's num_heads at their defaults, 64 and 4)
+        self.sparse_weighted_adjacency_matrices = _SparseWeightedAdjacency(
+            number_asymmetric_conv_layer=number_asymmetric_conv_layer, obs_len=obs_len, spa_in_dims=in_dims,
+            tem_in_dims=in_dims)
+        self.stsgcn = _SparseGraphConvolution(in_dims=in_dims, embedding_dims=embedding_dims // num_heads, dropout=dropout)
+        self.fusion_ = nn.Conv2d(num_heads, num_heads, kernel_size=1, bias=False)
+        self.tcns = nn.ModuleList()
+        self.tcns.append(nn.Sequential(nn.Conv2d(obs_len, pred_len, 3, padding=1), nn.PReLU()))
+        for _ in range(1, n_tcn):
+            self.tcns.append(nn.Sequential(nn.Conv2d(pred_len, pred_len, 3, padding=1), nn.PReLU()))
+        self.output = nn.Linear(embedding_dims // num_heads, out_dims)
+
+    def et_params(self):
+        """-> (et_sgcn_params, device): this module's tensors as the kernels read them (include/eigentraj.h)."""
+        p = L.SGCNParams()
+        p.n_asym, p.embedding_dims, p.n_gcn_layers = self.number_asymmetric_conv_layer, self.embedding_dims, self.number_gcn_layers
+        p.obs_len, p.pred_len, p.n_tcn, p.in_dims = self.obs_len, self.pred_len, self.n_tcn, self.in_dims
+        p.out_dims, p.num_heads, p.dropout = self.out_dims, self.num_heads, float(self.dropout)
+        tensors = list(self.parameters())
+        dev = tensors[0].device
+        if dev.type != "cuda" or any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
+            raise L.ETLibraryError("SGCN: every parameter must be a contiguous float32 tensor on ONE HIP device "
+                                   "(model.cuda()); there is no CPU path")
+        if (self.number_asymmetric_conv_layer > L.SGCN_MAX_LAYERS or self.n_tcn > L.SGCN_MAX_LAYERS or self.in_dims != 1
+                or self.num_heads != 4 or self.embedding_dims != 64):
+            return p, dev  # the kernels answer ET_ERR_UNSUPPORTED
+        swa = self.sparse_weighted_adjacency_matrices
+        for a, att in enumerate((swa.spatial_attention, swa.temporal_attention)):
+            s = p.att[a]
+            s.emb_w, s.emb_b = _p(att.embedding.weight), _p(att.embedding.bias)
+            s.q_w, s.q_b, s.k_w, s.k_b = _p(att.query.weight), _p(att.query.bias), _p(att.key.weight), _p(att.key.bias)
+        conv, act = swa.spa_fusion.conv[0], swa.spa_fusion.conv[1]
+        p.fus_w, p.fus_b, p.fus_a = _p(conv.weight), _p(conv.bias), _p(act.weight)
+        im = swa.interaction_mask
+        for dst, layers in ((p.asym_s, im.spatial_asymmetric_convolutions), (p.asym_t, im.temporal_asymmetric_convolutions)):
+            for j, m in enumerate(layers):
+                dst[j].conv1_w, dst[j].conv2_w = _p(m.conv1.weight), _p(m.conv2.weight)
+                dst[j].conv2_b, dst[j].act = _p(m.conv2.bias), _p(m.activation.weight)
+        gcns = list(self.stsgcn.spatial_temporal_sparse_gcn) + list(self.stsgcn.temporal_spatial_sparse_gcn)
+        for g, m in enumerate(gcns):
+            p.gcn[g].w, p.gcn[g].act = _p(m.embedding.weight), _p(m.activation.weight)
+        p.fusion_w = _p(self.fusion_.weight)
+        for j, seq in enumerate(self.tcns):
+            p.tcn_w[j], p.tcn_b[j], p.tcn_a[j] = _p(seq[0].weight), _p(seq[0].bias), _p(seq[1].weight)
+        p.out_w, p.out_b = _p(self.output.weight), _p(self.output.bias)
+        return p, dev
+
+    def _check_mode(self):
+        if self.training:
+            raise RuntimeError("SGCN: only inference is native (no dropout, no backward); training-mode forward is not "
+                               "implemented -- call .eval() first")
+        if self.dropout != 0:
+            raise RuntimeError(f"SGCN: dropout = {self.dropout} is not implemented natively (the reference's F.dropout is "
+                               "active even in eval mode); construct with dropout=0")
+
+    def forward(self, graph, identity):
+        self._check_mode()
+        from . import ops
+        return ops.sgcn_forward_graph(self, graph, identity)

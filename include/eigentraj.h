@@ -368,6 +368,73 @@ int et_stgcnn_forward_scenes(const et_stgcnn_params *params, const float *C_obs,
 int et_stgcnn_forward_graph(const et_stgcnn_params *params, const float *v, const float *a, int64_t N, float *out,
                             void *workspace, size_t workspace_bytes, et_stream_t stream);
 
+/* ---- SGCN predictor, inference (baseline/sgcn: bridge.py pre-hook + TrajectoryModel.forward + post-hook) -------------
+ * Eval mode, dropout = 0, fp32.  The parameters are read in place from the module's own tensors through the pointer table
+ * below (fp32, contiguous).  Field <-> state_dict name (SWA = sparse_weighted_adjacency_matrices, j = layer index):
+ *   att[0] / att[1]                  SWA.spatial_attention / SWA.temporal_attention: embedding.weight (64, 1) / .bias,
+ *                                    query.weight (64, 64) / .bias, key.weight (64, 64) / .bias
+ *   fus_w / fus_b / fus_a            SWA.spa_fusion.conv.0.weight (T, T, 1, 1) / .bias (T), conv.1.weight (1)
+ *   asym_s[j] / asym_t[j]            SWA.interaction_mask.{spatial,temporal}_asymmetric_convolutions.{j}: conv1.weight
+ *                                    (4, 4, 3, 1), conv2.weight (4, 4, 1, 3) / .bias (4), activation.weight (1)
+ *   gcn[0..3]                        stsgcn.spatial_temporal_sparse_gcn.{0,1}, stsgcn.temporal_spatial_sparse_gcn.{0,1}:
+ *                                    embedding.weight (16, 1 or 16), activation.weight (1)
+ *   fusion_w                         fusion_.weight (4, 4, 1, 1)
+ *   tcn_w[j] / tcn_b[j] / tcn_a[j]   tcns.{j}.0.weight (k, j ? k : T, 3, 3) / .bias (k), tcns.{j}.1.weight (1)
+ *   out_w / out_b                    output.weight (S, 16) / .bias (S)
+ * with T = obs_len, k = pred_len, S = out_dims.  Supported: in_dims = 1, num_heads = 4, embedding_dims = 64, dropout = 0,
+ * 1 <= number_asymmetric_conv_layer, n_tcn <= ET_SGCN_MAX_LAYERS, 1 <= pred_len <= ET_MAX_K, obs_len = pred_len + 2,
+ * 1 <= out_dims <= 64; anything else: ET_ERR_UNSUPPORTED.  A scene has at most ET_SGCN_MAX_N pedestrians.
+ *
+ *   et_sgcn_forward_graph   one scene as the bridge hands it over: v (1,T,N,1), identity_s (1 or T, N, N) (id_s_t = its
+ *                           first dimension), identity_t (N, 1, 1) or (N, T, T) (id_t_t = 1 or T) -> out (k, N, S).
+ *                           The identities are read as given (the bridge's temporal one is all ones, not eye(T)).
+ *   et_sgcn_forward_scenes  a whole split: C_obs (k,N), nrm (4,N) of et_norm_project (rows 0-1: last observed position);
+ *                           per scene v = [C_obs; nrm[0:2] - their mean over the scene], spatial identity eye(n), temporal
+ *                           identity all ones (what the bridge builds) -> C_pred_refine (k,N,S).  scene_offsets as
+ *                           et_traj_metrics (NULL = one scene of N rows); n_scenes = 0 takes N = 0 only.  sum_n2 = the sum
+ *                           of the scenes' squared sizes (sizes the dense stacks), max_scene_n the largest scene (sizes
+ *                           the grid).  A scene that is larger than ET_SGCN_MAX_N or does not fit the stacks is not
+ *                           computed: its outputs are NaN.
+ * logit_s / logit_t (may be NULL): the values that enter the interaction mask's two sigmoids, per scene (T,4,n,n) and
+ * (n,4,T,T), packed scene after scene (scene s at 4 T sum_{s'<s} n_s'^2 and at 4 T T off[s]).
+ * Layered form: the dense (T,4,n,n) stacks live in the caller's workspace (two of them, ping-pong); 6 +
+ * number_asymmetric_conv_layer launches for any number of scenes, no host synchronisation, no allocation (the calls can be
+ * captured in a graph).  Every sum has a fixed order: results are bit-identical from run to run, and a scene's result does
+ * not depend on the scenes around it. */
+#define ET_SGCN_MAX_LAYERS 8
+#define ET_SGCN_MAX_N 512
+typedef struct et_sgcn_attention {
+    const float *emb_w, *emb_b, *q_w, *q_b, *k_w, *k_b;
+} et_sgcn_attention;
+typedef struct et_sgcn_asym {
+    const float *conv1_w, *conv2_w, *conv2_b, *act;
+} et_sgcn_asym;
+typedef struct et_sgcn_gcn {
+    const float *w, *act;
+} et_sgcn_gcn;
+typedef struct et_sgcn_params {
+    int n_asym, embedding_dims, n_gcn_layers, obs_len, pred_len, n_tcn, in_dims, out_dims, num_heads;
+    float dropout;
+    et_sgcn_attention att[2];
+    const float *fus_w, *fus_b, *fus_a;
+    et_sgcn_asym asym_s[ET_SGCN_MAX_LAYERS];
+    et_sgcn_asym asym_t[ET_SGCN_MAX_LAYERS];
+    et_sgcn_gcn gcn[4];
+    const float *fusion_w;
+    const float *tcn_w[ET_SGCN_MAX_LAYERS];
+    const float *tcn_b[ET_SGCN_MAX_LAYERS];
+    const float *tcn_a[ET_SGCN_MAX_LAYERS];
+    const float *out_w, *out_b;
+} et_sgcn_params;
+size_t et_sgcn_workspace_bytes(const et_sgcn_params *params, int64_t N, int64_t sum_n2, int n_scenes);
+int et_sgcn_forward_scenes(const et_sgcn_params *params, const float *C_obs, const float *nrm, int64_t N,
+                           const int32_t *scene_offsets, int n_scenes, int64_t sum_n2, int64_t max_scene_n,
+                           float *C_pred_refine, float *logit_s, float *logit_t, void *workspace, size_t workspace_bytes,
+                           et_stream_t stream);
+int et_sgcn_forward_graph(const et_sgcn_params *params, const float *v, const float *identity_s, int id_s_t,
+                          const float *identity_t, int id_t_t, int64_t N, float *out, float *logit_s, float *logit_t,
+                          void *workspace, size_t workspace_bytes, et_stream_t stream);
+
 /* ---- fit ----------------------------------------------------------------------------
  * Gram matrices of the normalised trajectories routed to descriptor `which`
  * (1 moving / 0 static) under `mode`:  G_obs (2T_obs,2T_obs), G_pred (2T_pred,2T_pred)

@@ -1,0 +1,191 @@
+"""CPU checks of the native SGCN predictor (eigentrajectory_amd/sgcn.py, csrc/et_sgcn.hip): the fp64 numpy restatement
+(tests/_sgcn_np.py) against the reference's recorded outputs and logits (tests/golden/g20_sgcn_net.npz,
+tools/make_golden_sgcn_net.py) across the network's hard threshold, the synthetic inputs of the GPU tests against the caps
+on undecided entries, the module's state_dict against the reference's, and the refusals (training mode, dropout)."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from . import _golden as G
+from . import _sgcn_np as SN
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+Z = G.load("g20_sgcn_net.npz")
+PICKS = sorted({k.split(".")[0] for k in Z.files if k.startswith("pick")}, key=lambda t: int(t[4:]))
+GEN_ARGS = dict(number_asymmetric_conv_layer=3, n_tcn=2, out_dims=12)
+
+
+def net_state(prefix="net."):
+    return {k[len(prefix):]: Z[k] for k in Z.files
+            if k.startswith(prefix) and not k[len(prefix):].startswith(("net_out", "logit_", "pick"))}
+
+
+def et_module(**kw):
+    from eigentrajectory_amd.sgcn import SGCN
+    args = dict(number_asymmetric_conv_layer=7, embedding_dims=64, number_gcn_layers=1, dropout=0, obs_len=8, pred_len=6,
+                n_tcn=5, in_dims=1, out_dims=20)
+    args.update(kw)
+    return SGCN(**args)
+
+
+def test_fixture_covers_the_cases_the_tests_need():
+    sizes = {t: Z[f"{t}.v"].shape[2] for t in PICKS}
+    for s in G.SCENES:  # the largest scene of every split
+        assert any(str(Z[f"{t}.split"]) == s and sizes[t] == int(Z[f"{s}.scene_size"].max()) for t in PICKS), s
+        assert Z[f"{s}.ade"].shape == Z[f"{s}.fde"].shape == (int(Z[f"{s}.scene_size"].sum()),)
+        assert Z[f"{s}.min_abs_logit"].shape == Z[f"{s}.scene_size"].shape
+    assert max(sizes.values()) == 57 and min(sizes.values()) <= 2
+    mins = {t: float(Z[f"{str(Z[f'{t}.split'])}.min_abs_logit"][int(Z[f"{t}.index"])]) for t in PICKS}
+    assert any(m < SN.DELTA for m in mins.values())  # a scene with an undecided entry
+    for t in PICKS:  # the bridge's quirk: the temporal identity is (N, 1, 1) of ones, not eye(T)
+        n = sizes[t]
+        assert Z[f"{t}.identity_s"].shape == (1, n, n) and Z[f"{t}.identity_t"].shape == (n, 1, 1)
+        assert np.array_equal(Z[f"{t}.identity_t"], np.ones((n, 1, 1), np.float32))
+        assert min(float(np.abs(Z[f"{t}.logit_s"]).min()), float(np.abs(Z[f"{t}.logit_t"]).min())) == mins[t]
+    slopes = [v for k, v in net_state().items() if v.shape == (1,)]
+    assert len(slopes) == 24 and not any(np.allclose(v, 0.25) for v in slopes)  # no default PReLU slope left
+    # the share of scenes without an undecided entry the end-to-end GPU test relies on
+    for s in G.SCENES:
+        decided = float((Z[f"{s}.min_abs_logit"] >= SN.DELTA).mean())
+        assert decided >= (0.65 if s == "univ" else 0.90), (s, decided)
+
+
+def test_numpy_restatement_reproduces_the_reference():
+    """parts (a) to (c) with the reference's recorded fp32 logits and outputs in the implementation's place"""
+    sd = net_state()
+    und = total = 0
+    for t in PICKS:
+        fig = SN.check_against(sd, Z[f"{t}.v"][0, :, :, 0], Z[f"{t}.identity_s"], Z[f"{t}.identity_t"], Z[f"{t}.net_out"],
+                               Z[f"{t}.logit_s"], Z[f"{t}.logit_t"])
+        und, total = und + fig["undecided"], total + fig["entries"]
+    assert und <= SN.CAP_SPLIT * total
+    gen = net_state("gen.")
+    assert SN.n_layers(gen) == (3, 2) and SN.n_layers(sd) == (7, 5)
+    for i in range(2):
+        t = str(Z[f"gen.pick{i}"])
+        SN.check_against(gen, Z[f"{t}.v"][0, :, :, 0], Z[f"{t}.identity_s"], Z[f"{t}.identity_t"], Z[f"gen.net_out{i}"],
+                         Z[f"gen.logit_s{i}"], Z[f"gen.logit_t{i}"])
+
+
+def test_decide_overrides_only_inside_the_band():
+    sd = net_state()
+    t = PICKS[0]
+    v, ids, idt = Z[f"{t}.v"][0, :, :, 0], Z[f"{t}.identity_s"], Z[f"{t}.identity_t"]
+    own, ls, lt = SN.forward(sd, v, ids, idt)
+    flipped = (~(SN.sigmoid(ls) > 0.5), ~(SN.sigmoid(lt) > 0.5))
+    same, _, _ = SN.forward(sd, v, ids, idt, decide=(*flipped, 0.0))       # empty band: the given decisions are ignored
+    assert np.array_equal(same, own)
+    other, _, _ = SN.forward(sd, v, ids, idt, decide=(*flipped, 1e-2))     # a wide band: they are taken
+    assert np.abs(other - own).max() > 1e-4 * np.abs(own).max()
+
+
+def test_synthetic_scenes_stay_within_the_caps():
+    """the ragged scenes of the GPU test: each within the per-scene cap, all of them together within the per-split one"""
+    sd = net_state()
+    und_all = total_all = 0
+    for n in SN.RAGGED:
+        ids, idt = SN.bridge_identities(8, n)
+        _, ls, lt = SN.forward(sd, SN.synthetic_v(n), ids, idt)
+        und, total = SN.undecided(ls, lt)
+        assert und <= SN.CAP_SCENE * total, (n, und, total)
+        und_all, total_all = und_all + und, total_all + total
+    assert und_all <= SN.CAP_SPLIT * total_all, (und_all, total_all)
+
+
+def test_synthetic_split_stays_within_the_caps():
+    sd = net_state()
+    C_obs, nrm = SN.synthetic_split(SN.SPLIT_SIZES, SN.SPLIT_SEED)
+    lo = und_all = total_all = 0
+    for n in SN.SPLIT_SIZES:
+        ids, idt = SN.bridge_identities(8, n)
+        _, ls, lt = SN.forward(sd, SN.scene_input(C_obs, nrm, lo, lo + n), ids, idt)
+        und, total = SN.undecided(ls, lt)
+        assert und <= SN.CAP_SCENE * total, (n, und, total)
+        und_all, total_all, lo = und_all + und, total_all + total, lo + n
+    assert und_all <= SN.CAP_SPLIT * total_all, (und_all, total_all)
+
+
+def test_state_dict_names_and_shapes_are_the_references():
+    for prefix, kw in (("net.", {}), ("gen.", GEN_ARGS)):
+        ref = net_state(prefix)
+        net = et_module(**kw)
+        mine = net.state_dict()
+        assert sorted(mine) == sorted(ref)
+        assert all(tuple(mine[k].shape) == ref[k].shape for k in ref)
+        net.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in ref.items()}, strict=True)
+        assert torch.equal(net.output.bias, torch.from_numpy(ref["output.bias"]))
+    sd = et_module().state_dict()
+    assert "sparse_weighted_adjacency_matrices.spatial_attention.scaled_factor" not in sd
+    assert et_module().sparse_weighted_adjacency_matrices.spatial_attention.scaled_factor == 8.0
+    assert "sparse_weighted_adjacency_matrices.interaction_mask.temporal_asymmetric_convolutions.6.conv1.weight" in sd
+    assert "sparse_weighted_adjacency_matrices.interaction_mask.spatial_asymmetric_convolutions.0.conv1.bias" not in sd
+    assert "stsgcn.temporal_spatial_sparse_gcn.1.embedding.weight" in sd and "tcns.4.1.weight" in sd
+    from eigentrajectory_amd import SGCN
+    assert SGCN is type(et_module())
+    SGCN()  # the reference's defaults construct (their forward is outside the native family)
+
+
+def test_reference_checkpoint_loads():
+    from eigentrajectory_amd import EigenTrajectory
+    from eigentrajectory_amd.bridges import get_hook_func
+    from eigentrajectory_amd.utils import default_hyper_params
+    g2 = G.load("g2_fit_all_scenes.npz")
+    hp = default_hyper_params(static_dist=G.static_dist("eth"))
+    model = EigenTrajectory(et_module(), get_hook_func("sgcn"), hp)
+    ckpt = model.state_dict()
+    for k, v in net_state().items():
+        ckpt[f"baseline_model.{k}"] = torch.from_numpy(np.array(v))
+    for k in ckpt:
+        if k.startswith("ET_"):
+            ckpt[k] = torch.from_numpy(g2[f"eth.{k}"])
+    model.load_state_dict(ckpt, strict=True)  # a reference ET-SGCN checkpoint's keys, unchanged
+    assert torch.equal(model.baseline_model.fusion_.weight, torch.from_numpy(Z["net.fusion_.weight"]))
+
+
+def test_training_mode_and_dropout_raise():
+    v, ident = torch.zeros((1, 8, 3, 1)), [torch.eye(3)[None], torch.ones((3, 1, 1))]
+    net = et_module()
+    assert net.training
+    with pytest.raises(RuntimeError, match="training"):
+        net(v, ident)
+    with pytest.raises(RuntimeError, match="dropout"):
+        et_module(dropout=0.1).eval()(v, ident)
+
+
+def test_evaluate_split_refuses_other_predictors():
+    from eigentrajectory_amd import EigenTrajectory
+    from eigentrajectory_amd.bridges import get_hook_func
+    from eigentrajectory_amd.utils import default_hyper_params
+    hp = default_hyper_params(static_dist=G.static_dist("eth"))
+    obs, pred, sse = torch.zeros((3, 8, 2)), torch.zeros((3, 12, 2)), [[0, 3]]
+    for predictor, hooks in ((torch.nn.Linear(2, 2), "sgcn"), (et_module(), "stgcnn"), (torch.nn.Linear(2, 2), "pecnet")):
+        model = EigenTrajectory(predictor, get_hook_func(hooks), hp).eval()
+        with pytest.raises(NotImplementedError, match="SocialSTGCNN.*SGCN"):
+            model.evaluate_split(obs, pred, sse)
+
+
+def test_sgcn_abi_names_declared_and_listed():
+    from eigentrajectory_amd import _lib
+    with open(os.path.join(ROOT, "include", "eigentraj.h")) as f:
+        header = f.read()
+    for name in ("et_sgcn_workspace_bytes", "et_sgcn_forward_scenes", "et_sgcn_forward_graph"):
+        assert re.search(rf"\b{name}\(", header) and name in _lib.SYMBOLS, name
+    for struct, mirror in (("et_sgcn_attention", _lib.SGCNAttention), ("et_sgcn_asym", _lib.SGCNAsym),
+                           ("et_sgcn_gcn", _lib.SGCNGcn)):
+        fields = re.search(rf"typedef struct {struct} \{{(.*?)\}} {struct};", header, re.S).group(1)
+        assert re.findall(r"\*(\w+)", fields) == [f for f, _ in mirror._fields_], struct
+    body = re.search(r"typedef struct et_sgcn_params \{(.*?)\} et_sgcn_params;", header, re.S).group(1)
+    names = []
+    for decl in body.split(";"):
+        decl = re.sub(r"\[[^\]]*\]", "", decl).strip()
+        if decl:
+            names += [n.strip(" *") for n in re.sub(r"^(const\s+)?\w+\s", "", decl).split(",")]
+    assert names == [f for f, _ in _lib.SGCNParams._fields_]
+    assert f"#define ET_SGCN_MAX_LAYERS {_lib.SGCN_MAX_LAYERS}" in header and f"#define ET_SGCN_MAX_N {_lib.SGCN_MAX_N}" in header
+    if os.path.exists(_lib.LIB_PATH):
+        p = _lib.SGCNParams()
+        assert _lib.lib().et_sgcn_workspace_bytes(_lib.C.byref(p), _lib.i64(10), _lib.i64(100), 1) == 0  # not taken
+        assert all(hasattr(_lib.lib(), name) for name in _lib.SYMBOLS if name.startswith("et_sgcn_"))
