@@ -4,6 +4,14 @@ PyTorch is used here only for device memory and streams: every call passes raw
 device pointers (``tensor.data_ptr()``) and the current HIP stream across the C
 ABI.  There is no CPU fallback: if the shared library is missing, or no HIP
 device is present, the operations raise.
+
+``SIGNATURES`` states the C type of every entry point once; ``lib()`` declares them (``argtypes`` / ``restype``) on the
+one ``CDLL`` handle everybody shares, so call sites pass plain Python values -- ``data_ptr()`` ints, ``None`` for NULL,
+ints and floats, ``byref(struct)`` and ctypes arrays for host-side structs and tables -- and ctypes refuses a missing
+argument or a float where an integer or pointer belongs.  ``call(name, ...)`` is the usual way in (it raises on a
+non-zero status); the scene-size paths of model.py, where host microseconds are the cost, call ``lib().et_x(...)``
+themselves and look at the status inline.  Symbols outside the table (test hooks, the stamp readers of variant builds)
+stay reachable as plain attributes of ``lib()``, undeclared.
 """
 from __future__ import annotations
 
@@ -24,32 +32,118 @@ MAX_T, MAX_K, KMEANS_MAX_D, KMEANS_MAX_CLUSTERS = 32, 32, 32, 255
 SCENE_MAX_N = 16384  # ET_SCENE_MAX_N
 CURVE_MAX_FITS = 64  # ET_CURVE_MAX_FITS
 
+# One line per entry point of include/eigentraj.h, in its order: (return type, [argument types]).  const char * / char * ->
+# _S; every other pointer, et_stream_t, et_comm_t -> _P; int -> _I; int64_t -> _I64; float -> _F; double -> _D; size_t -> _Z
+# (tests/test_host_abi.py holds this table against the header's prototypes).
+_P, _S, _I, _I64, _F, _D, _Z = C.c_void_p, C.c_char_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
+SIGNATURES = {
+    "et_abi_version": (_I, []),
+    "et_status_string": (_S, [_I]),
+    "et_compiled_arch": (_S, []),
+    # ---- tuning switches
+    "et_set_option": (_I, [_S, _S]),
+    "et_get_option": (_I, [_S, _S, _Z]),
+    # ---- TrajNorm
+    "et_norm_params": (_I, [_P, _I64, _I, _P, _P, _P, _P]),
+    "et_norm_params_from_nrm": (_I, [_P, _I64, _P, _P, _P, _P]),
+    "et_normalize": (_I, [_P, _I64, _I, _P, _P, _P, _P, _P]),
+    "et_denormalize": (_I, [_P, _I64, _I, _P, _P, _P, _P, _P]),
+    # ---- projection
+    "et_norm_project": (_I, [_P, _P, _I64, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P]),
+    "et_norm_project_pose": (_I, [_P, _P, _I64, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P]),
+    "et_scene_project": (_I, [_P, _I64, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P, _P]),
+    # ---- training form of a wrapper call on one scene
+    "et_scene_project_train": (_I, [_P, _P, _I64, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P]),
+    "et_wrapper_losses_fwd": (_I, [_P, _I64, _I, _I, _I, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P, _P]),
+    "et_wrapper_losses_bwd": (_I, [_P, _P, _P, _P, _I64, _I, _I, _I, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P]),
+    # ---- anchor refinement + reconstruction
+    "et_anchor_reconstruct_fwd": (_I, [_P, _I64, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _F, _P, _P]),
+    "et_anchor_reconstruct_metrics": (_I, [_P, _I64, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P]),
+    "et_anchor_reconstruct_metrics_pose": (_I, [_P, _I64, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P]),
+    # ---- the reference's test metrics
+    "et_traj_metrics": (_I, [_P, _I64, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "et_anchor_reconstruct_metrics_scenes": (_I, [_P, _I64, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "et_anchor_reconstruct_bwd": (_I, [_P, _I64, _I, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P]),
+    # ---- curve-fitting baselines
+    "et_curve_fit_batch_workspace_bytes": (_Z, [_I, _I64]),
+    "et_curve_fit_batch": (_I, [_P, _P, _P, _I, _I64, _D, _D, _D, _D, _P, _P, _P, _P, _P, _Z, _P]),
+    # ---- t-SNE of descriptor coefficients
+    "et_tsne_neighbors": (_I, [_I64, _D]),
+    "et_tsne_affinities_workspace_bytes": (_Z, [_I64, _I, _I]),
+    "et_tsne_affinities": (_I, [_P, _I64, _I, _D, _I, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "et_tsne_kl_grad_workspace_bytes": (_Z, [_I64]),
+    "et_tsne_kl_grad": (_I, [_P, _I64, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "et_tsne_update": (_I, [_P, _P, _P, _P, _I64, _D, _D, _P]),
+    "et_tsne_optimize_workspace_bytes": (_Z, [_I64, _I64]),
+    "et_tsne_optimize": (_I, [_P, _I64, _P, _P, _P, _I64, _D, _D, _I, _P, _P, _P, _Z, _P]),
+    "et_tsne_pca_init_workspace_bytes": (_Z, [_I64, _I]),
+    "et_tsne_pca_init": (_I, [_P, _I64, _I, _P, _P, _Z, _P]),
+    # ---- Social-STGCNN predictor, inference
+    "et_stgcnn_workspace_bytes": (_Z, [_P, _I64, _I64]),
+    "et_stgcnn_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _Z, _P]),
+    "et_stgcnn_forward_graph": (_I, [_P, _P, _P, _I64, _P, _P, _Z, _P]),
+    # ---- SGCN predictor, inference
+    "et_sgcn_workspace_bytes": (_Z, [_P, _I64, _I64, _I]),
+    "et_sgcn_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _I64, _I64, _P, _P, _P, _P, _Z, _P]),
+    "et_sgcn_forward_graph": (_I, [_P, _P, _P, _I, _P, _I, _I64, _P, _P, _P, _P, _Z, _P]),
+    # ---- fit
+    "et_fit_gram_workspace_bytes": (_Z, [_I64, _I, _I]),
+    "et_fit_gram": (_I, [_P, _P, _I64, _I, _I, _I, _F, _I, _P, _P, _P, _P, _Z, _P]),
+    "et_fit_descriptor_workspace_bytes": (_Z, [_I64, _I, _I]),
+    "et_fit_descriptor": (_I, [_P, _P, _I64, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "et_eigh_topk": (_I, [_P, _I, _I, _P, _P, _P]),
+    "et_eigh_topk_batch": (_I, [_I, _P, _P, _P, _P, _P, _P]),
+    # ---- BatchKMeans
+    "et_euc_sim": (_I, [_P, _P, _I, _I64, _I64, _P, _P]),
+    "et_euc_sim_batch": (_I, [_P, _P, _I64, _I, _I64, _I64, _P, _P]),
+    "et_kmeans_partials_len": (_Z, [_I, _I]),
+    "et_kmeans_workspace_bytes": (_Z, [_I64, _I, _I]),
+    "et_kmeans_scan": (_I, [_P, _I64, _I, _P, _P]),
+    "et_kmeans_begin": (_I, [_P, _I64, _P, _I, _I, _P]),
+    "et_kmeans_init_step": (_I, [_P, _I64, _I, _I, _I, _P, _P, _I64, _P, _P, _Z, _P]),
+    "et_kmeans_init_set": (_I, [_P, _I, _I, _I, _P, _P]),
+    "et_kmeans_init_select": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "et_kmeans_gather_point": (_I, [_P, _I64, _I, _I64, _P, _P]),
+    "et_kmeans_init_farthest": (_I, [_P, _I64, _I, _I, _I64, _P, _P, _Z, _P]),
+    "et_kmeans_assign_accumulate": (_I, [_P, _I64, _I, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "et_kmeans_update": (_I, [_P, _P, _I, _I, _F, _P, _P, _P]),
+    "et_kmeans_joint_done": (_I, [_P, _I, _F, _P]),
+    "et_kmeans_labels_i64": (_I, [_P, _I64, _P, _P]),
+    "et_kmeans_fit": (_I, [_P, _I64, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "et_kmeans_batch_workspace_bytes": (_Z, [_I64, _I, _I, _I64]),
+    "et_kmeans_fit_batch": (_I, [_P, _I64, _I64, _I, _I, _I64, _I, _F, _P, _P, _P, _P, _Z, _P]),
+    # ---- opt-in: BatchKMeans in the reference's own fp32 summation orders
+    "et_kmeans_reforder_workspace_bytes": (_Z, [_I64, _I, _I]),
+    "et_euc_sim_reforder": (_I, [_P, _P, _I, _I64, _I64, _P, _P]),
+    "et_kmeans_init_farthest_reforder": (_I, [_P, _I64, _I, _I, _I64, _P, _P, _Z, _P]),
+    "et_kmeans_predict_reforder": (_I, [_P, _I64, _I, _P, _I, _P, _P, _P, _Z, _P]),
+    "et_kmeans_fit_reforder": (_I, [_P, _I64, _I, _I, _I, _F, _P, _P, _P, _P, _P, _Z, _P]),
+    "et_kmeans_reforder_batch_workspace_bytes": (_Z, [_I64, _I, _I, _I64]),
+    "et_kmeans_fit_reforder_batch": (_I, [_P, _I64, _I64, _I, _I, _I64, _I, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "et_kmeans_predict": (_I, [_P, _I64, _I, _P, _I, _P, _P, _P]),
+    "et_kmeans_predict_batch": (_I, [_P, _I64, _I64, _I64, _I, _P, _I, _P, _P, _P]),
+    # ---- anchor clustering as the reference runs it
+    "et_center_columns": (_I, [_P, _I64, _I, _F, _P, _P, _P, _Z, _P]),
+    "et_kmeanspp_workspace_bytes": (_Z, [_I64, _I, _I]),
+    "et_kmeanspp_seed": (_I, [_P, _I64, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "et_kmeanspp_batch_workspace_bytes": (_Z, [_I64, _I, _I, _I64]),
+    "et_kmeanspp_seed_batch": (_I, [_P, _I64, _I, _I, _I, _P, _I64, _P, _P, _P, _Z, _P]),
+    # ---- data-sharded fit and k-means (RCCL)
+    "et_comm_load": (_I, [_S]),
+    "et_comm_unique_id": (_I, [_P]),
+    "et_comm_init_rank": (_I, [_P, _I, _I, _P]),
+    "et_comm_destroy": (_I, [_P]),
+    "et_comm_info": (_I, [_P, _P, _P]),
+    "et_fit_gram_sharded": (_I, [_P, _P, _I64, _I, _I, _I, _F, _I, _P, _P, _P, _P, _Z, _P, _P]),
+    "et_kmeans_sharded_workspace_bytes": (_Z, [_I64, _I, _I, _I]),
+    "et_kmeans_init_farthest_sharded": (_I, [_P, _I64, _I, _I, _I64, _I64, _P, _P, _P, _Z, _P, _P]),
+    "et_kmeans_fit_sharded": (_I, [_P, _I64, _I64, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _P]),
+    "et_kmeans_reforder_shard_block": (_I64, [_I64, _I, _I]),
+    "et_kmeans_reforder_sharded_workspace_bytes": (_Z, [_P, _I, _I, _I, _I]),
+    "et_kmeans_fit_reforder_sharded": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _Z, _P, _P]),
+}
 #: every symbol include/eigentraj.h declares (tests check the library exports all of them)
-SYMBOLS = [
-    "et_abi_version", "et_status_string", "et_compiled_arch", "et_set_option", "et_get_option",
-    "et_norm_params", "et_norm_params_from_nrm", "et_normalize", "et_denormalize",
-    "et_norm_project", "et_norm_project_pose", "et_scene_project", "et_scene_project_train", "et_wrapper_losses_fwd", "et_wrapper_losses_bwd",
-    "et_anchor_reconstruct_fwd", "et_anchor_reconstruct_bwd", "et_anchor_reconstruct_metrics",
-    "et_anchor_reconstruct_metrics_pose", "et_traj_metrics", "et_anchor_reconstruct_metrics_scenes",
-    "et_curve_fit_batch_workspace_bytes", "et_curve_fit_batch",
-    "et_tsne_neighbors", "et_tsne_affinities_workspace_bytes", "et_tsne_affinities", "et_tsne_kl_grad_workspace_bytes",
-    "et_tsne_kl_grad", "et_tsne_update", "et_tsne_optimize_workspace_bytes", "et_tsne_optimize",
-    "et_tsne_pca_init_workspace_bytes", "et_tsne_pca_init",
-    "et_stgcnn_workspace_bytes", "et_stgcnn_forward_scenes", "et_stgcnn_forward_graph",
-    "et_sgcn_workspace_bytes", "et_sgcn_forward_scenes", "et_sgcn_forward_graph",
-    "et_fit_gram_workspace_bytes", "et_fit_gram", "et_eigh_topk", "et_eigh_topk_batch",
-    "et_fit_descriptor_workspace_bytes", "et_fit_descriptor",
-    "et_euc_sim", "et_euc_sim_batch", "et_kmeans_partials_len", "et_kmeans_workspace_bytes", "et_kmeans_scan", "et_kmeans_begin",
-    "et_kmeans_init_step", "et_kmeans_init_set", "et_kmeans_init_select", "et_kmeans_gather_point", "et_kmeans_init_farthest",
-    "et_kmeans_assign_accumulate", "et_kmeans_update", "et_kmeans_joint_done", "et_kmeans_labels_i64", "et_kmeans_fit", "et_kmeans_batch_workspace_bytes", "et_kmeans_fit_batch", "et_kmeans_predict", "et_kmeans_predict_batch",
-    "et_kmeans_reforder_workspace_bytes", "et_euc_sim_reforder", "et_kmeans_init_farthest_reforder",
-    "et_kmeans_predict_reforder", "et_kmeans_fit_reforder", "et_kmeans_reforder_batch_workspace_bytes",
-    "et_kmeans_fit_reforder_batch",
-    "et_center_columns", "et_kmeanspp_workspace_bytes", "et_kmeanspp_seed", "et_kmeanspp_batch_workspace_bytes", "et_kmeanspp_seed_batch",
-    "et_comm_load", "et_comm_unique_id", "et_comm_init_rank", "et_comm_destroy", "et_comm_info",
-    "et_fit_gram_sharded", "et_kmeans_sharded_workspace_bytes", "et_kmeans_init_farthest_sharded", "et_kmeans_fit_sharded",
-    "et_kmeans_reforder_shard_block", "et_kmeans_reforder_sharded_workspace_bytes", "et_kmeans_fit_reforder_sharded",
-]
+SYMBOLS = list(SIGNATURES)
 
 
 class KMeansState(C.Structure):
@@ -135,17 +229,13 @@ def lib():
         if l.et_abi_version() != ABI_VERSION:
             raise ETLibraryError(f"{LIB_PATH} has ABI version {l.et_abi_version()}, this binding is for {ABI_VERSION}: "
                                  "rebuild the library (make -C eigentrajectory_amd/csrc)")
-        l.et_status_string.restype = C.c_char_p
-        l.et_compiled_arch.restype = C.c_char_p
-        for name in ("et_fit_gram_workspace_bytes", "et_fit_descriptor_workspace_bytes", "et_kmeans_partials_len", "et_kmeans_workspace_bytes",
-                     "et_kmeanspp_workspace_bytes", "et_kmeans_sharded_workspace_bytes", "et_kmeans_batch_workspace_bytes",
-                     "et_kmeanspp_batch_workspace_bytes", "et_kmeans_reforder_workspace_bytes",
-                     "et_kmeans_reforder_batch_workspace_bytes", "et_kmeans_reforder_sharded_workspace_bytes",
-                     "et_curve_fit_batch_workspace_bytes", "et_tsne_affinities_workspace_bytes",
-                     "et_tsne_kl_grad_workspace_bytes", "et_tsne_optimize_workspace_bytes",
-                     "et_tsne_pca_init_workspace_bytes", "et_stgcnn_workspace_bytes", "et_sgcn_workspace_bytes"):
-            getattr(l, name).restype = C.c_size_t
-        l.et_kmeans_reforder_shard_block.restype = C.c_int64
+        for name, (restype, argtypes) in SIGNATURES.items():
+            try:
+                fn = getattr(l, name)
+            except AttributeError:
+                raise ETLibraryError(f"{LIB_PATH} does not export {name}, which include/eigentraj.h declares: rebuild the "
+                                     "library (make -C eigentrajectory_amd/csrc)") from None
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = l
         # the library reads nothing from the environment; ET_OPT_<KEY>=value is forwarded once, here (A/B scripts under tools/)
         # every variable is applied; the ones the library rejects are named in ONE warning (never an exception out of
@@ -170,7 +260,7 @@ def set_option(key: str, value) -> None:
 
 def get_option(key: str) -> str:
     buf = C.create_string_buffer(64)
-    if lib().et_get_option(str(key).encode(), buf, C.c_size_t(64)) != ET_OK:
+    if lib().et_get_option(str(key).encode(), buf, 64) != ET_OK:
         raise ValueError(f"et_get_option({key!r}): unknown key")
     return buf.value.decode()
 
@@ -197,6 +287,11 @@ def check(rc: int, what: str):
         if rc in (1, ET_ERR_BAD_DATA):
             raise ValueError(f"{what}: {msg}")
         raise ETLibraryError(f"{what}: {msg} (status {rc})")
+
+
+def call(name: str, *args):
+    """Call the status-returning entry point ``name`` and raise what :func:`check` raises for its status."""
+    check(getattr(lib(), name)(*args), name)
 
 
 def require_device(*tensors):
@@ -233,34 +328,6 @@ def i64(v):
 
 def f32(v):
     return C.c_float(float(v))
-
-
-# ---------------------------------------------------------------------------------------------------------------
-# Lean call path for the scene-size regime (N <= a few dozen pedestrians per forward: everything is launch- and
-# host-bound there).  The entry points below get ctypes ``argtypes`` once, so that plain Python ints (``data_ptr()``,
-# sizes, the raw stream handle) cross the boundary without per-call wrapper objects.
-_P, _I64, _I, _F = C.c_void_p, C.c_int64, C.c_int, C.c_float
-_FAST_SIGNATURES = {
-    "et_scene_project": [_P, _I64, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P, _P],
-    "et_anchor_reconstruct_fwd": [_P, _I64, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _F, _P, _P],
-    "et_anchor_reconstruct_metrics": [_P, _I64, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P],
-    "et_scene_project_train": [_P, _P, _I64, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P],
-    "et_wrapper_losses_fwd": [_P, _I64, _I, _I, _I, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P, _P],
-    "et_wrapper_losses_bwd": [_P, _P, _P, _P, _I64, _I, _I, _I, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P],
-    "et_fit_descriptor": [_P, _P, _I64, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
-}
-_fast = {}
-
-
-def fast(name):
-    """The C entry point ``name`` with its argument types declared (cached)."""
-    fn = _fast.get(name)
-    if fn is None:
-        fn = getattr(C.CDLL(LIB_PATH), name)  # a private handle: declaring argtypes must not affect lib()'s users
-        fn.argtypes = _FAST_SIGNATURES[name]
-        fn.restype = C.c_int
-        _fast[name] = fn
-    return fn
 
 
 try:

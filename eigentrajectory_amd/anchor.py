@@ -189,7 +189,7 @@ def sklearn_style_kmeans(C, K, *, random_state=0, n_init=10, max_iter=300, tol=1
         best = int(torch.argmin(inertia))  # first minimum = the earlier initialisation on ties
         return (cens[best] + mean[:, None]).contiguous(), float(inertia[best]) / n, seeds
 
-    nbytes = ops.L.lib().et_kmeanspp_workspace_bytes(ops.L.i64(n), d, ops.kmeanspp_trials(K))
+    nbytes = ops.L.lib().et_kmeanspp_workspace_bytes(n, d, ops.kmeanspp_trials(K))
     ws_seed = torch.empty((max(nbytes, 8),), device=dev, dtype=torch.uint8)
     best, seeds = None, []
     for i in range(n_init):

@@ -56,29 +56,28 @@ class Communicator:
     def __init__(self, device=None, group=None):
         self.dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.world, self.rank = _world(group)
-        lib = L.lib()
         # bind the RCCL instance PyTorch ships (the one torch.distributed's "nccl" backend uses), not a second copy
         torch_rccl = os.path.join(os.path.dirname(torch.__file__), "lib", "librccl.so")
-        L.check(lib.et_comm_load(torch_rccl.encode() if os.path.exists(torch_rccl) else None), "et_comm_load")
+        L.call("et_comm_load", torch_rccl.encode() if os.path.exists(torch_rccl) else None)
         uid = (C.c_ubyte * 128)()
         if self.rank == 0:
-            L.check(lib.et_comm_unique_id(uid), "et_comm_unique_id")
+            L.call("et_comm_unique_id", uid)
         if self.world > 1:
             box = [bytes(uid)]
             dist.broadcast_object_list(box, src=0, group=group)
             uid = (C.c_ubyte * 128).from_buffer_copy(box[0])
         self.handle = C.c_void_p()
         with torch.cuda.device(self.dev):
-            L.check(lib.et_comm_init_rank(uid, self.world, self.rank, C.byref(self.handle)), "et_comm_init_rank")
+            L.call("et_comm_init_rank", uid, self.world, self.rank, C.byref(self.handle))
 
     def info(self):
         n, r = C.c_int(), C.c_int()
-        L.check(L.lib().et_comm_info(self.handle, C.byref(n), C.byref(r)), "et_comm_info")
+        L.call("et_comm_info", self.handle, C.byref(n), C.byref(r))
         return n.value, r.value
 
     def close(self):
         if self.handle:
-            L.check(L.lib().et_comm_destroy(self.handle), "et_comm_destroy")
+            L.call("et_comm_destroy", self.handle)
             self.handle = C.c_void_p()
 
 
@@ -92,11 +91,10 @@ def fit_gram_native(obs, pred, mode, static_dist=0.0, which=1, comm=None):
     g_obs = torch.empty((2 * t_obs, 2 * t_obs), device=dev, dtype=torch.float64)
     g_pred = torch.empty((2 * t_pred, 2 * t_pred), device=dev, dtype=torch.float64)
     count = torch.zeros((1,), device=dev, dtype=torch.int64)
-    ws = torch.empty((max(L.lib().et_fit_gram_workspace_bytes(L.i64(n), t_obs, t_pred), 8),), device=dev, dtype=torch.uint8)
-    L.check(L.lib().et_fit_gram_sharded(L.ptr(obs), L.ptr(pred), L.i64(n), t_obs, t_pred, int(mode), L.f32(static_dist),
-                                        int(which), L.ptr(g_obs), L.ptr(g_pred), L.ptr(count), L.ptr(ws),
-                                        C.c_size_t(ws.numel()), comm.handle if comm is not None else None, L.stream(dev)),
-            "et_fit_gram_sharded")
+    ws = torch.empty((max(L.lib().et_fit_gram_workspace_bytes(n, t_obs, t_pred), 8),), device=dev, dtype=torch.uint8)
+    L.call("et_fit_gram_sharded", L.ptr(obs), L.ptr(pred), n, t_obs, t_pred, int(mode), float(static_dist), int(which),
+           L.ptr(g_obs), L.ptr(g_pred), L.ptr(count), L.ptr(ws), ws.numel(), comm.handle if comm is not None else None,
+           L.stream(dev))
     return g_obs, g_pred, count
 
 
@@ -157,7 +155,7 @@ class ShardedKMeans:
 
     def _native_workspace(self):
         if not hasattr(self, "_ws_native"):
-            nbytes = L.lib().et_kmeans_sharded_workspace_bytes(L.i64(self.n_local), self.d, self.K, self.world)
+            nbytes = L.lib().et_kmeans_sharded_workspace_bytes(self.n_local, self.d, self.K, self.world)
             self._ws_native = torch.empty((nbytes,), device=self.dev, dtype=torch.uint8)
         return self._ws_native
 
@@ -167,9 +165,8 @@ class ShardedKMeans:
         if self.comm is not None:
             sh, ws = self.shard, self._native_workspace()
             C0 = torch.zeros((d, K), dtype=torch.float32, device=self.dev)
-            L.check(L.lib().et_kmeans_init_farthest_sharded(
-                L.ptr(sh.X), L.i64(self.n_local), d, K, L.i64(first_index), L.i64(self.index_base), L.ptr(C0), L.ptr(sh.best),
-                L.ptr(ws), C.c_size_t(ws.numel()), self.comm.handle, L.stream(self.dev)), "et_kmeans_init_farthest_sharded")
+            L.call("et_kmeans_init_farthest_sharded", L.ptr(sh.X), self.n_local, d, K, int(first_index), self.index_base,
+                   L.ptr(C0), L.ptr(sh.best), L.ptr(ws), ws.numel(), self.comm.handle, L.stream(self.dev))
             return C0
         C0 = torch.zeros((d, K), dtype=torch.float32, device=self.dev)
         first = torch.zeros((d,), dtype=torch.float32, device=self.dev)
@@ -215,11 +212,9 @@ class ShardedKMeans:
             ws = self._native_workspace()
             st = L.KMeansState()
             labels = torch.empty((self.n_local,), device=self.dev, dtype=torch.int64)
-            L.check(L.lib().et_kmeans_fit_sharded(
-                L.ptr(sh.X), L.i64(self.n_local), L.i64(self.n_total), self.d, self.K, int(max_iter), L.f32(tol),
-                L.ptr(centroids), L.ptr(labels), L.ptr(trace), L.ptr(sh.state), L.ptr(sh.labels_u8), L.ptr(sh.partials),
-                C.byref(st), L.ptr(ws), C.c_size_t(ws.numel()), self.comm.handle, L.stream(self.dev)),
-                "et_kmeans_fit_sharded")
+            L.call("et_kmeans_fit_sharded", L.ptr(sh.X), self.n_local, self.n_total, self.d, self.K, int(max_iter),
+                   float(tol), L.ptr(centroids), L.ptr(labels), L.ptr(trace), L.ptr(sh.state), L.ptr(sh.labels_u8),
+                   L.ptr(sh.partials), C.byref(st), L.ptr(ws), ws.numel(), self.comm.handle, L.stream(self.dev))
             return dict(centroids=centroids, labels=labels, n_iter=int(st.iter), error=float(st.error),
                         inertia=float(st.inertia), done=bool(st.done))
         sh.scan()

@@ -37,7 +37,7 @@ class _SceneLosses(torch.autograd.Function):
         arg = torch.empty((3, n), device=dev, dtype=torch.int32)
         ptrs = (nrm.data_ptr(), model.ET_m_anchor.C_anchor.data_ptr(), model.ET_s_anchor.C_anchor.data_ptr(),
                 model.ET_m_descriptor.U_pred_trunc.data_ptr(), model.ET_s_descriptor.U_pred_trunc.data_ptr())
-        rc = ops.L.fast("et_wrapper_losses_fwd")(
+        rc = ops.L.lib().et_wrapper_losses_fwd(
             Cc.data_ptr(), n, s, k, t_pred, *ptrs, ops.MODE_SPLIT, model.static_dist, C_gt.data_ptr(), gt.data_ptr(),
             recon.data_ptr(), small.data_ptr(), arg.data_ptr(), small.data_ptr() + 12 * n, ops.L.raw_stream(dev.index))
         if rc:
@@ -63,7 +63,7 @@ class _SceneLosses(torch.autograd.Function):
                 g = g.to(device=Cc.device, dtype=torch.float32)
             return g
         gs = [scalar(g) for g in (g_e, g_ade, g_fde)]
-        rc = ops.L.fast("et_wrapper_losses_bwd")(
+        rc = ops.L.lib().et_wrapper_losses_bwd(
             *(None if g is None else g.data_ptr() for g in gs), Cc.data_ptr(), n, s, k, gt.shape[1], *ctx.ptrs, ops.MODE_SPLIT,
             ctx.static_dist, C_gt.data_ptr(), gt.data_ptr(), recon.data_ptr(), arg.data_ptr(), dC.data_ptr(),
             ops.L.raw_stream(Cc.device.index))
@@ -129,7 +129,7 @@ class EigenTrajectory(nn.Module):
         k = self.k
         block = torch.empty((k + 6, n), device=obs_traj.device)
         base = block.data_ptr()
-        rc = ops.L.fast("et_scene_project")(
+        rc = ops.L.lib().et_scene_project(
             obs_traj.data_ptr(), n, t_obs, k, self.ET_m_descriptor.U_obs_trunc.data_ptr(),
             self.ET_s_descriptor.U_obs_trunc.data_ptr(), ops.MODE_SPLIT, self.static_dist, base, base + 4 * (k + 2) * n,
             base + 4 * k * n, None, ops.L.raw_stream(obs_traj.device.index))
@@ -142,7 +142,7 @@ class EigenTrajectory(nn.Module):
         n, k = obs_traj.shape[0], self.k
         block = torch.empty((2 * k + 6, n), device=obs_traj.device)
         base = block.data_ptr()
-        rc = ops.L.fast("et_scene_project_train")(
+        rc = ops.L.lib().et_scene_project_train(
             obs_traj.data_ptr(), pred_traj.data_ptr(), n, obs_traj.shape[1], pred_traj.shape[1], k,
             self.ET_m_descriptor.U_obs_trunc.data_ptr(), self.ET_s_descriptor.U_obs_trunc.data_ptr(),
             self.ET_m_descriptor.U_pred_trunc.data_ptr(), self.ET_s_descriptor.U_pred_trunc.data_ptr(), ops.MODE_SPLIT,
@@ -226,7 +226,7 @@ class EigenTrajectory(nn.Module):
             Cc = C_pred_refine if C_pred_refine.is_contiguous() else C_pred_refine.contiguous()
             k, n, s = Cc.shape
             out = torch.empty((2, n), device=Cc.device)
-            rc = ops.L.fast("et_anchor_reconstruct_metrics")(
+            rc = ops.L.lib().et_anchor_reconstruct_metrics(
                 Cc.data_ptr(), n, s, k, obs_traj.shape[1], pred_traj.shape[1], None, nrm.data_ptr(),
                 self.ET_m_anchor.C_anchor.data_ptr(), self.ET_s_anchor.C_anchor.data_ptr(),
                 self.ET_m_descriptor.U_pred_trunc.data_ptr(), self.ET_s_descriptor.U_pred_trunc.data_ptr(), ops.MODE_SPLIT,
@@ -446,7 +446,7 @@ class EigenTrajectory(nn.Module):
                 Cc = C_pred_refine if C_pred_refine.is_contiguous() else C_pred_refine.contiguous()
                 k, n, s = Cc.shape
                 recon = torch.empty((s, n, self.t_pred, 2), device=Cc.device)
-                rc = ops.L.fast("et_anchor_reconstruct_fwd")(
+                rc = ops.L.lib().et_anchor_reconstruct_fwd(
                     Cc.data_ptr(), n, s, k, obs_traj.shape[1], self.t_pred, None, nrm.data_ptr(),
                     self.ET_m_anchor.C_anchor.data_ptr(), self.ET_s_anchor.C_anchor.data_ptr(),
                     self.ET_m_descriptor.U_pred_trunc.data_ptr(), self.ET_s_descriptor.U_pred_trunc.data_ptr(),

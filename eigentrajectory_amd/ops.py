@@ -29,8 +29,7 @@ def norm_params(obs, want_ori=True, want_rot=True, want_sca=True):
     ori = torch.empty((n, 1, 2), device=dev) if want_ori else None
     rot = torch.empty((n, 2, 2), device=dev) if want_rot else None
     sca = torch.empty((n, 1, 1), device=dev) if want_sca else None
-    L.check(L.lib().et_norm_params(L.ptr(obs), L.i64(n), t, L.ptr(ori), L.ptr(rot), L.ptr(sca), L.stream(dev)),
-            "et_norm_params")
+    L.call("et_norm_params", L.ptr(obs), n, t, L.ptr(ori), L.ptr(rot), L.ptr(sca), L.stream(dev))
     return ori, rot, sca
 
 
@@ -42,8 +41,7 @@ def norm_params_from_nrm(nrm, want_ori=True, want_rot=True, want_sca=True):
     ori = torch.empty((n, 1, 2), device=dev) if want_ori else None
     rot = torch.empty((n, 2, 2), device=dev) if want_rot else None
     sca = torch.empty((n, 1, 1), device=dev) if want_sca else None
-    L.check(L.lib().et_norm_params_from_nrm(L.ptr(nrm), L.i64(n), L.ptr(ori), L.ptr(rot), L.ptr(sca), L.stream(dev)),
-            "et_norm_params_from_nrm")
+    L.call("et_norm_params_from_nrm", L.ptr(nrm), n, L.ptr(ori), L.ptr(rot), L.ptr(sca), L.stream(dev))
     return ori, rot, sca
 
 
@@ -51,9 +49,7 @@ def _traj_transform(which, traj, ori, rot, sca):
     """which: "normalize" | "denormalize" -> et_normalize / et_denormalize on contiguous device tensors."""
     n, t, _ = traj.shape
     out = torch.empty_like(traj)
-    fn = L.lib().et_normalize if which == "normalize" else L.lib().et_denormalize
-    L.check(fn(L.ptr(traj), L.i64(n), t, L.ptr(ori), L.ptr(rot), L.ptr(sca), L.ptr(out), L.stream(traj.device)),
-            "et_" + which)
+    L.call("et_" + which, L.ptr(traj), n, t, L.ptr(ori), L.ptr(rot), L.ptr(sca), L.ptr(out), L.stream(traj.device))
     return out
 
 
@@ -117,15 +113,13 @@ def norm_project(obs, pred, U_obs_m, U_pred_m, U_obs_s, U_pred_s, mode, static_d
     flag = torch.empty((n,), device=dev, dtype=torch.uint8) if want_flag else None
     if want_pose:
         pose = torch.empty((5, n), device=dev)
-        L.check(L.lib().et_norm_project_pose(L.ptr(obs), L.ptr(pred), L.i64(n), t_obs, t_pred, k, L.ptr(U_obs_m),
-                                             L.ptr(U_pred_m), L.ptr(U_obs_s), L.ptr(U_pred_s), int(mode), L.f32(static_dist),
-                                             L.ptr(c_obs), L.ptr(c_pred), L.ptr(nrm), L.ptr(flag), L.ptr(pose), L.stream(dev)),
-                "et_norm_project_pose")
+        L.call("et_norm_project_pose", L.ptr(obs), L.ptr(pred), n, t_obs, t_pred, k, L.ptr(U_obs_m), L.ptr(U_pred_m),
+               L.ptr(U_obs_s), L.ptr(U_pred_s), int(mode), float(static_dist), L.ptr(c_obs), L.ptr(c_pred), L.ptr(nrm),
+               L.ptr(flag), L.ptr(pose), L.stream(dev))
         return c_obs, c_pred, nrm, flag, pose
-    L.check(L.lib().et_norm_project(L.ptr(obs), L.ptr(pred), L.i64(n), t_obs, t_pred, k, L.ptr(U_obs_m),
-                                    L.ptr(U_pred_m), L.ptr(U_obs_s), L.ptr(U_pred_s), int(mode), L.f32(static_dist),
-                                    L.ptr(c_obs), L.ptr(c_pred), L.ptr(nrm), L.ptr(flag), L.stream(dev)),
-            "et_norm_project")
+    L.call("et_norm_project", L.ptr(obs), L.ptr(pred), n, t_obs, t_pred, k, L.ptr(U_obs_m), L.ptr(U_pred_m), L.ptr(U_obs_s),
+           L.ptr(U_pred_s), int(mode), float(static_dist), L.ptr(c_obs), L.ptr(c_pred), L.ptr(nrm), L.ptr(flag),
+           L.stream(dev))
     return c_obs, c_pred, nrm, flag
 
 
@@ -136,10 +130,8 @@ def _reconstruct_fwd(Cc, obs, nrm, A_m, A_s, U_m, U_s, mode, static_dist, t_obs)
     u = U_m if U_m is not None else U_s
     t_pred = u.shape[0] // 2
     out = torch.empty((s, n, t_pred, 2), device=dev)
-    L.check(L.lib().et_anchor_reconstruct_fwd(L.ptr(Cc), L.i64(n), s, k, t_obs, t_pred, L.ptr(obs), L.ptr(nrm),
-                                              L.ptr(A_m), L.ptr(A_s), L.ptr(U_m), L.ptr(U_s), int(mode),
-                                              L.f32(static_dist), L.ptr(out), L.stream(dev)),
-            "et_anchor_reconstruct_fwd")
+    L.call("et_anchor_reconstruct_fwd", L.ptr(Cc), n, s, k, t_obs, t_pred, L.ptr(obs), L.ptr(nrm), L.ptr(A_m), L.ptr(A_s),
+           L.ptr(U_m), L.ptr(U_s), int(mode), float(static_dist), L.ptr(out), L.stream(dev))
     return out
 
 
@@ -149,9 +141,8 @@ def _reconstruct_bwd(dtraj, obs, nrm, U_m, U_s, mode, static_dist, t_obs):
     u = U_m if U_m is not None else U_s
     k = u.shape[1]
     dC = torch.empty((k, n, s), device=dev)
-    L.check(L.lib().et_anchor_reconstruct_bwd(L.ptr(dtraj), L.i64(n), s, k, t_obs, t_pred, L.ptr(obs), L.ptr(nrm),
-                                              L.ptr(U_m), L.ptr(U_s), int(mode), L.f32(static_dist), L.ptr(dC),
-                                              L.stream(dev)), "et_anchor_reconstruct_bwd")
+    L.call("et_anchor_reconstruct_bwd", L.ptr(dtraj), n, s, k, t_obs, t_pred, L.ptr(obs), L.ptr(nrm), L.ptr(U_m), L.ptr(U_s),
+           int(mode), float(static_dist), L.ptr(dC), L.stream(dev))
     return dC
 
 
@@ -200,10 +191,9 @@ def anchor_reconstruct_metrics(Cc, gt, A_m, A_s, U_m, U_s, mode, static_dist=0.0
     t_pred = gt.shape[1]
     ade = torch.empty((n,), device=dev)
     fde = torch.empty((n,), device=dev)
-    L.check(L.lib().et_anchor_reconstruct_metrics_pose(L.ptr(Cc), L.i64(n), s, k, int(t_obs), t_pred, L.ptr(obs), L.ptr(nrm),
-                                                       L.ptr(pose), L.ptr(A_m), L.ptr(A_s), L.ptr(U_m), L.ptr(U_s), int(mode),
-                                                       L.f32(static_dist), L.ptr(gt), L.ptr(ade), L.ptr(fde), L.stream(dev)),
-            "et_anchor_reconstruct_metrics_pose")
+    L.call("et_anchor_reconstruct_metrics_pose", L.ptr(Cc), n, s, k, int(t_obs), t_pred, L.ptr(obs), L.ptr(nrm), L.ptr(pose),
+           L.ptr(A_m), L.ptr(A_s), L.ptr(U_m), L.ptr(U_s), int(mode), float(static_dist), L.ptr(gt), L.ptr(ade), L.ptr(fde),
+           L.stream(dev))
     return ade, fde
 
 
@@ -257,9 +247,9 @@ def traj_metrics(pred, gt, scene_sizes=None, metrics=METRIC_KEYS):
         raise ValueError(f"gt {tuple(gt.shape)} does not match pred {tuple(pred.shape)}")
     off = scene_offsets(scene_sizes, n, dev)
     out = _metric_outputs(n, dev, metrics)
-    L.check(L.lib().et_traj_metrics(L.ptr(pred), L.i64(n), s, t, L.ptr(gt), L.ptr(off), 0 if off is None else off.numel() - 1,
-                                    L.ptr(out.get("ADE")), L.ptr(out.get("FDE")), L.ptr(out.get("TCC")),
-                                    L.ptr(out.get("COL")), L.ptr(out.get("best")), L.stream(dev)), "et_traj_metrics")
+    L.call("et_traj_metrics", L.ptr(pred), n, s, t, L.ptr(gt), L.ptr(off), 0 if off is None else off.numel() - 1,
+           L.ptr(out.get("ADE")), L.ptr(out.get("FDE")), L.ptr(out.get("TCC")), L.ptr(out.get("COL")),
+           L.ptr(out.get("best")), L.stream(dev))
     return out
 
 
@@ -279,17 +269,16 @@ def anchor_reconstruct_metrics_scenes(Cc, gt, A_m, A_s, U_m, U_s, mode, static_d
         raise ValueError(f"gt {tuple(gt.shape)} does not match C {tuple(Cc.shape)}")
     off = scene_offsets(scene_sizes, n, dev)
     out = _metric_outputs(n, dev, metrics)
-    L.check(L.lib().et_anchor_reconstruct_metrics_scenes(
-        L.ptr(Cc), L.i64(n), s, k, int(t_obs), t_pred, L.ptr(obs), L.ptr(nrm), L.ptr(pose), L.ptr(A_m), L.ptr(A_s), L.ptr(U_m),
-        L.ptr(U_s), int(mode), L.f32(static_dist), L.ptr(gt), L.ptr(off), 0 if off is None else off.numel() - 1,
-        L.ptr(out.get("ADE")), L.ptr(out.get("FDE")), L.ptr(out.get("TCC")), L.ptr(out.get("COL")), L.ptr(out.get("best")),
-        L.stream(dev)), "et_anchor_reconstruct_metrics_scenes")
+    L.call("et_anchor_reconstruct_metrics_scenes", L.ptr(Cc), n, s, k, int(t_obs), t_pred, L.ptr(obs), L.ptr(nrm),
+           L.ptr(pose), L.ptr(A_m), L.ptr(A_s), L.ptr(U_m), L.ptr(U_s), int(mode), float(static_dist), L.ptr(gt), L.ptr(off),
+           0 if off is None else off.numel() - 1, L.ptr(out.get("ADE")), L.ptr(out.get("FDE")), L.ptr(out.get("TCC")),
+           L.ptr(out.get("COL")), L.ptr(out.get("best")), L.stream(dev))
     return out
 
 
 # ------------------------------------------------------------------------ Social-STGCNN predictor (inference)
 def _stgcnn_ws(params, n, max_n, dev):
-    nbytes = L.lib().et_stgcnn_workspace_bytes(C.byref(params), L.i64(n), L.i64(max_n))
+    nbytes = L.lib().et_stgcnn_workspace_bytes(C.byref(params), n, max_n)
     return (torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None), nbytes
 
 
@@ -304,8 +293,7 @@ def stgcnn_forward_graph(model, v, a):
     v, a = _dev_args(dev, v, a)
     out = torch.empty((1, S, k, n), device=dev)
     ws, nbytes = _stgcnn_ws(params, n, n, dev)
-    L.check(L.lib().et_stgcnn_forward_graph(C.byref(params), L.ptr(v), L.ptr(a), L.i64(n), L.ptr(out), L.ptr(ws),
-                                            C.c_size_t(nbytes), L.stream(dev)), "et_stgcnn_forward_graph")
+    L.call("et_stgcnn_forward_graph", C.byref(params), L.ptr(v), L.ptr(a), n, L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
     return out
 
 
@@ -329,15 +317,14 @@ def stgcnn_forward_scenes(model, C_obs, nrm, scene_sizes=None):
         sizes, off, max_n = None, None, n
     out = torch.empty((k, n, params.output_feat), device=dev)
     ws, nbytes = _stgcnn_ws(params, n, max_n, dev)
-    L.check(L.lib().et_stgcnn_forward_scenes(C.byref(params), L.ptr(C_obs), L.ptr(nrm), L.i64(n), L.ptr(off),
-                                             0 if off is None else len(sizes), L.ptr(out), L.ptr(ws), C.c_size_t(nbytes),
-                                             L.stream(dev)), "et_stgcnn_forward_scenes")
+    L.call("et_stgcnn_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
+           0 if off is None else len(sizes), L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
     return out
 
 
 # ------------------------------------------------------------------------------ SGCN predictor (inference)
 def _sgcn_ws(params, n, sum_n2, n_scenes, dev):
-    nbytes = L.lib().et_sgcn_workspace_bytes(C.byref(params), L.i64(n), L.i64(sum_n2), int(n_scenes))
+    nbytes = L.lib().et_sgcn_workspace_bytes(C.byref(params), n, sum_n2, int(n_scenes))
     return (torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None), nbytes
 
 
@@ -370,9 +357,8 @@ def sgcn_forward_graph(model, v, identity, want_logits=False):
     out = torch.empty((k, n, S), device=dev)
     ls, lt = _sgcn_logits(want_logits, T, n, n * n, dev)
     ws, nbytes = _sgcn_ws(params, n, n * n, 1, dev)
-    L.check(L.lib().et_sgcn_forward_graph(C.byref(params), L.ptr(v.detach()), L.ptr(id_s.detach()), int(id_s.shape[0]),
-                                          L.ptr(id_t.detach()), int(id_t.shape[1]), L.i64(n), L.ptr(out), L.ptr(ls),
-                                          L.ptr(lt), L.ptr(ws), C.c_size_t(nbytes), L.stream(dev)), "et_sgcn_forward_graph")
+    L.call("et_sgcn_forward_graph", C.byref(params), L.ptr(v.detach()), L.ptr(id_s.detach()), int(id_s.shape[0]),
+           L.ptr(id_t.detach()), int(id_t.shape[1]), n, L.ptr(out), L.ptr(ls), L.ptr(lt), L.ptr(ws), nbytes, L.stream(dev))
     if want_logits:
         return out, ls.view(T, 4, n, n), lt.view(n, 4, T, T)
     return out
@@ -405,10 +391,9 @@ def sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_logits=False):
     out = torch.empty((k, n, params.out_dims), device=dev)
     ls, lt = _sgcn_logits(want_logits, T, n, sum_n2, dev)
     ws, nbytes = _sgcn_ws(params, n, sum_n2, len(sizes), dev)
-    L.check(L.lib().et_sgcn_forward_scenes(C.byref(params), L.ptr(C_obs), L.ptr(nrm), L.i64(n), L.ptr(off),
-                                           0 if off is None else len(sizes), L.i64(sum_n2), L.i64(max_n), L.ptr(out),
-                                           L.ptr(ls), L.ptr(lt), L.ptr(ws), C.c_size_t(nbytes), L.stream(dev)),
-            "et_sgcn_forward_scenes")
+    L.call("et_sgcn_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
+           0 if off is None else len(sizes), sum_n2, max_n, L.ptr(out), L.ptr(ls), L.ptr(lt), L.ptr(ws), nbytes,
+           L.stream(dev))
     return (out, ls, lt) if want_logits else out
 
 
@@ -442,14 +427,13 @@ def curve_fit_batch(trajs, bases, steps=100000, lr=1e-4, betas=(0.9, 0.999), eps
         cp = torch.empty((c_off,), device=dev, dtype=torch.float32) if want_cp else None
         loss = torch.empty((nf, int(steps)), device=dev, dtype=torch.float64) if want_loss else None
         best = torch.empty((nf,), device=dev, dtype=torch.int32)
-        nbytes = L.lib().et_curve_fit_batch_workspace_bytes(nf, L.i64(steps))
+        nbytes = L.lib().et_curve_fit_batch_workspace_bytes(nf, int(steps))
         if nbytes == 0:
             raise ValueError(f"curve_fit_batch: steps={steps} not taken")
         ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
-        L.check(L.lib().et_curve_fit_batch(
-            L.ptr(traj), L.ptr(basis), table, nf, L.i64(steps), C.c_double(lr), C.c_double(betas[0]),
-            C.c_double(betas[1]), C.c_double(eps), L.ptr(recon), L.ptr(cp), L.ptr(loss), L.ptr(best), L.ptr(ws),
-            C.c_size_t(nbytes), L.stream(dev)), "et_curve_fit_batch")
+        L.call("et_curve_fit_batch", L.ptr(traj), L.ptr(basis), table, nf, int(steps), float(lr), float(betas[0]),
+               float(betas[1]), float(eps), L.ptr(recon), L.ptr(cp), L.ptr(loss), L.ptr(best), L.ptr(ws), nbytes,
+               L.stream(dev))
         for (n, T, ncp, to, _, co) in fits:
             out["recon"].append(recon[to:to + n * T * 2].view(n, T, 2))
             if want_cp:
@@ -478,10 +462,10 @@ def tsne_affinities(X, perplexity=30.0):
     if X.dim() != 2:
         raise ValueError("tsne_affinities: X must be (N, d)")
     n, d = X.shape
-    k = L.lib().et_tsne_neighbors(L.i64(n), C.c_double(perplexity))
+    k = L.lib().et_tsne_neighbors(n, float(perplexity))
     if k < 1:
         raise ValueError(f"tsne_affinities: N={n}, perplexity={perplexity} not taken")
-    ws = _tsne_ws(L.lib().et_tsne_affinities_workspace_bytes(L.i64(n), d, k), dev)
+    ws = _tsne_ws(L.lib().et_tsne_affinities_workspace_bytes(n, d, k), dev)
     out = {"knn_idx": torch.empty((n, k), device=dev, dtype=torch.int32),
            "knn_dist": torch.empty((n, k), device=dev),
            "p_cond": torch.empty((n, k), device=dev, dtype=torch.float64),
@@ -489,10 +473,9 @@ def tsne_affinities(X, perplexity=30.0):
            "indices": torch.empty((2 * n * k,), device=dev, dtype=torch.int32),
            "P": torch.empty((2 * n * k,), device=dev, dtype=torch.float64),
            "total": torch.empty((1,), device=dev, dtype=torch.float64)}
-    L.check(L.lib().et_tsne_affinities(
-        L.ptr(X), L.i64(n), d, C.c_double(perplexity), k, L.ptr(out["knn_idx"]), L.ptr(out["knn_dist"]),
-        L.ptr(out["p_cond"]), L.ptr(out["indptr"]), L.ptr(out["indices"]), L.ptr(out["P"]), L.ptr(out["total"]),
-        L.ptr(ws), C.c_size_t(ws.numel()), L.stream(dev)), "et_tsne_affinities")
+    L.call("et_tsne_affinities", L.ptr(X), n, d, float(perplexity), k, L.ptr(out["knn_idx"]), L.ptr(out["knn_dist"]),
+           L.ptr(out["p_cond"]), L.ptr(out["indptr"]), L.ptr(out["indices"]), L.ptr(out["P"]), L.ptr(out["total"]),
+           L.ptr(ws), ws.numel(), L.stream(dev))
     nnz = int(out["indptr"][n].item())
     out["indices"], out["P"] = out["indices"][:nnz], out["P"][:nnz]
     return out
@@ -510,9 +493,9 @@ def tsne_kl_grad(Y, indptr, indices, P, want_kl=True):
     P = L.on_device(P, dev, torch.float32)
     grad = torch.empty_like(Y)
     kl = torch.empty((1,), device=dev, dtype=torch.float64) if want_kl else None
-    ws = _tsne_ws(L.lib().et_tsne_kl_grad_workspace_bytes(L.i64(n)), dev)
-    L.check(L.lib().et_tsne_kl_grad(L.ptr(Y), L.i64(n), L.ptr(indptr), L.ptr(indices), L.ptr(P), L.ptr(grad), L.ptr(kl),
-                                    L.ptr(ws), C.c_size_t(ws.numel()), L.stream(dev)), "et_tsne_kl_grad")
+    ws = _tsne_ws(L.lib().et_tsne_kl_grad_workspace_bytes(n), dev)
+    L.call("et_tsne_kl_grad", L.ptr(Y), n, L.ptr(indptr), L.ptr(indices), L.ptr(P), L.ptr(grad), L.ptr(kl), L.ptr(ws),
+           ws.numel(), L.stream(dev))
     return (kl[0] if want_kl else None), grad
 
 
@@ -523,8 +506,8 @@ def tsne_update(p, update, gains, grad, momentum, learning_rate):
         if t.dtype != dt or not t.is_contiguous() or t.numel() != p.numel():
             raise ValueError("tsne_update: p, gains, grad fp32 and update fp64, contiguous, of one size")
     dev = L.require_device(p)
-    L.check(L.lib().et_tsne_update(L.ptr(p), L.ptr(update), L.ptr(gains), L.ptr(grad), L.i64(p.numel()),
-                                   C.c_double(momentum), C.c_double(learning_rate), L.stream(dev)), "et_tsne_update")
+    L.call("et_tsne_update", L.ptr(p), L.ptr(update), L.ptr(gains), L.ptr(grad), p.numel(), float(momentum),
+           float(learning_rate), L.stream(dev))
 
 
 def tsne_optimize(Y0, indptr, indices, P, early_exaggeration=12.0, learning_rate=200.0, max_iter=1000):
@@ -535,12 +518,10 @@ def tsne_optimize(Y0, indptr, indices, P, early_exaggeration=12.0, learning_rate
     n = Y.shape[0]
     indptr, indices = L.on_device(indptr, dev, torch.int32), L.on_device(indices, dev, torch.int32)
     P = L.on_device(P, dev, torch.float64)
-    ws = _tsne_ws(L.lib().et_tsne_optimize_workspace_bytes(L.i64(n), L.i64(P.numel())), dev)
+    ws = _tsne_ws(L.lib().et_tsne_optimize_workspace_bytes(n, P.numel()), dev)
     kl, it = C.c_double(0.0), C.c_int(0)
-    L.check(L.lib().et_tsne_optimize(L.ptr(Y), L.i64(n), L.ptr(indptr), L.ptr(indices), L.ptr(P), L.i64(P.numel()),
-                                     C.c_double(early_exaggeration), C.c_double(learning_rate), int(max_iter),
-                                     C.byref(kl), C.byref(it), L.ptr(ws), C.c_size_t(ws.numel()), L.stream(dev)),
-            "et_tsne_optimize")
+    L.call("et_tsne_optimize", L.ptr(Y), n, L.ptr(indptr), L.ptr(indices), L.ptr(P), P.numel(), float(early_exaggeration),
+           float(learning_rate), int(max_iter), C.byref(kl), C.byref(it), L.ptr(ws), ws.numel(), L.stream(dev))
     return Y, kl.value, it.value
 
 
@@ -550,9 +531,8 @@ def tsne_pca_init(X):
     X = L.on_device(X, dev)
     n, d = X.shape
     Y = torch.empty((n, 2), device=dev)
-    ws = _tsne_ws(L.lib().et_tsne_pca_init_workspace_bytes(L.i64(n), d), dev)
-    L.check(L.lib().et_tsne_pca_init(L.ptr(X), L.i64(n), d, L.ptr(Y), L.ptr(ws), C.c_size_t(ws.numel()), L.stream(dev)),
-            "et_tsne_pca_init")
+    ws = _tsne_ws(L.lib().et_tsne_pca_init_workspace_bytes(n, d), dev)
+    L.call("et_tsne_pca_init", L.ptr(X), n, d, L.ptr(Y), L.ptr(ws), ws.numel(), L.stream(dev))
     return Y
 
 
@@ -566,11 +546,10 @@ def fit_gram(obs, pred, mode, static_dist=0.0, which=1):
     g_obs = torch.empty((2 * t_obs, 2 * t_obs), device=dev, dtype=torch.float64)
     g_pred = torch.empty((2 * t_pred, 2 * t_pred), device=dev, dtype=torch.float64)
     count = torch.empty((1,), device=dev, dtype=torch.int64)  # (written by the finish kernel, or zeroed for n == 0: no fill)
-    ws_bytes = L.lib().et_fit_gram_workspace_bytes(L.i64(n), t_obs, t_pred)
+    ws_bytes = L.lib().et_fit_gram_workspace_bytes(n, t_obs, t_pred)
     ws = torch.empty((max(ws_bytes, 8),), device=dev, dtype=torch.uint8)
-    L.check(L.lib().et_fit_gram(L.ptr(obs), L.ptr(pred), L.i64(n), t_obs, t_pred, int(mode), L.f32(static_dist),
-                                int(which), L.ptr(g_obs), L.ptr(g_pred), L.ptr(count), L.ptr(ws),
-                                C.c_size_t(ws.numel()), L.stream(dev)), "et_fit_gram")
+    L.call("et_fit_gram", L.ptr(obs), L.ptr(pred), n, t_obs, t_pred, int(mode), float(static_dist), int(which), L.ptr(g_obs),
+           L.ptr(g_pred), L.ptr(count), L.ptr(ws), ws.numel(), L.stream(dev))
     return g_obs, g_pred, count
 
 
@@ -597,7 +576,7 @@ def fit_descriptor(obs, pred, k, mode, static_dist=0.0, which=1, want_gram=False
     key = (n, t_obs, t_pred)
     ws_bytes = _FIT_WS_BYTES.get(key)
     if ws_bytes is None:
-        ws_bytes = _FIT_WS_BYTES[key] = max(int(L.lib().et_fit_descriptor_workspace_bytes(L.i64(n), t_obs, t_pred)), 8)
+        ws_bytes = _FIT_WS_BYTES[key] = max(int(L.lib().et_fit_descriptor_workspace_bytes(n, t_obs, t_pred)), 8)
     n_small = (do + dp) * k + 2 * k
     n_small += n_small % 2  # (the int64 count behind the floats: 8-byte aligned)
     buf = torch.empty((n_small + 2,), device=dev)
@@ -608,10 +587,10 @@ def fit_descriptor(obs, pred, k, mode, static_dist=0.0, which=1, want_gram=False
     g_pred = torch.empty((dp, dp), device=dev, dtype=torch.float64) if want_gram else None
     ws = torch.empty((ws_bytes,), device=dev, dtype=torch.uint8)
     p_buf = buf.data_ptr()
-    rc = L.fast("et_fit_descriptor")(obs.data_ptr(), pred.data_ptr(), n, t_obs, t_pred, k, int(mode), float(static_dist), int(which),
-                                     p_buf, p_buf + 4 * do * k, p_buf + 4 * (do + dp) * k, p_buf + 4 * ((do + dp) * k + k),
-                                     g_obs.data_ptr() if want_gram else None, g_pred.data_ptr() if want_gram else None,
-                                     p_buf + 4 * n_small, ws.data_ptr(), ws_bytes, L.raw_stream(dev.index))
+    rc = L.lib().et_fit_descriptor(obs.data_ptr(), pred.data_ptr(), n, t_obs, t_pred, k, int(mode), float(static_dist), int(which),
+                                   p_buf, p_buf + 4 * do * k, p_buf + 4 * (do + dp) * k, p_buf + 4 * ((do + dp) * k + k),
+                                   g_obs.data_ptr() if want_gram else None, g_pred.data_ptr() if want_gram else None,
+                                   p_buf + 4 * n_small, ws.data_ptr(), ws_bytes, L.raw_stream(dev.index))
     if rc:
         L.check(rc, "et_fit_descriptor")
     return (U_obs, U_pred, s_obs, s_pred, count) + ((g_obs, g_pred) if want_gram else ())
@@ -624,7 +603,7 @@ def eigh_topk(G, k):
     n = G.shape[0]
     U = torch.empty((n, k), device=dev)
     sigma = torch.empty((k,), device=dev)
-    L.check(L.lib().et_eigh_topk(L.ptr(G), n, int(k), L.ptr(U), L.ptr(sigma), L.stream(dev)), "et_eigh_topk")
+    L.call("et_eigh_topk", L.ptr(G), n, int(k), L.ptr(U), L.ptr(sigma), L.stream(dev))
     return U, sigma
 
 
@@ -641,9 +620,8 @@ def eigh_topk_batch(mats, k):
     outs = [(torch.empty((G.shape[0], kk), device=dev), torch.empty((kk,), device=dev)) for G, kk in zip(mats, ks)]
     b = len(mats)
     PD, PF, PI = C.c_void_p * b, C.c_void_p * b, C.c_int * b
-    L.check(L.lib().et_eigh_topk_batch(b, PD(*[G.data_ptr() for G in mats]), PI(*[G.shape[0] for G in mats]), PI(*ks),
-                                       PF(*[U.data_ptr() for U, _ in outs]), PF(*[s.data_ptr() for _, s in outs]),
-                                       L.stream(dev)), "et_eigh_topk_batch")
+    L.call("et_eigh_topk_batch", b, PD(*[G.data_ptr() for G in mats]), PI(*[G.shape[0] for G in mats]), PI(*ks),
+           PF(*[U.data_ptr() for U, _ in outs]), PF(*[s.data_ptr() for _, s in outs]), L.stream(dev))
     return outs
 
 
@@ -656,18 +634,17 @@ def euc_sim(a, b):
         B, d, m = a.shape
         n = b.shape[2]
         y = torch.empty((B, m, n), device=dev)
-        L.check(L.lib().et_euc_sim_batch(L.ptr(a), L.ptr(b), L.i64(B), d, L.i64(m), L.i64(n), L.ptr(y), L.stream(dev)),
-                "et_euc_sim_batch")
+        L.call("et_euc_sim_batch", L.ptr(a), L.ptr(b), B, d, m, n, L.ptr(y), L.stream(dev))
         return y
     d, m = a.shape
     n = b.shape[1]
     y = torch.empty((m, n), device=dev)
-    L.check(L.lib().et_euc_sim(L.ptr(a), L.ptr(b), d, L.i64(m), L.i64(n), L.ptr(y), L.stream(dev)), "et_euc_sim")
+    L.call("et_euc_sim", L.ptr(a), L.ptr(b), d, m, n, L.ptr(y), L.stream(dev))
     return y
 
 
 def kmeans_workspace(n, d, K, device):
-    nbytes = L.lib().et_kmeans_workspace_bytes(L.i64(n), int(d), int(K))
+    nbytes = L.lib().et_kmeans_workspace_bytes(n, int(d), int(K))
     if nbytes == 0:
         raise ValueError(f"k-means dimensions out of range: d={d} (<= {L.KMEANS_MAX_D}), K={K} (<= {L.KMEANS_MAX_CLUSTERS})")
     return torch.empty((nbytes,), device=device, dtype=torch.uint8)
@@ -680,8 +657,8 @@ def kmeans_init_farthest(X, K, first_index, workspace=None):
     d, n = X.shape
     ws = workspace if workspace is not None else kmeans_workspace(n, d, K, dev)
     c0 = torch.empty((d, K), device=dev)
-    L.check(L.lib().et_kmeans_init_farthest(L.ptr(X), L.i64(n), d, int(K), L.i64(first_index), L.ptr(c0), L.ptr(ws),
-                                            C.c_size_t(ws.numel()), L.stream(dev)), "et_kmeans_init_farthest")
+    L.call("et_kmeans_init_farthest", L.ptr(X), n, d, int(K), int(first_index), L.ptr(c0), L.ptr(ws), ws.numel(),
+           L.stream(dev))
     return c0
 
 
@@ -702,9 +679,8 @@ def kmeans_fit(X, centroids, max_iter=100, tol=1e-4, workspace=None, timing=Fals
     trace_t = torch.zeros((max_iter, 2), device=dev) if trace else None
     st = L.KMeansState()
     tm = L.KMeansTiming() if timing else None
-    L.check(L.lib().et_kmeans_fit(L.ptr(X), L.i64(n), d, K, int(max_iter), L.f32(tol), L.ptr(cen), L.ptr(labels),
-                                  L.ptr(trace_t), C.byref(st), C.byref(tm) if timing else None, L.ptr(ws),
-                                  C.c_size_t(ws.numel()), L.stream(dev)), "et_kmeans_fit")
+    L.call("et_kmeans_fit", L.ptr(X), n, d, K, int(max_iter), float(tol), L.ptr(cen), L.ptr(labels), L.ptr(trace_t),
+           C.byref(st), C.byref(tm) if timing else None, L.ptr(ws), ws.numel(), L.stream(dev))
     out = dict(centroids=cen, labels=labels, n_iter=int(st.iter), error=float(st.error), inertia=float(st.inertia),
                trace=trace_t[:int(st.iter)] if trace else None, done=bool(st.done))
     if timing:
@@ -722,16 +698,15 @@ def kmeans_fit_batch(X, centroids, max_iter=100, tol=1e-4, want_labels=False):
     B, d, K = centroids.shape
     n = X.shape[-1]
     x_stride = 0 if X.dim() == 2 else d * n
-    nbytes = L.lib().et_kmeans_batch_workspace_bytes(L.i64(n), int(d), int(K), L.i64(B))
+    nbytes = L.lib().et_kmeans_batch_workspace_bytes(n, int(d), int(K), B)
     if nbytes == 0:
         raise ValueError(f"k-means dimensions out of range: d={d}, K={K}")
     ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
     cen = centroids.clone()
     labels = torch.empty((B, n), device=dev, dtype=torch.int64) if want_labels else None
     states = (L.KMeansState * B)()
-    L.check(L.lib().et_kmeans_fit_batch(L.ptr(X), L.i64(x_stride), L.i64(n), int(d), int(K), L.i64(B), int(max_iter), L.f32(tol),
-                                        L.ptr(cen), L.ptr(labels), states, L.ptr(ws), C.c_size_t(ws.numel()), L.stream(dev)),
-            "et_kmeans_fit_batch")
+    L.call("et_kmeans_fit_batch", L.ptr(X), x_stride, n, int(d), int(K), B, int(max_iter), float(tol), L.ptr(cen),
+           L.ptr(labels), states, L.ptr(ws), ws.numel(), L.stream(dev))
     return dict(centroids=cen, labels=labels, n_iter=[int(s_.iter) for s_ in states], error=[float(s_.error) for s_ in states],
                 inertia=[float(s_.inertia) for s_ in states], done=[bool(s_.done) for s_ in states])
 
@@ -747,15 +722,14 @@ def kmeanspp_seed_batch(X, K, uniforms):
     B = uniforms.shape[0]
     if uniforms.dim() != 2 or uniforms.shape[1] != 1 + (K - 1) * nt:
         raise ValueError(f"k-means++ seeding of {K} centres consumes {1 + (K - 1) * nt} draws per initialisation")
-    nbytes = L.lib().et_kmeanspp_batch_workspace_bytes(L.i64(n), d, nt, L.i64(B))
+    nbytes = L.lib().et_kmeanspp_batch_workspace_bytes(n, d, nt, B)
     if nbytes == 0:
         raise ValueError(f"k-means++ dimensions out of range: N={n}, d={d}, K={K}")
     ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
     centers = torch.empty((B, d, K), device=dev)
     indices = torch.empty((B, K), device=dev, dtype=torch.int64)
-    L.check(L.lib().et_kmeanspp_seed_batch(L.ptr(X), L.i64(n), d, int(K), nt, L.ptr(uniforms), L.i64(B), L.ptr(centers),
-                                           L.ptr(indices), L.ptr(ws), C.c_size_t(ws.numel()), L.stream(dev)),
-            "et_kmeanspp_seed_batch")
+    L.call("et_kmeanspp_seed_batch", L.ptr(X), n, d, int(K), nt, L.ptr(uniforms), B, L.ptr(centers), L.ptr(indices),
+           L.ptr(ws), ws.numel(), L.stream(dev))
     return centers, indices
 
 
@@ -763,8 +737,7 @@ def kmeans_joint_done(state_ptrs, n_problems, tol):
     """kmeans.py:228-240 for a batch of problems run through the step API: ``state_ptrs`` = int64 device tensor of the
     problems' state-block addresses; sets every state's ``done`` from the SUM of their errors."""
     dev = L.require_device(state_ptrs)
-    L.check(L.lib().et_kmeans_joint_done(L.ptr(state_ptrs), int(n_problems), L.f32(tol), L.stream(dev)),
-            "et_kmeans_joint_done")
+    L.call("et_kmeans_joint_done", L.ptr(state_ptrs), int(n_problems), float(tol), L.stream(dev))
 
 
 def kmeans_predict(X, centroids, want_maxsims=True):
@@ -777,21 +750,20 @@ def kmeans_predict(X, centroids, want_maxsims=True):
         d, n = X.shape[-2], X.shape[-1]
         labels = torch.empty((B, n), device=dev, dtype=torch.int64)
         maxsims = torch.empty((B, n), device=dev) if want_maxsims else None
-        L.check(L.lib().et_kmeans_predict_batch(L.ptr(X), L.i64(d * n if X.dim() == 3 else 0), L.i64(B), L.i64(n), d,
-                                                L.ptr(centroids), centroids.shape[2], L.ptr(labels), L.ptr(maxsims),
-                                                L.stream(dev)), "et_kmeans_predict_batch")
+        L.call("et_kmeans_predict_batch", L.ptr(X), d * n if X.dim() == 3 else 0, B, n, d, L.ptr(centroids),
+               centroids.shape[2], L.ptr(labels), L.ptr(maxsims), L.stream(dev))
         return labels, maxsims
     d, n = X.shape
     labels = torch.empty((n,), device=dev, dtype=torch.int64)
     maxsims = torch.empty((n,), device=dev) if want_maxsims else None
-    L.check(L.lib().et_kmeans_predict(L.ptr(X), L.i64(n), d, L.ptr(centroids), centroids.shape[1], L.ptr(labels),
-                                      L.ptr(maxsims), L.stream(dev)), "et_kmeans_predict")
+    L.call("et_kmeans_predict", L.ptr(X), n, d, L.ptr(centroids), centroids.shape[1], L.ptr(labels), L.ptr(maxsims),
+           L.stream(dev))
     return labels, maxsims
 
 
 # ------------------------------------- BatchKMeans in the reference's own summation orders (opt-in)
 def _reforder_ws(n, d, K, dev):
-    nbytes = L.lib().et_kmeans_reforder_workspace_bytes(L.i64(n), int(d), int(K))
+    nbytes = L.lib().et_kmeans_reforder_workspace_bytes(n, int(d), int(K))
     if nbytes == 0:
         raise ValueError(f"k-means dimensions out of range: d={d} (<= {L.KMEANS_MAX_D}), K={K} (<= {L.KMEANS_MAX_CLUSTERS})")
     return torch.empty((nbytes,), device=dev, dtype=torch.uint8)
@@ -804,8 +776,7 @@ def euc_sim_reference_order(a, b):
     d, m = a.shape
     n = b.shape[1]
     y = torch.empty((m, n), device=dev)
-    L.check(L.lib().et_euc_sim_reforder(L.ptr(a), L.ptr(b), d, L.i64(m), L.i64(n), L.ptr(y), L.stream(dev)),
-            "et_euc_sim_reforder")
+    L.call("et_euc_sim_reforder", L.ptr(a), L.ptr(b), d, m, n, L.ptr(y), L.stream(dev))
     return y
 
 
@@ -816,8 +787,8 @@ def kmeans_init_farthest_reference_order(X, K, first_index):
     d, n = X.shape
     ws = _reforder_ws(n, d, K, dev)
     c0 = torch.empty((d, K), device=dev)
-    L.check(L.lib().et_kmeans_init_farthest_reforder(L.ptr(X), L.i64(n), d, int(K), L.i64(first_index), L.ptr(c0), L.ptr(ws),
-                                                     C.c_size_t(ws.numel()), L.stream(dev)), "et_kmeans_init_farthest_reforder")
+    L.call("et_kmeans_init_farthest_reforder", L.ptr(X), n, d, int(K), int(first_index), L.ptr(c0), L.ptr(ws), ws.numel(),
+           L.stream(dev))
     return c0
 
 
@@ -830,8 +801,8 @@ def kmeans_predict_reference_order(X, centroids):
     ws = _reforder_ws(n, d, K, dev)
     labels = torch.empty((n,), device=dev, dtype=torch.int64)
     maxsims = torch.empty((n,), device=dev)
-    L.check(L.lib().et_kmeans_predict_reforder(L.ptr(X), L.i64(n), d, L.ptr(centroids), K, L.ptr(labels), L.ptr(maxsims),
-                                               L.ptr(ws), C.c_size_t(ws.numel()), L.stream(dev)), "et_kmeans_predict_reforder")
+    L.call("et_kmeans_predict_reforder", L.ptr(X), n, d, L.ptr(centroids), K, L.ptr(labels), L.ptr(maxsims), L.ptr(ws),
+           ws.numel(), L.stream(dev))
     return labels, maxsims
 
 
@@ -850,7 +821,7 @@ def kmeans_fit_reference_order_batch(X, centroids, max_iter=100, tol=1e-4, trace
     X, centroids = _dev_args(dev, X, centroids)
     nb, d, n = X.shape
     K = centroids.shape[2]
-    nbytes = L.lib().et_kmeans_reforder_batch_workspace_bytes(L.i64(n), int(d), int(K), L.i64(nb))
+    nbytes = L.lib().et_kmeans_reforder_batch_workspace_bytes(n, int(d), int(K), nb)
     if nbytes == 0:
         if nb > 1:
             raise NotImplementedError(f"sums='reference-order' with l = {nb} > 1 problems takes d = 6, K <= 32, 1024 <= N < 2^29, "
@@ -862,10 +833,8 @@ def kmeans_fit_reference_order_batch(X, centroids, max_iter=100, tol=1e-4, trace
     trace_t = torch.zeros((nb, max_iter, 2), device=dev) if trace else None
     st = (L.KMeansState * nb)()
     tm = L.KMeansTiming() if timing else None
-    L.check(L.lib().et_kmeans_fit_reforder_batch(L.ptr(X), L.i64(d * n), L.i64(n), d, K, L.i64(nb), int(max_iter), L.f32(tol),
-                                                 L.ptr(cen), L.ptr(labels), L.ptr(trace_t), st, C.byref(tm) if timing else None,
-                                                 L.ptr(ws), C.c_size_t(ws.numel()), L.stream(dev)),
-            "et_kmeans_fit_reforder_batch")
+    L.call("et_kmeans_fit_reforder_batch", L.ptr(X), d * n, n, d, K, nb, int(max_iter), float(tol), L.ptr(cen),
+           L.ptr(labels), L.ptr(trace_t), st, C.byref(tm) if timing else None, L.ptr(ws), ws.numel(), L.stream(dev))
     out = []
     for b in range(nb):
         r = dict(centroids=cen[b], labels=labels[b], n_iter=int(st[b].iter), error=float(st[b].error),
@@ -880,7 +849,7 @@ def reference_order_shard_sizes(n_total, world, d=6, K=20):
     """How to split n_total points over `world` ranks so that sums="reference-order" gives the single-GPU bits: every
     rank before the last non-empty one holds whole level-2 blocks of ATen's cascade (include/eigentraj.h,
     et_kmeans_fit_reforder_sharded); as even as that allows.  -> list of `world` sizes (trailing ranks may be empty)."""
-    block = int(L.lib().et_kmeans_reforder_shard_block(L.i64(n_total), int(d), int(K)))
+    block = int(L.lib().et_kmeans_reforder_shard_block(int(n_total), int(d), int(K)))
     if block == 0:
         raise NotImplementedError(f"sharded sums='reference-order' takes d = 6, K <= 32, 1024 <= N < 2^29 (got d={d}, K={K}, N={n_total})")
     blocks = -(-int(n_total) // block)
@@ -913,11 +882,9 @@ def kmeans_fit_reference_order_sharded(X_local, centroids, n_locals, rank, comm=
     labels = torch.empty((n,), device=dev, dtype=torch.int64)
     trace_t = torch.zeros((max_iter, 2), device=dev) if trace else None
     st = L.KMeansState()
-    L.check(L.lib().et_kmeans_fit_reforder_sharded(L.ptr(X_local) if n else None, sizes, len(n_locals), int(rank), int(d), int(K),
-                                                   int(max_iter), L.f32(tol), L.ptr(cen), L.ptr(labels) if n else None,
-                                                   L.ptr(trace_t), C.byref(st), L.ptr(ws), C.c_size_t(ws.numel()),
-                                                   comm.handle if comm is not None else None, L.stream(dev)),
-            "et_kmeans_fit_reforder_sharded")
+    L.call("et_kmeans_fit_reforder_sharded", L.ptr(X_local) if n else None, sizes, len(n_locals), int(rank), int(d), int(K),
+           int(max_iter), float(tol), L.ptr(cen), L.ptr(labels) if n else None, L.ptr(trace_t), C.byref(st), L.ptr(ws),
+           ws.numel(), comm.handle if comm is not None else None, L.stream(dev))
     return dict(centroids=cen, labels=labels, n_iter=int(st.iter), error=float(st.error), inertia=float(st.inertia),
                 trace=trace_t[:int(st.iter)] if trace else None, done=bool(st.done))
 
@@ -932,8 +899,8 @@ def center_columns(X, rel_tol=1e-4):
     mean = torch.empty((d,), device=dev)
     tol = torch.empty((1,), device=dev)
     ws = torch.empty((2 * L.KMEANS_MAX_D,), device=dev)
-    L.check(L.lib().et_center_columns(L.ptr(Xc), L.i64(n), d, L.f32(rel_tol), L.ptr(mean), L.ptr(tol), L.ptr(ws),
-                                      C.c_size_t(ws.numel() * 4), L.stream(dev)), "et_center_columns")
+    L.call("et_center_columns", L.ptr(Xc), n, d, float(rel_tol), L.ptr(mean), L.ptr(tol), L.ptr(ws), ws.numel() * 4,
+           L.stream(dev))
     return Xc, mean, tol
 
 
@@ -954,14 +921,14 @@ def kmeanspp_seed(X, K, uniforms, workspace=None):
     if uniforms.numel() != 1 + (K - 1) * nt:
         raise ValueError(f"k-means++ seeding of {K} centres consumes {1 + (K - 1) * nt} draws, got {uniforms.numel()}")
     if workspace is None:
-        nbytes = L.lib().et_kmeanspp_workspace_bytes(L.i64(n), d, nt)
+        nbytes = L.lib().et_kmeanspp_workspace_bytes(n, d, nt)
         if nbytes == 0:
             raise ValueError(f"k-means++ dimensions out of range: N={n}, d={d}, K={K}")
         workspace = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
     centers = torch.empty((d, K), device=dev)
     indices = torch.empty((K,), device=dev, dtype=torch.int64)
-    L.check(L.lib().et_kmeanspp_seed(L.ptr(X), L.i64(n), d, int(K), nt, L.ptr(uniforms), L.ptr(centers), L.ptr(indices),
-                                     L.ptr(workspace), C.c_size_t(workspace.numel()), L.stream(dev)), "et_kmeanspp_seed")
+    L.call("et_kmeanspp_seed", L.ptr(X), n, d, int(K), nt, L.ptr(uniforms), L.ptr(centers), L.ptr(indices), L.ptr(workspace),
+           workspace.numel(), L.stream(dev))
     return centers, indices
 
 
@@ -991,24 +958,21 @@ class KMeansShard:
         return self.state.view(torch.float64)
 
     def scan(self):
-        L.check(L.lib().et_kmeans_scan(L.ptr(self.X), L.i64(self.n), self.d, L.ptr(self.state), L.stream(self.dev)),
-                "et_kmeans_scan")
+        L.call("et_kmeans_scan", L.ptr(self.X), self.n, self.d, L.ptr(self.state), L.stream(self.dev))
 
     def begin(self, n_total, centroids):
-        L.check(L.lib().et_kmeans_begin(L.ptr(self.state), L.i64(n_total), L.ptr(centroids), self.d, self.K,
-                                        L.stream(self.dev)), "et_kmeans_begin")
+        L.call("et_kmeans_begin", L.ptr(self.state), int(n_total), L.ptr(centroids), self.d, self.K, L.stream(self.dev))
 
     def init_step(self, i, C0, index_base):
         """candidate record of farthest-first step i: uint8 tensor {key u64, d floats}."""
-        L.check(L.lib().et_kmeans_init_step(L.ptr(self.X), L.i64(self.n), self.d, self.K, int(i), L.ptr(C0),
-                                            L.ptr(self.best), L.i64(index_base), L.ptr(self.cand), L.ptr(self.ws),
-                                            C.c_size_t(self.ws.numel()), L.stream(self.dev)), "et_kmeans_init_step")
+        L.call("et_kmeans_init_step", L.ptr(self.X), self.n, self.d, self.K, int(i), L.ptr(C0), L.ptr(self.best),
+               int(index_base), L.ptr(self.cand), L.ptr(self.ws), self.ws.numel(), L.stream(self.dev))
         return self.cand
 
     def init_select(self, cands, n_cands, stride, col, C0):
         """Column ``col`` of C0 <- the candidate record with the smallest key among ``n_cands`` gathered records."""
-        L.check(L.lib().et_kmeans_init_select(L.ptr(cands), int(n_cands), int(stride), self.d, self.K, int(col), L.ptr(C0),
-                                              L.stream(self.dev)), "et_kmeans_init_select")
+        L.call("et_kmeans_init_select", L.ptr(cands), int(n_cands), int(stride), self.d, self.K, int(col), L.ptr(C0),
+               L.stream(self.dev))
 
     def post_state(self):
         """Start an asynchronous copy of the state block to pinned host memory; -> handle for ``wait_state``."""
@@ -1028,25 +992,22 @@ class KMeansShard:
 
     def gather_point(self, local_index):
         pt = torch.empty((self.d,), device=self.dev)
-        L.check(L.lib().et_kmeans_gather_point(L.ptr(self.X), L.i64(self.n), self.d, L.i64(local_index), L.ptr(pt),
-                                               L.stream(self.dev)), "et_kmeans_gather_point")
+        L.call("et_kmeans_gather_point", L.ptr(self.X), self.n, self.d, int(local_index), L.ptr(pt), L.stream(self.dev))
         return pt
 
     def assign(self, centroids, given_labels=None):
-        L.check(L.lib().et_kmeans_assign_accumulate(L.ptr(self.X), L.i64(self.n), self.d, self.K, L.ptr(self.state),
-                                                    L.ptr(centroids), L.ptr(given_labels), L.ptr(self.labels_u8),
-                                                    L.ptr(self.partials), L.ptr(self.ws), C.c_size_t(self.ws.numel()),
-                                                    L.stream(self.dev)), "et_kmeans_assign_accumulate")
+        L.call("et_kmeans_assign_accumulate", L.ptr(self.X), self.n, self.d, self.K, L.ptr(self.state), L.ptr(centroids),
+               L.ptr(given_labels), L.ptr(self.labels_u8), L.ptr(self.partials), L.ptr(self.ws), self.ws.numel(),
+               L.stream(self.dev))
         return self.partials
 
     def update(self, partials, centroids, tol, trace=None):
-        L.check(L.lib().et_kmeans_update(L.ptr(self.state), L.ptr(partials), self.d, self.K, L.f32(tol),
-                                         L.ptr(centroids), L.ptr(trace), L.stream(self.dev)), "et_kmeans_update")
+        L.call("et_kmeans_update", L.ptr(self.state), L.ptr(partials), self.d, self.K, float(tol), L.ptr(centroids),
+               L.ptr(trace), L.stream(self.dev))
 
     def labels(self):
         out = torch.empty((self.n,), device=self.dev, dtype=torch.int64)
-        L.check(L.lib().et_kmeans_labels_i64(L.ptr(self.labels_u8), L.i64(self.n), L.ptr(out), L.stream(self.dev)),
-                "et_kmeans_labels_i64")
+        L.call("et_kmeans_labels_i64", L.ptr(self.labels_u8), self.n, L.ptr(out), L.stream(self.dev))
         return out
 
     def read_state(self):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from . import _abi_header as H
 from . import _golden as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,9 +17,7 @@ needs_no_gpu = pytest.mark.skipif(torch.cuda.is_available(), reason="asserts the
 
 
 def header_functions():
-    src = open(os.path.join(ROOT, "include", "eigentraj.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(et_[a-z0-9_]+)\s*\(", src)))
+    return sorted(set(re.findall(r"\b(et_[a-z0-9_]+)\s*\(", H.text())))
 
 
 def test_library_exports_every_declared_symbol():
@@ -171,7 +170,6 @@ def test_round2_entry_points_validate_arguments_on_the_host():
     from eigentrajectory_amd import _lib
     lib = _lib.lib()
     null, i64, f32 = ctypes.c_void_p(0), ctypes.c_int64, ctypes.c_float
-    lib.et_kmeans_sharded_workspace_bytes.restype = ctypes.c_size_t
     assert lib.et_kmeanspp_workspace_bytes(i64(10_000), 6, 4) > 4 * 10_000 * 5
     assert lib.et_kmeanspp_workspace_bytes(i64(10_000), 6, 9) == 0          # more candidates than 2 + ln(255)
     assert lib.et_kmeanspp_workspace_bytes(i64(0), 6, 4) == 0
@@ -220,3 +218,78 @@ def test_reference_order_shard_geometry_on_the_host():
     assert ws([16384, 0, 1000], 1) > 0         # (an empty rank holds zero blocks wherever it sits)
     assert ws([16384, 1000], 2) == 0 and ws([16384, 1000], 0, K=33) == 0
     assert ws([16384, 16384, 0], 2) > 0        # trailing empty ranks take part in the collectives
+
+
+def c_type_to_ctypes(spelling):
+    """The binding's mapping rule (eigentrajectory_amd/_lib.py); None for a spelling outside it."""
+    t = " ".join(spelling.replace("const", " ").split())
+    if "*" in t:
+        return ctypes.c_char_p if t.replace(" ", "") == "char*" else ctypes.c_void_p
+    return {"et_stream_t": ctypes.c_void_p, "et_comm_t": ctypes.c_void_p, "int": ctypes.c_int, "int64_t": ctypes.c_int64,
+            "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}.get(t)
+
+
+def test_signature_table_matches_the_header():
+    """Every prototype of include/eigentraj.h, mapped by the rule, is the table's entry; the prototypes the parser reads
+    are all the et_*( names of the header and all the table's keys; lib() declares exactly the table on the handle."""
+    from eigentrajectory_amd import _lib
+    protos = H.functions()
+    assert sorted(protos) == header_functions() == sorted(_lib.SIGNATURES)
+    assert list(protos) == list(_lib.SIGNATURES) == _lib.SYMBOLS  # the header's order
+    for name, (ret, params) in protos.items():
+        mapped = [c_type_to_ctypes(t) for t in [ret] + params]
+        assert None not in mapped, f"{name}: C type outside the mapping rule in {[ret] + params}"
+        assert _lib.SIGNATURES[name] == (mapped[0], mapped[1:]), name
+    lib = _lib.lib()
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+
+
+def test_mirrored_constants_equal_the_headers_defines():
+    from eigentrajectory_amd import _lib
+    d = H.defines()
+    mirrored = dict(ET_ABI_VERSION=_lib.ABI_VERSION, ET_OK=_lib.ET_OK, ET_ERR_BAD_DATA=_lib.ET_ERR_BAD_DATA,
+                    ET_MODE_STATIC=_lib.MODE_STATIC, ET_MODE_MOVING=_lib.MODE_MOVING, ET_MODE_SPLIT=_lib.MODE_SPLIT,
+                    ET_MODE_IDENTITY=_lib.MODE_IDENTITY, ET_MAX_T=_lib.MAX_T, ET_MAX_K=_lib.MAX_K,
+                    ET_KMEANS_MAX_D=_lib.KMEANS_MAX_D, ET_KMEANS_MAX_CLUSTERS=_lib.KMEANS_MAX_CLUSTERS,
+                    ET_SCENE_MAX_N=_lib.SCENE_MAX_N, ET_CURVE_MAX_FITS=_lib.CURVE_MAX_FITS,
+                    ET_STGCNN_MAX_LAYERS=_lib.STGCNN_MAX_LAYERS, ET_SGCN_MAX_LAYERS=_lib.SGCN_MAX_LAYERS,
+                    ET_SGCN_MAX_N=_lib.SGCN_MAX_N)
+    for name, value in mirrored.items():
+        assert d[name] == value, name
+
+
+def test_binding_refuses_wrong_calls_without_device_work():
+    """Declared signatures: a missing argument and a float in an integer slot are errors, and a plain int beyond 32 bits
+    reaches an int64_t parameter whole (as does the size_t on the way back)."""
+    from eigentrajectory_amd import _lib
+    lib = _lib.lib()
+    with pytest.raises(TypeError):
+        lib.et_kmeans_partials_len(6)
+    with pytest.raises(ctypes.ArgumentError):
+        lib.et_kmeans_partials_len(6.0, 20)
+    assert lib.et_kmeans_workspace_bytes(2**33, 6, 20) > 2**32
+
+
+def test_call_sites_pass_as_many_arguments_as_the_table_declares():
+    """ctypes accepts surplus arguments (cdecl), so the count is checked on the source: every L.call("et_x", ...) and
+    every ....et_x(...) of the package whose name is in the table and that spreads no * / ** argument."""
+    import ast
+    import glob
+    from eigentrajectory_amd import _lib
+    checked = 0
+    for path in sorted(glob.glob(os.path.join(ROOT, "eigentrajectory_amd", "*.py"))):
+        for node in ast.walk(ast.parse(open(path).read(), path)):
+            if not isinstance(node, ast.Call) or not isinstance(node.func, ast.Attribute):
+                continue
+            name, args = node.func.attr, node.args
+            if (name == "call" and args and isinstance(args[0], ast.Constant) and isinstance(args[0].value, str)
+                    and args[0].value.startswith("et_")):
+                name, args = args[0].value, args[1:]
+                assert name in _lib.SIGNATURES, f"{path}:{node.lineno}: call() of {name}, which the table lacks"
+            if name not in _lib.SIGNATURES or node.keywords or any(isinstance(a, ast.Starred) for a in args):
+                continue
+            assert len(args) == len(_lib.SIGNATURES[name][1]), f"{path}:{node.lineno}: {name}"
+            checked += 1
+    assert checked >= 70, checked

@@ -9,10 +9,10 @@ import numpy as np
 import pytest
 import torch
 
+from . import _abi_header as H
 from . import _golden as G
 from . import _sgcn_np as SN
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 Z = G.load("g20_sgcn_net.npz")
 PICKS = sorted({k.split(".")[0] for k in Z.files if k.startswith("pick")}, key=lambda t: int(t[4:]))
 GEN_ARGS = dict(number_asymmetric_conv_layer=3, n_tcn=2, out_dims=12)
@@ -169,20 +169,13 @@ def test_evaluate_split_refuses_other_predictors():
 
 def test_sgcn_abi_names_declared_and_listed():
     from eigentrajectory_amd import _lib
-    with open(os.path.join(ROOT, "include", "eigentraj.h")) as f:
-        header = f.read()
+    header = H.text()
     for name in ("et_sgcn_workspace_bytes", "et_sgcn_forward_scenes", "et_sgcn_forward_graph"):
         assert re.search(rf"\b{name}\(", header) and name in _lib.SYMBOLS, name
     for struct, mirror in (("et_sgcn_attention", _lib.SGCNAttention), ("et_sgcn_asym", _lib.SGCNAsym),
                            ("et_sgcn_gcn", _lib.SGCNGcn)):
-        fields = re.search(rf"typedef struct {struct} \{{(.*?)\}} {struct};", header, re.S).group(1)
-        assert re.findall(r"\*(\w+)", fields) == [f for f, _ in mirror._fields_], struct
-    body = re.search(r"typedef struct et_sgcn_params \{(.*?)\} et_sgcn_params;", header, re.S).group(1)
-    names = []
-    for decl in body.split(";"):
-        decl = re.sub(r"\[[^\]]*\]", "", decl).strip()
-        if decl:
-            names += [n.strip(" *") for n in re.sub(r"^(const\s+)?\w+\s", "", decl).split(",")]
+        assert H.struct_fields(struct) == [f for f, _ in mirror._fields_], struct
+    names = H.struct_fields("et_sgcn_params")
     assert names == [f for f, _ in _lib.SGCNParams._fields_]
     assert f"#define ET_SGCN_MAX_LAYERS {_lib.SGCN_MAX_LAYERS}" in header and f"#define ET_SGCN_MAX_N {_lib.SGCN_MAX_N}" in header
     if os.path.exists(_lib.LIB_PATH):

@@ -8,10 +8,10 @@ import numpy as np
 import pytest
 import torch
 
+from . import _abi_header as H
 from . import _golden as G
 from . import _stgcnn_np as SN
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 Z = G.load("g19_stgcnn.npz")
 PICKS = sorted({k.split(".")[0] for k in Z.files if k.startswith("pick")}, key=lambda t: int(t[4:]))
 
@@ -97,12 +97,10 @@ def test_training_mode_forward_raises():
 
 def test_stgcnn_abi_names_declared_and_listed():
     from eigentrajectory_amd import _lib
-    with open(os.path.join(ROOT, "include", "eigentraj.h")) as f:
-        header = f.read()
+    header = H.text()
     for name in ("et_stgcnn_workspace_bytes", "et_stgcnn_forward_scenes", "et_stgcnn_forward_graph"):
         assert re.search(rf"\b{name}\(", header) and name in _lib.SYMBOLS, name
-    fields = re.search(r"typedef struct et_stgcnn_layer \{(.*?)\} et_stgcnn_layer;", header, re.S).group(1)
-    names = re.findall(r"\*(\w+)", fields)
+    names = H.struct_fields("et_stgcnn_layer")
     assert names == [f for f, _ in _lib.STGCNNLayer._fields_]
     if os.path.exists(_lib.LIB_PATH):
         p = _lib.STGCNNParams()

@@ -8,10 +8,10 @@ import zlib
 import numpy as np
 import pytest
 
+from . import _abi_header as H
 from . import _golden as G
 from . import _tsne_np as T
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 Z = G.load("g18_tsne.npz")
 NAMES = ["et_tsne_neighbors", "et_tsne_affinities_workspace_bytes", "et_tsne_affinities",
          "et_tsne_kl_grad_workspace_bytes", "et_tsne_kl_grad", "et_tsne_update", "et_tsne_optimize_workspace_bytes",
@@ -24,8 +24,7 @@ def crc(a):
 
 def test_tsne_abi_names_declared_listed_and_exported():
     from eigentrajectory_amd import _lib
-    with open(os.path.join(ROOT, "include", "eigentraj.h")) as f:
-        header = f.read()
+    header = H.text()
     for name in NAMES:
         assert re.search(rf"\b{name}\(", header), name
         assert name in _lib.SYMBOLS, name

@@ -54,13 +54,13 @@ def main():
         L = ops.L
 
         def tensor_form(col=True):
-            L.check(L.lib().et_traj_metrics(L.ptr(pred), L.i64(n), S, 12, L.ptr(gt), L.ptr(off), len(sizes), *map(L.ptr, outs[:3]),
-                                            L.ptr(outs[3] if col else None), L.ptr(outs[4]), L.stream(dev)), "et_traj_metrics")
+            L.call("et_traj_metrics", L.ptr(pred), n, S, 12, L.ptr(gt), L.ptr(off), len(sizes), *map(L.ptr, outs[:3]),
+                   L.ptr(outs[3] if col else None), L.ptr(outs[4]), L.stream(dev))
 
         def fused():
-            L.check(L.lib().et_anchor_reconstruct_metrics_scenes(
-                L.ptr(C), L.i64(n), S, k, 8, 12, None, L.ptr(nrm), None, None, None, L.ptr(U[0]), L.ptr(U[1]), ops.MODE_SPLIT,
-                L.f32(0.3), L.ptr(gt), L.ptr(off), len(sizes), *map(L.ptr, outs), L.stream(dev)), "fused")
+            L.call("et_anchor_reconstruct_metrics_scenes", L.ptr(C), n, S, k, 8, 12, None, L.ptr(nrm), None, None, None,
+                   L.ptr(U[0]), L.ptr(U[1]), ops.MODE_SPLIT, 0.3, L.ptr(gt), L.ptr(off), len(sizes), *map(L.ptr, outs),
+                   L.stream(dev))
         res[name] = dict(rows=n, scenes=len(sizes), S=S, tensor_ms=timed(tensor_form, args.reps),
                          tensor_no_col_ms=timed(lambda: tensor_form(False), args.reps), fused_ms=timed(fused, args.reps))
         print(json.dumps({name: res[name]}), flush=True)
