@@ -31,16 +31,11 @@ constexpr int kTile = 256;  // trajectories (or pairs) per workgroup = threads p
 // workgroup -> tile.  Workgroup b runs on XCD b % 8, so the identity map deals consecutive tiles round-robin over the
 // XCDs.  The projection instead gives every XCD one contiguous eighth of the tiles: -1.1 ... -2.0 % on its 0.40 ms in
 // four same-box A/B runs (profiles/r04d_tile_maps.txt); the S = 1 reconstruction LOSES 3-4 % with the same map and keeps
-// the identity.  (-DET_TILE_MAP=0 / 1 forces one map for both; 2: projection walks the rows from the end -- the rows the
-// preceding fit read last might still be in the Infinity Cache: they are not, +-0.)
-#ifndef ET_TILE_MAP
-#define ET_TILE_MAP 3
-#endif
+// the identity.  (The projection walking its rows from the end -- the rows the preceding fit read last might still be in
+// the Infinity Cache: they are not -- measured +-0.)
 template <bool PROJECT = false>
 __device__ __forceinline__ int64_t tile_of_block() {
-    constexpr bool contiguous = ET_TILE_MAP == 1 || (ET_TILE_MAP == 3 && PROJECT);
-    if (ET_TILE_MAP == 2 && PROJECT) return (int64_t)gridDim.x - 1 - blockIdx.x;
-    if (contiguous) {
+    if (PROJECT) {
         // XCD x owns the tiles [x q + min(x, r), ...) with q = grid / 8, r = grid % 8: a bijection for EVERY grid size
         const unsigned q = gridDim.x / 8, r = gridDim.x % 8, x = blockIdx.x % 8;
         return (int64_t)(x * q + (x < r ? x : r) + blockIdx.x / 8);
@@ -353,10 +348,6 @@ __global__ __launch_bounds__(kTile) void scene_project_kernel(
 }
 
 constexpr int kNormStride = 8;  // floats per cached RowNorm in LDS
-#ifndef ET_RECON_DIRECT
-#define ET_RECON_DIRECT 0
-#endif
-constexpr bool kReconDirect = ET_RECON_DIRECT != 0;  // experiment: per-lane row stores instead of the LDS-staged tile
 
 __device__ __forceinline__ void store_row_norm(float *s, const RowNorm &p) {
     s[0] = p.ox;
@@ -387,10 +378,7 @@ __device__ __forceinline__ RowNorm fetch_row_norm(const float *s) {
 // The (S, TN, 2T) result tile is staged in LDS and written back with coalesced float4 stores
 // (each sample plane of the (S,N,T,2) output is a contiguous run of TN rows).
 // ------------------------------------------------------------------------------------------
-#ifndef ET_RECON_TILES
-#define ET_RECON_TILES 4
-#endif
-constexpr int kReconTiles = ET_RECON_TILES;  // consecutive tiles per workgroup when S > 1 (U / anchors staged once)
+constexpr int kReconTiles = 4;  // consecutive tiles per workgroup when S > 1 (U / anchors staged once)
 
 template <int TP, int K, bool STREAM>
 __global__ __launch_bounds__(kTile) void reconstruct_tile_kernel(
@@ -436,7 +424,6 @@ __global__ __launch_bounds__(kTile) void reconstruct_tile_kernel(
     }
     for (int it = 0; it < tiles && rows > 0; ++it) {
         const int npairs = rows * S;
-        const int64_t n = n0 + nl;
         if (S != 1 && tid < rows) store_row_norm(sNorm + tid * kNormStride, p);
         __syncthreads();  // U / anchors / this tile's normaliser state staged; the previous tile's write-back is done
 
@@ -447,8 +434,7 @@ __global__ __launch_bounds__(kTile) void reconstruct_tile_kernel(
             float c[K];
 #pragma unroll
             for (int j = 0; j < K; ++j) c[j] = a[j * S + s] + craw[j];  // anchor.py:87
-            float4 *dst = kReconDirect ? reinterpret_cast<float4 *>(out + (((int64_t)s * N + n) * DP))
-                                       : reinterpret_cast<float4 *>(sOut + ((size_t)s * rows + nl) * DP);
+            float4 *dst = reinterpret_cast<float4 *>(sOut + ((size_t)s * rows + nl) * DP);
 #pragma unroll
             for (int q = 0; q < QP; ++q) {
                 float v[4];
@@ -466,7 +452,6 @@ __global__ __launch_bounds__(kTile) void reconstruct_tile_kernel(
                 dst[q] = o;
             }
         }
-        if (kReconDirect) return;
         // the next tile's loads go out before this tile's write-back: they are in flight while the stores drain
         const int64_t n0_next = n0 + TN;
         const int rows_next = (it + 1 < tiles) ? (int)max((int64_t)0, min((int64_t)TN, N - n0_next)) : 0;
@@ -784,30 +769,8 @@ __host__ __device__ constexpr size_t metrics_mfma_lds_floats(int S, int n_desc) 
     return (size_t)kMetWaves * kMetSlice + (((size_t)n_desc * 6 * S + 3) & ~(size_t)3) + (size_t)kMetWaves * kMetStages * kMetStage;
 }
 
-#ifdef ET_EXP_METSTAMP  // development aid (tools/archive/metstamp.py): shader cycles (s_memtime) a wavefront spends in the phases of
-// a pass, summed over all wavefronts: [0] passes, [1] slice hand-over + stores + requests, [2] wait for this pass's
-// inputs, [3] LDS reads + ground-truth normalisation + operands, [4] matrix instructions + hand-over, [5] distances,
-// [6] best-of-S, [7] wavefronts
-__device__ unsigned long long g_metstamp[8];
-#define ET_METSTAMP(i)                                                  \
-    do {                                                                \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();     \
-        ms_acc[i] += t_ - ms_t;                                         \
-        ms_t = t_;                                                      \
-    } while (0)
-#else
-#define ET_METSTAMP(i)
-#endif
-
-#ifndef ET_EXP_MET
-#define ET_EXP_MET 0
-#endif
-#ifndef ET_MET_WGS
-#define ET_MET_WGS 6
-#endif
 template <int TP, int K, int MODE, bool POSE>
-__global__ __launch_bounds__(kMetWaves * 64, MODE == ET_MODE_SPLIT ? 5 : ET_MET_WGS) void reconstruct_metrics_mfma_kernel(
+__global__ __launch_bounds__(kMetWaves * 64, MODE == ET_MODE_SPLIT ? 5 : 6) void reconstruct_metrics_mfma_kernel(
     const float *__restrict__ C, int N, int S, int TNW, int T_obs,
     const float *__restrict__ obs, const float *__restrict__ nrm_or_pose,
     const float *__restrict__ A_m, const float *__restrict__ A_s,
@@ -935,9 +898,6 @@ __global__ __launch_bounds__(kMetWaves * 64, MODE == ET_MODE_SPLIT ? 5 : ET_MET_
         (unsigned)reinterpret_cast<unsigned long long>((__attribute__((address_space(3))) float *)sRing));
     auto first_row = [&](int ps) { return min(ps * TNW, N - TNW); };
     auto issue = [&](int ps, int stage) {  // (passes beyond the last re-request the last one: same count every time)
-#if ET_EXP_MET == 3  // measurement aid: every pass re-requests pass 0's inputs (cache resident: no memory traffic)
-        ps = 0;
-#endif
         const int n0 = __builtin_amdgcn_readfirstlane(first_row(min(ps, n_pass - 1)));
         const unsigned base = ring_addr + (unsigned)stage * (unsigned)(kMetStage * 4);
         const unsigned so_c = (unsigned)n0 * (unsigned)(S * 4), so_g = (unsigned)n0 * (unsigned)(DP * 4), so_n = (unsigned)n0 * 4u;
@@ -981,21 +941,12 @@ __global__ __launch_bounds__(kMetWaves * 64, MODE == ET_MODE_SPLIT ? 5 : ET_MET_
     // (Instantiating the pass body once per ring stage -- every LDS address a loop-invariant register + an immediate
     // offset -- saves ~10 vector instructions per pass and costs 4 registers, i.e. the sixth wavefront per SIMD: +-0.)
     int stage = 0;  // ring slot of the current pass
-#ifdef ET_EXP_METSTAMP
-    unsigned long long ms_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ms_t = __builtin_amdgcn_s_memtime();
-#endif
     for (; pass < n_pass; pass += stride) {
         const int n0 = first_row(pass);
-#ifdef ET_EXP_METSTAMP
-        ms_t = __builtin_amdgcn_s_memtime();
-        ms_acc[0] += 1;
-#endif
         wave_sync();  // the previous pass is done with the slice
         store_held(held, held_n0);
         issue(pass + (D - 1) * stride, stage == 0 ? D - 1 : stage - 1);  // travels while D - 1 passes are computed
-        ET_METSTAMP(1);
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(11 * (D - 1)) : "memory");
-        ET_METSTAMP(2);
         const float *sIn = sRing + stage * kMetStage;
         stage = stage + 1 == D ? 0 : stage + 1;
         float cur[2][3];
@@ -1078,15 +1029,6 @@ __global__ __launch_bounds__(kMetWaves * 64, MODE == ET_MODE_SPLIT ? 5 : ET_MET_
         const float big = fmaxf(fmaxf(fmaxf(fabsf(b[0][0]), fabsf(b[0][1])), fabsf(b[0][2])),
                                 fmaxf(fmaxf(fabsf(b[1][0]), fabsf(b[1][1])), fabsf(b[1][2])));
         f32x16_t acc[2];
-        ET_METSTAMP(3);
-#if ET_EXP_MET == 2  // measurement aid: no operand split, no matrix instructions
-        if (1) {
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[t][i] = b[t][i % 3] * aU[0][i % 3] + big;
-        } else
-#endif
         if (f16_ok && __ballot(!(big < 32768.f)) == 0ull) {
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
@@ -1130,7 +1072,6 @@ __global__ __launch_bounds__(kMetWaves * 64, MODE == ET_MODE_SPLIT ? 5 : ET_MET_
             }
         }
         wave_sync();  // the normalised ground truth is in the slice
-        ET_METSTAMP(4);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             // rows 8 g + 4 h + (0..3) of this column: steps 4 g + 2 h and 4 g + 2 h + 1 (g = 3 is padding)
@@ -1147,11 +1088,7 @@ __global__ __launch_bounds__(kMetWaves * 64, MODE == ET_MODE_SPLIT ? 5 : ET_MET_
                 const f32x2_t ey = __builtin_elementwise_fma((f32x2_t){acc[t][4 * g + 2], acc[t][4 * g + 3]}, un, (f32x2_t){gn.z, gn.w});
                 const f32x2_t d2 = __builtin_elementwise_fma(ey, ey, ex * ex);
                 // v_sqrt_f32 (1 ulp): the metric is compared at 1e-5 m
-#if ET_EXP_MET == 1  // measurement aid: no square roots
-                const f32x2_t d = d2;
-#else
                 const f32x2_t d = {__builtin_amdgcn_sqrtf(d2.x), __builtin_amdgcn_sqrtf(d2.y)};
-#endif
                 sum2 = sum2 + d;
                 last = d.y;  // h = 1, g = 2: step 11
             }
@@ -1165,7 +1102,6 @@ __global__ __launch_bounds__(kMetWaves * 64, MODE == ET_MODE_SPLIT ? 5 : ET_MET_
                     make_float2(((sum + other_sum) * (1.0f / (float)TP)) * back, other_last * back);
         }
         wave_sync();
-        ET_METSTAMP(5);
         {   // best of S (torch.min propagates NaN): lane (mr, mq) takes samples mq, mq + 4, ...; then the quad's four meet.
             // The metrics are >= +0 or NaN: as unsigned integers their order is the floats' and every NaN is above +inf,
             // so min AND max of the bit patterns decide -- max > 0x7f800000 means a NaN was among them.
@@ -1194,17 +1130,7 @@ __global__ __launch_bounds__(kMetWaves * 64, MODE == ET_MODE_SPLIT ? 5 : ET_MET_
             held = make_float2(__uint_as_float(mx.x > 0x7f800000u ? mx.x : mn.x), __uint_as_float(mx.y > 0x7f800000u ? mx.y : mn.y));
             held_n0 = n0;
         }
-#ifdef ET_EXP_METSTAMP
-        asm volatile("s_nop 0" ::"v"(held.x), "v"(held.y));
-#endif
-        ET_METSTAMP(6);
     }
-#ifdef ET_EXP_METSTAMP
-    if (lane == 0) {
-        for (int i = 0; i < 7; ++i) atomicAdd(&g_metstamp[i], ms_acc[i]);
-        atomicAdd(&g_metstamp[7], 1ull);
-    }
-#endif
     if (did_any) store_held(held, held_n0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the tail's surplus requests still write into this wavefront's LDS)
 }
@@ -1346,11 +1272,7 @@ extern "C" int et_anchor_reconstruct_fwd(const float *C, int64_t N, int S, int k
         const int TN = kTile / S;
         const size_t lds = sizeof(float) * ((size_t)TN * S * 24 + (size_t)TN * kNormStride + 2 * 24 * 6 + 2 * 6 * (size_t)S);
         const int64_t per_wg = (int64_t)TN * (S == 1 ? 1 : kReconTiles);
-#ifdef ET_EXP_RECON_NOSTREAM  // measurement aid
-        const bool stream = false;
-#else
         const bool stream = S > 1 && N * S * (int64_t)96 > kStreamBytes;  // (S = 1: the default policy is faster, see kStreamBytes)
-#endif
         auto kern = stream ? reconstruct_tile_kernel<12, 6, true> : reconstruct_tile_kernel<12, 6, false>;
         hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(N, per_wg)), dim3(kTile), lds, st, C, N, S, TN, T_obs, obs, nrm, A_m,
                            A_s, U_pred_m, U_pred_s, mode, static_dist, out);
@@ -1469,15 +1391,3 @@ extern "C" int et_anchor_reconstruct_bwd(const float *dtraj, int64_t N, int S, i
     ET_LAUNCH_CHECK();
     return ET_OK;
 }
-
-#ifdef ET_EXP_METSTAMP
-extern "C" int et_debug_metstamp(unsigned long long *host, int reset) {
-    if (hipDeviceSynchronize() != hipSuccess) return 1;
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(et::g_metstamp), sizeof(unsigned long long) * 8) != hipSuccess) return 1;
-    if (reset) {
-        unsigned long long z[8] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(et::g_metstamp), z, sizeof z) != hipSuccess) return 1;
-    }
-    return 0;
-}
-#endif

@@ -55,25 +55,13 @@ __host__ __device__ constexpr int gram4_pair(int qa, int qb) { return qa * 4 - q
 // fit stage inside the bench step 0.497-0.501 against 0.511-0.533 ms, profiles/r06p_gram4_ab.txt.)
 constexpr int kWaveGramThreads = 256;
 
+// one quad of a row, by value: the tail's `in range ? ld_rows(p) : zero` then chooses between two values
+__device__ __forceinline__ float4 ld_rows(const float4 *p) { return *p; }
+
 // normalize_point (et_common.h) on two points at once with the packed fp32 instructions (v_pk_add / v_pk_mul_f32: two
 // results per lane and issue slot): (tx c, ty c) + (ty s, tx (-s)), then * sca -- the same products and the same single
 // additions as normalize_point, hence the same bits (sca = 1 for the static descriptor: x * 1 is x).  Five instructions
 // per point instead of ten.
-#ifndef ET_EXP_GRAM_NT
-#define ET_EXP_GRAM_NT 0
-#endif
-#ifndef ET_EXP_GRAM
-#define ET_EXP_GRAM 0
-#endif
-typedef float f32x4_ld __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld_rows(const float4 *p) {
-#if ET_EXP_GRAM_NT
-    const f32x4_ld v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_ld *>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-#else
-    return *p;
-#endif
-}
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 struct NormPk {
     f32x2_t o, cc, sn, sc;
@@ -168,63 +156,53 @@ __global__ __launch_bounds__(kWaveGramThreads) void gram_wave_kernel(
         }
         if (tile + stride < n_tiles) fetch(tile + stride);  // in flight during the rest of this pass
         wave_sync();
-#if ET_EXP_GRAM >= 2  // measurement aid: loads + stage-in only
-        if (0)
-#endif
-        {
-            float4 *orow = sRow + lane * PR, *prow = orow + QO;
-            bool use = false;
-            if (lane < rows) {
-                float xo[DO];
+        float4 *orow = sRow + lane * PR, *prow = orow + QO;
+        bool use = false;
+        if (lane < rows) {
+            float xo[DO];
 #pragma unroll
-                for (int j = 0; j < QO; ++j) {
-                    const float4 v = orow[j];
-                    xo[4 * j] = v.x;
-                    xo[4 * j + 1] = v.y;
-                    xo[4 * j + 2] = v.z;
-                    xo[4 * j + 3] = v.w;
-                }
-                const float ox = xo[DO - 2], oy = xo[DO - 1];
-                const RowNorm p = row_norm(ox, oy, ox - xo[DO - 6], oy - xo[DO - 5], mode, static_dist);
-                use = p.mv == which;
-                if (use) {
-                    const NormPk np(p);
-#pragma unroll
-                    for (int j = 0; j < QO; ++j) orow[j] = np.quad(xo[4 * j], xo[4 * j + 1], xo[4 * j + 2], xo[4 * j + 3]);
-#pragma unroll
-                    for (int q = 0; q < QP; ++q) {
-                        const float4 v = prow[q];
-                        prow[q] = np.quad(v.x, v.y, v.z, v.w);
-                    }
-                    ++my_count;
-                }
+            for (int j = 0; j < QO; ++j) {
+                const float4 v = orow[j];
+                xo[4 * j] = v.x;
+                xo[4 * j + 1] = v.y;
+                xo[4 * j + 2] = v.z;
+                xo[4 * j + 3] = v.w;
             }
-            if (!use) {
-                const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float ox = xo[DO - 2], oy = xo[DO - 1];
+            const RowNorm p = row_norm(ox, oy, ox - xo[DO - 6], oy - xo[DO - 5], mode, static_dist);
+            use = p.mv == which;
+            if (use) {
+                const NormPk np(p);
 #pragma unroll
-                for (int j = 0; j < QO; ++j) orow[j] = z;
+                for (int j = 0; j < QO; ++j) orow[j] = np.quad(xo[4 * j], xo[4 * j + 1], xo[4 * j + 2], xo[4 * j + 3]);
 #pragma unroll
-                for (int q = 0; q < QP; ++q) prow[q] = z;
+                for (int q = 0; q < QP; ++q) {
+                    const float4 v = prow[q];
+                    prow[q] = np.quad(v.x, v.y, v.z, v.w);
+                }
+                ++my_count;
             }
         }
+        if (!use) {
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int j = 0; j < QO; ++j) orow[j] = z;
+#pragma unroll
+            for (int q = 0; q < QP; ++q) prow[q] = z;
+        }
         wave_sync();
-#if ET_EXP_GRAM >= 1  // measurement aid: no matrix phase
-        if (0)
-#endif
-        {
-            const float *fb = reinterpret_cast<const float *>(sRow);
+        const float *fb = reinterpret_cast<const float *>(sRow);
 #pragma unroll
-            for (int g = 0; g < 16; ++g) {  // group g: window g / 2, rows {0,3,6,1} or {4,7,2,5} of it
-                const int wo = (g >> 1) * (8 * 4 * PR);
-                double v[4];
+        for (int g = 0; g < 16; ++g) {  // group g: window g / 2, rows {0,3,6,1} or {4,7,2,5} of it
+            const int wo = (g >> 1) * (8 * 4 * PR);
+            double v[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = (double)fb[((g & 1) ? offB[q] : offA[q]) + wo];
+            for (int q = 0; q < 4; ++q) v[q] = (double)fb[((g & 1) ? offB[q] : offA[q]) + wo];
 #pragma unroll
-                for (int qa = 0; qa < 4; ++qa)
+            for (int qa = 0; qa < 4; ++qa)
 #pragma unroll
-                    for (int qb = qa; qb < 4; ++qb)
-                        acc[gram4_pair(qa, qb)] = __builtin_amdgcn_mfma_f64_4x4x4f64(v[qa], v[qb], acc[gram4_pair(qa, qb)], 0, 0, 0);
-            }
+                for (int qb = qa; qb < 4; ++qb)
+                    acc[gram4_pair(qa, qb)] = __builtin_amdgcn_mfma_f64_4x4x4f64(v[qa], v[qb], acc[gram4_pair(qa, qb)], 0, 0, 0);
         }
     }
 
@@ -279,7 +257,7 @@ __device__ __forceinline__ double gram_pred_entry(const double *S, int i, int j)
 }
 
 // Sum the workgroup partials of one entry: one wavefront per entry, a fixed strided + butterfly
-// order (reproducible for a given grid).  769 small workgroups on purpose: the partials are 4.7 MB, and ONE workgroup
+// order (reproducible for a given grid).  641 small workgroups on purpose: the partials are 4.7 MB, and ONE workgroup
 // pulling them through its CU (the reduction folded into the eigensolver's launch, tried in round 6) takes 80 us.
 __global__ __launch_bounds__(64) void gram_reduce_kernel(const double *__restrict__ partials, int n_partials, int stride,
                                                          double *__restrict__ sums) {
@@ -400,33 +378,8 @@ constexpr int kJacobiMaxSweeps = 30;
 // quadratically: the sweep that finds 1e-10 would leave ~1e-20.  Until round 5 the bound was 1e-15, one more sweep (of
 // nine on the bench's matrices); on the 22 Gram matrices of the five splits and the synthetic set the two bounds give
 // the same U to 4e-14 (fp32 results: the last bit of a near-zero entry in 3 of 22).
-#ifndef ET_EIGH_HEADSTART
-#define ET_EIGH_HEADSTART 0
-#endif
-#ifndef ET_JACOBI_STOP
-#define ET_JACOBI_STOP 1e-10
-#endif
-constexpr double kJacobiStop = ET_JACOBI_STOP;
-#ifdef ET_EXP_EIGHSTAMP  // development aid: s_memtime ticks of workgroup 0's first wavefront by phase of a round:
-// [0] rounds, [1] block / V items, [2] look-ahead entries, [3] rotation chain + stepping, [4] barrier, [5] sweep checks, [6] sweeps
-// (-DET_EXP_EIGHSTAMP=w + 1: wavefront w; 16 = the look-ahead wavefront)
-__device__ unsigned long long g_eighstamp[8];
-#define ET_EIGHSTAMP(i)                                              \
-    do {                                                             \
-        if (stamping) {                                              \
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       \
-            const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-            es_acc[i] += t_ - es_t;                                  \
-            es_t = t_;                                               \
-        }                                                            \
-    } while (0)
-#else
-#define ET_EIGHSTAMP(i)
-#endif
-#ifndef ET_EIGH_THREADS
-#define ET_EIGH_THREADS 1024
-#endif
-constexpr int kEighThreads = ET_EIGH_THREADS;  // 16 wavefronts share the element updates of a round: 290 us (256 threads) -> 245 us for 24 x 24; 64 threads: 630 us
+constexpr double kJacobiStop = 1e-10;
+constexpr int kEighThreads = 1024;  // 16 wavefronts share the element updates of a round: 290 us (256 threads) -> 245 us for 24 x 24; 64 threads: 630 us
 
 // sqrt(x) and 1 / sqrt(x) of a normal positive double to full precision (not correctly rounded): hardware estimate
 // (v_rsq_f64) + two coupled Goldschmidt steps, ~10 dependent fp64 operations instead of two ~25-operation IEEE sequences.
@@ -548,31 +501,25 @@ __device__ __forceinline__ void eigh_topk_body(GLoad gload, int n, int k, float 
     }
     __syncthreads();
     // work items of this thread in the update phase:
-    //   V: e = lane + t*T - T/2 -> (pair i, row j): columns p_i, q_i of row j
-    //   A: b = lane + t*T       -> (pair i1, pair i2): the 2 x 2 block rows {p1, q1} x columns {p2, q2}
-    // (the V items start half a workgroup away from the A blocks: for the usual small n the two kinds of work land on
-    // different wavefronts and a round's critical path is the longer of the two, not their sum)
+    //   V: e -> (pair i, row j): columns p_i, q_i of row j
+    //   A: b = lane + t*T -> (pair i1, pair i2): the 2 x 2 block rows {p1, q1} x columns {p2, q2}
+    // (the V items sit away from the A blocks: for the usual small n the two kinds of work land on different wavefronts
+    // and a round's critical path is the longer of the two, not their sum)
     // (round 6) ... and on wavefronts that do not share a SIMD with the look-ahead wavefront: a workgroup's wavefronts go to
     // the four SIMDs cyclically, w and w + 4 sit on the same one, and two busy wavefronts on a SIMD take turns issuing --
     // the V items on wavefront 11 doubled the latency of the chain on wavefront 15.  V items: wavefronts 4 5 6, 8 9 10,
     // 12 13 14 (in this order), 576 per slot.
-    constexpr bool kSpread = kEighThreads == 1024;
-    constexpr int kVShift = kEighThreads / 2;
-    constexpr int kVPerSlot = kSpread ? 9 * 64 : kEighThreads;
-    constexpr int kSlots = kSpread ? (32 * 64 + kVPerSlot - 1) / kVPerSlot : (32 * 64 + kVShift + kEighThreads - 1) / kEighThreads;
+    static_assert(kEighThreads == 1024, "the V items are dealt to wavefronts 4 ... 14 of sixteen");
+    constexpr int kVPerSlot = 9 * 64;
+    constexpr int kSlots = (32 * 64 + kVPerSlot - 1) / kVPerSlot;
     constexpr int kBlkSlots = (32 * 32 + kEighThreads - 1) / kEighThreads;
     constexpr int kChkSlots = (64 * 64 + kEighThreads - 1) / kEighThreads;
-    constexpr int kParBase = kEighThreads >= 128 ? kEighThreads - 64 : 0;  // the parameter lanes: first lanes of the last wavefront
+    constexpr int kParBase = kEighThreads - 64;  // the parameter lanes: first lanes of the last wavefront
     int slot_i[kSlots], slot_row[kSlots], blk_1[kBlkSlots], blk_2[kBlkSlots], chk[kChkSlots];
 #pragma unroll
     for (int t = 0; t < kSlots; ++t) {
-        int e;
-        if (kSpread) {
-            const int w = lane >> 6;
-            e = (w >= 4 && (w & 3) != 3) ? ((w - 4) - ((w - 4) >> 2)) * 64 + (lane & 63) + t * kVPerSlot : -1;
-        } else {
-            e = lane + t * kEighThreads - kVShift;
-        }
+        const int w = lane >> 6;
+        const int e = (w >= 4 && (w & 3) != 3) ? ((w - 4) - ((w - 4) >> 2)) * 64 + (lane & 63) + t * kVPerSlot : -1;
         const bool ok = e >= 0 && e < half * n;
         slot_i[t] = ok ? e / n : -1;
         slot_row[t] = ok ? (e % n) * m : 0;  // (row j) * m
@@ -617,18 +564,11 @@ __device__ __forceinline__ void eigh_topk_body(GLoad gload, int n, int k, float 
     // GPU / rank.  An inactive pair (a_pq == 0: also the padding pair of an odd n) runs the chain on zeros and drops it.
     auto rotation = [&](double apq, double app, double aqq, int buf) {
         const double alpha = aqq - app, beta = 2.0 * apq;
-#ifdef ET_EIGH_IEEE_PARAMS
-        const double h = sqrt(alpha * alpha + beta * beta);
-        const double D = fabs(alpha) + h;
-        const double g = sqrt(D * D + beta * beta);
-        const double rg = 1.0 / g;
-#else
         double h, rh;
         sqrt_rsqrt(alpha * alpha + beta * beta, h, rh);
         const double D = fabs(alpha) + h;
         double g, rg;
         sqrt_rsqrt(D * D + beta * beta, g, rg);
-#endif
         const double sgn = (alpha == 0.0 || ((alpha > 0.0) == (beta > 0.0))) ? 1.0 : -1.0;
         const bool act = apq != 0.0;
         sC[buf * 32 + L] = act ? D * rg : 1.0;
@@ -643,14 +583,7 @@ __device__ __forceinline__ void eigh_topk_body(GLoad gload, int n, int k, float 
         rotation(Abuf[__mul24(p, m) + q], Abuf[__mul24(p, m) + p], Abuf[__mul24(q, m) + q], 0);
     }
     uint2 ent[3] = {sTab[item0], sTab[split ? item0 : half + item0], sTab[split ? item0 : 2 * half + item0]};  // round 0's items
-#ifdef ET_EXP_EIGHSTAMP
-    const bool stamping = n == 24 && (int)(threadIdx.x >> 6) == ET_EXP_EIGHSTAMP - 1;  // wavefront ET_EXP_EIGHSTAMP - 1 (16: the look-ahead one)
-    unsigned long long es_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, es_t = __builtin_amdgcn_s_memtime();
-#endif
     for (int sweep = 0; sweep < kJacobiMaxSweeps; ++sweep) {
-#ifdef ET_EXP_EIGHSTAMP
-        if (stamping) { es_t = __builtin_amdgcn_s_memtime(); es_acc[6] += 1; }
-#endif
         // converged when max |off-diagonal| <= 1e-10 max |diagonal| (maxima: order independent)
         const double *Ac = Abuf + cur * m * m;
         unsigned long long *mx = sMax + 2 * (sweep & 1);
@@ -663,18 +596,8 @@ __device__ __forceinline__ void eigh_topk_body(GLoad gload, int n, int k, float 
         if (lane < 2) sMax[2 * ((sweep + 1) & 1) + lane] = 0ull;  // (the other parity: last read a sweep of barriers ago)
         __syncthreads();  // (also publishes the first round's parameters)
         const double off = __longlong_as_double(static_cast<long long>(mx[0])), diag = __longlong_as_double(static_cast<long long>(mx[1]));
-        ET_EIGHSTAMP(5);
         if (off <= kJacobiStop * diag) break;
         for (int r = 0; r < m - 1; ++r) {
-#ifdef ET_EXP_EIGHSTAMP
-            if (stamping) es_acc[0] += 1;
-#endif
-#if ET_EIGH_HEADSTART > 0
-            // the look-ahead wavefront's LDS reads go first: right after the barrier all sixteen wavefronts send theirs, and
-            // the reads the critical path waits for stood in that queue (profiles/r06c_eigh_stamps.txt: 900 of a round's 1 350
-            // ticks); the others have ~500 ticks of slack per round
-            if (pl < 0) __builtin_amdgcn_s_sleep(ET_EIGH_HEADSTART);
-#endif
             const double *Ar = Abuf + cur * m * m;
             double *Aw = Abuf + (cur ^ 1) * m * m;
             const double *pC = sC + pb * 32, *pS = sS + pb * 32;
@@ -709,7 +632,6 @@ __device__ __forceinline__ void eigh_topk_body(GLoad gload, int n, int k, float 
                     app = entry(ent[1]);
                     aqq = entry(ent[2]);
                 }
-                ET_EIGHSTAMP(2);  // [2] look-ahead entries (+ shuffles)
                 // the next round's items: in flight during the chain below
                 const int rn = r + 1 == m - 1 ? 0 : r + 1;
                 ent[0] = sTab[rn * nItems + item0];
@@ -719,7 +641,6 @@ __device__ __forceinline__ void eigh_topk_body(GLoad gload, int n, int k, float 
                 }
                 if (is_par) rotation(apq, app, aqq, pb ^ 1);
             }
-            ET_EIGHSTAMP(3);  // [3] rotation chain
             // A' = J^T A J for the round's disjoint rotations, one 2 x 2 block per work item: the row rotation of pair
             // i1 followed by the column rotation of pair i2 touches exactly these four entries, so "all row updates,
             // then all column updates" (the oracle's order, with its intermediate roundings) needs no barrier in between.
@@ -768,18 +689,12 @@ __device__ __forceinline__ void eigh_topk_body(GLoad gload, int n, int k, float 
                 b1[t].step(m);
                 b2[t].step(m);
             }
-            ET_EIGHSTAMP(1);  // [1] this wavefront's block / V items
             __syncthreads();
-            ET_EIGHSTAMP(4);
             cur ^= 1;
             pb ^= 1;
         }
     }
     double *A = Abuf + cur * m * m;
-#ifdef ET_EXP_EIGHSTAMP
-    if (stamping && (threadIdx.x & 63) == 0)
-        for (int i = 0; i < 7; ++i) atomicAdd(&g_eighstamp[i], es_acc[i]);
-#endif
     __syncthreads();
     // Top-k extraction, all columns at once (a single lane walking through n diagonal entries and n vector entries per
     // column cost ~4 us per column: 22 us of a 243 us solve).  Rank of eigenvalue i = number of eigenvalues that come before
@@ -1010,15 +925,3 @@ extern "C" int et_fit_descriptor(const float *obs, const float *pred, int64_t N,
     ET_LAUNCH_CHECK();
     return ET_OK;
 }
-
-#ifdef ET_EXP_EIGHSTAMP
-extern "C" int et_debug_eighstamp(unsigned long long *host, int reset) {
-    if (hipDeviceSynchronize() != hipSuccess) return 1;
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(et::g_eighstamp), sizeof(unsigned long long) * 8) != hipSuccess) return 1;
-    if (reset) {
-        unsigned long long z[8] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(et::g_eighstamp), z, sizeof z) != hipSuccess) return 1;
-    }
-    return 0;
-}
-#endif

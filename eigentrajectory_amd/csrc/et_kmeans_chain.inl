@@ -393,7 +393,6 @@ __global__ __launch_bounds__(kFilterMaxThreads) void kmeans_lloyd_chain_kernel(
     // and a kernel with a private segment pays for it at every wavefront launch)
     // Everything the prologue needs from memory is requested at once -- the convergence flag, the centroids (d K <= 192
     // <= blockDim.x values), the delta table and the previous totals: one round trip, not three dependent ones.
-    KM_PSTAMP(0);
     const int64_t done0 = ch.st_rd->done, iter0 = ch.st_rd->iter;
     __shared__ float sPkHdr[12];
     __shared__ u32x4 sPkTab[64];  // packed_assign_body's matrix operand per lane, when made beside the update
@@ -425,17 +424,12 @@ __global__ __launch_bounds__(kFilterMaxThreads) void kmeans_lloyd_chain_kernel(
         }
         return;
     }
-#ifdef ET_EXP_WAITSTAMP
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    KM_PSTAMP(1);
     if ((int)threadIdx.x < d * K) sCen[threadIdx.x] = cen0;
     if (!SIM && threadIdx.x < 9) sPkHdr[threadIdx.x] = pk_word;
     if ((int)threadIdx.x < kStateWords) reinterpret_cast<unsigned *>(&sSt)[threadIdx.x] = st_word;  // the state block, word by word
     if (has_pending) {
         fold_combine(fr, iter0 > 0, plen, sTot, true);
         __syncthreads();
-        KM_PSTAMP(2);
         // (trace-less fit on the packed copy: the next assignment's tables are made by wavefronts 2, 3 and 4 beside the
         // update's reductions -- 1.3 us of every launch's prologue when they followed it)
         const bool side_tables = !SIM && ch.pk.xh && ch.vec_ok && blockDim.x >= 320;
@@ -445,7 +439,6 @@ __global__ __launch_bounds__(kFilterMaxThreads) void kmeans_lloyd_chain_kernel(
         update_body(&sSt, sTot, d, K, tol, sCen, wg0 ? trace : nullptr, nullptr, wg0 ? ch.last : nullptr, SIM && wg0,
                     (!SIM && ch.pk.xh) ? sPkHdr : nullptr, &sPkBad, side);  // reads its copy in LDS
         tables_ready = side_tables;
-        KM_PSTAMP(3);
     }
     __syncthreads();
     const int64_t done1 = sSt.done;  // (requested together: the flag of the update just applied and its range test)
@@ -465,7 +458,6 @@ __global__ __launch_bounds__(kFilterMaxThreads) void kmeans_lloyd_chain_kernel(
         // wavefronts must not start clearing while the ones above still read (uniform per workgroup: only workgroup 0 waits)
         __syncthreads();
     }
-    KM_PSTAMP(4);
     if (done1) return;  // the update just applied met the tolerance: no further assignment (kmeans.py:239)
     const int copy_mask = -ch.copies;  // (-1: one compact copy)
     // a shard whose rows do not allow 16-byte loads (sharded runs cut the points anywhere), or a tiny one: the plain exact

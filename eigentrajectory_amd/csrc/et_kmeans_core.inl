@@ -11,10 +11,7 @@ constexpr int kKmThreads = 256;
 // not of wavefronts), but a wavefront then has 4/3 as many passes to do, and the count is an integer.  Per Lloyd
 // launch at N = 1e7 (same box): 256 threads 60.3 us, 512: 58.0, 640: 60.5, 704: 57.1, 768: 54.7, 832: 59.3, 896: 57.8,
 // 960: 58.7, 1024: 57.2 (sizes that load the four SIMDs unevenly lose); at N = 1e6 768 needs two passes, 1024 one.
-#ifndef ET_KM_MAXTHREADS
-#define ET_KM_MAXTHREADS 1024
-#endif
-constexpr int kFilterMaxThreads = ET_KM_MAXTHREADS;
+constexpr int kFilterMaxThreads = 1024;
 constexpr int kFilterMinThreads = 768;
 constexpr int kKmMaxBlocks = 4096;
 

@@ -79,65 +79,6 @@ __device__ __forceinline__ void filter_drain(const unsigned *q, int cnt, int K, 
     if (SIM) sim_acc += to_fixed(best, sfrac);
 }
 
-#ifdef ET_EXP_WAITSTAMP  // development aid (tools/archive/waitstamp.py): where a pass of packed_assign_body spends its time, in
-// shader cycles (s_memtime) summed over all wavefronts and launches: [0] passes, [1] cycles from a pass's start to the
-// arrival of its own (prefetched) rows = the exposed load wait, [2] cycles of whole passes, [3] cycles inside queue drains,
-// [4] drains, [5] cycles from kernel start to the first pass, [6] wavefronts
-__device__ unsigned long long g_waitstamp[8];
-// ... and where a LAUNCH of the chained kernel goes (thread 0 of every workgroup, cycles between consecutive stamps, summed
-// over workgroups and launches): [0] workgroup-launches, [1] entry -> prologue loads arrived, [2] fold + barrier, [3] update,
-// [4] barrier + publish, [5] tables, matrix operand, barrier, [6] the pass loop, [7] final drain + barrier,
-// [8] copies -> one + barrier + emit
-__device__ unsigned long long g_prostamp[16];
-__shared__ unsigned long long s_ps_last, s_ps_acc[16], s_ws_acc[8];
-#define KM_PSTAMP(i)                                                        \
-    do {                                                                    \
-        if (threadIdx.x == 0) {                                             \
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              \
-            const unsigned long long t_ = __builtin_amdgcn_s_memtime();     \
-            s_ps_acc[i] = (i) ? t_ - s_ps_last : 1ull;                      \
-            if ((i) == 0)                                                   \
-                for (int z_ = 0; z_ < 8; ++z_) s_ws_acc[z_] = 0ull;         \
-            s_ps_last = t_;                                                 \
-        }                                                                   \
-    } while (0)
-#define KM_PSTAMP_FLUSH()                                                               \
-    do {                                                                                \
-        __syncthreads();                                                                \
-        if (threadIdx.x == 0) {                                                         \
-            for (int i_ = 0; i_ < 9; ++i_) atomicAdd(&g_prostamp[i_], s_ps_acc[i_]);     \
-            for (int i_ = 0; i_ < 7; ++i_) atomicAdd(&g_waitstamp[i_], s_ws_acc[i_]);    \
-        }                                                                               \
-    } while (0)
-#else
-#define KM_PSTAMP(i)
-#define KM_PSTAMP_FLUSH()
-#endif
-
-#ifdef ET_PERSIST_STAMPS  // development aid (tools/archive/persist_stamps.py): per workgroup and iteration, 10 ns ticks
-// kinds 0..5 (persistent kernel): top (own arrival done), go, folded, updated, body start, body end;
-// kinds 6..9 (inside the filter body): operands staged, passes done (wavefront 0), queue drained, deltas emitted
-constexpr int kStampIters = 104, kStampKinds = 10;
-__device__ unsigned long long g_persist_stamps[256 * kStampIters * kStampKinds];
-__device__ int g_stamp_it[256];
-#define ET_STAMP(kind)                                                                                              \
-    do {                                                                                                            \
-        if (threadIdx.x == 0 && blockIdx.x < 256 && it < kStampIters) {                                             \
-            g_stamp_it[blockIdx.x] = it;                                                                            \
-            g_persist_stamps[((size_t)blockIdx.x * kStampIters + it) * kStampKinds + (kind)] = __builtin_amdgcn_s_memrealtime(); \
-        }                                                                                                           \
-    } while (0)
-#define ET_BSTAMP(kind)                                                                                             \
-    do {                                                                                                            \
-        if (threadIdx.x == 0 && blockIdx.x < 256 && g_stamp_it[blockIdx.x] < kStampIters)                           \
-            g_persist_stamps[((size_t)blockIdx.x * kStampIters + g_stamp_it[blockIdx.x]) * kStampKinds + (kind)] =  \
-                __builtin_amdgcn_s_memrealtime();                                                                   \
-    } while (0)
-#else
-#define ET_STAMP(kind) do { } while (0)
-#define ET_BSTAMP(kind) do { } while (0)
-#endif
-
 // issue the loads of pass `gg` (256 points: lane (half, col) owns points 4 col .. 4 col + 3 of its 128-point half)
 __device__ __forceinline__ void pass_issue(const float *__restrict__ X, int64_t N, const uint8_t *__restrict__ labels, int64_t gg,
                                            int half, int col, float4 (&vn)[6], unsigned &lpn) {
@@ -145,28 +86,9 @@ __device__ __forceinline__ void pass_issue(const float *__restrict__ X, int64_t 
     // lanes past the end (last pass only) read points 0..3 instead: finite data, results discarded through `valid`
     // (unconditional loads: no exec-masked branch and no zero fill of 25 registers in every pass)
     const int64_t nl = n < N ? n : 0;  // N % 4 == 0
-#ifdef ET_EXP_NOLOAD  // measurement aid (tools/archive/ab_lloyd.sh): the assignment without its memory traffic
-    const float f = (float)(nl & 1023) * 0.01f;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) vn[i] = make_float4(f + i, f - i, f * 0.5f, 1.0f + i);
-    lpn = 0x01010101u * (unsigned)(nl & 7);
-#else
-#ifdef ET_EXP_NT_EVERY  // measurement aid: every ET_EXP_NT_EVERY-th pass bypasses the caches (does the rest then stay in the MALL?)
-    if ((gg / 12) % ET_EXP_NT_EVERY == ET_EXP_NT_EVERY - 1) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const float4 *p = reinterpret_cast<const float4 *>(X + (int64_t)i * N + nl);
-            vn[i] = make_float4(__builtin_nontemporal_load(&p->x), __builtin_nontemporal_load(&p->y),
-                                __builtin_nontemporal_load(&p->z), __builtin_nontemporal_load(&p->w));
-        }
-        lpn = *reinterpret_cast<const unsigned *>(labels + nl);
-        return;
-    }
-#endif
 #pragma unroll
     for (int i = 0; i < 6; ++i) vn[i] = *reinterpret_cast<const float4 *>(X + (int64_t)i * N + nl);
     lpn = *reinterpret_cast<const unsigned *>(labels + nl);
-#endif
 }
 
 // The same for a HANDFUL of queued points (what a wavefront of a small shard holds at the end of its one pass: ~1 % of
@@ -282,7 +204,6 @@ __device__ __forceinline__ void filter_assign_body(const float *__restrict__ X, 
     if (tx == 0) sNext = (int)(blockDim.x >> 6);  // a wavefront's first pass is its own (static), the others are handed out
     __syncthreads();
 
-
     // A operands: this lane feeds accumulator row m = col, k-half = half.  Row m is read back by lanes
     // of half (m >> 2) & 1 in register 4 (m >> 3) + (m & 3); cluster j sits in register j >> 1 of half j & 1,
     // so both halves reduce over registers 0 .. ceil(K / 2) - 1 <= NREGS - 1 (rows of clusters >= K: -60000).
@@ -314,7 +235,6 @@ __device__ __forceinline__ void filter_assign_body(const float *__restrict__ X, 
         a2 = u32x4{cl[0], cl[1], cl[2], 0u};
     }
     const f16x8 A1 = __builtin_bit_cast(f16x8, a1), A2 = __builtin_bit_cast(f16x8, a2);
-    ET_BSTAMP(6);
     const float4 *s4 = reinterpret_cast<const float4 *>(sC);
 
     // Inertia: trunc(Y 2^sim_frac) is an integer below 2^(62 - bits(n_total)); a lane may add 2^(bits - 9) of them
@@ -407,17 +327,12 @@ __device__ __forceinline__ void filter_assign_body(const float *__restrict__ X, 
 #pragma unroll
             for (int r = 0; r < 16; ++r) accL[r] = accU[r] = 0.f;
             float bL, sL, bU, sU;
-#ifdef ET_EXP_NOMFMA  // measurement aid: no matrix-core work and no top-2 (every point is "kept")
-            bL = __uint_as_float(bLo[0]) * 1e-30f, sL = __uint_as_float(bLo[1]) * 1e-30f - 1e30f;
-            bU = __uint_as_float(bUp[2]) * 1e-30f, sU = __uint_as_float(bUp[3]) * 1e-30f - 1e30f;
-#else
             accL = __builtin_amdgcn_mfma_f32_32x32x16_f16(A1, BL, accL, 0, 0, 0);
             accU = __builtin_amdgcn_mfma_f32_32x32x16_f16(A1, BU, accU, 0, 0, 0);
             accL = __builtin_amdgcn_mfma_f32_32x32x16_f16(A2, BL, accL, 0, 0, 0);
             accU = __builtin_amdgcn_mfma_f32_32x32x16_f16(A2, BU, accU, 0, 0, 0);
             top2<NREGS>(accL, bL, sL);
             top2<NREGS>(accU, bU, sU);
-#endif
             // lower half-wave: both partials of its own points (tile L); upper half-wave: those of tile U
             const auto rb = __builtin_amdgcn_permlane32_swap(__float_as_uint(bL), __float_as_uint(bU), false, false);
             const auto rq = __builtin_amdgcn_permlane32_swap(__float_as_uint(sL), __float_as_uint(sU), false, false);
@@ -468,9 +383,6 @@ __device__ __forceinline__ void filter_assign_body(const float *__restrict__ X, 
                     e[7 * kFilterSlots] = (old_packed >> (8 * q)) & 0xffu;
                 }
                 qn += __popcll(m);
-#ifdef ET_FILTER_DEBUG
-                if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&sAcc[d * K + K + 1]), (unsigned long long)__popcll(m));
-#endif
                 if (qn >= 64) {
                     qn -= 64;
                     filter_drain<SIM>(queue + qn, 64, K, sC, labels, sAcc, frac, sfrac, lane, sim_acc);
@@ -489,17 +401,14 @@ __device__ __forceinline__ void filter_assign_body(const float *__restrict__ X, 
         if (g >= 0) pass_issue(X, N, labels, g, half, col, vn, lpn);
     }
     sim_acc += (long long)dsum;
-    ET_BSTAMP(7);
     if (qn > kSmallDrain) filter_drain<SIM>(queue, qn, K, sC, labels, sAcc, frac, sfrac, lane, sim_acc);
     else if (qn) filter_drain_small<SIM>(queue, qn, K, sC, labels, sAcc, frac, sfrac, lane, sim_acc);
-    ET_BSTAMP(8);
     if (SIM) {
         for (int o = 32; o > 0; o >>= 1) sim_acc += __shfl_xor(sim_acc, o);
         if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&sAcc[d * K + K]), (unsigned long long)sim_acc);
     }
     __syncthreads();
     emit_partials(sAcc, plen, n_thr, block_partials, lanes, copy_mask);
-    ET_BSTAMP(9);
 }
 
 }  // namespace et

@@ -695,29 +695,3 @@ extern "C" int et_kmeans_fit(const float *X, int64_t N, int d, int K, int max_it
     }
     return state_host->bad_input ? ET_ERR_BAD_DATA : ET_OK;
 }
-
-#ifdef ET_EXP_WAITSTAMP
-extern "C" int et_debug_waitstamp(unsigned long long *host, int reset) {
-    if (hipDeviceSynchronize() != hipSuccess) return 1;
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(et::g_waitstamp), sizeof(unsigned long long) * 8) != hipSuccess) return 1;
-    if (reset) {
-        unsigned long long z[8] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(et::g_waitstamp), z, sizeof z) != hipSuccess) return 1;
-    }
-    return 0;
-}
-extern "C" int et_debug_prostamp(unsigned long long *host, int reset) {
-    if (hipDeviceSynchronize() != hipSuccess) return 1;
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(et::g_prostamp), sizeof(unsigned long long) * 16) != hipSuccess) return 1;
-    if (reset) {
-        unsigned long long z[16] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(et::g_prostamp), z, sizeof z) != hipSuccess) return 1;
-    }
-    return 0;
-}
-#endif
-#ifdef ET_PERSIST_STAMPS
-extern "C" int et_debug_persist_stamps(void *host, size_t bytes) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(et::g_persist_stamps), bytes) == hipSuccess ? 0 : 1;
-}
-#endif

@@ -76,10 +76,7 @@ __device__ __forceinline__ float fma_mix_hi(unsigned w, float b, float a) {
 constexpr int kPkQueue = 2 * kFilterSlots;  // per wavefront: point index, old label
 constexpr int kPkRow = 12;                  // floats per cluster in the label table
 
-#ifndef ET_PK_ACC_COPIES
-#define ET_PK_ACC_COPIES 4
-#endif
-constexpr int kPkAccCopies = ET_PK_ACC_COPIES;  // copies of the workgroup's accumulators in LDS (packed_drain); a power of two
+constexpr int kPkAccCopies = 4;  // copies of the workgroup's accumulators in LDS (packed_drain); a power of two
 constexpr int kPkAccPitch = 228;   // int64 per copy: >= d K + K + 2 = 226 for K = 32; 456 words = 8 mod 64: eight different banks
 
 // full exact scan of `cnt` (<= 64) queued points, one per lane, on coordinates fetched from the side-by-side copy
@@ -354,7 +351,6 @@ __device__ __forceinline__ void packed_assign_body(const LloydPacked pk, const f
     }
     const f16x8 A1 = __builtin_bit_cast(f16x8, a1);
     __syncthreads();  // sL complete
-    KM_PSTAMP(5);
     const float4 *l4 = reinterpret_cast<const float4 *>(sL);
 
     int qn = 0;  // wave-uniform number of queued points
@@ -446,9 +442,6 @@ __device__ __forceinline__ void packed_assign_body(const LloydPacked pk, const f
                     e[kFilterSlots] = (old_packed >> (8 * q)) & 0xffu;
                 }
                 qn += __popcll(m);
-#ifdef ET_FILTER_DEBUG
-                if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&sAcc[d * K + K + 1]), (unsigned long long)__popcll(m));
-#endif
                 if (qn >= 64) {
                     qn -= 64;
                     packed_drain(queue + qn, 64, K, sC, pk.xa, labels, sAcc, frac, lane);
@@ -458,44 +451,19 @@ __device__ __forceinline__ void packed_assign_body(const LloydPacked pk, const f
     };
     // the loop, unrolled by two over the register sets ra / rb: a set is requested one pass ahead and never copied
     PkRows ra, rb;
-#ifdef ET_EXP_WAITSTAMP  // (passes and their cycles only: the exposed wait and the drains are no longer separable)
-    unsigned long long ws_wait = 0, ws_pass = 0, ws_drain = 0, ws_n = 0, ws_nd = 0;
-#define KM_WS_PASS(call)                                             \
-    do {                                                             \
-        const unsigned long long t0_ = __builtin_amdgcn_s_memtime(); \
-        call;                                                        \
-        ws_pass += __builtin_amdgcn_s_memtime() - t0_;               \
-        ++ws_n;                                                      \
-    } while (0)
-#else
-#define KM_WS_PASS(call) call
-#endif
     int64_t g = take();
     packed_issue_dual(src, g, lane_off, own_off, ra);
     while (g >= 0) {
         const int64_t g2 = take();
         packed_issue_dual(src, g2, lane_off, own_off, rb);
-        KM_WS_PASS(process(ra, g));
+        process(ra, g);
         if (g2 < 0) break;
         g = take();
         packed_issue_dual(src, g, lane_off, own_off, ra);
-        KM_WS_PASS(process(rb, g2));
+        process(rb, g2);
     }
-#undef KM_WS_PASS
-#ifdef ET_EXP_WAITSTAMP
-    if (lane == 0) {  // (into LDS: six device atomics per wavefront here made the build's launches 4-5x slower)
-        atomicAdd(&s_ws_acc[0], ws_n);
-        atomicAdd(&s_ws_acc[1], ws_wait);
-        atomicAdd(&s_ws_acc[2], ws_pass);
-        atomicAdd(&s_ws_acc[3], ws_drain);
-        atomicAdd(&s_ws_acc[4], ws_nd);
-        atomicAdd(&s_ws_acc[6], 1ull);
-    }
-#endif
-    KM_PSTAMP(6);
     if (qn) packed_drain(queue, qn, K, sC, pk.xa, labels, sAcc, frac, lane);
     __syncthreads();
-    KM_PSTAMP(7);
     for (int i = tx; i < plen; i += n_thr) {  // the copies -> copy 0
         long long v = sAcc[i];
 #pragma unroll
@@ -504,11 +472,6 @@ __device__ __forceinline__ void packed_assign_body(const LloydPacked pk, const f
     }
     __syncthreads();
     emit_partials(sAcc, plen, n_thr, nullptr, lanes, copy_mask);
-#ifdef ET_EXP_WAITSTAMP
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    KM_PSTAMP(8);
-    KM_PSTAMP_FLUSH();
 }
 
 }  // namespace et

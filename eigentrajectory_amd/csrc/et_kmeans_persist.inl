@@ -46,7 +46,6 @@ struct LloydPersist {
 };
 constexpr unsigned long long kSpinTimeoutTicks = 50000000ull;  // 0.5 s of the 100 MHz s_memrealtime clock
 
-
 template <int NREGS, bool SIM>
 __global__ __launch_bounds__(kFilterMaxThreads) void kmeans_lloyd_persist_kernel(
     const float *__restrict__ X, int64_t N, int K, LloydPersist pa, uint8_t *__restrict__ labels, float tol,
@@ -90,7 +89,6 @@ __global__ __launch_bounds__(kFilterMaxThreads) void kmeans_lloyd_persist_kernel
     const int copy_mask = gridDim.x <= 64 ? 0 : kAccLanes - 1;
     int it = 0;
     for (;; ++it) {
-        ET_STAMP(0);
         if (it > 0) {
             // ---- grid barrier: every workgroup has added the deltas of assignment it - 1 ----
             if (threadIdx.x == 0) {
@@ -108,7 +106,6 @@ __global__ __launch_bounds__(kFilterMaxThreads) void kmeans_lloyd_persist_kernel
             }
             __syncthreads();
             if (sAbort) return;
-            ET_STAMP(1);
             // ---- fold the 16 copies of the table this assignment filled (sc1 loads: the atomics were performed at the
             //      memory side) onto the running totals, in place: one lane per entry reads and writes it ----
             const long long *lanes = it % 3 == 0 ? pa.lanes0 : (it % 3 == 1 ? pa.lanes1 : pa.lanes2);
@@ -136,10 +133,8 @@ __global__ __launch_bounds__(kFilterMaxThreads) void kmeans_lloyd_persist_kernel
                 }
             }
             __syncthreads();
-            ET_STAMP(2);
             update_body(&sSt, sTot, d, K, tol, sCen, wg0 ? trace : nullptr, nullptr, wg0 ? pa.last : nullptr);
             __syncthreads();
-            ET_STAMP(3);
             if (wg0) {  // the table launch it - 1 read becomes the one assignment it + 1 adds onto
                 long long *zero = (it + 2) % 3 == 0 ? pa.lanes0 : ((it + 2) % 3 == 1 ? pa.lanes1 : pa.lanes2);
                 for (int i = threadIdx.x; i < total; i += n_threads)
@@ -158,9 +153,7 @@ __global__ __launch_bounds__(kFilterMaxThreads) void kmeans_lloyd_persist_kernel
         int64_t Ni = N;
         int Ki = K;
         asm volatile("" : "+s"(Xi), "+s"(li), "+s"(Ni), "+s"(Ki), "+s"(wr));
-        ET_STAMP(4);
         filter_assign_body<NREGS, SIM>(Xi, Ni, Ki, &sSt, sCen, li, nullptr, wr, copy_mask);
-        ET_STAMP(5);
         // arrival: this workgroup's atomics (and its table clear, workgroup 0) have been performed -- every wavefront
         // waits for its own outstanding memory operations (s_waitcnt vmcnt(0) expcnt(0) lgkmcnt(0); a workgroup-scope
         // release fence would omit the vmcnt), then the workgroup barrier, then one lane counts
@@ -283,7 +276,6 @@ __global__ void kmeans_inertia_finish_kernel(et_kmeans_state *state, const float
     else inertia = (float)(-(((double)sim_total[0] * ldexp(1.0, -sfrac)) / (double)state->n_total));  // kmeans.py:57
     state->inertia = (double)inertia;
 }
-
 
 // Single-GPU fit: the reduction above and the update in ONE launch.  One entry per WAVEFRONT (the filter kernel
 // runs one fat workgroup per CU, so an entry has only a few hundred workgroup partials); the workgroup that

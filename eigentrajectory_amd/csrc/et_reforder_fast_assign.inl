@@ -13,9 +13,6 @@ namespace fast {
 //      workgroup queue and gets the exact scan afterwards, four threads per point.  The same labels as the exact scan of
 //      every point, by construction; what it saves is the scan: ~300 vector + 16 matrix instructions per 256 points
 //      instead of ~720 vector instructions. ----
-#ifdef ET_EXP_RF_CHECK
-__device__ unsigned g_rf_check[64];
-#endif
 template <int NREGS>
 __device__ __forceinline__ double assign_group_filter(const float4 *__restrict__ x4, int L2, const float *sC, int K, float sg,
                                                       unsigned *sLab, unsigned *__restrict__ LTg, unsigned short *sQ, int q_cap,
@@ -121,11 +118,7 @@ __device__ __forceinline__ double assign_group_filter(const float4 *__restrict__
                 const float wv = (y + an) * sg2;
                 const float th = fmaf(fabsf(wv), 2.384185791015625e-7f,
                                       fmaf(rs, fmaf(rs, 1.52587890625e-5f, 9.5367431640625e-7f), 2.3283064365386963e-10f));
-#ifdef ET_EXP_RF_ALL_UNDECIDED
-                const bool keep = false;
-#else
                 const bool keep = wv - second > th;
-#endif
                 sim = sim + (keep ? (double)y : 0.0);
                 undecided |= keep ? 0u : (1u << q);
             }
@@ -235,8 +228,6 @@ __global__ __launch_bounds__(kFThreads, NREGS ? 6 : 7) void reforder_groups_kern
     // last slot freed up, alone on the chip for its whole 20 us (N = 1e7: the launch ended 113 us after it began, the groups 93)
     const int64_t gidx = blockIdx.x == 0 ? geo.G : (int64_t)blockIdx.x - 1;
     const bool is_tail = gidx == geo.G;
-    [[maybe_unused]] const int who = is_tail ? 1 : (gidx == 0 ? 0 : 9);
-    RF_STAMP(who, 0);
 
     // ---- prologue: centroid rows with |c_j|^2 in ATen's order for column j of K (kmeans.py:74), NaN / overflow test ----
     int bad = 0;
@@ -269,7 +260,6 @@ __global__ __launch_bounds__(kFThreads, NREGS ? 6 : 7) void reforder_groups_kern
     const bool nans = __syncthreads_or(bad) != 0 || !(max_abs_x < 1e18);
     double sim = 0.0;
     float4 acc1 = make_float4(0.f, 0.f, 0.f, 0.f), acc0 = acc1;
-    RF_STAMP(who, 1);
 
     if (!is_tail) {
         // ---- assignment of the group's 4 L^2 points (kmeans.py:143-158): a quad = four consecutive steps of one chain ----
@@ -324,13 +314,9 @@ __global__ __launch_bounds__(kFThreads, NREGS ? 6 : 7) void reforder_groups_kern
             atomicAdd(&sCnt[(l4 >> 16) & 255u], 1u);
             atomicAdd(&sCnt[l4 >> 24], 1u);
         }
-        RF_STAMP(who, 2);
-        RF_STAMP_MAX(0, 8);
         cascade_levels([&](int q, int rb, int ln, int i) { return x4[i * L2 + (q * RB + rb) * 64 + ln]; }, sLab, sAcc, K, L, TR, L, L,
                        acc1, acc0);
         if (tid < dk) S1[gidx * dk + tid] = acc1;
-        RF_STAMP(who, 3);
-        RF_STAMP_MAX(0, 9);
     } else {
         // ---- the tail: the points tail0 .. N-1 where they lie in X -- the chunks of the partial group (level 1 of their
         //      level-0 sums -> T[0 .. d K)), the lane terms after the last full chunk (level 0 -> T[d K ..)), and the
@@ -370,7 +356,6 @@ __global__ __launch_bounds__(kFThreads, NREGS ? 6 : 7) void reforder_groups_kern
                 }
         }
         __syncthreads();
-        RF_STAMP(who, 2);
         // the label words of the chains' steps; a step past the lane's range gets the dummy row
         const int tiles = (n_all + 15) >> 4;
         for (int w = tid; w < tiles * RB * 64; w += kFThreads) {
@@ -408,7 +393,6 @@ __global__ __launch_bounds__(kFThreads, NREGS ? 6 : 7) void reforder_groups_kern
             T[dk + tid] = acc0;
         }
         if (tid == 0) T[2 * dk] = make_float4(__uint_as_float(lw), 0.f, 0.f, 0.f);
-        RF_STAMP(who, 3);
     }
     // ---- this workgroup's counts and similarity sum (read by the next kernel) ----
     sim = wave_sum_f64(sim);
@@ -420,8 +404,6 @@ __global__ __launch_bounds__(kFThreads, NREGS ? 6 : 7) void reforder_groups_kern
         for (int w = 1; w < kFThreads / 64; ++w) s = s + sWsum[w];
         Sin[gidx] = s;
     }
-    RF_STAMP(who, 4);
-    RF_STAMP_MAX(0, 10);
 }
 
 // ATen's inner (contiguous) sum (inner_sum_f32) of v[0..size) in LDS, its 32 (vector lane, slot) cascades side by side;

@@ -265,38 +265,6 @@ __device__ __forceinline__ double wave_sum_f64(double v) {  // fixed tree: the s
     return v;
 }
 
-#ifdef ET_EXP_RFSTAMP  // measurement build (tools/archive/rfstamp.py): s_memrealtime at the phase boundaries of four workgroups
-__device__ unsigned long long g_rf_stamps[4 * 16];
-#define RF_STAMP(who, i)                                                                                           \
-    do {                                                                                                           \
-        if ((who) < 4 && threadIdx.x == 0 && blockIdx.y == 0) g_rf_stamps[(who) * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-// slot `i` of row `who`: the latest time any workgroup passed here
-#define RF_STAMP_MAX(who, i)                                                                               \
-    do {                                                                                                   \
-        if (threadIdx.x == 0 && blockIdx.y == 0) atomicMax(&g_rf_stamps[(who) * 16 + (i)], __builtin_amdgcn_s_memrealtime()); \
-    } while (0)
-// slot `i` of row 3 += ticks since *t (thread 0 of workgroup 0 only), *t = now
-#define RF_ACC(i, t)                                                                  \
-    do {                                                                              \
-        if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0) {                 \
-            const unsigned long long now_ = __builtin_amdgcn_s_memrealtime();         \
-            g_rf_stamps[3 * 16 + 8 + (i)] += now_ - (t);                              \
-            (t) = now_;                                                               \
-        }                                                                             \
-    } while (0)
-#else
-#define RF_ACC(i, t) \
-    do {             \
-    } while (0)
-#define RF_STAMP_MAX(who, i) \
-    do {                     \
-    } while (0)
-#define RF_STAMP(who, i) \
-    do {                 \
-    } while (0)
-#endif
-
 // Levels 0 and 1 of the cascade for the chunks 0 .. n_all-1 of one group (n_all <= L), TR tiles (of 16 chunks) at a time:
 //   level 0  wavefront = coordinate, lane = chain (chunk, lane k); the chain's K (+ one dummy) accumulators are the LDS
 //            words [row][chain]; a step = read, add, write of the row its label names;
@@ -316,6 +284,9 @@ __device__ __forceinline__ void cascade_levels(Load load, const unsigned *sLab, 
     // label) stays inside bank  lane mod 4 + a scrambled multiple of 4; level 1 (lane = (coordinate, cluster), a 16-byte
     // read of the four lanes k of chunk c) finds the rows of eight consecutive clusters in eight different bank groups --
     // without the swizzle every lane of a wavefront reads the same four banks.
+    // (Start value of the archived phase stamps, tools/archive/instrumentation/rfstamp.diff.txt.  Without them nothing
+    // reads it, but the compiler does not drop a clock read: one s_memrealtime per call.  Taking the stamps out moved no
+    // generated code; whoever removes this line re-measures the kernel.)
     [[maybe_unused]] unsigned long long tacc = __builtin_amdgcn_s_memrealtime();
     for (int q0 = 0; q0 < tiles; q0 += TR) {
         const int tr = tiles - q0 < TR ? tiles - q0 : TR;
@@ -325,7 +296,6 @@ __device__ __forceinline__ void cascade_levels(Load load, const unsigned *sLab, 
                 float4 *z = reinterpret_cast<float4 *>(blk);
                 for (int e = lane; e < rows * 16; e += 64) z[e] = make_float4(0.f, 0.f, 0.f, 0.f);
             }
-            RF_ACC(0, tacc);
             const unsigned *lr = sLab + (q0 + ql) * RB * 64 + lane;
             // the chain's values, four 16-byte loads (= 16 steps) in flight at a time: with one load per four steps the loop ran
             // at the latency of its loads, not of its LDS updates (eight in flight cost the registers of a seventh wavefront)
@@ -333,10 +303,6 @@ __device__ __forceinline__ void cascade_levels(Load load, const unsigned *sLab, 
                 float4 xc[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) xc[u] = load(q0 + ql, rb0 + u, lane, wave);
-#ifdef ET_EXP_RFSTAMP
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-                RF_ACC(1, tacc);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     // four steps: their accumulators are requested together and the additions chained in registers -- a
@@ -358,14 +324,9 @@ __device__ __forceinline__ void cascade_levels(Load load, const unsigned *sLab, 
                     *p2 = n2;
                     *p3 = n3;
                 }
-#ifdef ET_EXP_RFSTAMP
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-                RF_ACC(2, tacc);
             }
         }
         __syncthreads();
-        RF_ACC(3, tacc);
         if (tid < dk) {
             for (int ql = 0; ql < tr; ++ql) {
                 const float *row = sAcc + ((size_t)(ql * kD + ci) * rows + cj) * 64;
@@ -390,9 +351,7 @@ __device__ __forceinline__ void cascade_levels(Load load, const unsigned *sLab, 
                 }
             }
         }
-        RF_ACC(4, tacc);
         __syncthreads();
-        RF_ACC(5, tacc);
     }
 }
 

@@ -37,8 +37,6 @@ __global__ __launch_bounds__(TT) void reforder_update_kernel2(const Args a, int 
     __shared__ int sFlag[2];
     __shared__ float sScr[40];
     float4 *sRows = reinterpret_cast<float4 *>(smem);
-    [[maybe_unused]] const int who = blockIdx.x == 0 ? 2 : 9;
-    RF_STAMP(who, 0);
 
     // ---- level 2 ----
     const int blk = SINGLE ? tid / slot : (int)blockIdx.x;
@@ -140,18 +138,15 @@ __global__ __launch_bounds__(TT) void reforder_update_kernel2(const Args a, int 
             }
             st16_sc1(rS2, (unsigned)(((int64_t)blk * rowlen + tid) * sizeof(float4)), __builtin_bit_cast(float4, c2));
         }
-        RF_STAMP(who, 1);
         // ---- arrival: the stores have been performed at the memory side ----
         __builtin_amdgcn_s_waitcnt(0);
         __syncthreads();
         if (tid == 0) sFlag[0] = __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)geo.n_blk - 1u;
         __syncthreads();
-        RF_STAMP(who, 2);
         if (!sFlag[0]) return;
     }
 
     // ---- last workgroup of this problem: level 3 over the complete blocks, in block order ----
-    RF_STAMP(3, 0);
     float4 a3 = make_float4(0.f, 0.f, 0.f, 0.f);
     unsigned ctot[4] = {0u, 0u, 0u, 0u};
     __shared__ unsigned sCntTot[kFMaxK];
@@ -254,7 +249,6 @@ __global__ __launch_bounds__(TT) void reforder_update_kernel2(const Args a, int 
         for (int w = 1; w < kUThreads / 64; ++w) s = s + sWsum[w];
         __hip_atomic_store(&state->inertia, (double)(float)(-(s / (double)N)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    RF_STAMP(3, 1);
     if (a.batch > 1) {
         __builtin_amdgcn_s_waitcnt(0);
         __syncthreads();
@@ -266,10 +260,8 @@ __global__ __launch_bounds__(TT) void reforder_update_kernel2(const Args a, int 
         for (int e = tid; e < tot; e += TT) sSq[e] = __hip_atomic_load(&a.sq_all[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
     }
-    RF_STAMP(3, 2);
     const float error = inner_sum_parallel(sSq, a.batch * dk, sScr);
     const int done = (error <= a.tol) ? 1 : 0;
-    RF_STAMP(3, 3);
     for (int b = tid; b < a.batch; b += TT) {
         et_kmeans_state *st = at<et_kmeans_state>(a.ws + (int64_t)b * a.ws_stride, a.lay.state);
         const int64_t it = st->iter;
@@ -291,7 +283,6 @@ __global__ __launch_bounds__(TT) void reforder_update_kernel2(const Args a, int 
         if (tid == 0) at<unsigned>(wb, a.lay.arrive)[0] = 0u;
     }
     if (tid == 0) *a.batch_arrive = 0u;
-    RF_STAMP(3, 4);
 }
 
 }  // namespace fast

@@ -295,19 +295,6 @@ static int update_rows_cap(const Geo &g, int K, int batch, size_t *lds) {
     return want;
 }
 
-#ifdef ET_EXP_RF_CHECK
-extern "C" int et_debug_rfcheck(unsigned *host) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_rf_check), sizeof(unsigned) * 64) == hipSuccess ? 0 : 3;
-}
-#endif
-#ifdef ET_EXP_RFSTAMP
-extern "C" int et_debug_rfstamps(unsigned long long *host) {
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_rf_stamps), sizeof(unsigned long long) * 64) != hipSuccess) return 3;
-    static const unsigned long long zeros[64] = {};
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_rf_stamps), zeros, sizeof zeros) == hipSuccess ? 0 : 3;  // (reading resets)
-}
-#endif
-
 }  // namespace fast
 }  // namespace reforder
 }  // namespace et

@@ -53,7 +53,35 @@ def test_options_table_and_no_environment_reads():
             assert "getenv" not in open(os.path.join(csrc, name)).read(), name
     import subprocess
     syms = subprocess.run(["nm", "-D", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    assert "et_testhook" not in syms and "et_debug" not in syms  # (stamp readers exist in -DET_EXP_* variant builds only)
+    # (test hooks are in libetamd_testhooks.so only; the stamp readers come with the patches of tools/archive/instrumentation/)
+    assert "et_testhook" not in syms and "et_debug" not in syms
+
+
+def test_csrc_has_one_conditional_and_the_makefile_one_define():
+    """The product source is what a default build compiles: the only conditional compilation under csrc/ is ET_TEST_HOOKS
+    (measurement switches and stamps live in tools/archive/, as patches), and the Makefile defines nothing else."""
+    import re
+    import subprocess
+    csrc = os.path.join(ROOT, "eigentrajectory_amd", "csrc")
+    directive = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif)\b(.*)$")  # (#pragma once is no conditional; #else / #endif follow one)
+    seen = []
+    for name in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, name)
+        if not os.path.isfile(path) or name.endswith((".o", ".so")):
+            continue
+        for no, line in enumerate(open(path, errors="replace"), 1):
+            m = directive.match(line)
+            if m:
+                seen.append(name)
+                assert re.search(r"\bET_TEST_HOOKS\b", m.group(2)), f"{name}:{no}: {line.strip()}"
+    assert seen, "the ET_TEST_HOOKS sites were not found: the scan reads the wrong files"
+    makefile = open(os.path.join(csrc, "Makefile")).read()
+    assert set(re.findall(r"(?<![\w-])-D\s*\w+", makefile)) == {"-DET_TEST_HOOKS"}
+    # ... and none reaches a compile line through a variable: the commands of a full build, not run
+    dry = subprocess.run(["make", "-n", "-B", "-C", csrc, "all"], capture_output=True, text=True, check=True).stdout
+    n_srcs = len(subprocess.run(["make", "-s", "-C", csrc, "print-srcs"], capture_output=True, text=True, check=True).stdout.split())
+    assert n_srcs >= 15 and dry.count(" -c ") == n_srcs + 1  # every source, and et_kmeans.hip once more for the hooks
+    assert set(re.findall(r"(?<![\w-])-D\s*\w+", dry)) == {"-DET_TEST_HOOKS"}
 
 
 def test_state_struct_layout_matches_header():

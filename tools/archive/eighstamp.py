@@ -8,7 +8,7 @@ import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from eigentrajectory_amd import _lib as L, ops  # noqa: E402
 from eigentrajectory_amd.synth import synthetic_trajectories_torch  # noqa: E402
 

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Register / scratch / LDS / occupancy table of every kernel of one csrc/*.hip file, as the compiler reports it
-(-Rpass-analysis=kernel-resource-usage with the Makefile's flags).  *(container)*
+(-Rpass-analysis=kernel-resource-usage with the flags csrc/Makefile gives that file).  *(container)*
 usage: tools/kernel_usage.py et_fit.hip [-DFLAG ...] [--grep substring]
-       tools/kernel_usage.py et_kmeans.hip [-DFLAG ...] --digest   name and sha256 of every device function's assembly and of
-           every kernel's descriptor: `diff` the output of two checkouts to prove that a host-side change left the device code alone"""
+       tools/kernel_usage.py et_kmeans.hip [-DFLAG ...] --digest [--csrc DIR]   name and sha256 of every device function's
+           assembly and of every kernel's descriptor.  --csrc DIR compiles another checkout's csrc/ with THIS checkout's
+           flags: `diff` the two outputs to prove that a change left the device code alone.  `all` for the file: every
+           source of the Makefile, then et_kmeans.hip -DET_TEST_HOOKS"""
 import hashlib
 import os
 import re
@@ -11,16 +13,22 @@ import subprocess
 import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "eigentrajectory_amd", "csrc")
-FLAGS = ("--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form=1 "
-         "-fno-slp-vectorize --cuda-device-only -Rpass-analysis=kernel-resource-usage").split()
 
 
-def digest(src, extra):
+def ask_make(target):
+    """csrc/Makefile is the one place that lists the sources and their flags"""
+    return subprocess.run(["make", "-s", "-C", CSRC, target], stdout=subprocess.PIPE, text=True, check=True).stdout.split()
+
+
+def flags_of(src):
+    return ask_make("print-flags-" + os.path.splitext(os.path.basename(src))[0]) + ["--cuda-device-only"]
+
+
+def digest(src, extra, csrc):
     """Per symbol, because emission order follows the host code.  Local labels carry the function's position in the file
     (.LBB13_2, .Lfunc_end13, .LJTI13_0; "Header=BB13_29" in the loop comments) or a file-wide count (.Ltmp57): that number is
     taken out, the rest stays."""
-    flags = [f for f in FLAGS if not f.startswith("-Rpass")] + ["-S", "-o", "-"]
-    asm = subprocess.run(["/opt/rocm/bin/hipcc"] + flags + extra + [src], cwd=CSRC, stdout=subprocess.PIPE,
+    asm = subprocess.run(["/opt/rocm/bin/hipcc"] + flags_of(src) + ["-S", "-o", "-"] + extra + [src], cwd=csrc, stdout=subprocess.PIPE,
                          text=True, check=True).stdout  # (the compiler's diagnostics go to the terminal)
     bodies, cur = {}, None
     for line in asm.splitlines():
@@ -41,16 +49,26 @@ def digest(src, extra):
 
 def main():
     args = sys.argv[1:]
+    csrc = CSRC
+    if "--csrc" in args:
+        i = args.index("--csrc")
+        csrc = os.path.abspath(args[i + 1])
+        del args[i:i + 2]
     if "--digest" in args:
         args.remove("--digest")
-        return digest(args[0], args[1:])
+        if args[0] != "all":
+            return digest(args[0], args[1:], csrc)
+        for src, extra in [(s, []) for s in ask_make("print-srcs")] + [("et_kmeans.hip", ["-DET_TEST_HOOKS"])]:
+            print("==", src, *extra, flush=True)
+            digest(src, extra, csrc)
+        return
     pat = None
     if "--grep" in args:
         i = args.index("--grep")
         pat = args[i + 1]
         del args[i:i + 2]
     src, extra = args[0], args[1:]
-    out = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + extra + ["-c", src, "-o", "/dev/null"], cwd=CSRC,
+    out = subprocess.run(["/opt/rocm/bin/hipcc"] + flags_of(src) + ["-Rpass-analysis=kernel-resource-usage"] + extra + ["-c", src, "-o", "/dev/null"], cwd=csrc,
                          stderr=subprocess.PIPE, text=True).stderr
     rows, cur = [], {}
     for line in out.splitlines():
