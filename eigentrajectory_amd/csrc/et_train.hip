@@ -14,7 +14,8 @@
 //                            loss_euclidean_fde = mean_n min_s || recon[s,n,T-1] - gt[n,T-1] ||_2           (model.py:122-123)
 //                            + the arg-min sample of each term per pedestrian (for the backward)             [1 launch]
 //   et_wrapper_losses_bwd    dC (k,N,S) for given d(loss) factors: the three terms only reach the sample that attains
-//                            their minimum (torch.amin's gradient; ties have measure zero), through
+//                            their minimum (the gradient of the reference's .min(dim)[0]: on a tie, all of it to the
+//                            first minimal sample), through
 //                            d recon / d C = (g @ R) / sca @ U (ops._reconstruct_bwd's map)                  [1 launch]
 // One workgroup (scenes: N <= ET_SCENE_MAX_N); lane = pedestrian; the means are fixed-order sums (deterministic).
 #include "et_common.h"
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(kTrThreads) void wrapper_losses_fwd_kernel(
                 fd = dist;  // the last step's stays
             }
             ad = ad / (float)T;
-            // torch.amin / argmin: first minimum; a NaN takes over (and stays)
+            // torch's .min(dim): first minimum; a NaN takes over (and stays)
             if (e < be || (e != e && be == be)) be = e, ie = s;
             if (ad < ba || (ad != ad && ba == ba)) ba = ad, ia = s;
             if (fd < bf || (fd != fd && bf == bf)) bf = fd, ifd = s;
@@ -174,7 +175,11 @@ __global__ __launch_bounds__(kTrThreads) void wrapper_losses_bwd_kernel(
         const float *A = p.mv ? A_m : A_s;
         const float *U = p.mv ? U_m : U_s;
         const float *g = gt + (int64_t)n * 2 * T;
-        {   // coefficient term: (cp - cg) / ||cp - cg|| at its arg-min sample
+        // Each norm's gradient is x / ||x||, 0 where the norm is exactly 0 (torch's subgradient there) and NaN where it
+        // is NaN: a row whose loss is NaN hands a NaN gradient to its selected sample, as the reference's autograd does.
+        // A term that was not differentiated (g_* == NULL) is left out altogether, so it poisons nothing; one whose
+        // upstream gradient is a zero VALUE is evaluated, and 0 * NaN is NaN as in autograd.
+        if (g_e) {  // coefficient term: (cp - cg) / ||cp - cg|| at its arg-min sample
             const int s = arg[n];
             float df[ET_MAX_K];
             float e2 = 0.f;
@@ -184,7 +189,7 @@ __global__ __launch_bounds__(kTrThreads) void wrapper_losses_bwd_kernel(
                 e2 = fmaf(df[j], df[j], e2);
             }
             const float e = sqrtf(e2);
-            if (e > 0.f)
+            if (e != 0.f)
                 for (int j = 0; j < k; ++j) dC[((int64_t)j * N + n) * S + s] += ge * df[j] / e;
         }
         // displacement terms: d ||r - g|| / d r = (r - g) / ||r - g||, pulled back through the denormalisation and U
@@ -192,15 +197,16 @@ __global__ __launch_bounds__(kTrThreads) void wrapper_losses_bwd_kernel(
             const float *r = recon + (((int64_t)s * N + n) * T + t) * 2;
             const float ex = r[0] - g[2 * t], ey = r[1] - g[2 * t + 1];
             const float dist = sqrtf(fmaf(ex, ex, ey * ey));
-            if (!(dist > 0.f)) return;
+            if (dist == 0.f) return;
             float a, b;
             denormalize_point_bwd(p, w * ex / dist, w * ey / dist, a, b);
             for (int j = 0; j < k; ++j)
                 dC[((int64_t)j * N + n) * S + s] += fmaf(U[(2 * t) * k + j], a, U[(2 * t + 1) * k + j] * b);
         };
         const int sa = arg[N + n], sf = arg[2 * N + n];
-        for (int t = 0; t < T; ++t) pull(sa, t, ga);
-        pull(sf, T - 1, gf);
+        if (g_ade)
+            for (int t = 0; t < T; ++t) pull(sa, t, ga);
+        if (g_fde) pull(sf, T - 1, gf);
     }
 }
 
@@ -250,6 +256,8 @@ extern "C" int et_wrapper_losses_bwd(const float *g_eigentraj, const float *g_ad
                                      et_stream_t stream) {
     if (!tr_dims_ok(N, S, k, 3, T_pred) || N < 1 || mode < 0 || mode > 2) return ET_ERR_INVALID_ARG;
     if (!C || !nrm || !C_gt || !gt || !recon || !arg || !dC) return ET_ERR_INVALID_ARG;
+    const bool m = mode != ET_MODE_STATIC, s = mode != ET_MODE_MOVING;
+    if ((m && !U_pred_m) || (s && !U_pred_s)) return ET_ERR_INVALID_ARG;
     hipLaunchKernelGGL(wrapper_losses_bwd_kernel, dim3(1), dim3(kTrThreads), 0, (hipStream_t)stream, g_eigentraj, g_ade, g_fde, C,
                        (int)N, S, k,
                        T_pred, nrm, A_m, A_s, U_pred_m, U_pred_s, mode, static_dist, C_gt, gt, recon, (const int *)arg, dC);

@@ -504,8 +504,10 @@ class EigenTrajectory(nn.Module):
             # model.py:119-123: best-of-S distances in coefficient space and in metres (mean / final step)
             coef_err = torch.linalg.vector_norm(C_pred - C_pred_gt[:, :, None], dim=0)        # (N, S)
             step_err = torch.linalg.vector_norm(pred_traj_recon - gt[None], dim=-1)           # (S, N, t_pred)
-            output["loss_eigentraj"] = coef_err.amin(dim=-1).mean()
-            output["loss_euclidean_ade"] = step_err.mean(dim=-1).amin(dim=0).mean()
-            output["loss_euclidean_fde"] = step_err[:, :, -1].amin(dim=0).mean()
+            # (.min(dim)[0] like the reference, not amin: on an exact tie the whole gradient goes to the first minimal
+            # sample -- what csrc/et_train.hip does too -- where amin would split it among the tied ones)
+            output["loss_eigentraj"] = coef_err.min(dim=-1)[0].mean()
+            output["loss_euclidean_ade"] = step_err.mean(dim=-1).min(dim=0)[0].mean()
+            output["loss_euclidean_fde"] = step_err[:, :, -1].min(dim=0)[0].mean()
 
         return output

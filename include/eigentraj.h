@@ -162,8 +162,11 @@ int et_scene_project(const float *obs, int64_t N, int T_obs, int k, const float 
  *                             losses[2] loss_euclidean_fde = mean_n min_s ||recon[s,n,-1] - gt[n,-1]||        (model.py:122-123)
  *                           best (3,N): the per-pedestrian minima, arg (3,N) int32: the sample attaining each.
  *   et_wrapper_losses_bwd   dC (k,N,S) = sum_i g_i * d losses[i] / d C (g_*: the upstream gradient of each loss, a device
- *                           scalar, NULL = not differentiated); each term reaches only its arg-min sample (torch.amin's
- *                           gradient). */
+ *                           scalar, NULL = not differentiated); each term reaches only its arg-min sample, on an exact
+ *                           tie the first one (the gradient of the reference's .min(dim)[0]).  A distance that is exactly
+ *                           0 contributes 0; one that is NaN makes that sample's dC NaN, as the reference's autograd does
+ *                           (also under a non-NULL g_* whose value is 0: 0 * NaN; only a NULL g_* leaves its term out).
+ *                           Needs the U_pred of every descriptor the mode uses, like et_wrapper_losses_fwd. */
 int et_scene_project_train(const float *obs, const float *pred, int64_t N, int T_obs, int T_pred, int k,
                            const float *U_obs_m, const float *U_obs_s, const float *U_pred_m, const float *U_pred_s,
                            int mode, float static_dist, float *C_obs, float *nrm, float *obs_ori, float *C_gt,
