@@ -12,5 +12,7 @@ from .anchor import ETAnchor
 from .kmeans import BatchKMeans
 from .stgcnn import SocialSTGCNN
 from .sgcn import SGCN
+from .gpgraph import GPGraph, GPGraphSGCN, get_GPGraph_SGCN_model
 
-__all__ = ["EigenTrajectory", "TrajNorm", "ETDescriptor", "ETAnchor", "BatchKMeans", "SocialSTGCNN", "SGCN"]
+__all__ = ["EigenTrajectory", "TrajNorm", "ETDescriptor", "ETAnchor", "BatchKMeans", "SocialSTGCNN", "SGCN", "GPGraph",
+           "GPGraphSGCN", "get_GPGraph_SGCN_model"]

@@ -86,6 +86,10 @@ SIGNATURES = {
     "et_sgcn_workspace_bytes": (_Z, [_P, _I64, _I64, _I]),
     "et_sgcn_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _I64, _I64, _P, _P, _P, _P, _Z, _P]),
     "et_sgcn_forward_graph": (_I, [_P, _P, _P, _I, _P, _I, _I64, _P, _P, _P, _P, _Z, _P]),
+    # ---- GP-Graph-SGCN predictor, inference
+    "et_gpgraph_sgcn_workspace_bytes": (_Z, [_P, _I64, _I64, _I]),
+    "et_gpgraph_sgcn_forward_graph": (_I, [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "et_gpgraph_sgcn_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _I64, _I64, _P, _P, _P, _P, _P, _P, _Z, _P]),
     # ---- fit
     "et_fit_gram_workspace_bytes": (_Z, [_I64, _I, _I]),
     "et_fit_gram": (_I, [_P, _P, _I64, _I, _I, _I, _F, _I, _P, _P, _P, _P, _Z, _P]),
@@ -207,6 +211,12 @@ class SGCNParams(C.Structure):
                 ("asym_s", SGCNAsym * SGCN_MAX_LAYERS), ("asym_t", SGCNAsym * SGCN_MAX_LAYERS), ("gcn", SGCNGcn * 4),
                 ("fusion_w", C.c_void_p), ("tcn_w", C.c_void_p * SGCN_MAX_LAYERS), ("tcn_b", C.c_void_p * SGCN_MAX_LAYERS),
                 ("tcn_a", C.c_void_p * SGCN_MAX_LAYERS), ("out_w", C.c_void_p), ("out_b", C.c_void_p)]
+
+
+class GPGraphSGCNParams(C.Structure):
+    """Mirror of ``et_gpgraph_sgcn_params``."""
+    _fields_ = [("base", SGCNParams), ("group_w", C.c_void_p), ("group_b", C.c_void_p), ("th", C.c_void_p),
+                ("tau", C.c_float), ("mix_a", C.c_void_p), ("mix_w", C.c_void_p), ("mix_b", C.c_void_p)]
 
 
 STATE_BYTES = C.sizeof(KMeansState)

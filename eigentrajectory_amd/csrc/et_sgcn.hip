@@ -18,533 +18,13 @@
 //                           stored): spatial_temporal gcn 0 and temporal_spatial gcn 1
 //   tail    per pedestrian  spatial_temporal gcn 1, fusion_, the tcns and the output layer in one wavefront's LDS
 // Every sum runs in a fixed order inside one lane, so results do not depend on the launch geometry or on the other scenes.
+// The kernels themselves are in et_sgcn_core.inl, which et_gpgraph.hip (GP-Graph-SGCN) shares.
 #include "et_common.h"
 
 namespace et {
 namespace {
 
-constexpr int kSnThreads = 256;
-constexpr int kH = 4, kD = 16, kE = 64;
-constexpr int kSnMaxT = ET_MAX_K + 2;
-constexpr int kSnMaxS = 64;
-
-struct Lay {  // workspace layout, in floats
-    int64_t hdr, sq, v, rs_s, rs_t, xa, xb, ta, tb, at, f2, f1, ts, total;
-};
-
-__host__ __device__ inline int64_t up4(int64_t x) { return (x + 3) & ~(int64_t)3; }
-
-__host__ __device__ inline Lay lay_of(int T, int64_t N, int64_t n2, int64_t S) {
-    Lay L;
-    L.hdr = 0;
-    L.sq = 64;  // int64 [S]
-    L.v = up4(L.sq + 2 * (S + 1));
-    L.rs_s = up4(L.v + T * N);
-    L.rs_t = up4(L.rs_s + 2 * (int64_t)T * kH * N);
-    L.xa = up4(L.rs_t + 2 * (int64_t)T * kH * N);
-    L.xb = up4(L.xa + (int64_t)T * kH * n2);
-    L.ta = up4(L.xb + (int64_t)T * kH * n2);
-    L.tb = up4(L.ta + N * kH * T * T);
-    L.at = up4(L.tb + N * kH * T * T);
-    L.f2 = up4(L.at + N * kH * T * T);
-    L.f1 = up4(L.f2 + N * kH * T * kD);
-    L.ts = up4(L.f1 + N * kH * T * kD);
-    L.total = up4(L.ts + N * kH * T * kD);
-    return L;
-}
-
-struct Ctx {
-    const int32_t *off;  // scene offsets, or NULL: one scene of N rows
-    int64_t N, n2cap;
-    int S, T;
-    float *ws;
-    Lay L;
-};
-
-// identities as handed over (graph form), or NULL: eye(n) / all ones (what the bridge builds)
-struct Ident {
-    const float *s, *t;
-    int s_t, t_t;
-};
-
-__device__ __forceinline__ float ident_s(const Ident &I, int t, int i, int j, int n) {
-    if (!I.s) return i == j ? 1.f : 0.f;
-    return I.s[((int64_t)(I.s_t > 1 ? t : 0) * n + i) * n + j];
-}
-
-__device__ __forceinline__ float ident_t(const Ident &I, int i, int t, int u, int T) {
-    if (!I.t) return 1.f;
-    return I.t_t > 1 ? I.t[((int64_t)i * T + t) * T + u] : I.t[i];
-}
-
-__device__ __forceinline__ bool scene_at(const Ctx &c, int s, int64_t &b, int &n, int64_t &sq) {
-    b = c.off ? c.off[s] : 0;
-    const int64_t e = c.off ? c.off[s + 1] : c.N;
-    if (e <= b) return false;
-    sq = reinterpret_cast<const int64_t *>(c.ws + c.L.sq)[s];
-    if (sq < 0) return false;
-    n = (int)(e - b);
-    return true;
-}
-
-__device__ __forceinline__ float prelu(float x, float a) { return x > 0.f ? x : a * x; }
-__device__ __forceinline__ float dense(float ti, float xj, float m, float sum) { return expf(ti * xj - m) / sum; }
-// where(sigmoid(l) > 0.5, sigmoid(l), 0) + identity
-__device__ __forceinline__ float mask_of(float l, float ident) {
-    const float sg = 1.0f / (1.0f + expf(-l));
-    return (sg > 0.5f ? sg : 0.f) + ident;
-}
-__device__ __forceinline__ float zsm_num(float x) {
-    const float e = expf(x) - 1.0f;
-    return e * e;
-}
-
-// ---- prep: alpha / beta of the two attentions -> hdr[a * 8 + h], hdr[a * 8 + 4 + h]
-__global__ __launch_bounds__(kSnThreads) void sgcn_prep(et_sgcn_params p, float *ws) {
-    __shared__ double aq[2][kE], cq[2][kE], ak[2][kE];
-    const int tid = threadIdx.x;
-    if (tid < 2 * kE) {
-        const int a = tid / kE, c = tid % kE;
-        const et_sgcn_attention &A = p.att[a];
-        double s_aq = 0, s_cq = (double)A.q_b[c], s_ak = 0;
-        for (int e = 0; e < kE; ++e) {
-            const double we = A.emb_w[e], be = A.emb_b[e];
-            s_aq = fma((double)A.q_w[c * kE + e], we, s_aq);
-            s_cq = fma((double)A.q_w[c * kE + e], be, s_cq);
-            s_ak = fma((double)A.k_w[c * kE + e], we, s_ak);
-        }
-        aq[a][c] = s_aq;
-        cq[a][c] = s_cq;
-        ak[a][c] = s_ak;
-    }
-    __syncthreads();
-    if (tid < 2 * kH) {
-        const int a = tid / kH, h = tid % kH;
-        double al = 0, be = 0;
-        for (int d = 0; d < kD; ++d) {
-            al = fma(aq[a][h * kD + d], ak[a][h * kD + d], al);
-            be = fma(cq[a][h * kD + d], ak[a][h * kD + d], be);
-        }
-        ws[a * 8 + h] = (float)(al * 0.125);  // / scaled_factor = sqrt(64)
-        ws[a * 8 + 4 + h] = (float)(be * 0.125);
-    }
-}
-
-// ---- input: one workgroup per scene
-__global__ __launch_bounds__(kSnThreads) void sgcn_input(Ctx c, const float *__restrict__ gv, const float *__restrict__ C_obs,
-                                                         const float *__restrict__ nrm) {
-    __shared__ int64_t part[kSnThreads];
-    __shared__ float red[2 * kSnThreads / kWave];
-    const int s = blockIdx.x, tid = threadIdx.x;
-    const int64_t b = c.off ? c.off[s] : 0;
-    const int64_t e = c.off ? c.off[s + 1] : c.N;
-    if (e <= b) return;
-    // the scene's offset into the stacks: the squared sizes of the scenes before it
-    int64_t mine = 0;
-    for (int q = tid; q < s; q += kSnThreads) {
-        const int64_t m = (int64_t)c.off[q + 1] - c.off[q];
-        if (m > 0) mine += m * m;
-    }
-    part[tid] = mine;
-    __syncthreads();
-    int64_t sq = 0;
-    for (int q = 0; q < kSnThreads; ++q) sq += part[q];
-    const int64_t nn = e - b;
-    const bool ok = nn <= ET_SGCN_MAX_N && sq + nn * nn <= c.n2cap;
-    if (tid == 0) reinterpret_cast<int64_t *>(c.ws + c.L.sq)[s] = ok ? sq : -1;
-    if (!ok) return;
-    const int n = (int)nn, T = c.T;
-    float *v = c.ws + c.L.v + T * b;
-    if (gv) {
-        for (int i = tid; i < T * n; i += kSnThreads) v[i] = gv[i];
-    } else {
-        const int k = T - 2;
-        const int64_t N = c.N;
-        for (int i = tid; i < k * n; i += kSnThreads) v[i] = C_obs[(int64_t)(i / n) * N + b + (i % n)];
-        // obs_ori = last observed position - its mean over the scene, summed in et_scene_project's order
-        float sx = 0.f, sy = 0.f;
-        for (int w = tid; w < n; w += kSnThreads) {
-            sx += nrm[b + w];
-            sy += nrm[N + b + w];
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            sx += __shfl_xor(sx, o);
-            sy += __shfl_xor(sy, o);
-        }
-        if ((tid & (kWave - 1)) == 0) {
-            red[tid / kWave] = sx;
-            red[kSnThreads / kWave + tid / kWave] = sy;
-        }
-        __syncthreads();
-        float mx = 0.f, my = 0.f;
-        for (int w = 0; w < kSnThreads / kWave; ++w) {
-            mx += red[w];
-            my += red[kSnThreads / kWave + w];
-        }
-        mx = mx / (float)n;
-        my = my / (float)n;
-        for (int w = tid; w < n; w += kSnThreads) {
-            v[k * n + w] = nrm[b + w] - mx;
-            v[(k + 1) * n + w] = nrm[N + b + w] - my;
-        }
-    }
-    __syncthreads();
-    // softmax rows: maximum and sum, spatial (t,h,i) over j and temporal (i,h,t) over u
-    const float *hdr = c.ws + c.L.hdr;
-    float *rs_s = c.ws + c.L.rs_s + 2 * (int64_t)T * kH * b;
-    float *rs_t = c.ws + c.L.rs_t + 2 * (int64_t)T * kH * b;
-    const int rows = T * kH * n;
-    for (int r = tid; r < 2 * rows; r += kSnThreads) {
-        const bool temporal = r >= rows;
-        int t, h, i;
-        if (!temporal) {
-            i = r % n;
-            h = (r / n) % kH;
-            t = r / (n * kH);
-        } else {
-            const int q = r - rows;
-            t = q % T;
-            h = (q / T) % kH;
-            i = q / (T * kH);
-        }
-        const float ti = fmaf(v[t * n + i], hdr[(temporal ? 8 : 0) + h], hdr[(temporal ? 8 : 0) + 4 + h]);
-        const float *x = temporal ? v + i : v + t * n;
-        const int len = temporal ? T : n, stride = temporal ? n : 1;
-        float m = -INFINITY;
-        for (int j = 0; j < len; ++j) m = fmaxf(m, ti * x[j * stride]);
-        float sum = 0.f;
-        for (int j = 0; j < len; ++j) sum += expf(ti * x[j * stride] - m);
-        float *dst = temporal ? rs_t + 2 * (r - rows) : rs_s + 2 * r;
-        dst[0] = m;
-        dst[1] = sum;
-    }
-}
-
-// ---- fuse: spa_fusion (1x1 convolution over T, PReLU, + x) -> spatial stack; temporal stack = the attention
-__global__ __launch_bounds__(kSnThreads) void sgcn_fuse(Ctx c, et_sgcn_params p) {
-    int64_t b, sq;
-    int n;
-    if (!scene_at(c, blockIdx.x, b, n, sq)) return;
-    const int T = c.T;
-    const float *hdr = c.ws + c.L.hdr;
-    const float *v = c.ws + c.L.v + T * b;
-    const float *rs_s = c.ws + c.L.rs_s + 2 * (int64_t)T * kH * b;
-    const float *rs_t = c.ws + c.L.rs_t + 2 * (int64_t)T * kH * b;
-    float *xa = c.ws + c.L.xa + (int64_t)T * kH * sq;
-    float *ta = c.ws + c.L.ta + b * kH * T * T;
-    const int64_t ns = (int64_t)kH * n * n, nt = (int64_t)n * kH * T * T;
-    const float fa = p.fus_a[0];
-    for (int64_t it = (int64_t)blockIdx.y * kSnThreads + threadIdx.x; it < ns + nt; it += (int64_t)gridDim.y * kSnThreads) {
-        if (it < ns) {
-            const int j = (int)(it % n), i = (int)((it / n) % n), h = (int)(it / ((int64_t)n * n));
-            const float al = hdr[h], be = hdr[4 + h];
-            float d[kSnMaxT];
-#pragma unroll
-            for (int t = 0; t < kSnMaxT; ++t) {
-                d[t] = 0.f;
-                if (t < T) {
-                    const int r = (t * kH + h) * n + i;
-                    d[t] = dense(fmaf(v[t * n + i], al, be), v[t * n + j], rs_s[2 * r], rs_s[2 * r + 1]);
-                }
-            }
-            for (int u = 0; u < T; ++u) {
-                float acc = p.fus_b[u], du = 0.f;
-#pragma unroll
-                for (int t = 0; t < kSnMaxT; ++t) {
-                    if (t < T) {
-                        acc = fmaf(p.fus_w[u * T + t], d[t], acc);
-                        if (t == u) du = d[t];
-                    }
-                }
-                xa[(((int64_t)u * kH + h) * n + i) * n + j] = prelu(acc, fa) + du;
-            }
-        } else {
-            const int64_t q = it - ns;
-            const int u = (int)(q % T), t = (int)((q / T) % T), h = (int)((q / (T * T)) % kH), i = (int)(q / (T * T * kH));
-            const int r = (i * kH + h) * T + t;
-            ta[q] = dense(fmaf(v[t * n + i], hdr[8 + h], hdr[12 + h]), v[u * n + i], rs_t[2 * r], rs_t[2 * r + 1]);
-        }
-    }
-}
-
-// ---- asym: AsymmetricConvolution on (B,4,P,Q), entry `it` = (b,p,q): all four output channels
-__device__ __forceinline__ void asym_entry(const float *__restrict__ in, float *__restrict__ out, int P, int Q, int64_t it,
-                                           const et_sgcn_asym &A) {
-    const int q = (int)(it % Q), pp = (int)((it / Q) % P);
-    const int64_t bb = it / ((int64_t)P * Q);
-    const float *x = in + bb * 4 * P * Q;
-    float *y = out + bb * 4 * P * Q;
-    float xc[4], xl[4], xr[4], xu[4], xd[4];
-#pragma unroll
-    for (int ch = 0; ch < 4; ++ch) {
-        const int64_t at = ((int64_t)ch * P + pp) * Q + q;
-        xc[ch] = x[at];
-        xl[ch] = q > 0 ? x[at - 1] : 0.f;
-        xr[ch] = q + 1 < Q ? x[at + 1] : 0.f;
-        xu[ch] = pp > 0 ? x[at - Q] : 0.f;
-        xd[ch] = pp + 1 < P ? x[at + Q] : 0.f;
-    }
-    const float a = A.act[0];
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-        float acc2 = A.conv2_b[o], acc1 = 0.f;
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch) {
-            const float *w2 = A.conv2_w + (o * 4 + ch) * 3;  // (1,3): along q, with bias
-            acc2 = fmaf(w2[0], xl[ch], acc2);
-            acc2 = fmaf(w2[1], xc[ch], acc2);
-            acc2 = fmaf(w2[2], xr[ch], acc2);
-            const float *w1 = A.conv1_w + (o * 4 + ch) * 3;  // (3,1): along p, no bias
-            acc1 = fmaf(w1[0], xu[ch], acc1);
-            acc1 = fmaf(w1[1], xc[ch], acc1);
-            acc1 = fmaf(w1[2], xd[ch], acc1);
-        }
-        y[((int64_t)o * P + pp) * Q + q] = prelu(acc2 + acc1, a) + xc[o];
-    }
-}
-
-__global__ __launch_bounds__(kSnThreads) void sgcn_asym(Ctx c, et_sgcn_asym As, et_sgcn_asym At, const float *in_s,
-                                                        float *out_s, const float *in_t, float *out_t) {
-    int64_t b, sq;
-    int n;
-    if (!scene_at(c, blockIdx.x, b, n, sq)) return;
-    const int T = c.T;
-    const int64_t os = (int64_t)T * kH * sq, ot = b * kH * T * T;
-    const int64_t ns = (int64_t)T * n * n, nt = (int64_t)n * T * T;
-    for (int64_t it = (int64_t)blockIdx.y * kSnThreads + threadIdx.x; it < ns + nt; it += (int64_t)gridDim.y * kSnThreads) {
-        if (it < ns)
-            asym_entry(in_s + os, out_s + os, n, n, it, As);
-        else
-            asym_entry(in_t + ot, out_t + ot, T, T, it - ns, At);
-    }
-}
-
-// ---- tadj: temporal rows (i,h,t): mask, ZeroSoftmax -> A_t; temporal_spatial gcn 0 -> f2 (n,4,T,16)
-__global__ __launch_bounds__(kSnThreads) void sgcn_tadj(Ctx c, et_sgcn_params p, Ident I, const float *__restrict__ lt) {
-    int64_t b, sq;
-    int n;
-    if (!scene_at(c, blockIdx.x, b, n, sq)) return;
-    const int T = c.T;
-    const float *hdr = c.ws + c.L.hdr;
-    const float *v = c.ws + c.L.v + T * b;
-    const float *rs_t = c.ws + c.L.rs_t + 2 * (int64_t)T * kH * b;
-    float *at = c.ws + c.L.at + b * kH * T * T;
-    float *f2 = c.ws + c.L.f2 + b * kH * T * kD;
-    const float *lg = lt + b * kH * T * T;
-    const float a = p.gcn[2].act[0];
-    const int rows = n * kH * T;
-    for (int r = blockIdx.y * kSnThreads + threadIdx.x; r < rows; r += gridDim.y * kSnThreads) {
-        const int t = r % T, h = (r / T) % kH, i = r / (T * kH);
-        const float ti = fmaf(v[t * n + i], hdr[8 + h], hdr[12 + h]);
-        const float m = rs_t[2 * r], sum = rs_t[2 * r + 1];
-        float ssum = 0.f;
-        for (int u = 0; u < T; ++u)
-            ssum += zsm_num(dense(ti, v[u * n + i], m, sum) * mask_of(lg[(int64_t)r * T + u], ident_t(I, i, t, u, T)));
-        const float den = ssum + 1e-5f;
-        float acc = 0.f;
-        for (int u = 0; u < T; ++u) {
-            const float xu = v[u * n + i];
-            const float e = zsm_num(dense(ti, xu, m, sum) * mask_of(lg[(int64_t)r * T + u], ident_t(I, i, t, u, T)));
-            const float w = e / den;
-            at[(int64_t)r * T + u] = w;
-            acc = fmaf(w, xu, acc);
-        }
-        for (int d = 0; d < kD; ++d) f2[(int64_t)r * kD + d] = prelu(p.gcn[2].w[d] * acc, a);
-    }
-}
-
-// ---- sadj: spatial rows (t,h,i): mask, ZeroSoftmax; spatial_temporal gcn 0 -> f1 (T,4,n,16); temporal_spatial gcn 1 ->
-// ts (n,4,T,16)
-__global__ __launch_bounds__(kSnThreads) void sgcn_sadj(Ctx c, et_sgcn_params p, Ident I, const float *__restrict__ ls) {
-    int64_t b, sq;
-    int n;
-    if (!scene_at(c, blockIdx.x, b, n, sq)) return;
-    const int T = c.T;
-    const float *hdr = c.ws + c.L.hdr;
-    const float *v = c.ws + c.L.v + T * b;
-    const float *rs_s = c.ws + c.L.rs_s + 2 * (int64_t)T * kH * b;
-    const float *f2 = c.ws + c.L.f2 + b * kH * T * kD;
-    float *f1 = c.ws + c.L.f1 + b * kH * T * kD;
-    float *ts = c.ws + c.L.ts + b * kH * T * kD;
-    const float *lg = ls + (int64_t)T * kH * sq;
-    const float a0 = p.gcn[0].act[0], a3 = p.gcn[3].act[0];
-    const int rows = T * kH * n;
-    for (int r = blockIdx.y * kSnThreads + threadIdx.x; r < rows; r += gridDim.y * kSnThreads) {
-        const int i = r % n, h = (r / n) % kH, t = r / (n * kH);
-        const float ti = fmaf(v[t * n + i], hdr[h], hdr[4 + h]);
-        const float m = rs_s[2 * r], sum = rs_s[2 * r + 1];
-        const float *lrow = lg + (int64_t)r * n;
-        float acc[kD];
-#pragma unroll
-        for (int d = 0; d < kD; ++d) acc[d] = 0.f;
-        float ssum = 0.f, sx = 0.f;
-        for (int j = 0; j < n; ++j) {
-            const float xj = v[t * n + j];
-            const float e = zsm_num(dense(ti, xj, m, sum) * mask_of(lrow[j], ident_s(I, t, i, j, n)));
-            ssum += e;
-            sx = fmaf(e, xj, sx);
-            const float *fr = f2 + (((int64_t)j * kH + h) * T + t) * kD;
-#pragma unroll
-            for (int d = 0; d < kD; ++d) acc[d] = fmaf(e, fr[d], acc[d]);
-        }
-        const float den = ssum + 1e-5f;
-        const float ax = sx / den;
-#pragma unroll
-        for (int d = 0; d < kD; ++d) {
-            f1[(int64_t)r * kD + d] = prelu(p.gcn[0].w[d] * ax, a0);
-            acc[d] = acc[d] / den;
-        }
-        float *dst = ts + (((int64_t)i * kH + h) * T + t) * kD;
-        for (int d = 0; d < kD; ++d) {
-            float o = 0.f;
-#pragma unroll
-            for (int q = 0; q < kD; ++q) o = fmaf(p.gcn[3].w[d * kD + q], acc[q], o);
-            dst[d] = prelu(o, a3);
-        }
-    }
-}
-
-// ---- tail: one wavefront per pedestrian; lane = (h, d) of the (4,16) plane
-__global__ __launch_bounds__(kWave) void sgcn_tail(Ctx c, et_sgcn_params p, float *__restrict__ out) {
-    extern __shared__ float tail_lds[];  // two (T, 64) buffers
-    float *bufA = tail_lds, *bufB = tail_lds + c.T * kWave;
-    const int64_t r = blockIdx.x;
-    const int l = threadIdx.x, h = l >> 4, d = l & 15;
-    const int T = c.T, k = p.pred_len, S = p.out_dims;
-    int s = 0;
-    if (c.off) {  // the scene of row r: the first s with off[s + 1] > r
-        int lo = 0, hi = c.S - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (c.off[mid + 1] > r) hi = mid; else lo = mid + 1;
-        }
-        s = lo;
-    }
-    int64_t b, sq;
-    int n;
-    if (!scene_at(c, s, b, n, sq) || r < b || r >= b + n) {  // not computed: NaN, never an access outside the buffers
-        if (l < S)
-            for (int t = 0; t < k; ++t) out[((int64_t)t * c.N + r) * S + l] = __builtin_nanf("");
-        return;
-    }
-    const int i = (int)(r - b);
-    const float *at = c.ws + c.L.at + ((b + i) * kH + h) * T * T;
-    const float *f1 = c.ws + c.L.f1 + b * kH * T * kD;
-    const float *ts = c.ws + c.L.ts + ((b + i) * kH + h) * T * kD;
-    // spatial_temporal gcn 1: A_t (T,T) of (i,h) times f1[:,h,i,:]
-    for (int t = 0; t < T; ++t) {
-        float g = 0.f;
-        for (int u = 0; u < T; ++u) g = fmaf(at[t * T + u], f1[(((int64_t)u * kH + h) * n + i) * kD + d], g);
-        bufA[t * kWave + l] = g;
-    }
-    __syncthreads();
-    const float a1 = p.gcn[1].act[0];
-    for (int t = 0; t < T; ++t) {
-        float o = 0.f;
-#pragma unroll
-        for (int q = 0; q < kD; ++q) o = fmaf(p.gcn[1].w[d * kD + q], bufA[t * kWave + h * kD + q], o);
-        bufB[t * kWave + l] = prelu(o, a1);
-    }
-    __syncthreads();
-    // fusion_ (1x1 over heads) of the spatial-temporal features + the temporal-spatial ones -> channels t, plane (h,d)
-    for (int t = 0; t < T; ++t) {
-        float o = 0.f;
-#pragma unroll
-        for (int g = 0; g < kH; ++g) o = fmaf(p.fusion_w[h * kH + g], bufB[t * kWave + g * kD + d], o);
-        bufA[t * kWave + l] = o + ts[t * kD + d];
-    }
-    __syncthreads();
-    float *cur = bufA, *nxt = bufB;
-    for (int j = 0; j < p.n_tcn; ++j) {  // tcns[0] without, tcns[j >= 1] with the residual
-        const int Cin = j ? k : T;
-        const float aj = p.tcn_a[j][0];
-        // every output channel of this lane's position at once: k independent chains, the 9 taps read once per input
-        // channel (each chain still runs input channel by input channel, tap by tap)
-        float acc[ET_MAX_K];
-#pragma unroll
-        for (int o = 0; o < ET_MAX_K; ++o) acc[o] = o < k ? p.tcn_b[j][o] : 0.f;
-        for (int ci = 0; ci < Cin; ++ci) {
-            const float *pl = cur + ci * kWave;
-            float x[9];
-#pragma unroll
-            for (int dh = 0; dh < 3; ++dh) {
-#pragma unroll
-                for (int dd = 0; dd < 3; ++dd) {
-                    const int hh = h + dh - 1, d2 = d + dd - 1;
-                    const bool in = hh >= 0 && hh < kH && d2 >= 0 && d2 < kD;
-                    const float val = pl[in ? hh * kD + d2 : l];
-                    x[dh * 3 + dd] = in ? val : 0.f;  // zero padding
-                }
-            }
-#pragma unroll
-            for (int o = 0; o < ET_MAX_K; ++o) {
-                if (o < k) {
-                    const float *w = p.tcn_w[j] + ((int64_t)o * Cin + ci) * 9;
-#pragma unroll
-                    for (int q = 0; q < 9; ++q) acc[o] = fmaf(w[q], x[q], acc[o]);
-                }
-            }
-        }
-#pragma unroll
-        for (int o = 0; o < ET_MAX_K; ++o) {
-            if (o < k) {
-                float val = prelu(acc[o], aj);
-                if (j) val += cur[o * kWave + l];
-                nxt[o * kWave + l] = val;
-            }
-        }
-        __syncthreads();
-        float *tmp = cur;
-        cur = nxt;
-        nxt = tmp;
-    }
-    if (l < S) {  // output layer, mean over heads -> (k, N, S)
-        float w[kD];
-#pragma unroll
-        for (int q = 0; q < kD; ++q) w[q] = p.out_w[l * kD + q];
-        const float bias = p.out_b[l];
-        for (int t = 0; t < k; ++t) {
-            float tot = 0.f;
-            for (int g = 0; g < kH; ++g) {
-                float lin = bias;
-#pragma unroll
-                for (int q = 0; q < kD; ++q) lin = fmaf(w[q], cur[t * kWave + g * kD + q], lin);
-                tot += lin;
-            }
-            out[((int64_t)t * c.N + r) * S + l] = tot * 0.25f;
-        }
-    }
-}
-
-static int check_params(const et_sgcn_params *p) {
-    if (!p) return ET_ERR_INVALID_ARG;
-    if (p->in_dims != 1 || p->num_heads != kH || p->embedding_dims != kE || p->dropout != 0.f || p->n_asym < 1 ||
-        p->n_asym > ET_SGCN_MAX_LAYERS || p->n_tcn < 1 || p->n_tcn > ET_SGCN_MAX_LAYERS || p->pred_len < 1 ||
-        p->pred_len > ET_MAX_K || p->obs_len != p->pred_len + 2 || p->out_dims < 1 || p->out_dims > kSnMaxS)
-        return ET_ERR_UNSUPPORTED;
-    for (int a = 0; a < 2; ++a) {
-        const et_sgcn_attention &A = p->att[a];
-        if (!A.emb_w || !A.emb_b || !A.q_w || !A.q_b || !A.k_w || !A.k_b) return ET_ERR_INVALID_ARG;
-    }
-    if (!p->fus_w || !p->fus_b || !p->fus_a || !p->fusion_w || !p->out_w || !p->out_b) return ET_ERR_INVALID_ARG;
-    for (int j = 0; j < p->n_asym; ++j)
-        for (const et_sgcn_asym *A : {&p->asym_s[j], &p->asym_t[j]})
-            if (!A->conv1_w || !A->conv2_w || !A->conv2_b || !A->act) return ET_ERR_INVALID_ARG;
-    for (int g = 0; g < 4; ++g)
-        if (!p->gcn[g].w || !p->gcn[g].act) return ET_ERR_INVALID_ARG;
-    for (int j = 0; j < p->n_tcn; ++j)
-        if (!p->tcn_w[j] || !p->tcn_b[j] || !p->tcn_a[j]) return ET_ERR_INVALID_ARG;
-    return ET_OK;
-}
-
-// chunks per scene of the entry / row kernels: enough lanes for the largest scene, bounded over all scenes
-static unsigned chunks(int64_t work_max, int n_scenes) {
-    int64_t by = ceil_div(work_max, 4 * kSnThreads);
-    const int64_t cap = 65536 / n_scenes > 8 ? 65536 / n_scenes : 8;
-    if (by > cap) by = cap;
-    if (by > 1024) by = 1024;
-    return (unsigned)(by < 1 ? 1 : by);
-}
+#include "et_sgcn_core.inl"
 
 static int run(const et_sgcn_params &p, const float *gv, const Ident &I, const float *C_obs, const float *nrm, int64_t N,
                const int32_t *off, int n_scenes, int64_t sum_n2, int64_t max_n, float *out, float *logit_s,
@@ -558,27 +38,11 @@ static int run(const et_sgcn_params &p, const float *gv, const Ident &I, const f
     c.T = T;
     c.ws = (float *)workspace;
     c.L = lay_of(T, N, sum_n2, n_scenes);
+    c.Nr = N;
+    c.Sr = n_scenes;
     if (!workspace || workspace_bytes < (size_t)c.L.total * 4) return ET_ERR_WORKSPACE;
-    const dim3 blk(kSnThreads);
-    const unsigned S = (unsigned)n_scenes;
-    hipLaunchKernelGGL(sgcn_prep, dim3(1), blk, 0, st, p, c.ws);
-    hipLaunchKernelGGL(sgcn_input, dim3(S), blk, 0, st, c, gv, C_obs, nrm);
-    const unsigned by_e = chunks((int64_t)T * kH * max_n * max_n + max_n * kH * T * T, n_scenes);
-    const unsigned by_r = chunks((int64_t)T * kH * max_n * 4, n_scenes);
-    hipLaunchKernelGGL(sgcn_fuse, dim3(S, by_e), blk, 0, st, c, p);
-    float *xs[2] = {c.ws + c.L.xa, c.ws + c.L.xb}, *xt[2] = {c.ws + c.L.ta, c.ws + c.L.tb};
-    const float *ls = xs[0], *lt = xt[0];
-    for (int j = 0; j < p.n_asym; ++j) {
-        const bool last = j + 1 == p.n_asym;
-        float *os = last && logit_s ? logit_s : xs[(j + 1) & 1];
-        float *ot = last && logit_t ? logit_t : xt[(j + 1) & 1];
-        hipLaunchKernelGGL(sgcn_asym, dim3(S, by_e), blk, 0, st, c, p.asym_s[j], p.asym_t[j], ls, os, lt, ot);
-        ls = os;
-        lt = ot;
-    }
-    hipLaunchKernelGGL(sgcn_tadj, dim3(S, by_r), blk, 0, st, c, p, I, lt);
-    hipLaunchKernelGGL(sgcn_sadj, dim3(S, by_r), blk, 0, st, c, p, I, ls);
-    hipLaunchKernelGGL(sgcn_tail, dim3((unsigned)N), dim3(kWave), 2 * T * kWave * sizeof(float), st, c, p, out);
+    hipLaunchKernelGGL(sgcn_prep<false>, dim3(1), dim3(kSnThreads), 0, st, p, c.ws);
+    run_layers<false>(p, c, gv, I, C_obs, nrm, max_n, out, logit_s, logit_t, st);
     ET_LAUNCH_CHECK();
     return ET_OK;
 }

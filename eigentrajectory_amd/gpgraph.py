@@ -1,0 +1,135 @@
+"""GP-Graph-SGCN, the predictor of ET-GPGraph-SGCN (baseline/gpgraphsgcn/model.py: get_GPGraph_SGCN_model, the reference's
+default configuration), inference on HIP kernels.
+
+Same sub-module / parameter names as the reference's ``GPGraph`` -- ``baseline_model.*`` (the two-channel SGCN,
+:class:`eigentrajectory_amd.sgcn.SGCN` with ``position_channel=True``), ``group_gen.group_cnn.0``, ``group_gen.th``,
+``group_mix.st_gcns_mix.{0,1}`` -- so a reference ET-GPGraph-SGCN checkpoint's ``baseline_model.baseline_model.*``,
+``baseline_model.group_gen.*`` and ``baseline_model.group_mix.*`` keys load unchanged, and the module plugs into
+:class:`eigentrajectory_amd.EigenTrajectory` through the existing ``gpgraphsgcn`` bridge::
+
+    model = EigenTrajectory(get_GPGraph_SGCN_model(obs_len=hp.k + 2, pred_len=hp.k, in_dims=1, out_dims=hp.num_samples),
+                            get_hook_func("gpgraphsgcn"), hp).eval()
+
+``forward(v_abs, v_rel)`` in eval mode is ``et_gpgraph_sgcn_forward_graph`` (csrc/et_gpgraph.hip): v_abs (1, 1, T, N) and
+v_rel (1, 2, T, N) as the bridge builds them -> ``(v, indices)`` with v (1, out_dims, pred_len, N) and indices int64 (N,),
+the group of every pedestrian, as the reference returns them.  The weights, ``group_gen.th`` included, are read in place on
+the device at every call (an in-place edit is seen by the next call and by a captured graph's next replay).  A whole split
+runs in a fixed number of launches through :meth:`EigenTrajectory.evaluate_split` /
+:func:`eigentrajectory_amd.ops.gpgraph_sgcn_forward_scenes`.
+
+Native: the ET configuration -- ``d_type='learned_l2norm'``, ``d_th='learned'``, ``mix_type='mlp'``, ``group_type=(True,
+True, True)``, ``weight_share=True`` -- in eval mode with ``dropout = 0``.  Training, GP-Graph-STGCNN and the other
+``d_type`` / ``d_th`` / ``mix_type`` / ``group_type`` / ``weight_share=False`` variants are not: they construct (with the
+reference's parameters), and their forward raises.
+"""
+from __future__ import annotations
+
+import copy
+
+import torch
+import torch.nn as nn
+
+from . import _lib as L
+from .sgcn import SGCN, _p
+
+
+class _GroupGenerator(nn.Module):
+    def __init__(self, d_type="learned_l2norm", th=1.0, in_channels=16, hid_channels=32, n_head=1, dropout=0):
+        super().__init__()
+        self.d_type = d_type
+        if d_type == "learned":
+            self.group_cnn = nn.Sequential(nn.Conv2d(in_channels, hid_channels, 1), nn.ReLU(), nn.BatchNorm2d(hid_channels),
+                                           nn.Dropout(dropout, inplace=True), nn.Conv2d(hid_channels, n_head, 1))
+        elif d_type == "estimate_th":
+            self.group_cnn = nn.Sequential(nn.Conv2d(in_channels, n_head, 1))
+        elif d_type == "learned_l2norm":
+            self.group_cnn = nn.Sequential(nn.Conv2d(in_channels, hid_channels, kernel_size=(3, 1), padding=(1, 0)))
+        # (as in the reference: a float is a fixed threshold, anything else -- 'learned' -- a parameter that starts at 1)
+        self.th = th if type(th) == float else nn.Parameter(torch.Tensor([1]))
+
+
+class _GroupIntegrator(nn.Module):
+    def __init__(self, mix_type="mean", n_mix=3, out_channels=5, pred_seq_len=12):
+        super().__init__()
+        self.mix_type, self.pred_seq_len = mix_type, pred_seq_len
+        if mix_type == "mlp":
+            self.st_gcns_mix = nn.Sequential(nn.PReLU(), nn.Conv2d(out_channels * pred_seq_len * n_mix,
+                                                                    out_channels * pred_seq_len, kernel_size=1))
+        elif mix_type == "cnn":
+            self.st_gcns_mix = nn.Sequential(nn.PReLU(), nn.Conv2d(out_channels * n_mix, out_channels, kernel_size=(3, 1),
+                                                                    padding=(1, 0)))
+
+
+class GPGraph(nn.Module):
+    r"""baseline/gpgraphsgcn/model_groupwrapper.py's ``GPGraph`` around an :class:`SGCN` base (eval-mode inference on the
+    GPU).  ``forward(v_abs, v_rel)`` -> ``(v (1, S, k, N), indices (N,) int64)``."""
+
+    TAU = 0.1  # GroupGenerator.forward's default temperature; GPGraph.forward does not pass another
+
+    def __init__(self, baseline_model, in_channels=2, out_channels=5, obs_seq_len=8, pred_seq_len=12,
+                 d_type="learned_l2norm", d_th="learned", mix_type="mlp", group_type=None, weight_share=True):
+        super().__init__()
+        group_type = (True,) * 3 if group_type is None else tuple(bool(g) for g in group_type)
+        self.obs_seq_len, self.pred_seq_len, self.in_channels, self.out_channels = obs_seq_len, pred_seq_len, in_channels, out_channels
+        self.d_type, self.d_th, self.mix_type, self.weight_share = d_type, d_th, mix_type, weight_share
+        self.include_original, self.include_inter_group, self.include_intra_group = group_type
+        # (weight_share=False: one copy of the base per graph, as the callers of the reference build it)
+        self.baseline_model = baseline_model if weight_share else nn.ModuleList(
+            [baseline_model] + [copy.deepcopy(baseline_model) for _ in range(2)])
+        self.group_gen = _GroupGenerator(d_type=d_type, th=d_th, in_channels=in_channels, hid_channels=8)
+        self.group_mix = _GroupIntegrator(mix_type=mix_type, n_mix=sum(group_type), out_channels=out_channels,
+                                          pred_seq_len=pred_seq_len)
+
+    def _check_mode(self):
+        if (self.d_type != "learned_l2norm" or not isinstance(self.group_gen.th, nn.Parameter) or self.mix_type != "mlp"
+                or not (self.include_original and self.include_inter_group and self.include_intra_group)
+                or not self.weight_share or not isinstance(self.baseline_model, SGCN)
+                or not self.baseline_model.position_channel):
+            raise NotImplementedError("GPGraph: only the ET configuration is native -- d_type='learned_l2norm', d_th='learned', "
+                                      "mix_type='mlp', group_type=(True, True, True), weight_share=True around "
+                                      "SGCN(position_channel=True); the other variants are not implemented")
+        if self.training:
+            raise RuntimeError("GPGraph: only inference is native (no backward, no straight-through gradient); "
+                               "training-mode forward is not implemented -- call .eval() first")
+        self.baseline_model._check_mode()
+
+    def et_params(self):
+        """-> (et_gpgraph_sgcn_params, device): this module's tensors as the kernels read them (include/eigentraj.h)."""
+        base, dev = self.baseline_model.et_params()
+        p = L.GPGraphSGCNParams()
+        p.base = base
+        own = [t for m in (self.group_gen, self.group_mix) for t in m.parameters()]
+        if any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in own):
+            raise L.ETLibraryError("GPGraph: every parameter must be a contiguous float32 tensor on ONE HIP device "
+                                   "(model.cuda()); there is no CPU path")
+        if self.in_channels != 1 or self.out_channels != self.baseline_model.out_dims \
+                or self.pred_seq_len != self.baseline_model.pred_len or self.obs_seq_len != self.baseline_model.obs_len:
+            p.base.in_dims = -1  # the kernels answer ET_ERR_UNSUPPORTED
+            return p, dev
+        conv = self.group_gen.group_cnn[0]
+        p.group_w, p.group_b, p.th, p.tau = _p(conv.weight), _p(conv.bias), _p(self.group_gen.th), self.TAU
+        act, mix = self.group_mix.st_gcns_mix[0], self.group_mix.st_gcns_mix[1]
+        p.mix_a, p.mix_w, p.mix_b = _p(act.weight), _p(mix.weight), _p(mix.bias)
+        return p, dev
+
+    def forward(self, v_abs, v_rel):
+        self._check_mode()
+        from . import ops
+        return ops.gpgraph_sgcn_forward_graph(self, v_abs, v_rel)
+
+
+class GPGraphSGCN(GPGraph):
+    r"""``get_GPGraph_SGCN_model``'s network as a class: the ET base (7 asymmetric layers, 5 tcns, dropout 0) inside
+    :class:`GPGraph` with the reference's fixed arguments."""
+
+    def __init__(self, obs_len=8, pred_len=12, in_dims=2, out_dims=5):
+        base = SGCN(number_asymmetric_conv_layer=7, embedding_dims=64, number_gcn_layers=1, dropout=0, obs_len=obs_len,
+                    pred_len=pred_len, n_tcn=5, in_dims=in_dims, out_dims=out_dims, position_channel=True)
+        super().__init__(baseline_model=base, in_channels=in_dims, out_channels=out_dims, obs_seq_len=obs_len,
+                         pred_seq_len=pred_len, d_type="learned_l2norm", d_th="learned", mix_type="mlp",
+                         group_type=(True, True, True), weight_share=True)
+
+
+def get_GPGraph_SGCN_model(obs_len=8, pred_len=12, in_dims=2, out_dims=5):
+    """The reference's factory (baseline/gpgraphsgcn/model.py), without its ``.cuda()``: move the result yourself."""
+    return GPGraphSGCN(obs_len=obs_len, pred_len=pred_len, in_dims=in_dims, out_dims=out_dims)

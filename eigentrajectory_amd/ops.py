@@ -340,6 +340,8 @@ def sgcn_forward_graph(model, v, identity, want_logits=False):
     ``want_logits`` also the values that enter the interaction mask's sigmoids, logit_s (T, 4, N, N) and logit_t
     (N, 4, T, T).  The inputs must be contiguous float32 tensors on the model's device (they are read in place)."""
     model._check_mode()
+    if getattr(model, "position_channel", False):
+        raise NotImplementedError("sgcn_forward_graph: a two-channel SGCN (position_channel=True) runs only inside GPGraphSGCN")
     params, dev = model.et_params()
     T, k, S = params.obs_len, params.pred_len, params.out_dims
     id_s, id_t = identity
@@ -371,6 +373,8 @@ def sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_logits=False):
     (k, N, S).  With ``want_logits`` also the packed logits: scene s's (T, 4, n, n) block at 4 T (n_0^2 + ... + n_{s-1}^2)
     of the first and its (n, 4, T, T) block at 4 T T (n_0 + ... + n_{s-1}) of the second."""
     model._check_mode()
+    if getattr(model, "position_channel", False):
+        raise NotImplementedError("sgcn_forward_scenes: a two-channel SGCN (position_channel=True) runs only inside GPGraphSGCN")
     params, dev = model.et_params()
     C_obs, nrm = _dev_args(dev, C_obs, nrm)
     k, n = C_obs.shape
@@ -395,6 +399,100 @@ def sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_logits=False):
            0 if off is None else len(sizes), sum_n2, max_n, L.ptr(out), L.ptr(ls), L.ptr(lt), L.ptr(ws), nbytes,
            L.stream(dev))
     return (out, ls, lt) if want_logits else out
+
+
+# ------------------------------------------------------------------------ GP-Graph-SGCN predictor (inference)
+def _gpgraph_buffers(params, want, T, n, sum_n2, n_scenes, dev):
+    nbytes = L.lib().et_gpgraph_sgcn_workspace_bytes(C.byref(params), n, sum_n2, int(n_scenes))
+    if not nbytes:
+        L.check(3, "et_gpgraph_sgcn_workspace_bytes")  # outside the native family
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    gi = torch.empty((n,), device=dev, dtype=torch.int32)
+    if not want:
+        return ws, nbytes, gi, None, None, None
+    return (ws, nbytes, gi, torch.empty((sum_n2,), device=dev), torch.empty((3 * 4 * T * sum_n2,), device=dev),
+            torch.empty((3 * n * 4 * T * T,), device=dev))
+
+
+def gpgraph_sgcn_forward_graph(model, v_abs, v_rel, want_details=False):
+    """``model`` (:class:`eigentrajectory_amd.gpgraph.GPGraph`, eval mode) on one scene as the gpgraphsgcn bridge hands it
+    over: v_abs (1, 1, T, N), v_rel (1, 2, T, N) (channel 0 the position) -> ``(v (1, S, k, N), indices (N,) int64)``; with
+    ``want_details`` a dict is returned as third item: ``dist`` (N, N), ``n_groups``, and per pass m (0 pedestrian graph, 1
+    group means, 2 intra-group) ``logit_s[m]`` (T, 4, n_m, n_m) and ``logit_t[m]`` (n_m, 4, T, T), n_1 = the number of
+    groups.  The inputs must be contiguous float32 tensors on the model's device (they are read in place)."""
+    model._check_mode()
+    params, dev = model.et_params()
+    T, k, S = params.base.obs_len, params.base.pred_len, params.base.out_dims
+    n = v_abs.shape[3] if v_abs.dim() == 4 else -1
+    if tuple(v_abs.shape) != (1, 1, T, n) or tuple(v_rel.shape) != (1, 2, T, n):
+        raise ValueError(f"gpgraph_sgcn_forward_graph: v_abs {tuple(v_abs.shape)} / v_rel {tuple(v_rel.shape)} are not "
+                         f"(1,1,{T},N) / (1,2,{T},N)")
+    for name, t in (("v_abs", v_abs), ("v_rel", v_rel)):
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"gpgraph_sgcn_forward_graph: {name} must be a contiguous float32 tensor on {dev} (got "
+                             f"{t.dtype}, {t.device}, contiguous={t.is_contiguous()})")
+    if n > L.SGCN_MAX_N:
+        raise ValueError(f"gpgraph_sgcn_forward_graph: N = {n} exceeds the {L.SGCN_MAX_N} pedestrians a scene may have")
+    out = torch.empty((1, S, k, n), device=dev)
+    if n == 0:
+        L.call("et_gpgraph_sgcn_forward_graph", C.byref(params), None, None, 0, None, None, None, None, None, None, 0,
+               L.stream(dev))
+        res = (out, torch.empty((0,), device=dev, dtype=torch.int64))
+        return res + ({"dist": torch.empty((0, 0), device=dev), "n_groups": 0, "logit_s": [], "logit_t": []},) \
+            if want_details else res
+    ws, nbytes, gi, dist, ls, lt = _gpgraph_buffers(params, want_details, T, n, n * n, 1, dev)
+    L.call("et_gpgraph_sgcn_forward_graph", C.byref(params), L.ptr(v_abs.detach()), L.ptr(v_rel.detach()), n, L.ptr(out),
+           L.ptr(gi), L.ptr(dist), L.ptr(ls), L.ptr(lt), L.ptr(ws), nbytes, L.stream(dev))
+    idx = gi.long()
+    if not want_details:
+        return out, idx
+    g = int(idx.max()) + 1
+    sizes = (n, g, n)
+    det = {"dist": dist.view(n, n), "n_groups": g,
+           "logit_s": [ls[4 * T * m * n * n:4 * T * (m * n * n + sizes[m] ** 2)].view(T, 4, sizes[m], sizes[m]) for m in range(3)],
+           "logit_t": [lt[4 * T * T * m * n:4 * T * T * (m * n + sizes[m])].view(sizes[m], 4, T, T) for m in range(3)]}
+    return out, idx, det
+
+
+def gpgraph_sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
+    """The gpgraphsgcn bridge + ``model`` (eval mode) + the post-hook for every scene of a split in a fixed number of
+    launches (8 + the number of asymmetric convolution layers): C_obs (k, N) and nrm (4, N) of :func:`norm_project`,
+    ``scene_sizes`` as :func:`sgcn_forward_scenes` -> C_pred_refine (k, N, S).  With ``want_details`` also a dict:
+    ``group_index`` (N,) int32 scene-local, ``dist`` packed (scene s's (n, n) block at n_0^2 + ... + n_{s-1}^2), ``logit_s``
+    / ``logit_t`` packed as include/eigentraj.h describes (pass m of scene s at 4 T (m sum_n2 + sum_{s'<s} n_s'^2) and at
+    4 T T (m N + off[s]))."""
+    model._check_mode()
+    params, dev = model.et_params()
+    C_obs, nrm = _dev_args(dev, C_obs, nrm)
+    k, n = C_obs.shape
+    T = params.base.obs_len
+    if k != params.base.pred_len or nrm.dim() != 2 or nrm.shape[0] < 2 or nrm.shape[1] != n:
+        raise ValueError(f"gpgraph_sgcn_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
+                         f"k = {params.base.pred_len}")
+    if scene_sizes is not None:
+        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
+        if not sizes and n:
+            raise ValueError(f"gpgraph_sgcn_forward_scenes: no scenes for {n} rows")
+        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
+    else:
+        sizes, off = [n], None
+    if scene_sizes is None and n > L.SGCN_MAX_N:
+        raise ValueError(f"gpgraph_sgcn_forward_scenes: a scene of {n} pedestrians exceeds the {L.SGCN_MAX_N} a scene may have")
+    # (a listed scene above the limit is not refused: its rows come back NaN, the other scenes are computed)
+    sum_n2 = sum(s * s for s in sizes if s <= L.SGCN_MAX_N)
+    max_n = max(sizes, default=0)
+    out = torch.empty((k, n, params.base.out_dims), device=dev)
+    if n == 0:
+        L.call("et_gpgraph_sgcn_forward_scenes", C.byref(params), None, None, 0, L.ptr(off), 0 if off is None else len(sizes),
+               0, 0, None, None, None, None, None, None, 0, L.stream(dev))
+        return (out, {"group_index": torch.empty((0,), device=dev, dtype=torch.int32)}) if want_details else out
+    ws, nbytes, gi, dist, ls, lt = _gpgraph_buffers(params, want_details, T, n, sum_n2, len(sizes), dev)
+    L.call("et_gpgraph_sgcn_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
+           0 if off is None else len(sizes), sum_n2, max_n, L.ptr(out), L.ptr(gi), L.ptr(dist), L.ptr(ls), L.ptr(lt),
+           L.ptr(ws), nbytes, L.stream(dev))
+    if want_details:
+        return out, {"group_index": gi, "dist": dist, "logit_s": ls, "logit_t": lt}
+    return out
 
 
 # ----------------------------------------------------------------------- curve fitting

@@ -21,6 +21,12 @@ in training mode, or with ``dropout != 0``, raises.  A whole split runs in a fix
 Supported family: ``in_dims = 1``, ``num_heads = 4``, ``embedding_dims = 64``, ``1 <= number_asymmetric_conv_layer, n_tcn <=
 8``, ``pred_len <= 32``, ``obs_len = pred_len + 2``, ``1 <= out_dims <= 64``, ``N <= 512``; other shapes construct, but their
 forward raises.
+
+``SGCN(..., position_channel=True)`` is baseline/gpgraphsgcn/model_baseline.py's variant, the base of
+:class:`eigentrajectory_amd.gpgraph.GPGraphSGCN`: the graph carries a position channel in front of the coefficient channel,
+the temporal attention reads both (its embedding is ``Linear(in_dims + 1, 64)``), and ``forward(graph, identity, mask=None)``
+takes a (1, T, N, 2) graph.  Natively it runs only inside GP-Graph's call, where its three passes are the virtual scenes of
+one run of the kernels; called on its own its forward raises.
 """
 from __future__ import annotations
 
@@ -109,15 +115,16 @@ class SGCN(nn.Module):
     (1, T, N, 1) and the two identities as the sgcn bridge's pre-hook builds them -> (pred_len, N, out_dims)."""
 
     def __init__(self, number_asymmetric_conv_layer=7, embedding_dims=64, number_gcn_layers=1, dropout=0, obs_len=8,
-                 pred_len=12, n_tcn=5, in_dims=2, out_dims=5, num_heads=4):
+                 pred_len=12, n_tcn=5, in_dims=2, out_dims=5, num_heads=4, position_channel=False):
         super().__init__()
+        self.position_channel = bool(position_channel)
         self.number_asymmetric_conv_layer = number_asymmetric_conv_layer
         self.embedding_dims, self.number_gcn_layers, self.n_tcn, self.dropout = embedding_dims, number_gcn_layers, n_tcn, dropout
         self.obs_len, self.pred_len, self.in_dims, self.out_dims, self.num_heads = obs_len, pred_len, in_dims, out_dims, num_heads
         # (the reference leaves the adjacency's embedding_dims and the attention's num_heads at their defaults, 64 and 4)
         self.sparse_weighted_adjacency_matrices = _SparseWeightedAdjacency(
             number_asymmetric_conv_layer=number_asymmetric_conv_layer, obs_len=obs_len, spa_in_dims=in_dims,
-            tem_in_dims=in_dims)
+            tem_in_dims=in_dims + 1 if position_channel else in_dims)
         self.stsgcn = _SparseGraphConvolution(in_dims=in_dims, embedding_dims=embedding_dims // num_heads, dropout=dropout)
         self.fusion_ = nn.Conv2d(num_heads, num_heads, kernel_size=1, bias=False)
         self.tcns = nn.ModuleList()
@@ -169,7 +176,11 @@ class SGCN(nn.Module):
             raise RuntimeError(f"SGCN: dropout = {self.dropout} is not implemented natively (the reference's F.dropout is "
                                "active even in eval mode); construct with dropout=0")
 
-    def forward(self, graph, identity):
+    def forward(self, graph, identity, mask=None):
         self._check_mode()
+        if self.position_channel or mask is not None:
+            raise NotImplementedError("SGCN: the two-channel base (position_channel=True) and the mask argument run only as "
+                                      "the three passes of GPGraphSGCN's call (eigentrajectory_amd.gpgraph); there is no "
+                                      "stand-alone kernel entry for them")
         from . import ops
         return ops.sgcn_forward_graph(self, graph, identity)

@@ -438,6 +438,52 @@ int et_sgcn_forward_graph(const et_sgcn_params *params, const float *v, const fl
                           const float *identity_t, int id_t_t, int64_t N, float *out, float *logit_s, float *logit_t,
                           void *workspace, size_t workspace_bytes, et_stream_t stream);
 
+/* ---- GP-Graph-SGCN predictor, inference (baseline/gpgraphsgcn: bridge.py pre-hook + GPGraph.forward around the
+ * two-channel SGCN of model_baseline.py + post-hook) --------------------------------------------------------------------
+ * The ET configuration: d_type 'learned_l2norm', learned threshold, mix_type 'mlp', all three graphs, shared weights,
+ * eval mode, dropout = 0, fp32.  `base` is the SGCN table above with ONE difference: att[1].emb_w, the temporal
+ * attention's embedding.weight, is (64, 2) -- column 0 the position channel, column 1 the coefficient channel.
+ *   group_w / group_b   group_gen.group_cnn.0.weight (8, 1, 3, 1) / .bias (8)
+ *   th                  group_gen.th (1), read on the device at every call;  tau: the sigmoid's temperature (0.1)
+ *   mix_a               group_mix.st_gcns_mix.0.weight (1), the PReLU slope
+ *   mix_w / mix_b       group_mix.st_gcns_mix.1.weight (S k, 3 S k, 1, 1) / .bias (S k)
+ * Per scene: d[i][j] = mean over t of the L2 norm over the 8 channels of conv(v_abs)[:, t, i] - conv(v_abs)[:, t, j]; the
+ * pairs (r, c), c < r, d[r][c] <= th, in row-major order, each relabel every pedestrian that carries r's label with c (the
+ * reference's loop: the LAST close column of a row wins -- not connected components); labels made compact in the order of
+ * the surviving values.  v' = (v_rel - v_soft) + v_soft with v_soft = v_rel @ (sig / sig.sum(0)), sig = sigmoid(-(d - th) /
+ * tau).  The base runs on v_rel, on the group means of v' (G nodes, unpooled by gather) and on v' with the spatial mask
+ * times the same-group matrix, identities eye(n) and eye(T); out = mean of the three + mix(PReLU(cat of the three)).
+ *
+ *   et_gpgraph_sgcn_forward_graph   one scene as the bridge hands it over: v_abs (1,1,T,N), v_rel (1,2,T,N) (channel 0 the
+ *                                   position) -> out (1,S,k,N)
+ *   et_gpgraph_sgcn_forward_scenes  a whole split: C_obs (k,N), nrm (4,N), scene_offsets, sum_n2, max_scene_n as
+ *                                   et_sgcn_forward_scenes (v_abs = [C_obs; nrm[0:2] - their mean over the scene], position
+ *                                   t + 1) -> C_pred_refine (k,N,S).  A scene larger than ET_SGCN_MAX_N or one that does
+ *                                   not fit the stacks is not computed: its outputs are NaN (a scene larger than
+ *                                   ET_SGCN_MAX_N takes no room in the stacks: leave it out of sum_n2, and of the packed
+ *                                   dist / logit_s offsets).  n_scenes = 0 takes N = 0 only.
+ * Optional outputs (may be NULL): group_index int32 (N), the scene-local compact label; dist, n x n per scene, scene s at
+ * sum_{s'<s} n_s'^2; logit_s / logit_t of the three passes: pass m (0 pedestrian, 1 pooled, 2 intra-group) of scene s at
+ * 4 T (m sum_n2 + sum_{s'<s} n_s'^2) as (T,4,n_m,n_m) and at 4 T T (m N + off[s]) as (n_m,4,T,T), n_m = G for the pooled pass.
+ * The three passes of all scenes are 3 n_scenes virtual scenes of ONE run of the layered SGCN kernels (node counts from a
+ * device table): 8 + number_asymmetric_conv_layer launches for any number of scenes (prep, group, input, fuse, the
+ * asymmetric layers, tadj, sadj, tail, mix), no host synchronisation, no allocation (capturable in a graph); every sum has
+ * a fixed order: bit-identical from run to run, and a scene's result does not depend on the scenes around it. */
+typedef struct et_gpgraph_sgcn_params {
+    et_sgcn_params base;
+    const float *group_w, *group_b, *th;
+    float tau;
+    const float *mix_a, *mix_w, *mix_b;
+} et_gpgraph_sgcn_params;
+size_t et_gpgraph_sgcn_workspace_bytes(const et_gpgraph_sgcn_params *params, int64_t N, int64_t sum_n2, int n_scenes);
+int et_gpgraph_sgcn_forward_graph(const et_gpgraph_sgcn_params *params, const float *v_abs, const float *v_rel, int64_t N,
+                                  float *out, int32_t *group_index, float *dist, float *logit_s, float *logit_t,
+                                  void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_gpgraph_sgcn_forward_scenes(const et_gpgraph_sgcn_params *params, const float *C_obs, const float *nrm, int64_t N,
+                                   const int32_t *scene_offsets, int n_scenes, int64_t sum_n2, int64_t max_scene_n,
+                                   float *C_pred_refine, int32_t *group_index, float *dist, float *logit_s,
+                                   float *logit_t, void *workspace, size_t workspace_bytes, et_stream_t stream);
+
 /* ---- fit ----------------------------------------------------------------------------
  * Gram matrices of the normalised trajectories routed to descriptor `which`
  * (1 moving / 0 static) under `mode`:  G_obs (2T_obs,2T_obs), G_pred (2T_pred,2T_pred)
