@@ -90,6 +90,10 @@ SIGNATURES = {
     "et_gpgraph_sgcn_workspace_bytes": (_Z, [_P, _I64, _I64, _I]),
     "et_gpgraph_sgcn_forward_graph": (_I, [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "et_gpgraph_sgcn_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _I64, _I64, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    # ---- GP-Graph-STGCNN predictor, inference
+    "et_gpgraph_stgcnn_workspace_bytes": (_Z, [_P, _I64, _I64, _I]),
+    "et_gpgraph_stgcnn_forward_graph": (_I, [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _Z, _P]),
+    "et_gpgraph_stgcnn_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _I64, _I64, _P, _P, _P, _P, _P, _Z, _P]),
     # ---- fit
     "et_fit_gram_workspace_bytes": (_Z, [_I64, _I, _I]),
     "et_fit_gram": (_I, [_P, _P, _I64, _I, _I, _I, _F, _I, _P, _P, _P, _P, _Z, _P]),
@@ -216,6 +220,12 @@ class SGCNParams(C.Structure):
 class GPGraphSGCNParams(C.Structure):
     """Mirror of ``et_gpgraph_sgcn_params``."""
     _fields_ = [("base", SGCNParams), ("group_w", C.c_void_p), ("group_b", C.c_void_p), ("th", C.c_void_p),
+                ("tau", C.c_float), ("mix_a", C.c_void_p), ("mix_w", C.c_void_p), ("mix_b", C.c_void_p)]
+
+
+class GPGraphSTGCNNParams(C.Structure):
+    """Mirror of ``et_gpgraph_stgcnn_params``."""
+    _fields_ = [("base", STGCNNParams), ("group_w", C.c_void_p), ("group_b", C.c_void_p), ("th", C.c_void_p),
                 ("tau", C.c_float), ("mix_a", C.c_void_p), ("mix_w", C.c_void_p), ("mix_b", C.c_void_p)]
 
 

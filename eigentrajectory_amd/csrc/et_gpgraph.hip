@@ -12,6 +12,7 @@
 //                           the group means; the three virtual scenes' inputs, node counts and stack offsets
 //   input, fuse, asym x layers, tadj, sadj, tail   et_sgcn_core.inl on the 3 S virtual scenes -> (k, 3 N, S) in the workspace
 //   mix     per pedestrian  unpool by gather, mean of the three, PReLU, the (S k) x (3 S k) product, -> (k, N, S)
+// The group steps and the mix kernel are et_gpgraph_core.inl, shared with et_gpgraph_stgcnn.hip.
 // The merge.  The reference walks the close pairs (r, c), c < r, in row-major order and gives every pedestrian that carries
 // r's label the label c -- c itself, not c's label, so the result is NOT the connected components.  Within row r with close
 // columns c1 < .. < cm the walk moves label[r]'s carriers to c1, then c1's carriers (those included) to c2, ..: at the end
@@ -26,8 +27,7 @@ namespace {
 
 #include "et_sgcn_core.inl"
 
-constexpr int kGpHid = 8;  // group_cnn's output channels
-constexpr int kMixThreads = 128;
+#include "et_gpgraph_core.inl"
 
 struct GLay {  // the workspace behind the base's (floats): v_abs (T,N), conv features (8,T,N), dist and sig_norm (sum n^2),
     int64_t va, feat, dist, sn, po, total;  // the base's output for the 3 N virtual rows (k, 3 N, S)
@@ -44,19 +44,21 @@ __host__ __device__ inline GLay glay_of(const Lay &L, int T, int k, int S, int64
     return G;
 }
 
-__device__ __forceinline__ float sig_of(float d, float th, float tau) { return 1.0f / (1.0f + expf(-(-(d - th) / tau))); }
+static GpTab tab_of(const Ctx &c) {
+    return GpTab{c.off, c.Nr, c.Sr, reinterpret_cast<int64_t *>(c.ws + c.L.sq), reinterpret_cast<int32_t *>(c.ws + c.L.vn),
+                 reinterpret_cast<int32_t *>(c.ws + c.L.gidx)};
+}
 
-// ---- group: one workgroup per real scene
-__global__ __launch_bounds__(kSnThreads) void gp_group(Ctx c, et_gpgraph_sgcn_params p, GLay G, int64_t n2real,
+static GpWeights weights_of(const et_gpgraph_sgcn_params &p) {
+    return GpWeights{p.group_w, p.group_b, p.th, p.tau, p.mix_a, p.mix_w, p.mix_b, p.base.pred_len, p.base.out_dims};
+}
+
+// ---- group: one workgroup per real scene (the steps: et_gpgraph_core.inl)
+__global__ __launch_bounds__(kSnThreads) void gp_group(Ctx c, GpTab tab, GpWeights p, GLay G, int64_t n2real,
                                                        const float *__restrict__ g_abs, const float *__restrict__ g_rel,
                                                        const float *__restrict__ C_obs, const float *__restrict__ nrm,
                                                        int32_t *__restrict__ group_index, float *__restrict__ dist_out) {
     __shared__ int64_t part[kSnThreads];
-    __shared__ float red[2 * kSnThreads / kWave];
-    __shared__ int lab[ET_SGCN_MAX_N], cmx[ET_SGCN_MAX_N], idx[ET_SGCN_MAX_N], cnt[ET_SGCN_MAX_N];
-    __shared__ unsigned char hit[ET_SGCN_MAX_N];
-    __shared__ float cs[ET_SGCN_MAX_N];
-    __shared__ int n_groups;
     const int s = blockIdx.x, tid = threadIdx.x, T = c.T, Sr = c.Sr;
     const int64_t Nr = c.Nr;
     const int64_t b = c.off ? c.off[s] : 0;
@@ -66,169 +68,20 @@ __global__ __launch_bounds__(kSnThreads) void gp_group(Ctx c, et_gpgraph_sgcn_pa
     const int64_t nn = e - b;
     const bool ok = nn <= ET_SGCN_MAX_N && sq + nn * nn <= n2real;
     if (tid == 0) {
-        int64_t *sqt = reinterpret_cast<int64_t *>(c.ws + c.L.sq);
+        int64_t *sqt = tab.sq;
         for (int m = 0; m < 3; ++m) sqt[m * Sr + s] = ok ? m * n2real + sq : -1;
     }
     if (!ok) return;
-    const int n = (int)nn;
-    float *va = c.ws + G.va + T * b;
-    float *feat = c.ws + G.feat + (int64_t)kGpHid * T * b;
-    float *D = c.ws + G.dist + sq, *sn = c.ws + G.sn + sq;
-    float *v0 = c.ws + c.L.v + T * b, *p0 = c.ws + c.L.vp + T * b;
-    float *v1 = v0 + T * Nr, *p1 = p0 + T * Nr, *v2 = v1 + T * Nr, *p2 = p1 + T * Nr;
-    const float th = p.th[0], tau = p.tau;
-
-    // v_abs, and the pedestrian graph v_rel = [position; coefficients]
-    scene_v(va, g_abs, C_obs, nrm, Nr, b, n, T, red);
-    for (int q = tid; q < T * n; q += kSnThreads) {
-        p0[q] = g_rel ? g_rel[q] : (float)(q / n + 1);
-        if (g_rel) v0[q] = g_rel[T * n + q];
+    GpScene gs;
+    gs.va = c.ws + G.va + T * b;
+    gs.feat = c.ws + G.feat + (int64_t)kGpHid * T * b;
+    gs.D = c.ws + G.dist + sq;
+    gs.sn = c.ws + G.sn + sq;
+    for (int m = 0; m < 3; ++m) {  // the three virtual scenes' rows: pass m at m Nr + b
+        gs.in[m][0] = c.ws + c.L.vp + T * (m * Nr + b);
+        gs.in[m][1] = c.ws + c.L.v + T * (m * Nr + b);
     }
-    __syncthreads();
-    if (!g_rel)
-        for (int q = tid; q < T * n; q += kSnThreads) v0[q] = va[q];
-    // group_cnn: Conv2d(1, 8, (3, 1), padding (1, 0)) along t
-    for (int q = tid; q < kGpHid * T * n; q += kSnThreads) {
-        const int i = q % n, t = (q / n) % T, ch = q / (n * T);
-        float acc = p.group_b[ch];
-        for (int d = 0; d < 3; ++d) {
-            const int tt = t + d - 1;
-            if (tt >= 0 && tt < T) acc = fmaf(p.group_w[ch * 3 + d], va[tt * n + i], acc);
-        }
-        feat[q] = acc;
-    }
-    __syncthreads();
-    // d[i][j]: the mean over t of the L2 norm over the channels (symmetric bit for bit: (a - b)^2 = (b - a)^2, one order)
-    for (int q = tid; q < n * n; q += kSnThreads) {
-        const int i = q / n, j = q % n;
-        float tot = 0.f;
-        for (int t = 0; t < T; ++t) {
-            float ss = 0.f;
-            for (int ch = 0; ch < kGpHid; ++ch) {
-                const float df = feat[(ch * T + t) * n + i] - feat[(ch * T + t) * n + j];
-                ss = fmaf(df, df, ss);
-            }
-            tot += sqrtf(ss);
-        }
-        const float d = tot / (float)T;
-        D[q] = d;
-        if (dist_out) dist_out[sq + q] = d;
-    }
-    __syncthreads();
-    // the last close column of every row (-1: none), and the labels' start
-    for (int r = tid; r < n; r += kSnThreads) {
-        int cm = -1;
-        for (int cc = 0; cc < r; ++cc)
-            if (D[r * n + cc] <= th) cm = cc;
-        cmx[r] = cm;
-        lab[r] = r;
-    }
-    __syncthreads();
-    for (int r = 1; r < n; ++r) {
-        const int cm = cmx[r];
-        if (cm < 0) continue;  // (uniform)
-        const int lr = lab[r];
-        for (int cc = tid; cc < n; cc += kSnThreads) hit[cc] = cc < r && D[r * n + cc] <= th;
-        __syncthreads();
-        for (int i = tid; i < n; i += kSnThreads) {
-            const int l = lab[i];
-            if (hit[l] || l == lr) lab[i] = cm;
-        }
-        __syncthreads();
-    }
-    // compact labels in the order of the surviving values; group sizes
-    for (int i = tid; i < n; i += kSnThreads) {
-        hit[i] = 0;
-        cnt[i] = 0;
-    }
-    __syncthreads();
-    for (int i = tid; i < n; i += kSnThreads) hit[lab[i]] = 1;
-    __syncthreads();
-    for (int i = tid; i < n; i += kSnThreads) {
-        int rank = 0;
-        for (int l = 0; l < lab[i]; ++l) rank += hit[l];
-        idx[i] = rank;
-        atomicAdd(&cnt[rank], 1);
-    }
-    if (tid == 0) {
-        int g = 0;
-        for (int l = 0; l < n; ++l) g += hit[l];
-        n_groups = g;
-    }
-    __syncthreads();
-    const int ng = n_groups;
-    if (tid == 0) {
-        int32_t *vn = reinterpret_cast<int32_t *>(c.ws + c.L.vn);
-        vn[s] = n;
-        vn[Sr + s] = ng;
-        vn[2 * Sr + s] = n;
-    }
-    int32_t *gi = reinterpret_cast<int32_t *>(c.ws + c.L.gidx) + b;
-    for (int i = tid; i < n; i += kSnThreads) {
-        gi[i] = idx[i];
-        if (group_index) group_index[b + i] = idx[i];
-    }
-    // sig / sig.sum(dim = 0)
-    for (int j = tid; j < n; j += kSnThreads) {
-        float sum = 0.f;
-        for (int i = 0; i < n; ++i) sum += sig_of(D[i * n + j], th, tau);
-        cs[j] = sum;
-    }
-    __syncthreads();
-    for (int q = tid; q < n * n; q += kSnThreads) sn[q] = sig_of(D[q], th, tau) / cs[q % n];
-    __syncthreads();
-    // v' = (v_rel - v_soft) + v_soft, v_soft = v_rel @ sig_norm: both channels
-    for (int q = tid; q < 2 * T * n; q += kSnThreads) {
-        const int j = q % n, t = (q / n) % T, ch = q / (n * T);
-        const float *x = (ch ? v0 : p0) + t * n;
-        float soft = 0.f;
-        for (int i = 0; i < n; ++i) soft = fmaf(x[i], sn[i * n + j], soft);
-        (ch ? v2 : p2)[t * n + j] = (x[j] - soft) + soft;
-    }
-    __syncthreads();
-    // the group means of v', pedestrians in ascending order
-    for (int q = tid; q < 2 * T * ng; q += kSnThreads) {
-        const int g = q % ng, t = (q / ng) % T, ch = q / (ng * T);
-        const float *x = (ch ? v2 : p2) + t * n;
-        float sum = 0.f;
-        for (int i = 0; i < n; ++i)
-            if (idx[i] == g) sum += x[i];
-        (ch ? v1 : p1)[t * ng + g] = sum / (float)cnt[g];
-    }
-}
-
-// ---- mix: one workgroup per pedestrian
-__global__ __launch_bounds__(kMixThreads) void gp_mix(Ctx c, et_gpgraph_sgcn_params p, const float *__restrict__ po,
-                                                      float *__restrict__ out, int graph_layout) {
-    extern __shared__ float mix_lds[];  // the three passes' (S, k) as they are, and after the PReLU
-    const int k = p.base.pred_len, S = p.base.out_dims, Sk = S * k, tid = threadIdx.x;
-    float *raw = mix_lds, *act = mix_lds + 3 * Sk;
-    const int64_t r = blockIdx.x, Nr = c.Nr;
-    const int s = c.off ? scene_of_row(c.off, c.Sr, r) : 0;
-    const int64_t b = c.off ? c.off[s] : 0;
-    const int64_t e = c.off ? c.off[s + 1] : Nr;
-    const bool ok = r >= b && r < e && reinterpret_cast<const int64_t *>(c.ws + c.L.sq)[s] >= 0;
-    int64_t row[3] = {r, r, 2 * Nr + r};
-    if (ok) row[1] = Nr + b + reinterpret_cast<const int32_t *>(c.ws + c.L.gidx)[r];  // unpool: the group's row
-    const float a = p.mix_a[0];
-    for (int q = tid; q < 3 * Sk; q += kMixThreads) {
-        const int m = q / Sk, ss = (q % Sk) / k, t = q % k;
-        const float x = ok ? po[((int64_t)t * 3 * Nr + row[m]) * S + ss] : __builtin_nanf("");
-        raw[q] = x;
-        act[q] = prelu(x, a);
-    }
-    __syncthreads();
-    for (int o = tid; o < Sk; o += kMixThreads) {
-        const float *w = p.mix_w + (int64_t)o * 3 * Sk;
-        float acc = p.mix_b[o];
-        for (int q = 0; q < 3 * Sk; ++q) acc = fmaf(w[q], act[q], acc);
-        const float y = ((raw[o] + raw[Sk + o]) + raw[2 * Sk + o]) / 3.0f + acc;
-        const int ss = o / k, t = o % k;
-        if (graph_layout)
-            out[((int64_t)ss * k + t) * Nr + r] = y;
-        else
-            out[((int64_t)t * Nr + r) * S + ss] = y;
-    }
+    gp_group_scene<2>(tab, gs, p, s, b, (int)nn, T, sq, g_abs, g_rel, C_obs, nrm, group_index, dist_out);
 }
 
 static int check_gp(const et_gpgraph_sgcn_params *p) {
@@ -265,11 +118,13 @@ static int gp_run(const et_gpgraph_sgcn_params &p, const float *g_abs, const flo
     if (!workspace || workspace_bytes < (size_t)G.total * 4) return ET_ERR_WORKSPACE;
     const Ident I{nullptr, nullptr, 1, -1};  // eye(n) and eye(T): generate_identity_matrix
     hipLaunchKernelGGL(sgcn_prep<true>, dim3(1), dim3(kSnThreads), 0, st, bp, c.ws);
-    hipLaunchKernelGGL(gp_group, dim3((unsigned)n_scenes), dim3(kSnThreads), 0, st, c, p, G, sum_n2, g_abs, g_rel, C_obs, nrm,
-                       group_index, dist);
+    const GpTab tab = tab_of(c);
+    const GpWeights w = weights_of(p);
+    hipLaunchKernelGGL(gp_group, dim3((unsigned)n_scenes), dim3(kSnThreads), 0, st, c, tab, w, G, sum_n2, g_abs, g_rel, C_obs,
+                       nrm, group_index, dist);
     float *po = c.ws + G.po;
     run_layers<true>(bp, c, nullptr, I, nullptr, nullptr, max_n, po, logit_s, logit_t, st);
-    hipLaunchKernelGGL(gp_mix, dim3((unsigned)N), dim3(kMixThreads), 6 * bp.out_dims * bp.pred_len * sizeof(float), st, c, p,
+    hipLaunchKernelGGL(gp_mix, dim3((unsigned)N), dim3(kMixThreads), 6 * bp.out_dims * bp.pred_len * sizeof(float), st, tab, w,
                        po, out, graph_layout);
     ET_LAUNCH_CHECK();
     return ET_OK;

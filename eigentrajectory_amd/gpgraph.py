@@ -1,5 +1,6 @@
 """GP-Graph-SGCN, the predictor of ET-GPGraph-SGCN (baseline/gpgraphsgcn/model.py: get_GPGraph_SGCN_model, the reference's
-default configuration), inference on HIP kernels.
+default configuration), and GP-Graph-STGCNN, the predictor of ET-GPGraph-STGCNN (baseline/gpgraphstgcnn/model.py:
+get_GPGraph_STGCNN_model), inference on HIP kernels.
 
 Same sub-module / parameter names as the reference's ``GPGraph`` -- ``baseline_model.*`` (the two-channel SGCN,
 :class:`eigentrajectory_amd.sgcn.SGCN` with ``position_channel=True``), ``group_gen.group_cnn.0``, ``group_gen.th``,
@@ -17,8 +18,17 @@ the device at every call (an in-place edit is seen by the next call and by a cap
 runs in a fixed number of launches through :meth:`EigenTrajectory.evaluate_split` /
 :func:`eigentrajectory_amd.ops.gpgraph_sgcn_forward_scenes`.
 
+GP-Graph-STGCNN is the same wrapper around the original Social-STGCNN
+(:class:`eigentrajectory_amd.stgcnn.SocialSTGCNN` with ``graph_per_time_row=True``), under the ``gpgraphstgcnn`` bridge::
+
+    model = EigenTrajectory(get_GPGraph_STGCNN_model(obs_len=hp.k + 2, pred_len=hp.k, in_dims=1, out_dims=hp.num_samples),
+                            get_hook_func("gpgraphstgcnn"), hp).eval()
+
+``forward(v_abs, v_rel)`` is then ``et_gpgraph_stgcnn_forward_graph`` (csrc/et_gpgraph_stgcnn.hip, three launches), both
+inputs (1, 1, T, N); a whole split runs through :func:`eigentrajectory_amd.ops.gpgraph_stgcnn_forward_scenes`.
+
 Native: the ET configuration -- ``d_type='learned_l2norm'``, ``d_th='learned'``, ``mix_type='mlp'``, ``group_type=(True,
-True, True)``, ``weight_share=True`` -- in eval mode with ``dropout = 0``.  Training, GP-Graph-STGCNN and the other
+True, True)``, ``weight_share=True`` -- in eval mode with ``dropout = 0``, around either base.  Training and the other
 ``d_type`` / ``d_th`` / ``mix_type`` / ``group_type`` / ``weight_share=False`` variants are not: they construct (with the
 reference's parameters), and their forward raises.
 """
@@ -31,6 +41,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .sgcn import SGCN, _p
+from .stgcnn import SocialSTGCNN
 
 
 class _GroupGenerator(nn.Module):
@@ -61,8 +72,9 @@ class _GroupIntegrator(nn.Module):
 
 
 class GPGraph(nn.Module):
-    r"""baseline/gpgraphsgcn/model_groupwrapper.py's ``GPGraph`` around an :class:`SGCN` base (eval-mode inference on the
-    GPU).  ``forward(v_abs, v_rel)`` -> ``(v (1, S, k, N), indices (N,) int64)``."""
+    r"""model_groupwrapper.py's ``GPGraph`` (baseline/gpgraphsgcn and baseline/gpgraphstgcnn: the same class) around an
+    :class:`SGCN` (``position_channel=True``) or a :class:`SocialSTGCNN` (``graph_per_time_row=True``) base (eval-mode
+    inference on the GPU).  ``forward(v_abs, v_rel)`` -> ``(v (1, S, k, N), indices (N,) int64)``."""
 
     TAU = 0.1  # GroupGenerator.forward's default temperature; GPGraph.forward does not pass another
 
@@ -80,29 +92,48 @@ class GPGraph(nn.Module):
         self.group_mix = _GroupIntegrator(mix_type=mix_type, n_mix=sum(group_type), out_channels=out_channels,
                                           pred_seq_len=pred_seq_len)
 
+    @property
+    def stgcnn_base(self):
+        """True around a Social-STGCNN base (GP-Graph-STGCNN), False around an SGCN base (GP-Graph-SGCN)."""
+        return isinstance(self.baseline_model, SocialSTGCNN)
+
     def _check_mode(self):
+        base = self.baseline_model
+        base_ok = ((isinstance(base, SGCN) and base.position_channel)
+                   or (isinstance(base, SocialSTGCNN) and base.graph_per_time_row))
         if (self.d_type != "learned_l2norm" or not isinstance(self.group_gen.th, nn.Parameter) or self.mix_type != "mlp"
                 or not (self.include_original and self.include_inter_group and self.include_intra_group)
-                or not self.weight_share or not isinstance(self.baseline_model, SGCN)
-                or not self.baseline_model.position_channel):
+                or not self.weight_share or not base_ok):
             raise NotImplementedError("GPGraph: only the ET configuration is native -- d_type='learned_l2norm', d_th='learned', "
                                       "mix_type='mlp', group_type=(True, True, True), weight_share=True around "
-                                      "SGCN(position_channel=True); the other variants are not implemented")
+                                      "SGCN(position_channel=True) or SocialSTGCNN(graph_per_time_row=True); the other "
+                                      "variants are not implemented")
         if self.training:
             raise RuntimeError("GPGraph: only inference is native (no backward, no straight-through gradient); "
                                "training-mode forward is not implemented -- call .eval() first")
-        self.baseline_model._check_mode()
+        if isinstance(base, SGCN):
+            base._check_mode()
+        elif base.training:
+            raise RuntimeError("GPGraph: the SocialSTGCNN base is in training mode (BatchNorm batch statistics are not "
+                               "native) -- call .eval() on the whole model")
 
     def et_params(self):
-        """-> (et_gpgraph_sgcn_params, device): this module's tensors as the kernels read them (include/eigentraj.h)."""
+        """-> (et_gpgraph_sgcn_params or et_gpgraph_stgcnn_params, device): this module's tensors as the kernels read them
+        (include/eigentraj.h)."""
         base, dev = self.baseline_model.et_params()
-        p = L.GPGraphSGCNParams()
+        p = L.GPGraphSTGCNNParams() if self.stgcnn_base else L.GPGraphSGCNParams()
         p.base = base
         own = [t for m in (self.group_gen, self.group_mix) for t in m.parameters()]
         if any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in own):
             raise L.ETLibraryError("GPGraph: every parameter must be a contiguous float32 tensor on ONE HIP device "
                                    "(model.cuda()); there is no CPU path")
-        if self.in_channels != 1 or self.out_channels != self.baseline_model.out_dims \
+        if self.stgcnn_base:
+            b = self.baseline_model
+            if self.in_channels != 1 or self.out_channels != b.output_feat or self.pred_seq_len != b.pred_seq_len \
+                    or self.obs_seq_len != b.seq_len:
+                p.base.input_feat = -1  # the kernels answer ET_ERR_UNSUPPORTED
+                return p, dev
+        elif self.in_channels != 1 or self.out_channels != self.baseline_model.out_dims \
                 or self.pred_seq_len != self.baseline_model.pred_len or self.obs_seq_len != self.baseline_model.obs_len:
             p.base.in_dims = -1  # the kernels answer ET_ERR_UNSUPPORTED
             return p, dev
@@ -115,6 +146,8 @@ class GPGraph(nn.Module):
     def forward(self, v_abs, v_rel):
         self._check_mode()
         from . import ops
+        if self.stgcnn_base:
+            return ops.gpgraph_stgcnn_forward_graph(self, v_abs, v_rel)
         return ops.gpgraph_sgcn_forward_graph(self, v_abs, v_rel)
 
 
@@ -133,3 +166,20 @@ class GPGraphSGCN(GPGraph):
 def get_GPGraph_SGCN_model(obs_len=8, pred_len=12, in_dims=2, out_dims=5):
     """The reference's factory (baseline/gpgraphsgcn/model.py), without its ``.cuda()``: move the result yourself."""
     return GPGraphSGCN(obs_len=obs_len, pred_len=pred_len, in_dims=in_dims, out_dims=out_dims)
+
+
+class GPGraphSTGCNN(GPGraph):
+    r"""``get_GPGraph_STGCNN_model``'s network as a class: the original Social-STGCNN (one st_gcn, five tpcnns, kernel 3)
+    inside :class:`GPGraph` with the reference's fixed arguments."""
+
+    def __init__(self, obs_len=8, pred_len=12, in_dims=2, out_dims=5):
+        base = SocialSTGCNN(n_stgcnn=1, n_txpcnn=5, input_feat=in_dims, output_feat=out_dims, kernel_size=3, seq_len=obs_len,
+                            pred_seq_len=pred_len, graph_per_time_row=True)
+        super().__init__(baseline_model=base, in_channels=in_dims, out_channels=out_dims, obs_seq_len=obs_len,
+                         pred_seq_len=pred_len, d_type="learned_l2norm", d_th="learned", mix_type="mlp",
+                         group_type=(True, True, True), weight_share=True)
+
+
+def get_GPGraph_STGCNN_model(obs_len=8, pred_len=12, in_dims=2, out_dims=5):
+    """The reference's factory (baseline/gpgraphstgcnn/model.py), without its ``.cuda()``: move the result yourself."""
+    return GPGraphSTGCNN(obs_len=obs_len, pred_len=pred_len, in_dims=in_dims, out_dims=out_dims)

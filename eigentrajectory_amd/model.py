@@ -267,31 +267,37 @@ class EigenTrajectory(nn.Module):
     def evaluate_split(self, obs_traj, pred_traj, seq_start_end, metrics=("ADE", "FDE")):
         r"""A whole test split in a fixed number of launches: the projection of every row, the bridge + predictor +
         post-hook of every scene (``et_stgcnn_forward_scenes``: one launch; ``et_sgcn_forward_scenes``: 6 + the number of
-        asymmetric convolution layers; ``et_gpgraph_sgcn_forward_scenes``: 8 + that number), the reconstruction + metrics of every scene -- what the reference's test loop
+        asymmetric convolution layers; ``et_gpgraph_sgcn_forward_scenes``: 8 + that number;
+        ``et_gpgraph_stgcnn_forward_scenes``: three), the reconstruction + metrics of every scene -- what the reference's test loop
         (utils/trainer.py:173-195) computes with one :meth:`evaluate` per scene.
 
         ``obs_traj`` (N, t_obs, 2), ``pred_traj`` (N, t_pred, 2): the split's rows, scene after scene; ``seq_start_end``
         (M, 2): each scene's (start, end) rows, consecutive and covering all N.  ``metrics``: any of ADE, FDE, TCC, COL.
         Returns a dict of (N,) tensors.  Only for a :class:`~eigentrajectory_amd.stgcnn.SocialSTGCNN` predictor under the
         ``stgcnn`` hooks, a :class:`~eigentrajectory_amd.sgcn.SGCN` predictor under the ``sgcn`` hooks or a
-        :class:`~eigentrajectory_amd.gpgraph.GPGraph` predictor under the ``gpgraphsgcn`` hooks, in eval mode; any other
-        predictor raises (use :meth:`evaluate` scene by scene)."""
+        :class:`~eigentrajectory_amd.gpgraph.GPGraph` predictor under the hooks of its base (``gpgraphsgcn`` around SGCN,
+        ``gpgraphstgcnn`` around SocialSTGCNN), in eval mode; any other predictor or pairing raises (use :meth:`evaluate`
+        scene by scene)."""
         from .bridges import BRIDGES
         from .gpgraph import GPGraph
         from .sgcn import SGCN
         from .stgcnn import SocialSTGCNN
         hooks = self.hook_func
         forward_scenes = None
-        for cls, name, fn in ((SocialSTGCNN, "stgcnn", ops.stgcnn_forward_scenes), (SGCN, "sgcn", ops.sgcn_forward_scenes),
-                              (GPGraph, "gpgraphsgcn", ops.gpgraph_sgcn_forward_scenes)):
+        for cls, name, fn, stgcnn_base in ((SocialSTGCNN, "stgcnn", ops.stgcnn_forward_scenes, None),
+                                           (SGCN, "sgcn", ops.sgcn_forward_scenes, None),
+                                           (GPGraph, "gpgraphsgcn", ops.gpgraph_sgcn_forward_scenes, False),
+                                           (GPGraph, "gpgraphstgcnn", ops.gpgraph_stgcnn_forward_scenes, True)):
             pre, fwd, post = BRIDGES[name]
             if (isinstance(self.baseline_model, cls) and hooks.model_forward_pre_hook is pre
-                    and hooks.model_forward is fwd and hooks.model_forward_post_hook is post):
+                    and hooks.model_forward is fwd and hooks.model_forward_post_hook is post
+                    and (stgcnn_base is None or self.baseline_model.stgcnn_base == stgcnn_base)):
                 forward_scenes = fn
         if forward_scenes is None:
             raise NotImplementedError("evaluate_split: the whole-split path is built for a SocialSTGCNN predictor under the "
                                       "'stgcnn' hooks, an SGCN predictor under the 'sgcn' hooks and a GPGraph predictor under "
-                                      "the 'gpgraphsgcn' hooks only; call evaluate() scene by scene for other predictors")
+                                      "the hooks of its base ('gpgraphsgcn' around SGCN, 'gpgraphstgcnn' around SocialSTGCNN) "
+                                      "only; call evaluate() scene by scene for other predictors")
         if self.baseline_model.training:
             raise RuntimeError("evaluate_split: the predictor is in training mode; call .eval() first")
         sse = torch.as_tensor(seq_start_end).detach().cpu().long().reshape(-1, 2)

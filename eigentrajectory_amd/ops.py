@@ -285,6 +285,9 @@ def _stgcnn_ws(params, n, max_n, dev):
 def stgcnn_forward_graph(model, v, a):
     """``model`` (:class:`eigentrajectory_amd.stgcnn.SocialSTGCNN`, eval mode) on one scene as the stgcnn bridge hands it
     over: v (1, 1, K, N), a (K, N, N) -> the raw output (1, S, k, N).  One launch."""
+    if getattr(model, "graph_per_time_row", False):
+        raise NotImplementedError("stgcnn_forward_graph: a per-time-row SocialSTGCNN (graph_per_time_row=True) runs only inside "
+                                  "GPGraphSTGCNN")
     params, dev = model.et_params()
     K, k, S = params.seq_len, params.pred_seq_len, params.output_feat
     n = v.shape[-1]
@@ -301,6 +304,9 @@ def stgcnn_forward_scenes(model, C_obs, nrm, scene_sizes=None):
     """The stgcnn bridge + ``model`` (eval mode) + the post-hook for every scene of a split in ONE launch: C_obs (k, N) and
     nrm (4, N) of :func:`norm_project` (rows 0-1: the last observed positions, centred here per scene), ``scene_sizes``
     pedestrians per scene in row order (None = one scene; an empty list takes N = 0) -> C_pred_refine (k, N, S)."""
+    if getattr(model, "graph_per_time_row", False):
+        raise NotImplementedError("stgcnn_forward_scenes: a per-time-row SocialSTGCNN (graph_per_time_row=True) runs only inside "
+                                  "GPGraphSTGCNN")
     params, dev = model.et_params()
     C_obs, nrm = _dev_args(dev, C_obs, nrm)
     k, n = C_obs.shape
@@ -492,6 +498,113 @@ def gpgraph_sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_detail
            L.ptr(ws), nbytes, L.stream(dev))
     if want_details:
         return out, {"group_index": gi, "dist": dist, "logit_s": ls, "logit_t": lt}
+    return out
+
+
+# ---------------------------------------------------------------------- GP-Graph-STGCNN predictor (inference)
+def _gpgraph_stgcnn_buffers(params, want, T, n, sum_n2, n_scenes, dev):
+    nbytes = L.lib().et_gpgraph_stgcnn_workspace_bytes(C.byref(params), n, sum_n2, int(n_scenes))
+    if not nbytes:
+        L.check(3, "et_gpgraph_stgcnn_workspace_bytes")  # outside the native family
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    gi = torch.empty((n,), device=dev, dtype=torch.int32)
+    if not want:
+        return ws, nbytes, gi, None, None
+    return ws, nbytes, gi, torch.empty((sum_n2,), device=dev), torch.zeros((3, T * n), device=dev)
+
+
+def _stgcnn_base_of(model, who):
+    from .stgcnn import SocialSTGCNN
+    if not isinstance(getattr(model, "baseline_model", None), SocialSTGCNN):
+        raise NotImplementedError(f"{who}: the model is not a GPGraph around a SocialSTGCNN base (a GPGraph around SGCN runs "
+                                  "through gpgraph_sgcn_forward_*)")
+
+
+def gpgraph_stgcnn_forward_graph(model, v_abs, v_rel, want_details=False):
+    """``model`` (:class:`eigentrajectory_amd.gpgraph.GPGraph` around a per-time-row SocialSTGCNN, eval mode) on one scene as
+    the gpgraphstgcnn bridge hands it over: v_abs (1, 1, T, N), v_rel (1, 1, T, N) -> ``(v (1, S, k, N), indices (N,)
+    int64)``; with ``want_details`` a dict is returned as third item: ``dist`` (N, N), ``group_index`` (N,) int32,
+    ``n_groups``, and ``graph_inputs``, the three passes' inputs as the kernel reads them: [(T, N), (T, G), (T, N)].  The
+    inputs must be contiguous float32 tensors on the model's device (they are read in place).  Three launches."""
+    _stgcnn_base_of(model, "gpgraph_stgcnn_forward_graph")
+    model._check_mode()
+    params, dev = model.et_params()
+    T, k, S = params.base.seq_len, params.base.pred_seq_len, params.base.output_feat
+    n = v_abs.shape[3] if v_abs.dim() == 4 else -1
+    if tuple(v_abs.shape) != (1, 1, T, n) or tuple(v_rel.shape) != (1, 1, T, n):
+        raise ValueError(f"gpgraph_stgcnn_forward_graph: v_abs {tuple(v_abs.shape)} / v_rel {tuple(v_rel.shape)} are not "
+                         f"(1,1,{T},N) / (1,1,{T},N)")
+    for name, t in (("v_abs", v_abs), ("v_rel", v_rel)):
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"gpgraph_stgcnn_forward_graph: {name} must be a contiguous float32 tensor on {dev} (got "
+                             f"{t.dtype}, {t.device}, contiguous={t.is_contiguous()})")
+    if n > L.SGCN_MAX_N:
+        raise ValueError(f"gpgraph_stgcnn_forward_graph: N = {n} exceeds the {L.SGCN_MAX_N} pedestrians a scene may have")
+    out = torch.empty((1, S, k, n), device=dev)
+    if n == 0:
+        L.call("et_gpgraph_stgcnn_forward_graph", C.byref(params), None, None, 0, None, None, None, None, None, 0,
+               L.stream(dev))
+        res = (out, torch.empty((0,), device=dev, dtype=torch.int64))
+        return res + ({"dist": torch.empty((0, 0), device=dev), "n_groups": 0, "graph_inputs": [],
+                       "group_index": torch.empty((0,), device=dev, dtype=torch.int32)},) if want_details else res
+    ws, nbytes, gi, dist, gin = _gpgraph_stgcnn_buffers(params, want_details, T, n, n * n, 1, dev)
+    L.call("et_gpgraph_stgcnn_forward_graph", C.byref(params), L.ptr(v_abs.detach()), L.ptr(v_rel.detach()), n, L.ptr(out),
+           L.ptr(gi), L.ptr(dist), L.ptr(gin), L.ptr(ws), nbytes, L.stream(dev))
+    idx = gi.long()
+    if not want_details:
+        return out, idx
+    g = int(idx.max()) + 1
+    return out, idx, {"dist": dist.view(n, n), "group_index": gi, "n_groups": g,
+                      "graph_inputs": [gin[m, :T * nm].view(T, nm) for m, nm in enumerate((n, g, n))]}
+
+
+def gpgraph_stgcnn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
+    """The gpgraphstgcnn bridge + ``model`` (eval mode) + the post-hook for every scene of a split in three launches: C_obs
+    (k, N) and nrm (4, N) of :func:`norm_project`, ``scene_sizes`` as :func:`sgcn_forward_scenes` -> C_pred_refine (k, N, S).
+    With ``want_details`` also a dict: ``group_index`` (N,) int32 scene-local, ``dist`` packed (scene s's (n, n) block at
+    n_0^2 + ... + n_{s-1}^2), ``n_groups`` (per scene, int64) and ``graph_inputs`` (3, T N) as include/eigentraj.h describes
+    (pass m of scene s a (T, n_m) block at T (m N + off[s]))."""
+    _stgcnn_base_of(model, "gpgraph_stgcnn_forward_scenes")
+    model._check_mode()
+    params, dev = model.et_params()
+    C_obs, nrm = _dev_args(dev, C_obs, nrm)
+    k, n = C_obs.shape
+    T = params.base.seq_len
+    if k != params.base.pred_seq_len or nrm.dim() != 2 or nrm.shape[0] < 2 or nrm.shape[1] != n:
+        raise ValueError(f"gpgraph_stgcnn_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
+                         f"k = {params.base.pred_seq_len}")
+    if scene_sizes is not None:
+        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
+        if not sizes and n:
+            raise ValueError(f"gpgraph_stgcnn_forward_scenes: no scenes for {n} rows")
+        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
+    else:
+        sizes, off = [n], None
+    if scene_sizes is None and n > L.SGCN_MAX_N:
+        raise ValueError(f"gpgraph_stgcnn_forward_scenes: a scene of {n} pedestrians exceeds the {L.SGCN_MAX_N} a scene may "
+                         "have")
+    # (a listed scene above the limit is not refused: its rows come back NaN, the other scenes are computed)
+    sum_n2 = sum(s * s for s in sizes if s <= L.SGCN_MAX_N)
+    max_n = max(sizes, default=0)
+    out = torch.empty((k, n, params.base.output_feat), device=dev)
+    if n == 0:
+        L.call("et_gpgraph_stgcnn_forward_scenes", C.byref(params), None, None, 0, L.ptr(off), 0 if off is None else len(sizes),
+               0, 0, None, None, None, None, None, 0, L.stream(dev))
+        empty = {"group_index": torch.empty((0,), device=dev, dtype=torch.int32), "dist": torch.empty((0,), device=dev),
+                 "graph_inputs": torch.empty((3, 0), device=dev), "n_groups": torch.zeros((len(sizes),), dtype=torch.int64)}
+        return (out, empty) if want_details else out
+    ws, nbytes, gi, dist, gin = _gpgraph_stgcnn_buffers(params, want_details, T, n, sum_n2, len(sizes), dev)
+    L.call("et_gpgraph_stgcnn_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
+           0 if off is None else len(sizes), sum_n2, max_n, L.ptr(out), L.ptr(gi), L.ptr(dist), L.ptr(gin), L.ptr(ws), nbytes,
+           L.stream(dev))
+    if want_details:
+        lo, groups = 0, []
+        host = gi.cpu()
+        for s_ in sizes:
+            groups.append(int(host[lo:lo + s_].max()) + 1 if 0 < s_ <= L.SGCN_MAX_N else 0)
+            lo += s_
+        return out, {"group_index": gi, "dist": dist, "graph_inputs": gin,
+                     "n_groups": torch.tensor(groups, dtype=torch.int64)}
     return out
 
 

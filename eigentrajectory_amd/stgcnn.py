@@ -16,6 +16,11 @@ statistics, the backward pass) is not implemented natively: a forward in trainin
 launch through :meth:`EigenTrajectory.evaluate_split` / :func:`eigentrajectory_amd.ops.stgcnn_forward_scenes`.
 Supported family: ``input_feat = 1``, ``kernel_size = 3``, ``seq_len = pred_seq_len + 2``, ``1 <= output_feat <= 64``,
 ``pred_seq_len <= 32``, ``1 <= n_stgcnn, n_txpcnn <= 8``; other shapes construct, but their forward raises.
+
+``SocialSTGCNN(..., graph_per_time_row=True)`` is baseline/gpgraphstgcnn/model_baseline.py's variant -- the original
+Social-STGCNN gcn, the base of :class:`eigentrajectory_amd.gpgraph.GPGraphSTGCNN`: ``gcn.conv`` has ``output_feat`` channels
+(not ``output_feat * seq_len``) and time row t is contracted with its own graph only (``einsum('nctv,tvw->nctw')``).  It runs
+only as the three passes of GPGraphSTGCNN's call; its own forward raises.
 """
 from __future__ import annotations
 
@@ -28,19 +33,19 @@ from . import _lib as L
 class _GraphConv(nn.Module):
     """The gcn of an st_gcn block: a 1x1 convolution to out * K channels, contracted with the (K, V, V) graph."""
 
-    def __init__(self, in_channels, out_channels, kernel_size):
+    def __init__(self, in_channels, out_channels, kernel_size, per_time_row=False):
         super().__init__()
         self.kernel_size = kernel_size
-        self.conv = nn.Conv2d(in_channels, out_channels * kernel_size, kernel_size=(1, 1))
+        self.conv = nn.Conv2d(in_channels, out_channels * (1 if per_time_row else kernel_size), kernel_size=(1, 1))
 
 
 class _STGCNBlock(nn.Module):
     """One st_gcn block: gcn -> BN -> PReLU -> (t, 1) temporal conv -> BN (-> dropout, off), + residual, PReLU."""
 
-    def __init__(self, in_channels, out_channels, kernel_size):
+    def __init__(self, in_channels, out_channels, kernel_size, per_time_row=False):
         super().__init__()
         t_kernel, graph_kernel = kernel_size
-        self.gcn = _GraphConv(in_channels, out_channels, graph_kernel)
+        self.gcn = _GraphConv(in_channels, out_channels, graph_kernel, per_time_row)
         self.tcn = nn.Sequential(nn.BatchNorm2d(out_channels), nn.PReLU(),
                                  nn.Conv2d(out_channels, out_channels, (t_kernel, 1), (1, 1), ((t_kernel - 1) // 2, 0)),
                                  nn.BatchNorm2d(out_channels), nn.Dropout(0.0, inplace=True))
@@ -60,13 +65,15 @@ class SocialSTGCNN(nn.Module):
     r"""baseline/stgcnn/model.py's ``social_stgcnn`` (eval-mode inference on the GPU).  ``forward(v, a)``: v (1, 1, K, N),
     a (K, N, N) as the stgcnn bridge's pre-hook builds them -> (1, S, k, N), the raw output the post-hook permutes."""
 
-    def __init__(self, n_stgcnn=1, n_txpcnn=1, input_feat=2, output_feat=5, seq_len=8, pred_seq_len=12, kernel_size=3):
+    def __init__(self, n_stgcnn=1, n_txpcnn=1, input_feat=2, output_feat=5, seq_len=8, pred_seq_len=12, kernel_size=3,
+                 graph_per_time_row=False):
         super().__init__()
-        self.n_stgcnn, self.n_txpcnn = n_stgcnn, n_txpcnn
+        self.n_stgcnn, self.n_txpcnn, self.graph_per_time_row = n_stgcnn, n_txpcnn, bool(graph_per_time_row)
         self.input_feat, self.output_feat = input_feat, output_feat
         self.seq_len, self.pred_seq_len, self.kernel_size = seq_len, pred_seq_len, kernel_size
         self.st_gcns = nn.ModuleList(
-            [_STGCNBlock(input_feat if i == 0 else output_feat, output_feat, (kernel_size, seq_len)) for i in range(n_stgcnn)])
+            [_STGCNBlock(input_feat if i == 0 else output_feat, output_feat, (kernel_size, seq_len), self.graph_per_time_row)
+             for i in range(n_stgcnn)])
         self.tpcnns = nn.ModuleList(
             [nn.Conv2d(seq_len if j == 0 else pred_seq_len, pred_seq_len, 3, padding=1) for j in range(n_txpcnn)])
         self.tpcnn_ouput = nn.Conv2d(pred_seq_len, pred_seq_len, 3, padding=1)  # (sic: the reference's name)
@@ -116,5 +123,9 @@ class SocialSTGCNN(nn.Module):
         if self.training:
             raise RuntimeError("SocialSTGCNN: only inference is native (BatchNorm running statistics, no dropout); "
                                "training-mode forward and backward are not implemented -- call .eval() first")
+        if self.graph_per_time_row:
+            raise NotImplementedError("SocialSTGCNN: the per-time-row variant (graph_per_time_row=True) runs only as the three "
+                                      "passes of GPGraphSTGCNN's call (eigentrajectory_amd.gpgraph); there is no stand-alone "
+                                      "kernel for it")
         from . import ops
         return ops.stgcnn_forward_graph(self, v, a)

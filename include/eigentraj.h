@@ -484,6 +484,40 @@ int et_gpgraph_sgcn_forward_scenes(const et_gpgraph_sgcn_params *params, const f
                                    float *C_pred_refine, int32_t *group_index, float *dist, float *logit_s,
                                    float *logit_t, void *workspace, size_t workspace_bytes, et_stream_t stream);
 
+/* ---- GP-Graph-STGCNN predictor, inference (baseline/gpgraphstgcnn: bridge.py pre-hook + GPGraph.forward around the
+ * social_stgcnn of model_baseline.py + post-hook) ------------------------------------------------------------------------
+ * The ET configuration, as for GP-Graph-SGCN; group_w .. mix_b as there.  `base` is the Social-STGCNN table above with ONE
+ * difference: the base is the ORIGINAL Social-STGCNN, whose gcn convolves to S channels and contracts time row t with its
+ * own Laplacian (einsum 'nctv,tvw->nctw'), so st_gcns[i].gcn_w is (S, C_in, 1, 1) and gcn_b (S).  The bridge hands over
+ * v_abs = v_rel = v (1,1,T,N), v = [C_obs; obs_ori].  Per scene: the grouping of GP-Graph-SGCN on one channel; the base runs
+ * on v with L = laplacian(v), on the group means of v' (G nodes, unpooled by gather) and on v' with a_inv multiplied by the
+ * same-group matrix BEFORE + I (so the mask enters the degree); laplacian: a = |v_i - v_j| per time row, a_inv = 1 / a (0
+ * where a == 0), a_hat = a_inv + I, L = I - D^-1/2 a_hat D^-1/2, formed where it is used, never stored.
+ *
+ *   et_gpgraph_stgcnn_forward_graph   one scene as the bridge hands it over -> out (1,S,k,N)
+ *   et_gpgraph_stgcnn_forward_scenes  a whole split, arguments as et_gpgraph_sgcn_forward_scenes -> C_pred_refine (k,N,S);
+ *                                     a scene larger than ET_SGCN_MAX_N or one that does not fit the workspace: NaN rows
+ * Optional outputs (may be NULL): group_index int32 (N); dist, packed as for GP-Graph-SGCN; graph_inputs (3, T N) float: the
+ * three passes' inputs exactly as the second kernel reads them, pass m of scene s a (T, n_m) block at T (m N + off[s]),
+ * n_m = n, G, n (the rest of a pass-1 block is not written).
+ * Three launches for any number of scenes (group, the 3 n_scenes virtual scenes, mix), no host synchronisation, no
+ * allocation; a virtual scene's arena is in LDS when it fits (n_m <= 33 at S = 20, k = 6), else in the workspace.  Every
+ * sum has a fixed order: bit-identical from run to run, and a scene's result does not depend on the scenes around it. */
+typedef struct et_gpgraph_stgcnn_params {
+    et_stgcnn_params base;
+    const float *group_w, *group_b, *th;
+    float tau;
+    const float *mix_a, *mix_w, *mix_b;
+} et_gpgraph_stgcnn_params;
+size_t et_gpgraph_stgcnn_workspace_bytes(const et_gpgraph_stgcnn_params *params, int64_t N, int64_t sum_n2, int n_scenes);
+int et_gpgraph_stgcnn_forward_graph(const et_gpgraph_stgcnn_params *params, const float *v_abs, const float *v_rel, int64_t N,
+                                    float *out, int32_t *group_index, float *dist, float *graph_inputs, void *workspace,
+                                    size_t workspace_bytes, et_stream_t stream);
+int et_gpgraph_stgcnn_forward_scenes(const et_gpgraph_stgcnn_params *params, const float *C_obs, const float *nrm, int64_t N,
+                                     const int32_t *scene_offsets, int n_scenes, int64_t sum_n2, int64_t max_scene_n,
+                                     float *C_pred_refine, int32_t *group_index, float *dist, float *graph_inputs,
+                                     void *workspace, size_t workspace_bytes, et_stream_t stream);
+
 /* ---- fit ----------------------------------------------------------------------------
  * Gram matrices of the normalised trajectories routed to descriptor `which`
  * (1 moving / 0 static) under `mode`:  G_obs (2T_obs,2T_obs), G_pred (2T_pred,2T_pred)
