@@ -94,6 +94,10 @@ SIGNATURES = {
     "et_gpgraph_stgcnn_workspace_bytes": (_Z, [_P, _I64, _I64, _I]),
     "et_gpgraph_stgcnn_forward_graph": (_I, [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _Z, _P]),
     "et_gpgraph_stgcnn_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _I64, _I64, _P, _P, _P, _P, _P, _Z, _P]),
+    # ---- DMRGCN predictor, inference
+    "et_dmrgcn_workspace_bytes": (_Z, [_P, _I64, _I64]),
+    "et_dmrgcn_forward_graph": (_I, [_P, _P, _P, _I64, _P, _P, _Z, _P]),
+    "et_dmrgcn_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _Z, _P]),
     # ---- fit
     "et_fit_gram_workspace_bytes": (_Z, [_I64, _I, _I]),
     "et_fit_gram": (_I, [_P, _P, _I64, _I, _I, _I, _F, _I, _P, _P, _P, _P, _Z, _P]),
@@ -227,6 +231,31 @@ class GPGraphSTGCNNParams(C.Structure):
     """Mirror of ``et_gpgraph_stgcnn_params``."""
     _fields_ = [("base", STGCNNParams), ("group_w", C.c_void_p), ("group_b", C.c_void_p), ("th", C.c_void_p),
                 ("tau", C.c_float), ("mix_a", C.c_void_p), ("mix_w", C.c_void_p), ("mix_b", C.c_void_p)]
+
+
+DMRGCN_MAX_STGCN = 4  # ET_DMRGCN_MAX_STGCN
+DMRGCN_MAX_TPCNN = 8  # ET_DMRGCN_MAX_TPCNN
+DMRGCN_BINS = 5       # ET_DMRGCN_BINS
+
+
+class DMRGCNLayer(C.Structure):
+    """Mirror of ``et_dmrgcn_layer``: device pointers to one st_dmrgcn block's tensors (field order: include/eigentraj.h)."""
+    _fields_ = [("gcn_w", C.c_void_p * 2), ("gcn_b", C.c_void_p * 2)] + [(name, C.c_void_p) for name in (
+        "tcn_prelu", "tcn_w", "tcn_b", "res_w", "res_b", "prelu")]
+
+
+class DMRGCNTpcnn(C.Structure):
+    """Mirror of ``et_dmrgcn_tpcnn``: device pointers to one tpcnn block's tensors."""
+    _fields_ = [("conv_w", C.c_void_p * 2), ("conv_b", C.c_void_p * 2), ("conv_a", C.c_void_p * 2)] + [
+        (name, C.c_void_p) for name in ("gta_w", "gta_b", "gta_a", "res_w", "res_b")]
+
+
+class DMRGCNParams(C.Structure):
+    """Mirror of ``et_dmrgcn_params``."""
+    _fields_ = [("n_stgcn", C.c_int), ("n_tpcnn", C.c_int), ("input_feat", C.c_int), ("output_feat", C.c_int),
+                ("seq_len", C.c_int), ("pred_seq_len", C.c_int), ("kernel_size", C.c_int),
+                ("split", (C.c_float * DMRGCN_BINS) * 2), ("st_dmrgcns", DMRGCNLayer * DMRGCN_MAX_STGCN),
+                ("tpcnns", DMRGCNTpcnn * DMRGCN_MAX_TPCNN)]
 
 
 STATE_BYTES = C.sizeof(KMeansState)

@@ -608,6 +608,54 @@ def gpgraph_stgcnn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_deta
     return out
 
 
+# ------------------------------------------------------------------------------ DMRGCN predictor (inference)
+def _dmrgcn_ws(params, n, max_n, dev):
+    nbytes = L.lib().et_dmrgcn_workspace_bytes(C.byref(params), n, max_n)
+    return (torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None), nbytes
+
+
+def dmrgcn_forward_graph(model, v, a):
+    """``model`` (:class:`eigentrajectory_amd.dmrgcn.SocialDMRGCN`, eval mode) on one scene as the dmrgcn bridge hands it
+    over: v (1, 1, K, N), a (1, 2, K, N, N) = [A_disp, A_dist], read as given -> the raw output (1, S, k, N).  One launch."""
+    params, dev = model.et_params()
+    K, k, S = params.seq_len, params.pred_seq_len, params.output_feat
+    n = v.shape[-1]
+    if tuple(v.shape) != (1, 1, K, n) or tuple(a.shape) != (1, 2, K, n, n):
+        raise ValueError(f"dmrgcn_forward_graph: v {tuple(v.shape)} / a {tuple(a.shape)} are not (1,1,{K},N) / (1,2,{K},N,N)")
+    v, a = _dev_args(dev, v, a)
+    out = torch.empty((1, S, k, n), device=dev)
+    ws, nbytes = _dmrgcn_ws(params, n, n, dev)
+    L.call("et_dmrgcn_forward_graph", C.byref(params), L.ptr(v), L.ptr(a), n, L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
+    return out
+
+
+def dmrgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
+    """The dmrgcn bridge + ``model`` (eval mode) + the post-hook for every scene of a split in ONE launch: C_obs (k, N) and
+    nrm (4, N) of :func:`norm_project` (rows 0-1: the last observed positions, centred here per scene), ``scene_sizes``
+    pedestrians per scene in row order (None = one scene; an empty list takes N = 0) -> C_pred_refine (k, N, S).  With
+    ``want_details`` also a dict: ``graph_inputs`` (K, N), the fp32 v = [C_obs; obs_ori] the kernel used."""
+    params, dev = model.et_params()
+    C_obs, nrm = _dev_args(dev, C_obs, nrm)
+    k, n = C_obs.shape
+    if k != params.pred_seq_len or nrm.dim() != 2 or nrm.shape[0] < 2 or nrm.shape[1] != n:
+        raise ValueError(f"dmrgcn_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
+                         f"k = {params.pred_seq_len}")
+    if scene_sizes is not None:
+        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
+        if not sizes and n:
+            raise ValueError(f"dmrgcn_forward_scenes: no scenes for {n} rows")
+        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
+        max_n = max(sizes, default=0)
+    else:
+        sizes, off, max_n = None, None, n
+    out = torch.empty((k, n, params.output_feat), device=dev)
+    gin = torch.empty((params.seq_len, n), device=dev) if want_details else None
+    ws, nbytes = _dmrgcn_ws(params, n, max_n, dev)
+    L.call("et_dmrgcn_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
+           0 if off is None else len(sizes), L.ptr(out), L.ptr(gin), L.ptr(ws), nbytes, L.stream(dev))
+    return (out, {"graph_inputs": gin}) if want_details else out
+
+
 # ----------------------------------------------------------------------- curve fitting
 def curve_fit_batch(trajs, bases, steps=100000, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, want_cp=False, want_loss=False):
     """CurveModel/curve_fitting.py for a batch of fits: fit f fits basis ``bases[f]`` (T_f, ncp_f) to every trajectory of

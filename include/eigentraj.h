@@ -518,6 +518,72 @@ int et_gpgraph_stgcnn_forward_scenes(const et_gpgraph_stgcnn_params *params, con
                                      float *C_pred_refine, int32_t *group_index, float *dist, float *graph_inputs,
                                      void *workspace, size_t workspace_bytes, et_stream_t stream);
 
+/* ---- DMRGCN predictor, inference (baseline/dmrgcn: bridge.py pre-hook + social_dmrgcn.forward + post-hook) -------------
+ * Eval mode only (no drop_edge, no dropout); the network has no BatchNorm.  The parameters are read in place from the
+ * module's own tensors through the pointer tables below (fp32, contiguous).  Field <-> state_dict name (i = st_dmrgcn
+ * block, r = relation 0 displacement / 1 distance, j = tpcnn block, m = 0, 1):
+ *   st_dmrgcns[i].gcn_w[r] / gcn_b[r]   st_dmrgcns.{i}.gcns.{r}.conv.weight (5 S, C_in, 1, 1) / .bias (5 S): channel b S + c
+ *   st_dmrgcns[i].tcn_prelu             st_dmrgcns.{i}.tcn.0.weight (1)
+ *   st_dmrgcns[i].tcn_w / tcn_b         st_dmrgcns.{i}.tcn.1.weight (S, S, 3, 1) / .bias (S)
+ *   st_dmrgcns[i].res_w / res_b         st_dmrgcns.{i}.residual.0.weight (S, C_in, 1, 1) / .bias (S); NULL when C_in == S
+ *   st_dmrgcns[i].prelu                 st_dmrgcns.{i}.prelu.weight (1)
+ *   tpcnns[j].conv_w[m] / conv_b[m]     tpcnns.{j}.tpcn.{m}.0.weight (k, m == 0 && j == 0 ? K : k, 3, 3) / .bias (k)
+ *   tpcnns[j].conv_a[m]                 tpcnns.{j}.tpcn.{m}.1.weight (1)
+ *   tpcnns[j].gta_w / gta_b / gta_a     tpcnns.{j}.gtacn.0.0.weight (S, S, k, 1) / .bias (S), gtacn.0.1.weight (1)
+ *   tpcnns[j].res_w / res_b             tpcnns.0.residual.0.weight (k, K, 1, 1) / .bias (k); NULL for j > 0 (identity)
+ * with K = seq_len, k = pred_seq_len, S = output_feat, C_in = 1 in block 0 and S afterwards.  `split` holds the two
+ * disentangling scale sets, which the reference keeps as constructor constants ([0, 1/4, 2/4, 3/4, 1] for the
+ * displacement relation, [0, 1/2, 1, 2, 4] for the distance relation); 1e10 closes the last bin.
+ * Supported: input_feat = 1, kernel_size = 3, seq_len = pred_seq_len + 2, 1 <= pred_seq_len <= ET_MAX_K,
+ * 1 <= output_feat <= 64, 1 <= n_stgcn <= ET_DMRGCN_MAX_STGCN, 1 <= n_tpcnn <= ET_DMRGCN_MAX_TPCNN, ET_DMRGCN_BINS
+ * bins per relation with 0 <= split[r][0] < split[r][1] < ... < 1e10; anything else: ET_ERR_UNSUPPORTED.  A missing
+ * pointer: ET_ERR_INVALID_ARG.
+ *
+ * The graphs (bridge.py:4-19, dmrgcn.py:12-35): A_dist[t,i,j] = |v[t,i] - v[t,j]|, A_disp the same on v_rel (v_rel[0] = 0,
+ * v_rel[t] = v[t] - v[t-1]); bin b of relation r is the indicator of the OPEN interval split[r][b] < A < split[r][b+1] --
+ * a distance equal to a split value is in no bin, nor is 0 (the diagonal); per (r, b, t): L = I - D^-1/2 (A_b + I) D^-1/2
+ * with D = rowsum(A_b + I) >= 1.  The decisions are fp32 comparisons of fp32 distances: exactly the reference's.
+ *   et_dmrgcn_forward_graph   one scene as the bridge hands it over: v (1,1,K,N), a (1,2,K,N,N) = [A_disp, A_dist], read
+ *                             as given -> out (1,S,k,N), the network's raw output v.  N <= ET_SCENE_MAX_N.
+ *   et_dmrgcn_forward_scenes  a whole split: C_obs (k,N), nrm (4,N) of et_norm_project; per scene v = [C_obs; nrm[0:2] -
+ *                             their mean over the scene], summed in et_scene_project's order; v_rel and the distances
+ *                             are formed where they are used, the (2,5,K,n,n) stacks are never stored -> C_pred_refine
+ *                             (k,N,S).  scene_offsets as et_traj_metrics (NULL = one scene of N rows); n_scenes = 0
+ *                             takes N = 0 only.  Optional output graph_inputs (K,N) float (may be NULL): the fp32 v the
+ *                             kernel used, scene s at columns [off[s], off[s+1]).  One launch.
+ * Workspace: a scene whose activations fit a workgroup's LDS arena (at S = 20, k = 6: up to 26 pedestrians) needs none;
+ * larger ones use workspace rows [off[s], off[s+1]) of et_dmrgcn_workspace_bytes(p, N, max_scene_n) bytes (0 when a
+ * scene of max_scene_n pedestrians fits the arena).  A scene larger than ET_SCENE_MAX_N, or one that fits neither, is
+ * not computed: its outputs are NaN.  No host synchronisation, no allocation: the calls can be captured in a graph.
+ * Every sum has a fixed order: a scene's result does not depend on the scenes around it or on where its arena lies. */
+#define ET_DMRGCN_MAX_STGCN 4
+#define ET_DMRGCN_MAX_TPCNN 8
+#define ET_DMRGCN_BINS 5
+typedef struct et_dmrgcn_layer {
+    const float *gcn_w[2], *gcn_b[2];
+    const float *tcn_prelu;
+    const float *tcn_w, *tcn_b;
+    const float *res_w, *res_b;
+    const float *prelu;
+} et_dmrgcn_layer;
+typedef struct et_dmrgcn_tpcnn {
+    const float *conv_w[2], *conv_b[2], *conv_a[2];
+    const float *gta_w, *gta_b, *gta_a;
+    const float *res_w, *res_b;
+} et_dmrgcn_tpcnn;
+typedef struct et_dmrgcn_params {
+    int n_stgcn, n_tpcnn, input_feat, output_feat, seq_len, pred_seq_len, kernel_size;
+    float split[2][ET_DMRGCN_BINS];
+    et_dmrgcn_layer st_dmrgcns[ET_DMRGCN_MAX_STGCN];
+    et_dmrgcn_tpcnn tpcnns[ET_DMRGCN_MAX_TPCNN];
+} et_dmrgcn_params;
+size_t et_dmrgcn_workspace_bytes(const et_dmrgcn_params *params, int64_t N, int64_t max_scene_n);
+int et_dmrgcn_forward_graph(const et_dmrgcn_params *params, const float *v, const float *a, int64_t N, float *out,
+                            void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_dmrgcn_forward_scenes(const et_dmrgcn_params *params, const float *C_obs, const float *nrm, int64_t N,
+                             const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *graph_inputs,
+                             void *workspace, size_t workspace_bytes, et_stream_t stream);
+
 /* ---- fit ----------------------------------------------------------------------------
  * Gram matrices of the normalised trajectories routed to descriptor `which`
  * (1 moving / 0 static) under `mode`:  G_obs (2T_obs,2T_obs), G_pred (2T_pred,2T_pred)
