@@ -13,7 +13,10 @@ from .kmeans import BatchKMeans
 from .stgcnn import SocialSTGCNN
 from .sgcn import SGCN
 from .dmrgcn import SocialDMRGCN
+from .pecnet import PECNet
+from .lbebm import LBEBM
 from .gpgraph import GPGraph, GPGraphSGCN, GPGraphSTGCNN, get_GPGraph_SGCN_model, get_GPGraph_STGCNN_model
 
 __all__ = ["EigenTrajectory", "TrajNorm", "ETDescriptor", "ETAnchor", "BatchKMeans", "SocialSTGCNN", "SGCN", "GPGraph",
-           "GPGraphSGCN", "get_GPGraph_SGCN_model", "GPGraphSTGCNN", "get_GPGraph_STGCNN_model", "SocialDMRGCN"]
+           "GPGraphSGCN", "get_GPGraph_SGCN_model", "GPGraphSTGCNN", "get_GPGraph_STGCNN_model", "SocialDMRGCN", "PECNet",
+           "LBEBM"]

@@ -98,6 +98,13 @@ SIGNATURES = {
     "et_dmrgcn_workspace_bytes": (_Z, [_P, _I64, _I64]),
     "et_dmrgcn_forward_graph": (_I, [_P, _P, _P, _I64, _P, _P, _Z, _P]),
     "et_dmrgcn_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _Z, _P]),
+    # ---- PECNet / LBEBM predictors, inference
+    "et_pecnet_workspace_bytes": (_Z, [_P, _I64]),
+    "et_pecnet_predict": (_I, [_P, _P, _P, _P, _P, _I64, _P, _P, _Z, _P]),
+    "et_pecnet_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _Z, _P]),
+    "et_lbebm_workspace_bytes": (_Z, [_P, _I64]),
+    "et_lbebm_predict": (_I, [_P, _P, _P, _I64, _P, _P, _Z, _P]),
+    "et_lbebm_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _Z, _P]),
     # ---- fit
     "et_fit_gram_workspace_bytes": (_Z, [_I64, _I, _I]),
     "et_fit_gram": (_I, [_P, _P, _I64, _I, _I, _I, _F, _I, _P, _P, _P, _P, _Z, _P]),
@@ -256,6 +263,25 @@ class DMRGCNParams(C.Structure):
                 ("seq_len", C.c_int), ("pred_seq_len", C.c_int), ("kernel_size", C.c_int),
                 ("split", (C.c_float * DMRGCN_BINS) * 2), ("st_dmrgcns", DMRGCNLayer * DMRGCN_MAX_STGCN),
                 ("tpcnns", DMRGCNTpcnn * DMRGCN_MAX_TPCNN)]
+
+
+MLP_MAX_LAYERS = 5    # ET_MLP_MAX_LAYERS
+MLP_MAX_WIDTH = 1024  # ET_MLP_MAX_WIDTH
+MLP_MAX_POOLS = 8     # ET_MLP_MAX_POOLS
+MLP_MAX_RANGE = 4096  # ET_MLP_MAX_RANGE
+
+
+class MLPChain(C.Structure):
+    """Mirror of ``et_mlp_chain``: one chain of Linear + ReLU, device pointers to its weights and biases."""
+    _fields_ = [("n_layers", C.c_int), ("widths", C.c_int * (MLP_MAX_LAYERS + 1)), ("w", C.c_void_p * MLP_MAX_LAYERS),
+                ("b", C.c_void_p * MLP_MAX_LAYERS)]
+
+
+class MLPParams(C.Structure):
+    """Mirror of ``et_mlp_params`` (PECNet and LBEBM)."""
+    _fields_ = [("fdim", C.c_int), ("nonlocal_pools", C.c_int), ("non_local_dim", C.c_int), ("out_width", C.c_int),
+                ("pos_width", C.c_int)] + [(name, MLPChain) for name in (
+                    "encoder_past", "encoder_dest", "non_local_theta", "non_local_phi", "non_local_g", "predictor")]
 
 
 STATE_BYTES = C.sizeof(KMeansState)

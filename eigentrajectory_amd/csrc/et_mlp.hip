@@ -1,0 +1,497 @@
+// et_mlp.hip -- PECNet / LBEBM inference (baseline/pecnet, baseline/lbebm: the bridges' hooks and the two predict bodies;
+// include/eigentraj.h "PECNet / LBEBM predictors").  Two kernels:
+//
+// mlp_chain_kernel   a workgroup takes kMlRows = 16 rows through ALL layers of one chain of Linear + ReLU.  The activations
+//   ping-pong between two LDS images of (16, kMlStride) floats; the weights W (out, in) are read in place from global memory
+//   (L2: every workgroup reads the same tensors).  A wavefront owns 16-column blocks of a layer's output, two at a time (two
+//   independent accumulators hide the MFMA's dependent latency), and forms them with v_mfma_f32_16x16x4_f32: A = the
+//   activations (lane l: row l & 15, k = k0 + (l >> 4)), B = W^T (lane l: k = k0 + (l >> 4), column l & 15), D row
+//   4 (l >> 4) + r, column l & 15.  The instruction is a k-ordered fp32 fmaf chain, the loop runs k0 ascending from a zero
+//   accumulator and the bias is added last, so an output element's value depends on its input row and the layer's shape
+//   only -- not on the row's place in the tile, the tile, or the number of rows.  Rows past N, the columns in .. up4(in) of
+//   every image and the weights read for them are written / taken as zeros, and a block's columns past `out` are stored
+//   as zeros, so nothing uninitialised is ever multiplied.  blockIdx.y picks one of up to three chains of the launch; the
+//   first layer gathers its input from up to three sources side by side (element (row, c) at p[row rs + c cs]).
+//   In the scene form the encoder_dest chain's workgroups form their rows' obs_ori themselves (the scene's mean in
+//   scene_v's summation order), use it as their input and store it for the later launches and the caller.
+// nonlocal_pool_kernel   one wavefront per row: the row's logits against every phi row of its range (fp32 fmaf, ascending),
+//   softmax over the whole range, times the mask, / max(sum |w|, 1e-12), times g, + feat.  The range is the row's scene
+//   (or all N rows in the module form); a range longer than ET_MLP_MAX_RANGE is not computed: its rows are NaN.
+#include "et_common.h"
+
+namespace et {
+namespace {
+
+#include "et_scene_helpers.inl"  // scene_of_row, up4, kSnThreads
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kMlThreads = kSnThreads;
+constexpr int kMlWaves = kMlThreads / kWave;
+constexpr int kMlRows = 16;
+constexpr int kMlStride = ET_MLP_MAX_WIDTH + 4;  // row r of an image starts at bank 4 r: the 64 lanes of an A read hit 64 banks
+constexpr int kMlLdsBytes = 2 * kMlRows * kMlStride * 4;
+constexpr int kMlMaxJobs = 3;
+constexpr int kAtRows = kMlWaves;  // rows per workgroup of the pooling kernel, one per wavefront
+constexpr int kAtLdsBytes = kAtRows * ET_MLP_MAX_RANGE * 4;
+
+struct MlSrc {
+    const float *p;
+    int width;
+    int64_t rs, cs;  // element (row, c) = p[row * rs + c * cs]
+};
+
+struct MlJob {
+    int n_layers, n_src;
+    int widths[ET_MLP_MAX_LAYERS + 1];
+    const float *w[ET_MLP_MAX_LAYERS], *b[ET_MLP_MAX_LAYERS];
+    MlSrc src[3];
+    float *out;
+    int out_s;  // element (row, col) of the last layer at out[(col / out_s) N out_s + row out_s + col % out_s]
+};
+
+// the scene form's first launch: the workgroups of job 1 (encoder_dest) centre their rows
+struct MlScene {
+    const float *C_obs, *nrm;
+    const int32_t *off;
+    int n_scenes, k;
+    float *pos;  // (N, 2) obs_ori
+    float *gin;  // (k + 2, N) or null
+};
+
+struct MlLaunch {
+    MlJob job[kMlMaxJobs];
+    MlScene sc;
+    int64_t N;
+};
+
+// the range [b, e) of row r: its scene, or all rows; offsets outside [0, N] are clamped
+__device__ __forceinline__ void range_of_row(const int32_t *off, int n_scenes, int64_t N, int64_t r, int &s, int64_t &b,
+                                             int64_t &e) {
+    if (!off) {
+        s = 0, b = 0, e = N;
+        return;
+    }
+    s = scene_of_row(off, n_scenes, r);
+    b = min((int64_t)max(off[s], 0), N);
+    e = min((int64_t)max(off[s + 1], 0), N);
+    if (e < b) e = b;
+}
+
+__device__ __forceinline__ float gather(const MlSrc *src, int n_src, int64_t row, int c) {
+    for (int s = 0; s < n_src; ++s) {
+        if (c < src[s].width) return src[s].p[row * src[s].rs + c * src[s].cs];
+        c -= src[s].width;
+    }
+    return 0.f;
+}
+
+__global__ __launch_bounds__(kMlThreads) void mlp_chain_kernel(MlLaunch L) {
+    extern __shared__ float lds[];
+    __shared__ float red[2 * kMlWaves];
+    const MlJob &J = L.job[blockIdx.y];
+    const int64_t N = L.N, row0 = (int64_t)blockIdx.x * kMlRows;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    float *cur = lds, *nxt = lds + kMlRows * kMlStride;
+
+    if (L.sc.nrm && blockIdx.y == 1) {
+        // obs_ori of the tile's rows: a scene's mean once per run of rows of that scene, in scene_v's order
+        const MlScene &S = L.sc;
+        int prev = -1;
+        float mx = 0.f, my = 0.f;
+        for (int i = 0; i < kMlRows; ++i) {
+            const int64_t row = row0 + i;
+            if (row >= N) {
+                if (tid < 4) cur[i * kMlStride + tid] = 0.f;
+                continue;
+            }
+            int s;
+            int64_t b, e;
+            range_of_row(S.off, S.n_scenes, N, row, s, b, e);
+            if (s != prev) {
+                prev = s;
+                const int n = (int)(e - b);
+                float sx = 0.f, sy = 0.f;
+                for (int w = tid; w < n; w += kMlThreads) {
+                    sx += S.nrm[b + w];
+                    sy += S.nrm[N + b + w];
+                }
+                for (int o = 32; o > 0; o >>= 1) {
+                    sx += __shfl_xor(sx, o);
+                    sy += __shfl_xor(sy, o);
+                }
+                __syncthreads();  // the previous scene's partials have been read
+                if (lane == 0) {
+                    red[wave] = sx;
+                    red[kMlWaves + wave] = sy;
+                }
+                __syncthreads();
+                mx = 0.f, my = 0.f;
+                for (int w = 0; w < kMlWaves; ++w) {
+                    mx += red[w];
+                    my += red[kMlWaves + w];
+                }
+                mx = mx / (float)n;
+                my = my / (float)n;
+            }
+            if (tid == 0) {
+                const float ox = S.nrm[row] - mx, oy = S.nrm[N + row] - my;
+                float *c = cur + i * kMlStride;
+                c[0] = ox, c[1] = oy, c[2] = 0.f, c[3] = 0.f;
+                S.pos[row * 2] = ox, S.pos[row * 2 + 1] = oy;
+                if (S.gin) S.gin[(int64_t)S.k * N + row] = ox, S.gin[(int64_t)(S.k + 1) * N + row] = oy;
+            }
+            if (S.gin)
+                for (int c = tid; c < S.k; c += kMlThreads) S.gin[(int64_t)c * N + row] = S.C_obs[(int64_t)c * N + row];
+        }
+    } else {
+        const int in = J.widths[0], inp = (int)up4(in);
+        for (int idx = tid; idx < kMlRows * inp; idx += kMlThreads) {
+            const int i = idx / inp, c = idx - i * inp;
+            const int64_t row = row0 + i;
+            cur[i * kMlStride + c] = (row < N && c < in) ? gather(J.src, J.n_src, row, c) : 0.f;
+        }
+    }
+    __syncthreads();
+
+    const int col = lane & 15, kq = lane >> 4;
+    for (int l = 0; l < J.n_layers; ++l) {
+        const int in = J.widths[l], out = J.widths[l + 1];
+        const bool last = l + 1 == J.n_layers;
+        const float *__restrict__ W = J.w[l], *__restrict__ B = J.b[l];
+        const int nblk = (out + 15) / 16;
+        const float *ar = cur + col * kMlStride + kq;  // A: row `col` of the tile, k = k0 + kq
+        for (int blk = wave; blk < nblk; blk += 2 * kMlWaves) {
+            const int j0 = blk * 16 + col, j1 = (blk + kMlWaves) * 16 + col;
+            const bool ok0 = j0 < out, ok1 = j1 < out;
+            const float *w0 = W + (int64_t)(ok0 ? j0 : 0) * in + kq, *w1 = W + (int64_t)(ok1 ? j1 : 0) * in + kq;
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+            const int inm = in & ~3;  // whole k steps; the weights of a block past `out` are read from row 0 and dropped
+            int k0 = 0;
+            for (; k0 + 16 <= inm; k0 += 16) {  // four steps' operands in flight, then the products in k order
+                float a[4], t0[4], t1[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) a[u] = ar[k0 + 4 * u], t0[u] = w0[k0 + 4 * u], t1[u] = w1[k0 + 4 * u];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], ok0 ? t0[u] : 0.f, acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], ok1 ? t1[u] : 0.f, acc1, 0, 0, 0);
+                }
+            }
+            for (; k0 < inm; k0 += 4) {
+                const float a = ar[k0], t0 = w0[k0], t1 = w1[k0];
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, ok0 ? t0 : 0.f, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, ok1 ? t1 : 0.f, acc1, 0, 0, 0);
+            }
+            if (inm < in) {  // the last, partial step: the image holds zeros in columns in .. inp
+                const bool kok = inm + kq < in;
+                const float a = ar[inm];
+                const float b0 = (ok0 && kok) ? w0[inm] : 0.f, b1 = (ok1 && kok) ? w1[inm] : 0.f;
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b1, acc1, 0, 0, 0);
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int j = h ? j1 : j0;
+                const bool ok = h ? ok1 : ok0;
+                if ((h ? blk + kMlWaves : blk) >= nblk) continue;
+                const f32x4 acc = h ? acc1 : acc0;
+                const float bias = ok ? B[j] : 0.f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int i = 4 * kq + r;
+                    float v = acc[r] + bias;
+                    if (!last) {
+                        v = v < 0.f ? 0.f : v;  // ReLU; a NaN stays a NaN
+                        nxt[i * kMlStride + j] = ok ? v : 0.f;  // j < 16 nblk <= ET_MLP_MAX_WIDTH: inside the row
+                    } else if (ok && row0 + i < N) {
+                        J.out[(int64_t)(j / J.out_s) * N * J.out_s + (row0 + i) * J.out_s + j % J.out_s] = v;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        float *t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+}
+
+struct AtLaunch {
+    const float *theta, *phi, *g;  // (N, D), (N, D), (N, F)
+    int D, F, n_src;
+    MlSrc src[3];       // feat (N, F), gathered
+    const float *mask;  // (N, N) or null
+    const int32_t *off;
+    int n_scenes;
+    int64_t N;
+    float *out;  // (N, F)
+};
+
+__global__ __launch_bounds__(kMlThreads) void nonlocal_pool_kernel(AtLaunch A) {
+    extern __shared__ float lds[];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const int64_t N = A.N, row = (int64_t)blockIdx.x * kAtRows + wave;
+    float *lg = lds + wave * ET_MLP_MAX_RANGE;
+    int s = 0;
+    int64_t b = 0, e = 0;
+    if (row < N) range_of_row(A.off, A.n_scenes, N, row, s, b, e);
+    const bool fits = e - b <= ET_MLP_MAX_RANGE;
+    const int n = (row < N && fits) ? (int)(e - b) : 0;
+    const int D = A.D, F = A.F;
+
+    const float *th = A.theta + row * D;
+    float m = -INFINITY;
+    for (int j = lane; j < n; j += kWave) {
+        const float *ph = A.phi + (b + j) * D;
+        float acc = 0.f;
+        for (int c = 0; c < D; ++c) acc = fmaf(th[c], ph[c], acc);
+        lg[j] = acc;
+        m = fmaxf(m, acc);
+    }
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    float z = 0.f;
+    for (int j = lane; j < n; j += kWave) {
+        const float ex = expf(lg[j] - m);
+        lg[j] = ex;
+        z += ex;
+    }
+    for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o);
+    float l1 = 0.f;
+    for (int j = lane; j < n; j += kWave) {
+        float w = lg[j] / z;
+        if (A.mask) w = w * A.mask[row * N + b + j];
+        lg[j] = w;
+        l1 += fabsf(w);
+    }
+    for (int o = 32; o > 0; o >>= 1) l1 += __shfl_xor(l1, o);
+    const float den = fmaxf(l1, 1e-12f);
+    for (int j = lane; j < n; j += kWave) lg[j] = lg[j] / den;
+    __syncthreads();  // (every wavefront gets here: no early exit above) the row's weights are in LDS
+    if (row < N) {
+        for (int c = lane; c < F; c += kWave) {
+            float acc = 0.f;
+            for (int j = 0; j < n; ++j) acc = fmaf(lg[j], A.g[(b + j) * F + c], acc);
+            A.out[row * F + c] = fits ? acc + gather(A.src, A.n_src, row, c) : __builtin_nanf("");
+        }
+    }
+}
+
+static int chain_check(const et_mlp_chain &c, int in, int out) {
+    if (c.n_layers < 2 || c.n_layers > ET_MLP_MAX_LAYERS) return ET_ERR_UNSUPPORTED;
+    for (int i = 0; i <= c.n_layers; ++i)
+        if (c.widths[i] < 1 || c.widths[i] > ET_MLP_MAX_WIDTH) return ET_ERR_UNSUPPORTED;
+    if (c.widths[0] != in || c.widths[c.n_layers] != out) return ET_ERR_UNSUPPORTED;
+    for (int i = 0; i < c.n_layers; ++i)
+        if (!c.w[i] || !c.b[i]) return ET_ERR_INVALID_ARG;
+    return ET_OK;
+}
+
+// the feature width: ftraj | dest features | initial_pos
+static int feat_width(const et_mlp_params &p) { return 2 * p.fdim + p.pos_width; }
+
+static int ml_check_params(const et_mlp_params *p, bool pecnet) {
+    if (!p) return ET_ERR_INVALID_ARG;
+    if (p->fdim < 1 || p->fdim > ET_MLP_MAX_WIDTH || p->out_width < 1 || p->pos_width != (pecnet ? 2 : 0) ||
+        p->nonlocal_pools < 0 || p->nonlocal_pools > (pecnet ? ET_MLP_MAX_POOLS : 0))
+        return ET_ERR_UNSUPPORTED;
+    const int F = feat_width(*p);
+    if (F > ET_MLP_MAX_WIDTH) return ET_ERR_UNSUPPORTED;
+    int rc = chain_check(p->encoder_past, p->encoder_past.widths[0], p->fdim);
+    if (rc == ET_OK) rc = chain_check(p->encoder_dest, p->encoder_dest.widths[0], p->fdim);
+    if (rc == ET_OK) rc = chain_check(p->predictor, F, p->out_width);
+    if (rc == ET_OK && p->nonlocal_pools > 0) {
+        if (p->non_local_dim < 1) return ET_ERR_UNSUPPORTED;
+        rc = chain_check(p->non_local_theta, F, p->non_local_dim);
+        if (rc == ET_OK) rc = chain_check(p->non_local_phi, F, p->non_local_dim);
+        if (rc == ET_OK) rc = chain_check(p->non_local_g, F, F);
+    }
+    return rc;
+}
+
+// the workspace, in floats: every block starts on a multiple of 4
+struct MlWs {
+    int64_t ftraj, dfeat, pos, theta, phi, g, feat[2], total;
+};
+
+static MlWs ml_workspace(const et_mlp_params &p, int64_t N) {
+    MlWs w{};
+    int64_t at = 0;
+    auto take = [&](int64_t width) {
+        const int64_t here = at;
+        at += up4(N * width);
+        return here;
+    };
+    const int F = feat_width(p);
+    w.ftraj = take(p.fdim);
+    w.dfeat = take(p.fdim);
+    w.pos = take(2);
+    if (p.nonlocal_pools > 0) {
+        w.theta = take(p.non_local_dim);
+        w.phi = take(p.non_local_dim);
+        w.g = take(F);
+        w.feat[0] = take(F);
+        w.feat[1] = take(F);
+    }
+    w.total = at;
+    return w;
+}
+
+static void job_of(MlJob &j, const et_mlp_chain &c, float *out, int out_s) {
+    j.n_layers = c.n_layers;
+    for (int i = 0; i <= c.n_layers; ++i) j.widths[i] = c.widths[i];
+    for (int i = 0; i < c.n_layers; ++i) j.w[i] = c.w[i], j.b[i] = c.b[i];
+    j.out = out;
+    j.out_s = out_s;
+}
+
+static MlSrc rows_of(const float *p, int width) { return MlSrc{p, width, width, 1}; }
+
+static int lds_attributes() {
+    static PerDevice<bool> lds_set;
+    bool &ok = lds_set.current();
+    if (ok) return ET_OK;
+    ET_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(mlp_chain_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, kMlLdsBytes));
+    ET_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(nonlocal_pool_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, kAtLdsBytes));
+    ok = true;
+    return ET_OK;
+}
+
+// Both predictors, both forms.  Module form: past / dest / pos given (nrm null).  Scene form: C_obs, nrm (past, dest, pos
+// null); out is then C_pred_refine.  1 + 2 nonlocal_pools + 1 launches.
+static int ml_run(const et_mlp_params &p, const float *past, const float *dest, const float *pos, const float *mask,
+                  const float *C_obs, const float *nrm, const int32_t *off, int n_scenes, int64_t N, float *out,
+                  float *gin, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+    const MlWs W = ml_workspace(p, N);
+    if (!workspace || workspace_bytes < (size_t)W.total * 4) return ET_ERR_WORKSPACE;
+    const int rc = lds_attributes();
+    if (rc != ET_OK) return rc;
+    float *ws = (float *)workspace;
+    const int F = feat_width(p), kp = p.encoder_past.widths[0], kd = p.encoder_dest.widths[0];
+    const unsigned tiles = (unsigned)((N + kMlRows - 1) / kMlRows);
+    const bool scenes = nrm != nullptr;
+
+    MlLaunch L{};
+    L.N = N;
+    job_of(L.job[0], p.encoder_past, ws + W.ftraj, p.fdim);
+    job_of(L.job[1], p.encoder_dest, ws + W.dfeat, p.fdim);
+    L.job[0].n_src = L.job[1].n_src = 1;
+    if (scenes) {
+        L.job[0].src[0] = MlSrc{C_obs, kp, 1, N};  // past = C_obs^T
+        L.sc = MlScene{C_obs, nrm, off, n_scenes, kp, ws + W.pos, gin};
+        pos = ws + W.pos;
+    } else {
+        L.job[0].src[0] = rows_of(past, kp);
+        L.job[1].src[0] = rows_of(dest, kd);
+    }
+    hipLaunchKernelGGL(mlp_chain_kernel, dim3(tiles, 2), dim3(kMlThreads), kMlLdsBytes, stream, L);
+    ET_LAUNCH_CHECK();
+
+    MlSrc feat[3] = {rows_of(ws + W.ftraj, p.fdim), rows_of(ws + W.dfeat, p.fdim), rows_of(pos, p.pos_width)};
+    int n_feat = p.pos_width ? 3 : 2;
+    for (int r = 0; r < p.nonlocal_pools; ++r) {
+        MlLaunch Q{};
+        Q.N = N;
+        job_of(Q.job[0], p.non_local_theta, ws + W.theta, p.non_local_dim);
+        job_of(Q.job[1], p.non_local_phi, ws + W.phi, p.non_local_dim);
+        job_of(Q.job[2], p.non_local_g, ws + W.g, F);
+        for (int j = 0; j < 3; ++j) {
+            Q.job[j].n_src = n_feat;
+            for (int s = 0; s < n_feat; ++s) Q.job[j].src[s] = feat[s];
+        }
+        hipLaunchKernelGGL(mlp_chain_kernel, dim3(tiles, 3), dim3(kMlThreads), kMlLdsBytes, stream, Q);
+        ET_LAUNCH_CHECK();
+        AtLaunch A{};
+        A.theta = ws + W.theta, A.phi = ws + W.phi, A.g = ws + W.g;
+        A.D = p.non_local_dim, A.F = F, A.n_src = n_feat;
+        for (int s = 0; s < n_feat; ++s) A.src[s] = feat[s];
+        A.mask = mask, A.off = off, A.n_scenes = n_scenes, A.N = N;
+        A.out = ws + W.feat[r & 1];
+        hipLaunchKernelGGL(nonlocal_pool_kernel, dim3((unsigned)((N + kAtRows - 1) / kAtRows)), dim3(kMlThreads),
+                           kAtLdsBytes, stream, A);
+        ET_LAUNCH_CHECK();
+        feat[0] = rows_of(A.out, F);
+        n_feat = 1;
+    }
+
+    MlLaunch P{};
+    P.N = N;
+    job_of(P.job[0], p.predictor, out, scenes ? p.out_width / kp : p.out_width);
+    P.job[0].n_src = n_feat;
+    for (int s = 0; s < n_feat; ++s) P.job[0].src[s] = feat[s];
+    hipLaunchKernelGGL(mlp_chain_kernel, dim3(tiles, 1), dim3(kMlThreads), kMlLdsBytes, stream, P);
+    ET_LAUNCH_CHECK();
+    return ET_OK;
+}
+
+static size_t ml_workspace_bytes(const et_mlp_params *p, bool pecnet, int64_t N) {
+    if (ml_check_params(p, pecnet) != ET_OK || N < 0) return 0;
+    return (size_t)ml_workspace(*p, N).total * 4;
+}
+
+static int ml_predict(const et_mlp_params *p, bool pecnet, const float *past, const float *dest, const float *mask,
+                      const float *pos, int64_t N, float *out, void *workspace, size_t workspace_bytes, et_stream_t stream) {
+    const int rc = ml_check_params(p, pecnet);
+    if (rc != ET_OK) return rc;
+    if (N < 0 || N > INT32_MAX) return ET_ERR_INVALID_ARG;
+    if (p->nonlocal_pools > 0 && N > ET_MLP_MAX_RANGE) return ET_ERR_UNSUPPORTED;
+    if (N == 0) return ET_OK;
+    if (!past || !dest || !out || (pecnet && !pos)) return ET_ERR_INVALID_ARG;
+    return ml_run(*p, past, dest, pos, mask, nullptr, nullptr, nullptr, 0, N, out, nullptr, workspace, workspace_bytes,
+                  (hipStream_t)stream);
+}
+
+static int ml_scenes(const et_mlp_params *p, bool pecnet, const float *C_obs, const float *nrm, int64_t N,
+                     const int32_t *off, int n_scenes, float *out, float *gin, void *workspace, size_t workspace_bytes,
+                     et_stream_t stream) {
+    const int rc = ml_check_params(p, pecnet);
+    if (rc != ET_OK) return rc;
+    if (p->encoder_dest.widths[0] != 2 || p->out_width % p->encoder_past.widths[0] != 0) return ET_ERR_UNSUPPORTED;
+    if (N < 0 || N > INT32_MAX || n_scenes < 0) return ET_ERR_INVALID_ARG;
+    if (off && n_scenes == 0) return N == 0 ? ET_OK : ET_ERR_INVALID_ARG;
+    if (!off && N > ET_SCENE_MAX_N) return ET_ERR_INVALID_ARG;
+    if (N == 0) return ET_OK;
+    if (!C_obs || !nrm || !out) return ET_ERR_INVALID_ARG;
+    return ml_run(*p, nullptr, nullptr, nullptr, nullptr, C_obs, nrm, off, n_scenes, N, out, gin, workspace,
+                  workspace_bytes, (hipStream_t)stream);
+}
+
+}  // namespace
+}  // namespace et
+
+using namespace et;
+
+extern "C" size_t et_pecnet_workspace_bytes(const et_mlp_params *params, int64_t N) {
+    return ml_workspace_bytes(params, true, N);
+}
+
+extern "C" int et_pecnet_predict(const et_mlp_params *params, const float *past, const float *dest, const float *mask,
+                                 const float *initial_pos, int64_t N, float *out, void *workspace, size_t workspace_bytes,
+                                 et_stream_t stream) {
+    return ml_predict(params, true, past, dest, mask, initial_pos, N, out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int et_pecnet_forward_scenes(const et_mlp_params *params, const float *C_obs, const float *nrm, int64_t N,
+                                        const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *net_inputs,
+                                        void *workspace, size_t workspace_bytes, et_stream_t stream) {
+    return ml_scenes(params, true, C_obs, nrm, N, scene_offsets, n_scenes, C_pred_refine, net_inputs, workspace,
+                     workspace_bytes, stream);
+}
+
+extern "C" size_t et_lbebm_workspace_bytes(const et_mlp_params *params, int64_t N) {
+    return ml_workspace_bytes(params, false, N);
+}
+
+extern "C" int et_lbebm_predict(const et_mlp_params *params, const float *past, const float *dest, int64_t N, float *out,
+                                void *workspace, size_t workspace_bytes, et_stream_t stream) {
+    return ml_predict(params, false, past, dest, nullptr, nullptr, N, out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int et_lbebm_forward_scenes(const et_mlp_params *params, const float *C_obs, const float *nrm, int64_t N,
+                                       const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *net_inputs,
+                                       void *workspace, size_t workspace_bytes, et_stream_t stream) {
+    return ml_scenes(params, false, C_obs, nrm, N, scene_offsets, n_scenes, C_pred_refine, net_inputs, workspace,
+                     workspace_bytes, stream);
+}

@@ -268,7 +268,8 @@ class EigenTrajectory(nn.Module):
         r"""A whole test split in a fixed number of launches: the projection of every row, the bridge + predictor +
         post-hook of every scene (``et_stgcnn_forward_scenes``: one launch; ``et_sgcn_forward_scenes``: 6 + the number of
         asymmetric convolution layers; ``et_gpgraph_sgcn_forward_scenes``: 8 + that number;
-        ``et_gpgraph_stgcnn_forward_scenes``: three; ``et_dmrgcn_forward_scenes``: one), the reconstruction + metrics of every
+        ``et_gpgraph_stgcnn_forward_scenes``: three; ``et_dmrgcn_forward_scenes``: one; ``et_pecnet_forward_scenes``: 2 + 2
+        nonlocal_pools; ``et_lbebm_forward_scenes``: two), the reconstruction + metrics of every
         scene -- what the reference's test loop (utils/trainer.py:173-195) computes with one :meth:`evaluate` per scene.
 
         ``obs_traj`` (N, t_obs, 2), ``pred_traj`` (N, t_pred, 2): the split's rows, scene after scene; ``seq_start_end``
@@ -277,10 +278,15 @@ class EigenTrajectory(nn.Module):
         ``stgcnn`` hooks, a :class:`~eigentrajectory_amd.sgcn.SGCN` predictor under the ``sgcn`` hooks or a
         :class:`~eigentrajectory_amd.gpgraph.GPGraph` predictor under the hooks of its base (``gpgraphsgcn`` around SGCN,
         ``gpgraphstgcnn`` around SocialSTGCNN) or a :class:`~eigentrajectory_amd.dmrgcn.SocialDMRGCN` predictor under the
-        ``dmrgcn`` hooks, in eval mode; any other predictor or pairing raises (use :meth:`evaluate` scene by scene)."""
+        ``dmrgcn`` hooks, a :class:`~eigentrajectory_amd.pecnet.PECNet` predictor under the ``pecnet`` hooks (every scene
+        under its own all-ones mask, as the reference's test loader hands them over) or a
+        :class:`~eigentrajectory_amd.lbebm.LBEBM` predictor under the ``lbebm`` hooks, in eval mode; any other predictor or
+        pairing raises (use :meth:`evaluate` scene by scene)."""
         from .bridges import BRIDGES
         from .dmrgcn import SocialDMRGCN
         from .gpgraph import GPGraph
+        from .lbebm import LBEBM
+        from .pecnet import PECNet
         from .sgcn import SGCN
         from .stgcnn import SocialSTGCNN
         hooks = self.hook_func
@@ -289,7 +295,9 @@ class EigenTrajectory(nn.Module):
                                            (SGCN, "sgcn", ops.sgcn_forward_scenes, None),
                                            (GPGraph, "gpgraphsgcn", ops.gpgraph_sgcn_forward_scenes, False),
                                            (GPGraph, "gpgraphstgcnn", ops.gpgraph_stgcnn_forward_scenes, True),
-                                           (SocialDMRGCN, "dmrgcn", ops.dmrgcn_forward_scenes, None)):
+                                           (SocialDMRGCN, "dmrgcn", ops.dmrgcn_forward_scenes, None),
+                                           (PECNet, "pecnet", ops.pecnet_forward_scenes, None),
+                                           (LBEBM, "lbebm", ops.lbebm_forward_scenes, None)):
             pre, fwd, post = BRIDGES[name]
             if (isinstance(self.baseline_model, cls) and hooks.model_forward_pre_hook is pre
                     and hooks.model_forward is fwd and hooks.model_forward_post_hook is post
@@ -298,9 +306,10 @@ class EigenTrajectory(nn.Module):
         if forward_scenes is None:
             raise NotImplementedError("evaluate_split: the whole-split path is built for a SocialSTGCNN predictor under the "
                                       "'stgcnn' hooks, an SGCN predictor under the 'sgcn' hooks, a GPGraph predictor under "
-                                      "the hooks of its base ('gpgraphsgcn' around SGCN, 'gpgraphstgcnn' around SocialSTGCNN) "
-                                      "and a SocialDMRGCN predictor under the 'dmrgcn' hooks only; call evaluate() scene by "
-                                      "scene for other predictors")
+                                      "the hooks of its base ('gpgraphsgcn' around SGCN, 'gpgraphstgcnn' around SocialSTGCNN), "
+                                      "a SocialDMRGCN predictor under the 'dmrgcn' hooks, a PECNet predictor under the "
+                                      "'pecnet' hooks and an LBEBM predictor under the 'lbebm' hooks only; call evaluate() "
+                                      "scene by scene for other predictors")
         if self.baseline_model.training:
             raise RuntimeError("evaluate_split: the predictor is in training mode; call .eval() first")
         sse = torch.as_tensor(seq_start_end).detach().cpu().long().reshape(-1, 2)

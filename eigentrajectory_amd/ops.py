@@ -656,6 +656,94 @@ def dmrgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=Fals
     return (out, {"graph_inputs": gin}) if want_details else out
 
 
+# ------------------------------------------------------------------------------ PECNet / LBEBM predictors (inference)
+def _mlp_ws(kind, params, n, dev):
+    nbytes = getattr(L.lib(), f"et_{kind}_workspace_bytes")(C.byref(params), n)
+    return (torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None), nbytes
+
+
+def _mlp_rows(who, dev, width, **tensors):
+    """(N, width_i) float32 rows on ``dev``, all of one N"""
+    out = _dev_args(dev, *tensors.values())
+    n = out[0].shape[0]
+    for (name, _), t, w in zip(tensors.items(), out, width):
+        if t.dim() != 2 or tuple(t.shape) != (n, w):
+            raise ValueError(f"{who}: {name} {tuple(t.shape)} is not ({n}, {w})")
+    return n, out
+
+
+def pecnet_predict(model, past, generated_dest, mask, initial_pos):
+    """``model`` (:class:`eigentrajectory_amd.pecnet.PECNet`, eval mode): past (N, 2 past_length), generated_dest (N, 2),
+    mask (N, N) bool or float32 (None: all ones), initial_pos (N, 2) -> (N, out_width), the reference's ``predict``.
+    2 + 2 nonlocal_pools launches."""
+    params, dev = model.et_params()
+    n, (past, dest, pos) = _mlp_rows("pecnet_predict", dev, (params.encoder_past.widths[0], params.encoder_dest.widths[0], 2),
+                                     past=past, generated_dest=generated_dest, initial_pos=initial_pos)
+    if mask is not None:
+        (mask,) = _dev_args(dev, mask)  # bool -> float32
+        if tuple(mask.shape) != (n, n):
+            raise ValueError(f"pecnet_predict: mask {tuple(mask.shape)} is not ({n}, {n})")
+    out = torch.empty((n, params.out_width), device=dev)
+    ws, nbytes = _mlp_ws("pecnet", params, n, dev)
+    L.call("et_pecnet_predict", C.byref(params), L.ptr(past), L.ptr(dest), L.ptr(mask), L.ptr(pos), n, L.ptr(out), L.ptr(ws),
+           nbytes, L.stream(dev))
+    return out
+
+
+def lbebm_predict(model, past, generated_dest):
+    """``model`` (:class:`eigentrajectory_amd.lbebm.LBEBM`, eval mode): past (N, 2 past_length), generated_dest
+    (N, 2 sub-goals) -> (N, out_width), the reference's ``predict``.  2 launches."""
+    params, dev = model.et_params()
+    n, (past, dest) = _mlp_rows("lbebm_predict", dev, (params.encoder_past.widths[0], params.encoder_dest.widths[0]),
+                                past=past, generated_dest=generated_dest)
+    out = torch.empty((n, params.out_width), device=dev)
+    ws, nbytes = _mlp_ws("lbebm", params, n, dev)
+    L.call("et_lbebm_predict", C.byref(params), L.ptr(past), L.ptr(dest), n, L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
+    return out
+
+
+def _mlp_forward_scenes(kind, model, C_obs, nrm, scene_sizes, want_details):
+    params, dev = model.et_params()
+    C_obs, nrm = _dev_args(dev, C_obs, nrm)
+    k, n = C_obs.shape
+    if k != params.encoder_past.widths[0] or nrm.dim() != 2 or nrm.shape[0] < 2 or nrm.shape[1] != n:
+        raise ValueError(f"{kind}_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
+                         f"k = {params.encoder_past.widths[0]}")
+    if scene_sizes is not None:
+        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
+        if not sizes and n:
+            raise ValueError(f"{kind}_forward_scenes: no scenes for {n} rows")
+        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
+    else:
+        sizes, off = None, None
+    largest = n if sizes is None else max(sizes, default=0)
+    if params.nonlocal_pools > 0 and largest > L.MLP_MAX_RANGE:
+        raise ValueError(f"{kind}_forward_scenes: a scene of {largest} pedestrians is beyond the pooling step's range of "
+                         f"{L.MLP_MAX_RANGE} (ET_MLP_MAX_RANGE)")
+    out = torch.empty((k, n, params.out_width // max(k, 1)), device=dev)
+    gin = torch.empty((k + 2, n), device=dev) if want_details else None
+    ws, nbytes = _mlp_ws(kind, params, n, dev)
+    L.call(f"et_{kind}_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
+           0 if off is None else len(sizes), L.ptr(out), L.ptr(gin), L.ptr(ws), nbytes, L.stream(dev))
+    return (out, {"net_inputs": gin}) if want_details else out
+
+
+def pecnet_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
+    """The pecnet bridge + ``model.predict`` (eval mode) + the post-hook for every scene of a split in 2 + 2 nonlocal_pools
+    launches: C_obs (k, N) and nrm (4, N) of :func:`norm_project` (rows 0-1: the last observed positions, centred here per
+    scene), ``scene_sizes`` pedestrians per scene in row order (None = one scene; an empty list takes N = 0) ->
+    C_pred_refine (k, N, S).  Every scene is its own softmax range under an all-ones mask, as in the reference's test loop
+    (one scene per call); a scene of more than ET_MLP_MAX_RANGE (4096) pedestrians raises ValueError before any launch.  With
+    ``want_details`` also a dict: ``net_inputs`` (k + 2, N), the fp32 [C_obs; obs_ori] used."""
+    return _mlp_forward_scenes("pecnet", model, C_obs, nrm, scene_sizes, want_details)
+
+
+def lbebm_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
+    """The lbebm bridge + ``model.predict`` (eval mode) + the post-hook for every scene of a split in 2 launches; arguments
+    and results as :func:`pecnet_forward_scenes`."""
+    return _mlp_forward_scenes("lbebm", model, C_obs, nrm, scene_sizes, want_details)
+
+
 # ----------------------------------------------------------------------- curve fitting
 def curve_fit_batch(trajs, bases, steps=100000, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, want_cp=False, want_loss=False):
     """CurveModel/curve_fitting.py for a batch of fits: fit f fits basis ``bases[f]`` (T_f, ncp_f) to every trajectory of

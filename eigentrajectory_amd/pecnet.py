@@ -1,0 +1,107 @@
+"""PECNet, the predictor of ET-PECNet (baseline/pecnet/model.py), inference on HIP kernels.
+
+Same constructor signature and the same sub-module / parameter names as the reference (``encoder_past.layers.{i}``,
+``encoder_dest``, ``encoder_latent``, ``decoder``, ``non_local_theta``, ``non_local_phi``, ``non_local_g``, ``predictor``),
+so a reference ET-PECNet checkpoint's ``baseline_model.*`` keys load unchanged (``strict=True``), and the module plugs into
+:class:`eigentrajectory_amd.EigenTrajectory` through the existing ``pecnet`` bridge, which calls ``predict`` only::
+
+    model = EigenTrajectory(PECNet([512, 256], [8, 16], [8, 50], [1024, 512, 1024], [1024, 512, 256], [256, 128, 64],
+                                   [256, 128, 64], [256, 128, 64], 16, 16, 3, 128, 1.3, hp.k // 2,
+                                   hp.k * hp.num_samples // 2 + 1, False), get_hook_func("pecnet"), hp).eval()
+
+``predict(past, generated_dest, mask, initial_pos)`` in eval mode is ``2 + 2 * nonlocal_pools`` launches of
+csrc/et_mlp.hip (8 for the ET configuration): the two encoders side by side; per pooling round theta, phi and g side by
+side, then the attention step; the predictor.  Every Linear runs on the f32-input MFMA in exact fp32.  The pooling follows
+the reference's order: softmax over ALL columns of the row, then the mask, then ``F.normalize(p=1)``.  ``mask`` (N, N) may
+be bool or float32 (it is converted to float32 here); the weights are read in place from this module's tensors.
+``encoder_latent`` and ``decoder`` only hold their tensors: ``forward`` (the CVAE path, random sampling) and a ``predict``
+in training mode raise.  A whole split runs in the same fixed number of launches through
+:meth:`EigenTrajectory.evaluate_split` / :func:`eigentrajectory_amd.ops.pecnet_forward_scenes`.
+Supported family: ``activation='relu'``, ``discrim=False``, ``dropout=-1``, 1 to 4 hidden layers per MLP, widths 1 to 1024,
+``nonlocal_pools`` 0 to 8, up to 4096 rows per ``predict`` call with pooling; other shapes construct, but their use raises.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from . import _lib as L
+
+
+class MLP(nn.Module):
+    """The reference's MLP as a holder of ``layers.{i}`` (``nn.Linear``); the native chain is Linear + ReLU, no activation
+    after the last layer."""
+
+    def __init__(self, input_dim, output_dim, hidden_size=(1024, 512), activation="relu", discrim=False, dropout=-1):
+        super().__init__()
+        dims = [input_dim, *hidden_size, output_dim]
+        self.layers = nn.ModuleList([nn.Linear(dims[i], dims[i + 1]) for i in range(len(dims) - 1)])
+        self.activation = {"relu": nn.ReLU, "sigmoid": nn.Sigmoid}[activation]()
+        self.activation_name, self.discrim, self.dropout = activation, discrim, dropout
+
+    def et_chain(self, chain, who):
+        """Fill the ``et_mlp_chain`` mirror ``chain`` from this module's tensors."""
+        if self.activation_name != "relu" or self.discrim or self.dropout != -1:
+            raise L.ETLibraryError(f"{who}: only activation='relu', discrim=False, dropout=-1 are native "
+                                   f"(got {self.activation_name!r}, {self.discrim}, {self.dropout})")
+        chain.n_layers = len(self.layers)
+        if len(self.layers) > L.MLP_MAX_LAYERS:
+            return  # the library answers ET_ERR_UNSUPPORTED
+        chain.widths[0] = self.layers[0].in_features
+        for i, lin in enumerate(self.layers):
+            chain.widths[i + 1] = lin.out_features
+            chain.w[i], chain.b[i] = lin.weight.data_ptr(), lin.bias.data_ptr()
+
+
+def check_tensors(module, who):
+    """-> the one HIP device every parameter of ``module`` lives on (fp32, contiguous); there is no CPU path"""
+    tensors = list(module.parameters())
+    dev = tensors[0].device
+    if dev.type != "cuda" or any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
+        raise L.ETLibraryError(f"{who}: every parameter must be a contiguous float32 tensor on ONE HIP device "
+                               "(model.cuda()); there is no CPU path")
+    return dev
+
+
+def require_eval(module, who):
+    if module.training:
+        raise RuntimeError(f"{who}: only predict() in eval mode is native (no CVAE, no sampling, no backward pass) -- call "
+                           ".eval() first")
+
+
+class PECNet(nn.Module):
+    """baseline/pecnet/model.py's ``PECNet``: ``predict`` natively in eval mode, everything else a tensor holder."""
+
+    def __init__(self, enc_past_size, enc_dest_size, enc_latent_size, dec_size, predictor_size, non_local_theta_size,
+                 non_local_phi_size, non_local_g_size, fdim, zdim, nonlocal_pools, non_local_dim, sigma, past_length,
+                 future_length, verbose=False):
+        super().__init__()
+        self.fdim, self.zdim, self.nonlocal_pools, self.non_local_dim, self.sigma = fdim, zdim, nonlocal_pools, non_local_dim, sigma
+        self.encoder_past = MLP(past_length * 2, fdim, enc_past_size)
+        self.encoder_dest = MLP(2, fdim, enc_dest_size)
+        self.encoder_latent = MLP(2 * fdim, 2 * zdim, enc_latent_size)
+        self.decoder = MLP(fdim + zdim, 2, dec_size)
+        self.non_local_theta = MLP(2 * fdim + 2, non_local_dim, non_local_theta_size)
+        self.non_local_phi = MLP(2 * fdim + 2, non_local_dim, non_local_phi_size)
+        self.non_local_g = MLP(2 * fdim + 2, 2 * fdim + 2, non_local_g_size)
+        self.predictor = MLP(2 * fdim + 2, 2 * (future_length - 1), predictor_size)
+
+    def et_params(self):
+        """-> (et_mlp_params, device): this module's tensors as the kernels read them (include/eigentraj.h)."""
+        p = L.MLPParams()
+        p.fdim, p.nonlocal_pools, p.non_local_dim, p.pos_width = self.fdim, self.nonlocal_pools, self.non_local_dim, 2
+        p.out_width = self.predictor.layers[-1].out_features
+        for name in ("encoder_past", "encoder_dest", "non_local_theta", "non_local_phi", "non_local_g", "predictor"):
+            getattr(self, name).et_chain(getattr(p, name), f"PECNet.{name}")
+        return p, check_tensors(self, "PECNet")
+
+    def forward(self, *args, **kwargs):
+        raise NotImplementedError("PECNet: only predict() is native; forward() (the CVAE path with its random sampling) is "
+                                  "not implemented")
+
+    def predict(self, past, generated_dest, mask, initial_pos):
+        """past (N, 2 past_length), generated_dest (N, 2), mask (N, N) bool or float32, initial_pos (N, 2) ->
+        (N, 2 (future_length - 1))"""
+        require_eval(self, "PECNet")
+        from . import ops
+        return ops.pecnet_predict(self, past, generated_dest, mask, initial_pos)

@@ -584,6 +584,57 @@ int et_dmrgcn_forward_scenes(const et_dmrgcn_params *params, const float *C_obs,
                              const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *graph_inputs,
                              void *workspace, size_t workspace_bytes, et_stream_t stream);
 
+/* ---- PECNet / LBEBM predictors, inference (baseline/pecnet, baseline/lbebm: bridge.py hooks + predict) ---------------
+ * Both predict bodies are chains of Linear + ReLU (no activation after a chain's last layer) in exact fp32: every product
+ * on the f32-input MFMA, accumulated in fp32 ascending in k, the bias added last.  The weights are read in place from the
+ * module's tensors: chain.w[i] is <chain>.layers.{i}.weight (widths[i+1], widths[i]) row-major, chain.b[i] its bias.
+ *   LBEBM.predict    predictor(encoder_past(past) | encoder_dest(dest))                                  2 launches
+ *   PECNet.predict   the same with initial_pos appended (pos_width = 2) and nonlocal_pools rounds of non-local social
+ *                    pooling in between: feat <- normalize_1(softmax(theta(feat) phi(feat)^T) * mask) g(feat) + feat,
+ *                    the softmax over every column of the row's range BEFORE the mask, normalize_1 the division by
+ *                    max(sum |w|, 1e-12) (an all-zero mask row gives feat back).      2 + 2 nonlocal_pools launches
+ * A launch takes 16 rows per workgroup through ALL layers of a chain (activations in LDS) and runs up to three chains side
+ * by side (encoder_past + encoder_dest; theta + phi + g); the concatenated inputs are gathered, never stored.  An output
+ * element's summation order depends on the layer's shape only: a row's result does not depend on the rows around it.
+ *   et_*_predict          the module form: past (N, encoder_past.widths[0]), dest (N, encoder_dest.widths[0]),
+ *                         initial_pos (N, 2), mask (N, N) float or NULL (all ones), one range of N rows -> out (N, out_width)
+ *   et_*_forward_scenes   a whole split: C_obs (k, N), nrm (4, N) of et_norm_project; past = C_obs^T, dest = initial_pos =
+ *                         obs_ori = nrm[0:2] - their mean over the scene (summed in et_scene_project's order), one softmax
+ *                         range per scene (the reference's test loader: one scene per call, all-ones mask), the post-hook's
+ *                         layout -> C_pred_refine (k, N, out_width / k).  scene_offsets as et_traj_metrics (NULL = one
+ *                         scene); n_scenes = 0 takes N = 0 only.  Optional net_inputs (k + 2, N): the fp32 [C_obs; obs_ori]
+ *                         the call used.  k = encoder_past.widths[0], dest width 2.
+ * Supported: 2 to ET_MLP_MAX_LAYERS Linear layers per chain (1 to 4 hidden), widths 1 to ET_MLP_MAX_WIDTH, nonlocal_pools
+ * 0 to ET_MLP_MAX_POOLS, a softmax range of up to ET_MLP_MAX_RANGE rows (a longer scene's rows are NaN; the module form
+ * with pooling and N beyond it: ET_ERR_UNSUPPORTED); anything else ET_ERR_UNSUPPORTED, before any launch.  The workspace
+ * (et_*_workspace_bytes) holds the activations between launches.  No host synchronisation, no allocation. */
+#define ET_MLP_MAX_LAYERS 5
+#define ET_MLP_MAX_WIDTH 1024
+#define ET_MLP_MAX_POOLS 8
+#define ET_MLP_MAX_RANGE 4096
+typedef struct et_mlp_chain {
+    int n_layers;
+    int widths[ET_MLP_MAX_LAYERS + 1];
+    const float *w[ET_MLP_MAX_LAYERS], *b[ET_MLP_MAX_LAYERS];
+} et_mlp_chain;
+typedef struct et_mlp_params {
+    int fdim, nonlocal_pools, non_local_dim, out_width, pos_width;
+    et_mlp_chain encoder_past, encoder_dest, non_local_theta, non_local_phi, non_local_g, predictor;
+} et_mlp_params;
+size_t et_pecnet_workspace_bytes(const et_mlp_params *params, int64_t N);
+int et_pecnet_predict(const et_mlp_params *params, const float *past, const float *dest, const float *mask,
+                      const float *initial_pos, int64_t N, float *out, void *workspace, size_t workspace_bytes,
+                      et_stream_t stream);
+int et_pecnet_forward_scenes(const et_mlp_params *params, const float *C_obs, const float *nrm, int64_t N,
+                             const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *net_inputs,
+                             void *workspace, size_t workspace_bytes, et_stream_t stream);
+size_t et_lbebm_workspace_bytes(const et_mlp_params *params, int64_t N);
+int et_lbebm_predict(const et_mlp_params *params, const float *past, const float *dest, int64_t N, float *out,
+                     void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_lbebm_forward_scenes(const et_mlp_params *params, const float *C_obs, const float *nrm, int64_t N,
+                            const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *net_inputs,
+                            void *workspace, size_t workspace_bytes, et_stream_t stream);
+
 /* ---- fit ----------------------------------------------------------------------------
  * Gram matrices of the normalised trajectories routed to descriptor `which`
  * (1 moving / 0 static) under `mode`:  G_obs (2T_obs,2T_obs), G_pred (2T_pred,2T_pred)
