@@ -15,8 +15,9 @@ from .sgcn import SGCN
 from .dmrgcn import SocialDMRGCN
 from .pecnet import PECNet
 from .lbebm import LBEBM
+from .implicit import SocialImplicitLight
 from .gpgraph import GPGraph, GPGraphSGCN, GPGraphSTGCNN, get_GPGraph_SGCN_model, get_GPGraph_STGCNN_model
 
 __all__ = ["EigenTrajectory", "TrajNorm", "ETDescriptor", "ETAnchor", "BatchKMeans", "SocialSTGCNN", "SGCN", "GPGraph",
            "GPGraphSGCN", "get_GPGraph_SGCN_model", "GPGraphSTGCNN", "get_GPGraph_STGCNN_model", "SocialDMRGCN", "PECNet",
-           "LBEBM"]
+           "LBEBM", "SocialImplicitLight"]

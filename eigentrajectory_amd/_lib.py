@@ -98,6 +98,10 @@ SIGNATURES = {
     "et_dmrgcn_workspace_bytes": (_Z, [_P, _I64, _I64]),
     "et_dmrgcn_forward_graph": (_I, [_P, _P, _P, _I64, _P, _P, _Z, _P]),
     "et_dmrgcn_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _Z, _P]),
+    # ---- Social-Implicit predictor, inference
+    "et_implicit_workspace_bytes": (_Z, [_P, _I64]),
+    "et_implicit_forward_graph": (_I, [_P, _P, _I64, _P, _P, _Z, _P]),
+    "et_implicit_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _P, _Z, _P]),
     # ---- PECNet / LBEBM predictors, inference
     "et_pecnet_workspace_bytes": (_Z, [_P, _I64]),
     "et_pecnet_predict": (_I, [_P, _P, _P, _P, _P, _I64, _P, _P, _Z, _P]),
@@ -263,6 +267,22 @@ class DMRGCNParams(C.Structure):
                 ("seq_len", C.c_int), ("pred_seq_len", C.c_int), ("kernel_size", C.c_int),
                 ("split", (C.c_float * DMRGCN_BINS) * 2), ("st_dmrgcns", DMRGCNLayer * DMRGCN_MAX_STGCN),
                 ("tpcnns", DMRGCNTpcnn * DMRGCN_MAX_TPCNN)]
+
+
+IMPLICIT_MAX_BINS = 8  # ET_IMPLICIT_MAX_BINS
+
+
+class ImplicitCell(C.Structure):
+    """Mirror of ``et_implicit_cell``: device pointers to one Social-Zone cell's tensors (order: include/eigentraj.h)."""
+    _fields_ = [("global_t", C.c_void_p * 8), ("local_t", C.c_void_p * 8), ("noise_w", C.c_void_p),
+                ("global_w", C.c_void_p), ("local_w", C.c_void_p)]
+
+
+class ImplicitParams(C.Structure):
+    """Mirror of ``et_implicit_params``."""
+    _fields_ = [("spatial_input", C.c_int), ("spatial_output", C.c_int), ("temporal_input", C.c_int),
+                ("temporal_output", C.c_int), ("n_bins", C.c_int), ("bins", C.c_float * IMPLICIT_MAX_BINS),
+                ("cells", ImplicitCell * IMPLICIT_MAX_BINS)]
 
 
 MLP_MAX_LAYERS = 5    # ET_MLP_MAX_LAYERS

@@ -269,8 +269,9 @@ class EigenTrajectory(nn.Module):
         post-hook of every scene (``et_stgcnn_forward_scenes``: one launch; ``et_sgcn_forward_scenes``: 6 + the number of
         asymmetric convolution layers; ``et_gpgraph_sgcn_forward_scenes``: 8 + that number;
         ``et_gpgraph_stgcnn_forward_scenes``: three; ``et_dmrgcn_forward_scenes``: one; ``et_pecnet_forward_scenes``: 2 + 2
-        nonlocal_pools; ``et_lbebm_forward_scenes``: two), the reconstruction + metrics of every
-        scene -- what the reference's test loop (utils/trainer.py:173-195) computes with one :meth:`evaluate` per scene.
+        nonlocal_pools; ``et_lbebm_forward_scenes``: two; ``et_implicit_forward_scenes``: two), the reconstruction + metrics
+        of every scene -- what the reference's test loop (utils/trainer.py:173-195) computes with one :meth:`evaluate` per
+        scene.
 
         ``obs_traj`` (N, t_obs, 2), ``pred_traj`` (N, t_pred, 2): the split's rows, scene after scene; ``seq_start_end``
         (M, 2): each scene's (start, end) rows, consecutive and covering all N.  ``metrics``: any of ADE, FDE, TCC, COL.
@@ -279,12 +280,14 @@ class EigenTrajectory(nn.Module):
         :class:`~eigentrajectory_amd.gpgraph.GPGraph` predictor under the hooks of its base (``gpgraphsgcn`` around SGCN,
         ``gpgraphstgcnn`` around SocialSTGCNN) or a :class:`~eigentrajectory_amd.dmrgcn.SocialDMRGCN` predictor under the
         ``dmrgcn`` hooks, a :class:`~eigentrajectory_amd.pecnet.PECNet` predictor under the ``pecnet`` hooks (every scene
-        under its own all-ones mask, as the reference's test loader hands them over) or a
-        :class:`~eigentrajectory_amd.lbebm.LBEBM` predictor under the ``lbebm`` hooks, in eval mode; any other predictor or
-        pairing raises (use :meth:`evaluate` scene by scene)."""
+        under its own all-ones mask, as the reference's test loader hands them over), a
+        :class:`~eigentrajectory_amd.lbebm.LBEBM` predictor under the ``lbebm`` hooks or a
+        :class:`~eigentrajectory_amd.implicit.SocialImplicitLight` predictor under the ``implicit`` hooks, in eval mode; any
+        other predictor or pairing raises (use :meth:`evaluate` scene by scene)."""
         from .bridges import BRIDGES
         from .dmrgcn import SocialDMRGCN
         from .gpgraph import GPGraph
+        from .implicit import SocialImplicitLight
         from .lbebm import LBEBM
         from .pecnet import PECNet
         from .sgcn import SGCN
@@ -297,7 +300,8 @@ class EigenTrajectory(nn.Module):
                                            (GPGraph, "gpgraphstgcnn", ops.gpgraph_stgcnn_forward_scenes, True),
                                            (SocialDMRGCN, "dmrgcn", ops.dmrgcn_forward_scenes, None),
                                            (PECNet, "pecnet", ops.pecnet_forward_scenes, None),
-                                           (LBEBM, "lbebm", ops.lbebm_forward_scenes, None)):
+                                           (LBEBM, "lbebm", ops.lbebm_forward_scenes, None),
+                                           (SocialImplicitLight, "implicit", ops.implicit_forward_scenes, None)):
             pre, fwd, post = BRIDGES[name]
             if (isinstance(self.baseline_model, cls) and hooks.model_forward_pre_hook is pre
                     and hooks.model_forward is fwd and hooks.model_forward_post_hook is post
@@ -308,8 +312,9 @@ class EigenTrajectory(nn.Module):
                                       "'stgcnn' hooks, an SGCN predictor under the 'sgcn' hooks, a GPGraph predictor under "
                                       "the hooks of its base ('gpgraphsgcn' around SGCN, 'gpgraphstgcnn' around SocialSTGCNN), "
                                       "a SocialDMRGCN predictor under the 'dmrgcn' hooks, a PECNet predictor under the "
-                                      "'pecnet' hooks and an LBEBM predictor under the 'lbebm' hooks only; call evaluate() "
-                                      "scene by scene for other predictors")
+                                      "'pecnet' hooks, an LBEBM predictor under the 'lbebm' hooks and a SocialImplicitLight "
+                                      "predictor under the 'implicit' hooks only; call evaluate() scene by scene for other "
+                                      "predictors")
         if self.baseline_model.training:
             raise RuntimeError("evaluate_split: the predictor is in training mode; call .eval() first")
         sse = torch.as_tensor(seq_start_end).detach().cpu().long().reshape(-1, 2)

@@ -656,6 +656,56 @@ def dmrgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=Fals
     return (out, {"graph_inputs": gin}) if want_details else out
 
 
+# ------------------------------------------------------------------------------ Social-Implicit predictor (inference)
+def _implicit_ws(params, n, dev):
+    nbytes = L.lib().et_implicit_workspace_bytes(C.byref(params), n)
+    return (torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None), nbytes
+
+
+def implicit_forward_graph(model, v):
+    """``model`` (:class:`eigentrajectory_amd.implicit.SocialImplicitLight`, eval mode) on one scene as the implicit bridge
+    hands it over: v (1, 1, T, N) -> the raw output (1, S, T_out, N).  Two launches."""
+    params, dev = model.et_params()
+    T, To, S = params.temporal_input, params.temporal_output, params.spatial_output
+    if v.dim() != 4 or tuple(v.shape[:3]) != (1, 1, T):
+        raise ValueError(f"implicit_forward_graph: v {tuple(v.shape)} is not (1,1,{T},N)")
+    n = v.shape[-1]
+    (v,) = _dev_args(dev, v)
+    out = torch.empty((1, S, To, n), device=dev)
+    ws, nbytes = _implicit_ws(params, n, dev)
+    L.call("et_implicit_forward_graph", C.byref(params), L.ptr(v), n, L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
+    return out
+
+
+def implicit_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
+    """The implicit bridge + ``model`` (eval mode) + the post-hook for every scene of a split in TWO launches: C_obs (k, N)
+    and nrm (4, N) of :func:`norm_project` (rows 0-1: the last observed positions, centred here per scene), ``scene_sizes``
+    pedestrians per scene in row order (None = one scene; an empty list takes N = 0) -> C_pred_refine (T_out, N, S).  With
+    ``want_details`` also a dict: ``graph_inputs`` (k + 2, N), the fp32 v = [C_obs; obs_ori] the kernel used, and ``zone``
+    (N,) int32, every pedestrian's Social-Zone."""
+    params, dev = model.et_params()
+    C_obs, nrm = _dev_args(dev, C_obs, nrm)
+    if C_obs.dim() != 2 or C_obs.shape[0] != params.temporal_input - 2 or nrm.dim() != 2 or nrm.shape[0] < 2 \
+            or nrm.shape[1] != C_obs.shape[1]:
+        raise ValueError(f"implicit_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
+                         f"temporal_input - 2 = {params.temporal_input - 2}")
+    n = C_obs.shape[1]
+    if scene_sizes is not None:
+        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
+        if not sizes and n:
+            raise ValueError(f"implicit_forward_scenes: no scenes for {n} rows")
+        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
+    else:
+        sizes, off = None, None
+    out = torch.empty((params.temporal_output, n, params.spatial_output), device=dev)
+    gin = torch.empty((params.temporal_input, n), device=dev) if want_details else None
+    zone = torch.empty((n,), device=dev, dtype=torch.int32) if want_details else None
+    ws, nbytes = _implicit_ws(params, n, dev)
+    L.call("et_implicit_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
+           0 if off is None else len(sizes), L.ptr(out), L.ptr(gin), L.ptr(zone), L.ptr(ws), nbytes, L.stream(dev))
+    return (out, {"graph_inputs": gin, "zone": zone}) if want_details else out
+
+
 # ------------------------------------------------------------------------------ PECNet / LBEBM predictors (inference)
 def _mlp_ws(kind, params, n, dev):
     nbytes = getattr(L.lib(), f"et_{kind}_workspace_bytes")(C.byref(params), n)

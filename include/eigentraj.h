@@ -584,6 +584,55 @@ int et_dmrgcn_forward_scenes(const et_dmrgcn_params *params, const float *C_obs,
                              const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *graph_inputs,
                              void *workspace, size_t workspace_bytes, et_stream_t stream);
 
+/* ---- Social-Implicit predictor, inference (baseline/implicit: bridge.py pre-hook + SocialImplicitLight.forward + post-hook)
+ * Eval mode, the Light form (its noise is identically zero, so the noise_w term is not computed; noise_w is carried so
+ * that the table is complete).  The parameters are read in place from the module's tensors (fp32, contiguous).  Per cell
+ * i = zone, global_t[j] / local_t[j] with j = 0..7 are, of implicit_cells.{i}. and implicit_cells.{i}.ped.:
+ *   0, 1  feat.weight (S,1,3,3) / (S,1,3), .bias (S)          2, 3  highway_input.weight (S,1,1,1) / (S,1,1), .bias (S)
+ *   4, 5  highway.weight (T_out,T,1,1) / (T_out,T,1), .bias   6, 7  tpcnn.weight (T_out,T,3,3) / (T_out,T,3), .bias (T_out)
+ * and noise_w, global_w, local_w the cell's three scalars; S = spatial_output, T = temporal_input, T_out =
+ * temporal_output.  `bins` are the n_bins ascending zone bounds ([0, 0.01, 0.1, 1.2] in the reference's configuration).
+ * Supported: spatial_input = 1, 1 <= S <= 64, 1 <= T, T_out <= 16, 1 <= n_bins <= ET_IMPLICIT_MAX_BINS, bins[b] <=
+ * bins[b+1]; anything else: ET_ERR_UNSUPPORTED.  A missing pointer: ET_ERR_INVALID_ARG.
+ *
+ * The network (model.py:9-88,126-159): zone[n] = (number of bins b with bins[b] <= |v[0,n]|) - 1, an exact fp32
+ * comparison (a NaN lands in the last zone; a norm below bins[0] is in no zone and its output is 0).  Each zone's cell
+ * runs on the zone's pedestrians COMPACTED in scene order.  Global stream: u = relu(feat(v)) + highway_input(v) (S,T,n_z),
+ * then with T as channels highway(u) + tpcnn(u), tpcnn's 3x3 over the (S, n_z) plane zero-padding u; local stream, per
+ * pedestrian: the same with 1-d convolutions, whose (T_out,S) result is reinterpreted (reshape, no transpose) as
+ * (S,T_out); out = global_w global + local_w local, written at the pedestrian's own column.
+ *   et_implicit_forward_graph   one scene as the bridge hands it over: v (1,1,T,N) -> out (1,S,T_out,N).
+ *                               N <= ET_SCENE_MAX_N.
+ *   et_implicit_forward_scenes  a whole split: C_obs (T-2,N), nrm (4,N) of et_norm_project; per scene v = [C_obs;
+ *                               nrm[0:2] - their mean over the scene], summed in et_scene_project's order ->
+ *                               C_pred_refine (T_out,N,S), the post-hook's permute.  T >= 3.  scene_offsets as
+ *                               et_traj_metrics (NULL = one scene of N <= ET_SCENE_MAX_N rows); n_scenes = 0 takes N = 0
+ *                               only.  Optional outputs (may be NULL): graph_inputs (T,N) float, the fp32 v used, scene
+ *                               s at columns [off[s], off[s+1]); zone (N,) int32.  A scene larger than
+ *                               ET_SCENE_MAX_N is not computed: its outputs are NaN and its zones -2.
+ * Two launches per call whatever the number of scenes: one finds every pedestrian's zone and its two predecessors and two
+ * successors of the same zone within its scene, one computes every pedestrian on its own from those five columns.
+ * Workspace: et_implicit_workspace_bytes(p, N) bytes (0 for N = 0 or parameters outside the family).  No host
+ * synchronisation, no allocation: the calls can be captured in a graph.  Every sum has a fixed order: a pedestrian's
+ * result depends on its scene alone, not on the scenes around it, the launch size or the tiling. */
+#define ET_IMPLICIT_MAX_BINS 8
+typedef struct et_implicit_cell {
+    const float *global_t[8];
+    const float *local_t[8];
+    const float *noise_w, *global_w, *local_w;
+} et_implicit_cell;
+typedef struct et_implicit_params {
+    int spatial_input, spatial_output, temporal_input, temporal_output, n_bins;
+    float bins[ET_IMPLICIT_MAX_BINS];
+    et_implicit_cell cells[ET_IMPLICIT_MAX_BINS];
+} et_implicit_params;
+size_t et_implicit_workspace_bytes(const et_implicit_params *params, int64_t N);
+int et_implicit_forward_graph(const et_implicit_params *params, const float *v, int64_t N, float *out, void *workspace,
+                              size_t workspace_bytes, et_stream_t stream);
+int et_implicit_forward_scenes(const et_implicit_params *params, const float *C_obs, const float *nrm, int64_t N,
+                               const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *graph_inputs,
+                               int32_t *zone, void *workspace, size_t workspace_bytes, et_stream_t stream);
+
 /* ---- PECNet / LBEBM predictors, inference (baseline/pecnet, baseline/lbebm: bridge.py hooks + predict) ---------------
  * Both predict bodies are chains of Linear + ReLU (no activation after a chain's last layer) in exact fp32: every product
  * on the f32-input MFMA, accumulated in fp32 ascending in k, the bias added last.  The weights are read in place from the
