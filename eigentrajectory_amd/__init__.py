@@ -16,8 +16,9 @@ from .dmrgcn import SocialDMRGCN
 from .pecnet import PECNet
 from .lbebm import LBEBM
 from .implicit import SocialImplicitLight
+from .agentformer import AgentFormerLight
 from .gpgraph import GPGraph, GPGraphSGCN, GPGraphSTGCNN, get_GPGraph_SGCN_model, get_GPGraph_STGCNN_model
 
 __all__ = ["EigenTrajectory", "TrajNorm", "ETDescriptor", "ETAnchor", "BatchKMeans", "SocialSTGCNN", "SGCN", "GPGraph",
            "GPGraphSGCN", "get_GPGraph_SGCN_model", "GPGraphSTGCNN", "get_GPGraph_STGCNN_model", "SocialDMRGCN", "PECNet",
-           "LBEBM", "SocialImplicitLight"]
+           "LBEBM", "SocialImplicitLight", "AgentFormerLight"]

@@ -109,6 +109,10 @@ SIGNATURES = {
     "et_lbebm_workspace_bytes": (_Z, [_P, _I64]),
     "et_lbebm_predict": (_I, [_P, _P, _P, _I64, _P, _P, _Z, _P]),
     "et_lbebm_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _Z, _P]),
+    # ---- AgentFormer predictor, inference
+    "et_agentformer_workspace_bytes": (_Z, [_P, _I64, _I64]),
+    "et_agentformer_forward_graph": (_I, [_P, _P, _I64, _P, _P, _Z, _P]),
+    "et_agentformer_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _Z, _P]),
     # ---- fit
     "et_fit_gram_workspace_bytes": (_Z, [_I64, _I, _I]),
     "et_fit_gram": (_I, [_P, _P, _I64, _I, _I, _I, _F, _I, _P, _P, _P, _P, _Z, _P]),
@@ -302,6 +306,37 @@ class MLPParams(C.Structure):
     _fields_ = [("fdim", C.c_int), ("nonlocal_pools", C.c_int), ("non_local_dim", C.c_int), ("out_width", C.c_int),
                 ("pos_width", C.c_int)] + [(name, MLPChain) for name in (
                     "encoder_past", "encoder_dest", "non_local_theta", "non_local_phi", "non_local_g", "predictor")]
+
+
+AGENTFORMER_MAX_LAYERS = 4     # ET_AGENTFORMER_MAX_LAYERS
+AGENTFORMER_MAX_SCENE_N = 128  # ET_AGENTFORMER_MAX_SCENE_N
+
+
+class AgentFormerAttn(C.Structure):
+    """Mirror of ``et_agentformer_attn``: device pointers to one AgentAwareAttention's tensors."""
+    _fields_ = [(name, C.c_void_p) for name in ("in_proj_weight", "in_proj_bias", "in_proj_weight_self",
+                                                "in_proj_bias_self", "out_proj_weight", "out_proj_bias")]
+
+
+class AgentFormerLayer(C.Structure):
+    """Mirror of ``et_agentformer_layer`` (``multihead_attn`` and the third norm: decoder layers only)."""
+    _fields_ = [("self_attn", AgentFormerAttn), ("multihead_attn", AgentFormerAttn), ("linear1_weight", C.c_void_p),
+                ("linear1_bias", C.c_void_p), ("linear2_weight", C.c_void_p), ("linear2_bias", C.c_void_p),
+                ("norm_weight", C.c_void_p * 3), ("norm_bias", C.c_void_p * 3)]
+
+
+class AgentFormerEmbed(C.Structure):
+    """Mirror of ``et_agentformer_embed``."""
+    _fields_ = [(name, C.c_void_p) for name in ("input_fc_weight", "input_fc_bias", "fc_weight", "fc_bias", "pe")]
+
+
+class AgentFormerParams(C.Structure):
+    """Mirror of ``et_agentformer_params``."""
+    _fields_ = [(name, C.c_int) for name in ("motion_dim", "model_dim", "ff_dim", "nhead", "forecast_dim", "past_frames",
+                                             "future_frames", "n_enc", "n_dec")] + [
+        ("enc_embed", AgentFormerEmbed), ("dec_embed", AgentFormerEmbed), ("out_fc_weight", C.c_void_p),
+        ("out_fc_bias", C.c_void_p), ("enc", AgentFormerLayer * AGENTFORMER_MAX_LAYERS),
+        ("dec", AgentFormerLayer * AGENTFORMER_MAX_LAYERS)]
 
 
 STATE_BYTES = C.sizeof(KMeansState)

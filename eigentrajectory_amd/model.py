@@ -269,7 +269,8 @@ class EigenTrajectory(nn.Module):
         post-hook of every scene (``et_stgcnn_forward_scenes``: one launch; ``et_sgcn_forward_scenes``: 6 + the number of
         asymmetric convolution layers; ``et_gpgraph_sgcn_forward_scenes``: 8 + that number;
         ``et_gpgraph_stgcnn_forward_scenes``: three; ``et_dmrgcn_forward_scenes``: one; ``et_pecnet_forward_scenes``: 2 + 2
-        nonlocal_pools; ``et_lbebm_forward_scenes``: two; ``et_implicit_forward_scenes``: two), the reconstruction + metrics
+        nonlocal_pools; ``et_lbebm_forward_scenes``: two; ``et_implicit_forward_scenes``: two; ``et_agentformer_forward_scenes``: 2 + 2 encoder
+        layers + 4 decoder layers), the reconstruction + metrics
         of every scene -- what the reference's test loop (utils/trainer.py:173-195) computes with one :meth:`evaluate` per
         scene.
 
@@ -281,9 +282,11 @@ class EigenTrajectory(nn.Module):
         ``gpgraphstgcnn`` around SocialSTGCNN) or a :class:`~eigentrajectory_amd.dmrgcn.SocialDMRGCN` predictor under the
         ``dmrgcn`` hooks, a :class:`~eigentrajectory_amd.pecnet.PECNet` predictor under the ``pecnet`` hooks (every scene
         under its own all-ones mask, as the reference's test loader hands them over), a
-        :class:`~eigentrajectory_amd.lbebm.LBEBM` predictor under the ``lbebm`` hooks or a
-        :class:`~eigentrajectory_amd.implicit.SocialImplicitLight` predictor under the ``implicit`` hooks, in eval mode; any
-        other predictor or pairing raises (use :meth:`evaluate` scene by scene)."""
+        :class:`~eigentrajectory_amd.lbebm.LBEBM` predictor under the ``lbebm`` hooks, a
+        :class:`~eigentrajectory_amd.implicit.SocialImplicitLight` predictor under the ``implicit`` hooks or an
+        :class:`~eigentrajectory_amd.agentformer.AgentFormerLight` predictor under the ``agentformer`` hooks, in eval mode;
+        any other predictor or pairing raises (use :meth:`evaluate` scene by scene)."""
+        from .agentformer import AgentFormerLight
         from .bridges import BRIDGES
         from .dmrgcn import SocialDMRGCN
         from .gpgraph import GPGraph
@@ -301,7 +304,8 @@ class EigenTrajectory(nn.Module):
                                            (SocialDMRGCN, "dmrgcn", ops.dmrgcn_forward_scenes, None),
                                            (PECNet, "pecnet", ops.pecnet_forward_scenes, None),
                                            (LBEBM, "lbebm", ops.lbebm_forward_scenes, None),
-                                           (SocialImplicitLight, "implicit", ops.implicit_forward_scenes, None)):
+                                           (SocialImplicitLight, "implicit", ops.implicit_forward_scenes, None),
+                                           (AgentFormerLight, "agentformer", ops.agentformer_forward_scenes, None)):
             pre, fwd, post = BRIDGES[name]
             if (isinstance(self.baseline_model, cls) and hooks.model_forward_pre_hook is pre
                     and hooks.model_forward is fwd and hooks.model_forward_post_hook is post
@@ -312,9 +316,9 @@ class EigenTrajectory(nn.Module):
                                       "'stgcnn' hooks, an SGCN predictor under the 'sgcn' hooks, a GPGraph predictor under "
                                       "the hooks of its base ('gpgraphsgcn' around SGCN, 'gpgraphstgcnn' around SocialSTGCNN), "
                                       "a SocialDMRGCN predictor under the 'dmrgcn' hooks, a PECNet predictor under the "
-                                      "'pecnet' hooks, an LBEBM predictor under the 'lbebm' hooks and a SocialImplicitLight "
-                                      "predictor under the 'implicit' hooks only; call evaluate() scene by scene for other "
-                                      "predictors")
+                                      "'pecnet' hooks, an LBEBM predictor under the 'lbebm' hooks, a SocialImplicitLight "
+                                      "predictor under the 'implicit' hooks and an AgentFormerLight predictor under the "
+                                      "'agentformer' hooks only; call evaluate() scene by scene for other predictors")
         if self.baseline_model.training:
             raise RuntimeError("evaluate_split: the predictor is in training mode; call .eval() first")
         sse = torch.as_tensor(seq_start_end).detach().cpu().long().reshape(-1, 2)

@@ -706,6 +706,66 @@ def implicit_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=Fa
     return (out, {"graph_inputs": gin, "zone": zone}) if want_details else out
 
 
+# ------------------------------------------------------------------------------ AgentFormer predictor (inference)
+def _agentformer_ws(params, n, max_n, dev):
+    nbytes = L.lib().et_agentformer_workspace_bytes(C.byref(params), n, max_n)
+    return (torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None), nbytes
+
+
+def agentformer_forward_graph(model, pre_motion):
+    """``model`` (:class:`eigentrajectory_amd.agentformer.AgentFormerLight`, eval mode) on one scene as the agentformer
+    bridge hands it over: pre_motion (T, N, 1) or (T, N) -> ``_seq_out`` (k, N, S).  1 + 2 encoder layers + 4 decoder layers
+    launches."""
+    params, dev = model.et_params()
+    T, k, S = params.past_frames, params.future_frames, params.forecast_dim
+    if pre_motion.dim() == 3 and pre_motion.shape[2] == 1:
+        pre_motion = pre_motion[:, :, 0]
+    if pre_motion.dim() != 2 or pre_motion.shape[0] != T:
+        raise ValueError(f"agentformer_forward_graph: pre_motion {tuple(pre_motion.shape)} is not ({T},N,1)")
+    n = pre_motion.shape[1]
+    if n > L.AGENTFORMER_MAX_SCENE_N:
+        raise ValueError(f"agentformer_forward_graph: a scene of {n} pedestrians exceeds the {L.AGENTFORMER_MAX_SCENE_N} a "
+                         "scene may have")
+    (u,) = _dev_args(dev, pre_motion)
+    out = torch.empty((k, n, S), device=dev)
+    ws, nbytes = _agentformer_ws(params, n, n, dev)
+    L.call("et_agentformer_forward_graph", C.byref(params), L.ptr(u), n, L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
+    return out
+
+
+def agentformer_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
+    """The agentformer bridge + ``model`` (eval mode) + the post-hook for every scene of a split in 2 + 2 encoder layers + 4
+    decoder layers launches: C_obs (k, N) and nrm (4, N) of :func:`norm_project` (rows 0-1: the last observed positions,
+    centred here per scene), ``scene_sizes`` pedestrians per scene in row order (None = one scene; an empty list takes
+    N = 0) -> C_pred_refine (k, N, S).  A scene of more than 128 pedestrians is not computed: its rows are NaN.  With
+    ``want_details`` also a dict: ``graph_inputs`` (k + 2, N), the fp32 pre_motion = [C_obs; obs_ori] the kernels used."""
+    params, dev = model.et_params()
+    C_obs, nrm = _dev_args(dev, C_obs, nrm)
+    k = params.future_frames
+    if C_obs.dim() != 2 or C_obs.shape[0] != k or params.past_frames != k + 2 or nrm.dim() != 2 or nrm.shape[0] < 2 \
+            or nrm.shape[1] != C_obs.shape[1]:
+        raise ValueError(f"agentformer_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
+                         f"future_frames = {k}, past_frames = {params.past_frames}")
+    n = C_obs.shape[1]
+    if scene_sizes is not None:
+        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
+        if not sizes and n:
+            raise ValueError(f"agentformer_forward_scenes: no scenes for {n} rows")
+        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
+        max_n = max(sizes, default=0)
+    else:
+        sizes, off, max_n = None, None, n
+        if n > L.AGENTFORMER_MAX_SCENE_N:
+            raise ValueError(f"agentformer_forward_scenes: one scene of {n} pedestrians exceeds the "
+                             f"{L.AGENTFORMER_MAX_SCENE_N} a scene may have")
+    out = torch.empty((k, n, params.forecast_dim), device=dev)
+    gin = torch.empty((k + 2, n), device=dev) if want_details else None
+    ws, nbytes = _agentformer_ws(params, n, max_n, dev)
+    L.call("et_agentformer_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
+           0 if off is None else len(sizes), L.ptr(out), L.ptr(gin), L.ptr(ws), nbytes, L.stream(dev))
+    return (out, {"graph_inputs": gin}) if want_details else out
+
+
 # ------------------------------------------------------------------------------ PECNet / LBEBM predictors (inference)
 def _mlp_ws(kind, params, n, dev):
     nbytes = getattr(L.lib(), f"et_{kind}_workspace_bytes")(C.byref(params), n)

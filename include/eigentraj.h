@@ -684,6 +684,80 @@ int et_lbebm_forward_scenes(const et_mlp_params *params, const float *C_obs, con
                             const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *net_inputs,
                             void *workspace, size_t workspace_bytes, et_stream_t stream);
 
+/* ---- AgentFormer predictor, inference (baseline/agentformer: bridge.py hooks + AgentFormerLight.forward) -------------
+ * Eval mode, the ET configuration family: input_type = ['pos'], pred_type = 'pos', nz = 0, no learnt prior, pos_concat,
+ * no agent encoding, dot-product scores (gaussian_kernel off) with separate same-agent projections (sep_attn on), an
+ * all-zero agent mask (conn_dist >= 1000), out_fc straight after the decoder.  Exact fp32: every Linear on the f32-input
+ * MFMA, accumulated ascending in k, the bias added last.  The parameters are read in place from the module's tensors
+ * (fp32, contiguous).  Field <-> state_dict name (E = context_encoder, F = future_decoder, i = layer):
+ *   enc_embed / dec_embed .input_fc_weight / _bias   E|F.input_fc.weight (D, 1) / .bias (D)
+ *                         .fc_weight / _bias         E|F.pos_encoder.fc.weight (D, 2 D) / .bias (D)
+ *                         .pe                        E|F.pos_encoder.pe (max_t_len, 1, D), the buffer; rows 0 .. T-1 are read
+ *   enc[i] / dec[i]       .self_attn                 E.tf_encoder.layers.{i}.self_attn. | F.tf_decoder.layers.{i}.self_attn.
+ *                         .multihead_attn            F.tf_decoder.layers.{i}.multihead_attn. (decoder only; unused in enc[])
+ *      an attention's     .in_proj_weight / _bias             (3 D, D) / (3 D): q | k | v
+ *                         .in_proj_weight_self / _bias_self   (2 D, D) / (2 D): q_self | k_self
+ *                         .out_proj_weight / _bias            out_proj.weight (D, D) / out_proj.bias (D)
+ *                         .linear1_weight / _bias    layers.{i}.linear1.weight (ff, D) / .bias (ff)
+ *                         .linear2_weight / _bias    layers.{i}.linear2.weight (D, ff) / .bias (D)
+ *                         .norm_weight[j] / norm_bias[j]   layers.{i}.norm{j+1}.weight / .bias (D); j = 0, 1 and, decoder, 2
+ *   out_fc_weight / _bias                            F.out_fc.weight (S, D) / .bias (S)
+ * with D = model_dim, ff = ff_dim, T = past_frames, k = future_frames, S = forecast_dim.
+ * Supported: motion_dim = 1, model_dim a multiple of 16 up to 256, nhead dividing model_dim with head_dim a multiple of 4,
+ * 1 <= ff_dim <= 512, 1 to ET_AGENTFORMER_MAX_LAYERS layers each side, 1 <= T, k <= 16, 1 <= S <= 64; anything else:
+ * ET_ERR_UNSUPPORTED.  A missing pointer: ET_ERR_INVALID_ARG.
+ *
+ * The network: a scene of n pedestrians is T n encoder tokens (token t n + a = frame t of pedestrian a), x =
+ * fc(cat[input_fc(u[t, a]), pe[t]]); post-norm layers LN(x + attn(x)), LN(x + linear2(relu(linear1(x)))).  The decoder's
+ * k-pass loop feeds the same input every pass under a block-causal mask, so ONE pass over k n tokens (token t n + a, input
+ * u[T-1, a], positional row pe[t]) gives what its last pass gives; decoder layers add LN(x + cross-attn(x, memory))
+ * between the two; out_fc maps D -> S.  Agent-aware scores: score(i, j) = q_self_i . k_self_j when i % n == j % n, else
+ * q_i . k_j, both q scaled by head_dim^-0.5 after the bias; decoder self-attention masks keys of a later frame; softmax
+ * over the scene's keys; cross-attention takes q, q_self from the decoder rows and k, v, k_self from the encoder output.
+ *   et_agentformer_forward_graph   one scene as the bridge hands it over: pre_motion (T, N[, 1]) -> seq_out (k, N, S)
+ *                                  (_dec_motion is its (N, k, S) transpose).  N <= ET_AGENTFORMER_MAX_SCENE_N.
+ *   et_agentformer_forward_scenes  a whole split: C_obs (k, N), nrm (4, N) of et_norm_project; per scene u = [C_obs;
+ *                                  nrm[0:2] - their mean over the scene], summed in et_scene_project's order (T = k + 2)
+ *                                  -> C_pred_refine (k, N, S).  scene_offsets as et_implicit_forward_scenes (NULL = one
+ *                                  scene of N <= ET_AGENTFORMER_MAX_SCENE_N rows; n_scenes = 0 takes N = 0 only).
+ *                                  Optional output graph_inputs (k + 2, N) (may be NULL): the fp32 u used, scene s at
+ *                                  columns [off[s], off[s+1]).  A scene of more than ET_AGENTFORMER_MAX_SCENE_N
+ *                                  pedestrians (the reference's max_agent_len) is not computed: its outputs and its
+ *                                  graph_inputs are NaN.
+ * Launches: 2 + 2 n_enc + 4 n_dec whatever N and the number of scenes (14 for 2 + 2 layers; the graph form one fewer).
+ * Workspace: et_agentformer_workspace_bytes(p, N_total, max_scene_n) bytes, linear in N_total (max_scene_n is accepted
+ * for symmetry with the other predictors and does not change the size); 0 for N_total = 0 or parameters outside the
+ * family.  No host synchronisation, no allocation: the calls can be captured in a graph.  Every reduction (softmax
+ * maximum and sum, P V, LayerNorm mean and variance) has a fixed order that depends on the scene and the layer shape only:
+ * a token's result does not depend on the scenes around it, the tile it landed in or the launch size. */
+#define ET_AGENTFORMER_MAX_LAYERS 4
+#define ET_AGENTFORMER_MAX_SCENE_N 128
+typedef struct et_agentformer_attn {
+    const float *in_proj_weight, *in_proj_bias;
+    const float *in_proj_weight_self, *in_proj_bias_self;
+    const float *out_proj_weight, *out_proj_bias;
+} et_agentformer_attn;
+typedef struct et_agentformer_layer {
+    et_agentformer_attn self_attn, multihead_attn;
+    const float *linear1_weight, *linear1_bias, *linear2_weight, *linear2_bias;
+    const float *norm_weight[3], *norm_bias[3];
+} et_agentformer_layer;
+typedef struct et_agentformer_embed {
+    const float *input_fc_weight, *input_fc_bias, *fc_weight, *fc_bias, *pe;
+} et_agentformer_embed;
+typedef struct et_agentformer_params {
+    int motion_dim, model_dim, ff_dim, nhead, forecast_dim, past_frames, future_frames, n_enc, n_dec;
+    et_agentformer_embed enc_embed, dec_embed;
+    const float *out_fc_weight, *out_fc_bias;
+    et_agentformer_layer enc[ET_AGENTFORMER_MAX_LAYERS], dec[ET_AGENTFORMER_MAX_LAYERS];
+} et_agentformer_params;
+size_t et_agentformer_workspace_bytes(const et_agentformer_params *params, int64_t N_total, int64_t max_scene_n);
+int et_agentformer_forward_graph(const et_agentformer_params *params, const float *pre_motion, int64_t N, float *seq_out,
+                                 void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_agentformer_forward_scenes(const et_agentformer_params *params, const float *C_obs, const float *nrm, int64_t N,
+                                  const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *graph_inputs,
+                                  void *workspace, size_t workspace_bytes, et_stream_t stream);
+
 /* ---- fit ----------------------------------------------------------------------------
  * Gram matrices of the normalised trajectories routed to descriptor `which`
  * (1 moving / 0 static) under `mode`:  G_obs (2T_obs,2T_obs), G_pred (2T_pred,2T_pred)
