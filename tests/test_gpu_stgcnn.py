@@ -1,7 +1,16 @@
 """Native Social-STGCNN on the GPU (csrc/et_stgcnn.hip): the graph form against the reference's recorded network outputs
 (tests/golden/g19_stgcnn.npz), the scene form against the graph form through the bridge, whole splits end to end against
 the reference's per-pedestrian ADE / FDE, large scenes (workspace path) against tests/_stgcnn_np.py, the generic loop
-structure, errors, empty inputs and graph capture."""
+structure, errors, empty inputs and graph capture.
+
+Below those: the kernels across layer counts, widths and arena edges (the configurations of tests/_stgcnn_np.py: CONFIGS,
+seeded weights with nothing left at its default) against the fp64 restatement -- the scene form in LDS and in the workspace
+in one launch on inputs whose scene mean is exact (SN.exact_split), any order of scenes and a scene alone bit for bit, the
+graph form with a non-symmetric a, the recorded generic calls of g19b_stgcnn_generic.npz, another BatchNorm eps, a NaN that
+stays in its scene, a scene beyond the scene limit, and every limit accepted and refused.  Every comparison is within TOL
+of the largest entry, no scene or row excluded; the largest errors measured on the MI355X are in DESIGN §4."""
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
@@ -167,3 +176,240 @@ def test_hook_path_captured_and_replayed(dev):
     rep2 = model.forward_replayed(o)["recon_traj"].clone()
     assert not torch.equal(eager2, eager)
     assert torch.equal(rep2, eager2)
+
+
+# ------------------------------------------------------------------ layer counts, widths and arena edges
+ZB = G.load("g19b_stgcnn_generic.npz")
+CFG = SN.CONFIGS
+_NETS, _REFS = {}, {}
+
+
+def gnet(dev, name, eps=None):
+    """-> (module on the GPU, its state_dict as numpy): configuration `name` with SN.random_state's weights (seed 0), every
+    BatchNorm's eps set to `eps` if given.  Shared between the tests, which leave it unchanged."""
+    if (name, eps) not in _NETS:
+        from eigentrajectory_amd.stgcnn import SocialSTGCNN
+        m = SocialSTGCNN(**SN.module_kw(*CFG[name]))
+        sd = SN.random_state(m, 0)
+        for bn in m.modules():
+            if eps is not None and isinstance(bn, torch.nn.BatchNorm2d):
+                bn.eps = eps
+        _NETS[name, eps] = (m.to(dev).eval(), sd)
+    return _NETS[name, eps]
+
+
+def offsets(sizes):
+    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+
+
+def scene_refs(name, sd, C_obs, nrm, sizes, key=None, **fw):
+    """the fp64 restatement of every non-empty scene of a split (None for an empty one), computed once per `key`"""
+    if key is None or (name, key) not in _REFS:
+        n_st, n_tp = CFG[name][:2]
+        off = offsets(sizes)
+        refs = [SN.c_pred_refine(SN.forward(sd, SN.scene_input(C_obs, nrm, off[i], off[i + 1]), n_stgcnn=n_st,
+                                            n_txpcnn=n_tp, **fw)) if n else None for i, n in enumerate(sizes)]
+        if key is None:
+            return refs
+        _REFS[name, key] = refs
+    return _REFS[name, key]
+
+
+def run_scenes(ops, m, dev, C_obs, nrm, sizes):
+    return N_(ops.stgcnn_forward_scenes(m, T(C_obs, dev), T(nrm, dev), scene_sizes=sizes))
+
+
+def run_alone(ops, m, dev, C_obs, nrm, lo, hi):
+    c, r = np.ascontiguousarray(C_obs[:, lo:hi]), np.ascontiguousarray(nrm[:, lo:hi])
+    return N_(ops.stgcnn_forward_scenes(m, T(c, dev), T(r, dev)))
+
+
+@pytest.mark.parametrize("name", list(CFG))
+def test_arena_arithmetic_agrees_with_the_library(dev, name):
+    """tests/_stgcnn_np.py restates the arena formula; the library takes no workspace up to the LDS limit and 4 per N bytes
+    one pedestrian above it"""
+    from eigentrajectory_amd import _lib as L
+    per, lim = SN.arena_per_ped(*CFG[name]), SN.lds_max_n(*CFG[name])
+    assert (per, lim) == SN.ARENA[name]
+    p, _ = gnet(dev, name)[0].et_params()
+    N = 3 * lim + 7
+    assert L.lib().et_stgcnn_workspace_bytes(C.byref(p), L.i64(N), L.i64(lim)) == 0
+    assert L.lib().et_stgcnn_workspace_bytes(C.byref(p), L.i64(N), L.i64(lim + 1)) == 4 * per * N
+
+
+@pytest.mark.parametrize("name", list(CFG))
+def test_scene_form_matches_the_restatement_in_both_arenas(dev, ops, name):
+    """one launch over scenes of 1, 2, 3, L-1, L, L+1, 0, 2L+5 and 2 pedestrians (L the LDS limit; `max`: up to 17), LDS
+    and workspace scenes side by side, every scene against the fp64 restatement fed exactly the same input; the scenes in
+    another order, and each scene alone, give the same bits"""
+    n_st, n_tp, S, k = CFG[name]
+    m, sd = gnet(dev, name)
+    sizes = SN.split_sizes(name)
+    off = offsets(sizes)
+    C_obs, nrm = SN.exact_split(sizes, k, 1)
+    refs = scene_refs(name, sd, C_obs, nrm, sizes, key="split")
+    out = run_scenes(ops, m, dev, C_obs, nrm, sizes)
+    assert out.shape == (k, off[-1], S)
+    errs = {(i, n): scale_err(out[:, off[i]:off[i + 1]], refs[i]) for i, n in enumerate(sizes) if n}
+    print(f"{name} scene form, (scene, n): error {({key: float(f'{e:.2e}') for key, e in errs.items()})}")
+    print(f"{name} scene form: largest error {max(errs.values()):.2e}")
+    assert np.isfinite(out).all() and max(errs.values()) <= TOL, errs
+    order = list(range(len(sizes)))[::-1]
+    order[1], order[3] = order[3], order[1]
+    cols = np.concatenate([np.arange(off[i], off[i + 1]) for i in order])
+    moved = run_scenes(ops, m, dev, C_obs[:, cols], nrm[:, cols], [sizes[i] for i in order])
+    assert np.array_equal(moved, out[:, cols])  # column for column
+    for i, n in enumerate(sizes):
+        if n:
+            assert np.array_equal(run_alone(ops, m, dev, C_obs, nrm, off[i], off[i + 1]), out[:, off[i]:off[i + 1]]), (i, n)
+
+
+@pytest.mark.parametrize("name", ["et", "gen", "tp1"])
+def test_graph_form_takes_any_adjacency_in_both_arenas(dev, name):
+    """a dense non-symmetric normal a at n = 1, L, L+1 and 70; with a transposed over its last two axes the output is the
+    restatement's of THAT a and far from the first (n = 1 has nothing to transpose)"""
+    n_st, n_tp, S, k = CFG[name]
+    m, sd = gnet(dev, name)
+    lim = SN.lds_max_n(*CFG[name])
+    rng = np.random.default_rng(17)
+    errs = {}
+    for n in (1, lim, lim + 1, 70):
+        v = rng.normal(0, 1, (1, 1, k + 2, n)).astype(np.float32)
+        a = rng.normal(0, 1, (k + 2, n, n)).astype(np.float32)
+        at = np.ascontiguousarray(np.swapaxes(a, 1, 2))
+        out, out_t = N_(m(T(v, dev), T(a, dev))), N_(m(T(v, dev), T(at, dev)))
+        assert out.shape == (1, S, k, n)
+        ref, ref_t = (SN.forward(sd, v[0, 0], x, n_stgcnn=n_st, n_txpcnn=n_tp) for x in (a, at))
+        errs[n] = (scale_err(out[0], ref), scale_err(out_t[0], ref_t), scale_err(out_t[0], ref))
+    print(f"{name} graph form, n: (error, error with a transposed, change by transposing) "
+          f"{({n: tuple(float(f'{e:.2e}') for e in es) for n, es in errs.items()})}")
+    print(f"{name} graph form: largest error {max(max(es[:2]) for es in errs.values()):.2e}")
+    for n, (err, err_t, change) in errs.items():
+        assert err <= TOL and err_t <= TOL, (n, err, err_t)
+        assert n == 1 or change > 1e-3, (n, change)
+
+
+def test_recorded_generic_calls_through_the_module(dev):
+    """g19b: n_txpcnn = 1, 2, 8, three and eight st_gcn layers, k = 1; the bridge's a and a non-symmetric one; against the
+    reference's float64 output and its float32 output"""
+    from eigentrajectory_amd.stgcnn import SocialSTGCNN
+    worst = {}
+    for i in range(4):
+        cfg = tuple(int(c) for c in ZB[f"c{i}.cfg"])
+        pre = f"c{i}.sd."
+        m = SocialSTGCNN(**SN.module_kw(*cfg))
+        m.load_state_dict({key[len(pre):]: torch.from_numpy(np.array(ZB[key])) for key in ZB.files if key.startswith(pre)})
+        m = m.to(dev).eval()
+        for call in ("s3", "s11", "ns"):
+            out = N_(m(T(ZB[f"c{i}.{call}.v"], dev), T(ZB[f"c{i}.{call}.a"], dev)))
+            assert out.shape == ZB[f"c{i}.{call}.out"].shape
+            worst[cfg, call] = (scale_err(out, ZB[f"c{i}.{call}.out64"]), scale_err(out, ZB[f"c{i}.{call}.out"]))
+    print("g19b (float64 reference, float32 reference): "
+          f"{({key: tuple(float(f'{e:.2e}') for e in es) for key, es in worst.items()})}")
+    print(f"g19b: largest error {max(max(es) for es in worst.values()):.2e}")
+    assert all(max(es) <= TOL for es in worst.values()), worst
+
+
+def test_batchnorm_eps_is_read_from_the_module(dev, ops):
+    name, eps = "gen", 1e-3
+    m, sd = gnet(dev, name, eps=eps)
+    lim = SN.lds_max_n(*CFG[name])
+    sizes = [3, lim, lim + 1]
+    off = offsets(sizes)
+    C_obs, nrm = SN.exact_split(sizes, CFG[name][3], 2)
+    out = run_scenes(ops, m, dev, C_obs, nrm, sizes)
+    refs = scene_refs(name, sd, C_obs, nrm, sizes, eps=eps)
+    errs = [scale_err(out[:, off[i]:off[i + 1]], refs[i]) for i in range(len(sizes))]
+    usual = run_scenes(ops, gnet(dev, name)[0], dev, C_obs, nrm, sizes)
+    print(f"{name} eps {eps}: errors {[float(f'{e:.2e}') for e in errs]}, from the eps 1e-5 result {scale_err(out, usual):.2e}")
+    assert max(errs) <= TOL
+    assert scale_err(out, usual) > 10 * TOL
+
+
+@pytest.mark.parametrize("poisoned", ["lds", "workspace"])
+@pytest.mark.parametrize("name", ["et", "gen"])
+def test_a_nan_stays_in_its_scene(dev, ops, name, poisoned):
+    """an LDS scene and a workspace scene on either side of a scene with one NaN coefficient: they are what they are
+    without the NaN, bit for bit; the poisoned scene is NaN where the restatement of the same input is"""
+    m, sd = gnet(dev, name)
+    lim = SN.lds_max_n(*CFG[name])
+    sizes = [5, lim + 1, 7 if poisoned == "lds" else lim + 2, 4, lim + 3]
+    off = offsets(sizes)
+    C_obs, nrm = SN.exact_split(sizes, CFG[name][3], 3)
+    clean = run_scenes(ops, m, dev, C_obs, nrm, sizes)
+    bad = C_obs.copy()
+    bad[2, off[2] + 1] = np.nan
+    out = run_scenes(ops, m, dev, bad, nrm, sizes)
+    assert np.isfinite(clean).all()
+    for i in (0, 1, 3, 4):
+        assert np.array_equal(out[:, off[i]:off[i + 1]], clean[:, off[i]:off[i + 1]]), i
+    with np.errstate(invalid="ignore"):
+        ref = SN.c_pred_refine(SN.forward(sd, SN.scene_input(bad, nrm, off[2], off[3]), n_stgcnn=CFG[name][0],
+                                          n_txpcnn=CFG[name][1]))
+    assert np.isnan(ref).any()
+    assert np.array_equal(np.isnan(out[:, off[2]:off[3]]), np.isnan(ref))
+
+
+def test_a_scene_beyond_the_scene_limit_is_not_computed(dev, ops):
+    """a scene of more than ET_SCENE_MAX_N pedestrians gets NaN columns, the scenes around it are computed as if alone; the
+    same rows as ONE scene without offsets are refused.  A scene that fits neither LDS nor the workspace given (here: none)
+    takes the same branch."""
+    from eigentrajectory_amd import _lib as L
+    m, _ = gnet(dev, "et")
+    sizes = [3, L.SCENE_MAX_N + 1, 4]
+    C_obs, nrm = _synthetic(sum(sizes), 6)
+    out = run_scenes(ops, m, dev, C_obs, nrm, sizes)
+    assert np.isnan(out[:, 3:-4]).all()
+    for lo, hi in ((0, 3), (sum(sizes) - 4, sum(sizes))):
+        assert np.array_equal(run_alone(ops, m, dev, C_obs, nrm, lo, hi), out[:, lo:hi]) and np.isfinite(out[:, lo:hi]).all()
+    with pytest.raises(ValueError):
+        ops.stgcnn_forward_scenes(m, T(C_obs, dev), T(nrm, dev))
+    lim = SN.lds_max_n(*CFG["et"])
+    sizes = [3, lim + 1, lim]
+    C_obs, nrm = _synthetic(sum(sizes), 7)
+    whole = run_scenes(ops, m, dev, C_obs, nrm, sizes)
+    p, _ = m.et_params()
+    c, r, off = T(C_obs, dev), T(nrm, dev), ops.scene_offsets(sizes, sum(sizes), dev)
+    got = torch.full((6, sum(sizes), 20), 7.0, device=dev)
+    L.call("et_stgcnn_forward_scenes", C.byref(p), L.ptr(c), L.ptr(r), sum(sizes), L.ptr(off), len(sizes), L.ptr(got), None, 0,
+           L.stream(dev))
+    got = N_(got)
+    assert np.isnan(got[:, 3:3 + lim + 1]).all()
+    assert np.array_equal(got[:, :3], whole[:, :3]) and np.array_equal(got[:, -lim:], whole[:, -lim:])
+
+
+REFUSED = {"S = 65": dict(output_feat=65), "k = 33": dict(pred_seq_len=33, seq_len=35), "n_stgcnn = 9": dict(n_stgcnn=9),
+           "n_txpcnn = 9": dict(n_txpcnn=9), "seq_len != k + 2": dict(seq_len=7), "input_feat = 2": dict(input_feat=2),
+           "kernel_size = 5": dict(kernel_size=5)}
+
+
+def test_limits_refused(dev, ops):
+    """one step outside each limit of the family (the accepted side: `wide`, `max`, `deep_tp`, `deep_st` above): status 3;
+    BatchNorms that disagree on eps, a module on the CPU, and a workspace that is missing or short"""
+    from eigentrajectory_amd import _lib as L
+    from eigentrajectory_amd.stgcnn import SocialSTGCNN
+    for what, kw in REFUSED.items():
+        args = dict(SN.module_kw(*CFG["et"]), **kw)
+        bad = SocialSTGCNN(**args).to(dev).eval()
+        K = args["seq_len"]
+        with pytest.raises(L.ETLibraryError, match="status 3"):
+            ops.stgcnn_forward_graph(bad, torch.zeros((1, 1, K, 3), device=dev), torch.zeros((K, 3, 3), device=dev))
+    v, a = torch.zeros((1, 1, 8, 3), device=dev), torch.zeros((8, 3, 3), device=dev)
+    two = SocialSTGCNN(**SN.module_kw(*CFG["et"])).to(dev).eval()
+    two.st_gcns[0].tcn[3].eps = 1e-3
+    with pytest.raises(L.ETLibraryError, match="eps"):
+        two(v, a)
+    with pytest.raises(L.ETLibraryError, match="HIP"):
+        SocialSTGCNN(**SN.module_kw(*CFG["et"])).eval()(v.cpu(), a.cpu())
+    m, _ = gnet(dev, "et")
+    p, _ = m.et_params()
+    n = SN.lds_max_n(*CFG["et"]) + 1
+    v, a = torch.zeros((1, 1, 8, n), device=dev), torch.zeros((8, n, n), device=dev)
+    out = torch.full((1, 20, 6, n), 7.0, device=dev)
+    short = torch.empty((4 * SN.arena_per_ped(*CFG["et"]) * n - 4,), device=dev, dtype=torch.uint8)
+    for ws in (None, short):
+        rc = L.lib().et_stgcnn_forward_graph(C.byref(p), L.ptr(v), L.ptr(a), n, L.ptr(out), L.ptr(ws),
+                                             0 if ws is None else ws.numel(), L.stream(dev))
+        assert rc == 4  # ET_ERR_WORKSPACE
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all())  # nothing was launched

@@ -18,8 +18,22 @@ The ET descriptors and anchors are G2's (tests/golden/g2_fit_all_scenes.npz), pe
                                 coefficient values
   gen.<state_dict key>, gen.net_out<i>
                                 a second weight set, n_stgcnn = 2, n_txpcnn = 3, S = 12, on the inputs of picks 0 and 1
+
+    python tools/make_golden_stgcnn.py --ref <reference checkout> --out tests/golden --generic
+
+writes g19b_stgcnn_generic.npz instead (g19_stgcnn.npz is left alone): the reference's social_stgcnn alone, for the loop
+structures the ET configuration never takes.  For each (n_stgcnn, n_txpcnn, S, k) of GENERIC, tag c<i>:
+  c<i>.cfg                      the four numbers
+  c<i>.sd.<state_dict key>      seeded weights, randomised like the above
+  c<i>.{s3,s11,ns}.{v,a,out,out64}
+                                three calls: scenes of 3 and of 11 pedestrians (two of the 11 coincident) with the v and
+                                a the reference's bridge builds, and one with a dense NON-symmetric normal a (the network
+                                takes any a); out is the float32 network's output, out64 the same network's in float64 on
+                                the same float32 v and a
+MANIFEST.json gets the entry `g19b_stgcnn_generic`.
 Only data is written; nothing of the reference is copied."""
 import argparse
+import json
 import os
 import sys
 import time
@@ -46,14 +60,68 @@ def randomise(net, gen):
                 m.weight.copy_(0.05 + 0.4 * torch.rand(m.weight.shape, generator=gen))
 
 
+GENERIC = [(1, 1, 20, 6), (1, 2, 5, 1), (3, 8, 7, 3), (8, 3, 4, 2)]  # (n_stgcnn, n_txpcnn, S, k)
+
+
+def generic(out_dir):
+    """g19b: the reference's network on CPU for the configurations of GENERIC (cwd and sys.path are the reference's)"""
+    from baseline.stgcnn import TrajectoryPredictor, model_forward_pre_hook
+    torch.set_num_threads(1)
+    out, man = {}, {"configs": [list(c) for c in GENERIC], "torch": torch.__version__, "numpy": np.__version__,
+                    "largest": {}}
+    for i, (n_st, n_tp, S, k) in enumerate(GENERIC):
+        tag = f"c{i}"
+        torch.manual_seed(500 + i)
+        net = TrajectoryPredictor(n_stgcnn=n_st, n_txpcnn=n_tp, input_feat=1, output_feat=S, kernel_size=3, seq_len=k + 2,
+                                  pred_seq_len=k)
+        randomise(net, torch.Generator().manual_seed(600 + i))
+        net.eval()
+        out[f"{tag}.cfg"] = np.asarray([n_st, n_tp, S, k], np.int64)
+        for key, val in net.state_dict().items():
+            out[f"{tag}.sd.{key}"] = val.detach().numpy().copy()
+        gen = torch.Generator().manual_seed(700 + i)
+        calls = {}
+        for n in (3, 11):
+            obs_data = torch.randn((k, n), generator=gen)
+            obs_ori = 3.0 * torch.randn((2, n), generator=gen)
+            if n == 11:
+                obs_data[:, 4], obs_ori[:, 4] = obs_data[:, 3], obs_ori[:, 3]  # one coincident pair
+            calls[f"s{n}"] = model_forward_pre_hook(obs_data, obs_ori)
+        calls["ns"] = (torch.randn((1, 1, k + 2, 7), generator=gen), torch.randn((k + 2, 7, 7), generator=gen))
+        net64 = TrajectoryPredictor(n_stgcnn=n_st, n_txpcnn=n_tp, input_feat=1, output_feat=S, kernel_size=3,
+                                    seq_len=k + 2, pred_seq_len=k).double().eval()
+        net64.load_state_dict({key: val.double() for key, val in net.state_dict().items()})
+        for name, (v, a) in calls.items():
+            with torch.no_grad():
+                res, res64 = net(v, a), net64(v.double(), a.double())
+            assert res.dtype == torch.float32 and res64.dtype == torch.float64 and res.shape == (1, S, k, v.shape[-1])
+            out[f"{tag}.{name}.v"], out[f"{tag}.{name}.a"] = v.numpy().copy(), a.numpy().copy()
+            out[f"{tag}.{name}.out"], out[f"{tag}.{name}.out64"] = res.numpy(), res64.numpy()
+            man["largest"][f"{tag}.{name}"] = repr(float(res64.abs().max()))
+        assert not np.allclose(out[f"{tag}.ns.a"], np.swapaxes(out[f"{tag}.ns.a"], 1, 2))
+    path = os.path.join(out_dir, "g19b_stgcnn_generic.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path))
+    mpath = os.path.join(out_dir, "MANIFEST.json")
+    with open(mpath) as f:
+        m = json.load(f)
+    m["g19b_stgcnn_generic"] = man
+    with open(mpath, "w") as f:
+        json.dump(m, f, indent=1, sort_keys=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
+    ap.add_argument("--generic", action="store_true", help="write g19b_stgcnn_generic.npz only (g19_stgcnn.npz is not touched)")
     args = ap.parse_args()
+    args.out = os.path.abspath(args.out)
     from tests import _golden as G
     sys.path.insert(0, args.ref)
     os.chdir(args.ref)
+    if args.generic:
+        return generic(args.out)
 
     from baseline.stgcnn import TrajectoryPredictor, model_forward, model_forward_post_hook, model_forward_pre_hook
     from EigenTrajectory import EigenTrajectory
