@@ -1,6 +1,7 @@
 """CPU checks of the native AgentFormer predictor (eigentrajectory_amd/agentformer.py, csrc/et_agentformer.hip): the numpy
 restatement (tests/_agentformer_np.py) against the reference's recorded outputs (tests/golden/g26_agentformer_net.npz,
-tools/make_golden_agentformer_net.py), its k-pass form against its one-pass form, the mutants, the module's state_dict
+tools/make_golden_agentformer_net.py), its k-pass form against its one-pass form, the mutants, the helper's CONFIGS (each
+inside the family, the mutants visible at each, float32 mode within TOL of float64), the module's state_dict
 against the reference's key and shape lists, the positional rows, what raises, the dispatch of evaluate_split and the entry
 points' argument validation (host side, before any device work)."""
 import ctypes as C
@@ -88,6 +89,120 @@ def test_every_mutant_misses_the_recorded_outputs(mutant):
         ref = Z[f"{tag}.{scene}.seq_out"]
         got = AN.forward(weights(tag), Z[f"{tag}.{scene}.u"], int(Z[f"{tag}.nhead"]), mutant=mutant)
         assert np.abs(got - ref).max() / np.abs(ref).max() > 1e-3, (tag, scene)
+
+
+# ------------------------------------------------------------------------- the configurations of the GPU shape tests
+_REF = {}
+
+
+def config_case(name, n):
+    """(state_dict, u (T, n), the fp64 restatement's output) of CONFIGS[name] on one seeded scene of n, computed once"""
+    if (name, n) not in _REF:
+        c = AN.CONFIGS[name]
+        _, sd = AN.config_module(name)
+        C_obs, nrm = AN.random_scenes([n], 3 + n, c["T"] - 2)
+        u = AN.scene_input(C_obs, nrm, 0, n)
+        ref = AN.forward(sd, u, c["nhead"], frames=c["k"])
+        ref.setflags(write=False)
+        _REF[name, n] = (sd, u, ref)
+    return _REF[name, n]
+
+
+def test_configs_name_the_paths_they_open():
+    C_ = AN.CONFIGS
+    assert AN.SCENE_CONFIGS == ("min", "h3", "h6", "hd4", "hd20", "hd128", "hd256", "deep")
+    assert AN.MODULE_ONLY_CONFIGS == ("long_dec", "long_enc")
+    assert [C_[n]["D"] // C_[n]["nhead"] for n in AN.SCENE_CONFIGS] == [16, 16, 16, 4, 20, 128, 256, 16]
+    assert [C_[n]["nhead"] % 4 for n in ("min", "h3", "h6")] == [1, 3, 2]             # three, one, two idle wavefronts
+    assert [C_[n]["ff"] % 4 for n in ("min", "h3", "h6", "hd20", "hd128")] == [1, 2, 1, 0, 3]  # live k of the partial step
+    assert [C_[n]["D"] // 16 for n in ("min", "h3", "hd20", "h6")] == [1, 3, 5, 6]    # column blocks, none a multiple of 8
+    assert [C_[n]["S"] for n in ("min", "h3", "hd128")] == [1, 17, 64]
+    assert (C_["deep"]["n_enc"], C_["deep"]["n_dec"], C_["deep"]["T"]) == (4, 4, 16)
+    assert (C_["long_dec"]["T"], C_["long_dec"]["k"], C_["long_enc"]["T"], C_["long_enc"]["k"]) == (3, 16, 16, 1)
+
+
+@pytest.mark.parametrize("name", list(AN.CONFIGS))
+def test_every_config_is_inside_the_family_and_loads_strictly(name):
+    c = AN.CONFIGS[name]
+    net, sd = AN.config_module(name)  # constructs (inside the family) and loads strict=True
+    assert (net.model_dim, net.nhead, net.ff_dim, net.forecast_dim) == (c["D"], c["nhead"], c["ff"], c["S"])
+    assert (net.past_frames, net.future_frames) == (c["T"], c["k"])
+    assert (len(net.context_encoder.tf_encoder.layers), len(net.future_decoder.tf_decoder.layers)) == (c["n_enc"], c["n_dec"])
+    back = {k: v.numpy() for k, v in net.state_dict().items()}
+    assert sorted(back) == sorted(sd) and all(np.array_equal(back[k], v) for k, v in sd.items() if v is not None)
+    drawn = [v for v in sd.values() if v is not None]
+    assert all(v.dtype == np.float32 and np.abs(v).min() > 0 for v in drawn)  # nothing left at zero
+    for stem, count in ((AN.E + "tf_encoder.layers.", c["n_enc"]), (AN.F + "tf_decoder.layers.", c["n_dec"])):
+        for i in range(1, count):  # no two layers alike
+            for k0 in [k for k in sd if k.startswith(stem + "0.")]:
+                assert not np.array_equal(sd[k0], sd[k0.replace(stem + "0.", f"{stem}{i}.")]), (k0, i)
+
+
+@pytest.mark.parametrize("name", ["long_dec", "deep"])
+def test_frames_k_pass_form_equals_the_one_pass_form(name):
+    c = AN.CONFIGS[name]
+    for n in (2, 17):
+        sd, u, one = config_case(name, n)
+        assert one.shape == (c["k"], n, c["S"])
+        assert np.abs(AN.forward(sd, u, c["nhead"], loop=True, frames=c["k"]) - one).max() <= 1e-12
+        if c["n_dec"] >= 2:  # (one decoder layer attends over embeddings only: a pass's newest block sees them all anyway)
+            assert np.abs(AN.forward(sd, u, c["nhead"], loop=True, frames=c["k"], mutant="no_causal") - one).max() > 1e-3
+    if name == "deep":  # frames = None is T - 2, today's behaviour
+        assert np.array_equal(AN.forward(sd, u, c["nhead"]), one)
+
+
+@pytest.mark.parametrize("name", list(AN.CONFIGS))
+@pytest.mark.parametrize("mutant", AN.MUTANTS)
+def test_every_mutant_misses_the_restatement_at_every_config(mutant, name):
+    """by more than 100 TOL on scenes of 2 and 17.  Where a mutant cannot be expressed (layers 0 and 1 swapped with one
+    layer a side, no causal mask over one decoder frame: AN.vacuous) it must be the identity instead."""
+    c = AN.CONFIGS[name]
+    for n in (2, 17):
+        sd, u, ref = config_case(name, n)
+        got = AN.forward(sd, u, c["nhead"], frames=c["k"], mutant=mutant)
+        miss = np.abs(got - ref).max() / np.abs(ref).max()
+        print(f"{name} {mutant} n={n}: {miss:.2e}")
+        if AN.vacuous(mutant, name):
+            assert miss == 0.0, (name, mutant, n)
+        else:
+            assert miss > 100 * TOL, (name, mutant, n, miss)
+
+
+@pytest.mark.parametrize("name", list(AN.CONFIGS))
+def test_float32_mode_is_float32_and_within_tol_of_float64(name):
+    """the reference arithmetic's own error (measured 1.2e-7 .. 6.1e-7 of the largest entry over all configurations)"""
+    c = AN.CONFIGS[name]
+    for n in (1, 2, 17):
+        sd, u, ref = config_case(name, n)
+        stats = {}
+        got = AN.forward(sd, u, c["nhead"], frames=c["k"], dtype=np.float32, stats=stats)
+        assert got.dtype == np.float32 and ref.dtype == np.float64 and got.shape == ref.shape
+        assert np.isfinite(stats["max_score"])
+        err = scale_err(got, ref)
+        print(f"{name} n={n}: fp32 against fp64 {err:.2e}, max score {stats['max_score']:.1f}")
+        assert err <= TOL, (name, n, err)
+
+
+@pytest.mark.parametrize("name", AN.LARGE_LOGITS["configs"])
+def test_large_logit_inputs_need_the_row_maximum(name):
+    """in_proj weights x 8: the largest score passes 88.7, above which exp overflows fp32 unless the row maximum is taken
+    off first.  Near-argmax attention is ill-conditioned in fp32 itself: the float32 restatement's error against fp64
+    (measured 1.5e-5 at h3, 3.6e-5 at hd20; largest scores 136 and 318) is what the GPU test scales its bound from."""
+    c, sizes = AN.CONFIGS[name], AN.LARGE_LOGITS["sizes"]
+    _, sd = AN.config_module(name, in_proj_scale=AN.LARGE_LOGITS["scale"])
+    C_obs, nrm = AN.random_scenes(sizes, AN.LARGE_LOGITS["seed"], c["k"])
+    stats, lo, e32 = {}, 0, 0.0
+    for n in sizes:
+        u = AN.scene_input(C_obs, nrm, lo, lo + n)
+        ref = AN.forward(sd, u, c["nhead"], stats=stats)
+        got = AN.forward(sd, u, c["nhead"], dtype=np.float32)
+        assert np.isfinite(ref).all() and np.isfinite(got).all()
+        e32 = max(e32, scale_err(got, ref))
+        lo += n
+    print(f"{name}: max score {stats['max_score']:.1f}, fp32 against fp64 {e32:.2e}")
+    assert stats["max_score"] > 88.7
+    with np.errstate(over="ignore"):
+        assert np.isinf(np.exp(np.float32(stats["max_score"])))
 
 
 @pytest.mark.parametrize("tag", ["et", "gen"])
@@ -220,7 +335,7 @@ def test_arguments_are_validated_on_the_host():
 
     for call in (graph, scenes):
         for bad in (dict(motion_dim=2), dict(model_dim=272), dict(model_dim=40, nhead=4), dict(nhead=3), dict(model_dim=24,
-                    nhead=4), dict(ff_dim=513), dict(ff_dim=0), dict(n_enc=0), dict(n_dec=5), dict(past_frames=17),
+                    nhead=4), dict(model_dim=32, nhead=16), dict(model_dim=96, nhead=16), dict(ff_dim=513), dict(ff_dim=0), dict(n_enc=0), dict(n_dec=5), dict(past_frames=17),
                     dict(future_frames=0), dict(forecast_dim=65), dict(forecast_dim=0)):
             assert call(_params(**bad)) == UNSUPPORTED, bad
         p = _params()
