@@ -17,8 +17,9 @@ from .pecnet import PECNet
 from .lbebm import LBEBM
 from .implicit import SocialImplicitLight
 from .agentformer import AgentFormerLight
+from .graphtern import GraphTERNLight
 from .gpgraph import GPGraph, GPGraphSGCN, GPGraphSTGCNN, get_GPGraph_SGCN_model, get_GPGraph_STGCNN_model
 
 __all__ = ["EigenTrajectory", "TrajNorm", "ETDescriptor", "ETAnchor", "BatchKMeans", "SocialSTGCNN", "SGCN", "GPGraph",
            "GPGraphSGCN", "get_GPGraph_SGCN_model", "GPGraphSTGCNN", "get_GPGraph_STGCNN_model", "SocialDMRGCN", "PECNet",
-           "LBEBM", "SocialImplicitLight", "AgentFormerLight"]
+           "LBEBM", "SocialImplicitLight", "AgentFormerLight", "GraphTERNLight"]

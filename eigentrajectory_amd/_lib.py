@@ -113,6 +113,10 @@ SIGNATURES = {
     "et_agentformer_workspace_bytes": (_Z, [_P, _I64, _I64]),
     "et_agentformer_forward_graph": (_I, [_P, _P, _I64, _P, _P, _Z, _P]),
     "et_agentformer_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _Z, _P]),
+    # ---- Graph-TERN predictor, inference
+    "et_graphtern_workspace_bytes": (_Z, [_P, _I64, _I64]),
+    "et_graphtern_forward_graph": (_I, [_P, _P, _I64, _P, _P, _Z, _P]),
+    "et_graphtern_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _Z, _P]),
     # ---- fit
     "et_fit_gram_workspace_bytes": (_Z, [_I64, _I, _I]),
     "et_fit_gram": (_I, [_P, _P, _I64, _I, _I, _I, _F, _I, _P, _P, _P, _P, _Z, _P]),
@@ -337,6 +341,28 @@ class AgentFormerParams(C.Structure):
         ("enc_embed", AgentFormerEmbed), ("dec_embed", AgentFormerEmbed), ("out_fc_weight", C.c_void_p),
         ("out_fc_bias", C.c_void_p), ("enc", AgentFormerLayer * AGENTFORMER_MAX_LAYERS),
         ("dec", AgentFormerLayer * AGENTFORMER_MAX_LAYERS)]
+
+
+GRAPHTERN_MAX_EPGCN = 4  # ET_GRAPHTERN_MAX_EPGCN
+GRAPHTERN_MAX_EPCNN = 8  # ET_GRAPHTERN_MAX_EPCNN
+
+
+class GraphTERNLayer(C.Structure):
+    """Mirror of ``et_graphtern_layer``: device pointers to one st_mrgcn block's tensors (field order: include/eigentraj.h)."""
+    _fields_ = [(name, C.c_void_p) for name in ("gcn_w", "gcn_b", "tcn_prelu", "tcn_w", "tcn_b", "res_w", "res_b", "prelu")]
+
+
+class GraphTERNEpcnn(C.Structure):
+    """Mirror of ``et_graphtern_epcnn``: device pointers to one epcnn block's tensors."""
+    _fields_ = [(name, C.c_void_p) for name in ("tpcn_w", "tpcn_b", "tpcn_a", "cpcn_w", "cpcn_b", "cpcn_a", "rest_w",
+                                                "rest_b", "resc_w", "resc_b")]
+
+
+class GraphTERNParams(C.Structure):
+    """Mirror of ``et_graphtern_params``."""
+    _fields_ = [(name, C.c_int) for name in ("n_epgcn", "n_epcnn", "input_feat", "hidden_feat", "seq_len", "pred_seq_len",
+                                             "n_smpl")] + [
+        ("tp_mrgcns", GraphTERNLayer * GRAPHTERN_MAX_EPGCN), ("tpcnns", GraphTERNEpcnn * GRAPHTERN_MAX_EPCNN)]
 
 
 STATE_BYTES = C.sizeof(KMeansState)

@@ -7,9 +7,8 @@ The reference resolves, per baseline, three hooks (`trainval.py:24-28`, `baselin
     C_pred_refine = model_forward_post_hook(output_data, addl_info)        # must be (k,N,S)
 
 and the wrapper calls them between projection and reconstruction (`EigenTrajectory/model.py:93-95`).
-Nine of the predictors are native here (stgcnn, sgcn, gpgraphsgcn, gpgraphstgcnn, dmrgcn, pecnet, lbebm, implicit and agentformer:
-eigentrajectory_amd.stgcnn, .sgcn, .gpgraph, .dmrgcn, .pecnet, .lbebm, .implicit, .agentformer); the others are third-party networks and out of scope
-(SURVEY.md §2 rows 7-9).  What this
+All ten predictors are native here (stgcnn, sgcn, gpgraphsgcn, gpgraphstgcnn, dmrgcn, pecnet, lbebm, implicit, agentformer and
+graphtern: eigentrajectory_amd.stgcnn, .sgcn, .gpgraph, .dmrgcn, .pecnet, .lbebm, .implicit, .agentformer, .graphtern).  What this
 module keeps is the *contract*, so that any of them plugs into
 :class:`eigentrajectory_amd.EigenTrajectory` unchanged::
 

@@ -270,7 +270,7 @@ class EigenTrajectory(nn.Module):
         asymmetric convolution layers; ``et_gpgraph_sgcn_forward_scenes``: 8 + that number;
         ``et_gpgraph_stgcnn_forward_scenes``: three; ``et_dmrgcn_forward_scenes``: one; ``et_pecnet_forward_scenes``: 2 + 2
         nonlocal_pools; ``et_lbebm_forward_scenes``: two; ``et_implicit_forward_scenes``: two; ``et_agentformer_forward_scenes``: 2 + 2 encoder
-        layers + 4 decoder layers), the reconstruction + metrics
+        layers + 4 decoder layers; ``et_graphtern_forward_scenes``: one), the reconstruction + metrics
         of every scene -- what the reference's test loop (utils/trainer.py:173-195) computes with one :meth:`evaluate` per
         scene.
 
@@ -284,12 +284,14 @@ class EigenTrajectory(nn.Module):
         under its own all-ones mask, as the reference's test loader hands them over), a
         :class:`~eigentrajectory_amd.lbebm.LBEBM` predictor under the ``lbebm`` hooks, a
         :class:`~eigentrajectory_amd.implicit.SocialImplicitLight` predictor under the ``implicit`` hooks or an
-        :class:`~eigentrajectory_amd.agentformer.AgentFormerLight` predictor under the ``agentformer`` hooks, in eval mode;
+        :class:`~eigentrajectory_amd.agentformer.AgentFormerLight` predictor under the ``agentformer`` hooks or a
+        :class:`~eigentrajectory_amd.graphtern.GraphTERNLight` predictor under the ``graphtern`` hooks, in eval mode;
         any other predictor or pairing raises (use :meth:`evaluate` scene by scene)."""
         from .agentformer import AgentFormerLight
         from .bridges import BRIDGES
         from .dmrgcn import SocialDMRGCN
         from .gpgraph import GPGraph
+        from .graphtern import GraphTERNLight
         from .implicit import SocialImplicitLight
         from .lbebm import LBEBM
         from .pecnet import PECNet
@@ -305,7 +307,8 @@ class EigenTrajectory(nn.Module):
                                            (PECNet, "pecnet", ops.pecnet_forward_scenes, None),
                                            (LBEBM, "lbebm", ops.lbebm_forward_scenes, None),
                                            (SocialImplicitLight, "implicit", ops.implicit_forward_scenes, None),
-                                           (AgentFormerLight, "agentformer", ops.agentformer_forward_scenes, None)):
+                                           (AgentFormerLight, "agentformer", ops.agentformer_forward_scenes, None),
+                                           (GraphTERNLight, "graphtern", ops.graphtern_forward_scenes, None)):
             pre, fwd, post = BRIDGES[name]
             if (isinstance(self.baseline_model, cls) and hooks.model_forward_pre_hook is pre
                     and hooks.model_forward is fwd and hooks.model_forward_post_hook is post
@@ -318,7 +321,8 @@ class EigenTrajectory(nn.Module):
                                       "a SocialDMRGCN predictor under the 'dmrgcn' hooks, a PECNet predictor under the "
                                       "'pecnet' hooks, an LBEBM predictor under the 'lbebm' hooks, a SocialImplicitLight "
                                       "predictor under the 'implicit' hooks and an AgentFormerLight predictor under the "
-                                      "'agentformer' hooks only; call evaluate() scene by scene for other predictors")
+                                      "'agentformer' hooks only; call evaluate() scene by scene for other predictors "
+                                      "(a GraphTERNLight predictor under the 'graphtern' hooks takes the whole-split path too)")
         if self.baseline_model.training:
             raise RuntimeError("evaluate_split: the predictor is in training mode; call .eval() first")
         sse = torch.as_tensor(seq_start_end).detach().cpu().long().reshape(-1, 2)

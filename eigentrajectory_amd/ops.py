@@ -766,6 +766,53 @@ def agentformer_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details
     return (out, {"graph_inputs": gin}) if want_details else out
 
 
+# ------------------------------------------------------------------------------ Graph-TERN predictor (inference)
+def _graphtern_ws(params, n, max_n, dev):
+    nbytes = L.lib().et_graphtern_workspace_bytes(C.byref(params), n, max_n)
+    return (torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None), nbytes
+
+
+def graphtern_forward_graph(model, S_obs):
+    """``model`` (:class:`eigentrajectory_amd.graphtern.GraphTERNLight`, eval mode) on one scene as the graphtern bridge
+    hands it over: S_obs (1, 2, T, N, 1) = [abs, rel], both read as given -> the raw output (1, k, N, S).  One launch."""
+    params, dev = model.et_params()
+    T, k, S = params.seq_len, params.pred_seq_len, params.n_smpl
+    n = S_obs.shape[3] if S_obs.dim() == 5 else -1
+    if tuple(S_obs.shape) != (1, 2, T, n, 1):
+        raise ValueError(f"graphtern_forward_graph: S_obs {tuple(S_obs.shape)} is not (1,2,{T},N,1)")
+    (S_obs,) = _dev_args(dev, S_obs)
+    out = torch.empty((1, k, n, S), device=dev)
+    ws, nbytes = _graphtern_ws(params, n, n, dev)
+    L.call("et_graphtern_forward_graph", C.byref(params), L.ptr(S_obs), n, L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
+    return out
+
+
+def graphtern_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
+    """The graphtern bridge + ``model`` (eval mode) + the post-hook for every scene of a split in ONE launch: C_obs (k, N)
+    and nrm (4, N) of :func:`norm_project` (rows 0-1: the last observed positions, centred here per scene), ``scene_sizes``
+    pedestrians per scene in row order (None = one scene; an empty list takes N = 0) -> C_pred_refine (k, N, S).  With
+    ``want_details`` also a dict: ``graph_inputs`` (T, N), the fp32 u = [C_obs; obs_ori] the kernel used."""
+    params, dev = model.et_params()
+    C_obs, nrm = _dev_args(dev, C_obs, nrm)
+    k, n = C_obs.shape
+    if k != params.pred_seq_len or nrm.dim() != 2 or nrm.shape[0] < 2 or nrm.shape[1] != n:
+        raise ValueError(f"graphtern_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
+                         f"k = {params.pred_seq_len}")
+    if scene_sizes is not None:
+        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
+        if not sizes and n:
+            raise ValueError(f"graphtern_forward_scenes: no scenes for {n} rows")
+        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
+        max_n = max(sizes, default=0)
+    else:
+        sizes, off, max_n = None, None, n
+    out = torch.empty((k, n, params.n_smpl), device=dev)
+    gin = torch.empty((params.seq_len, n), device=dev) if want_details else None
+    ws, nbytes = _graphtern_ws(params, n, max_n, dev)
+    L.call("et_graphtern_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
+           0 if off is None else len(sizes), L.ptr(out), L.ptr(gin), L.ptr(ws), nbytes, L.stream(dev))
+    return (out, {"graph_inputs": gin}) if want_details else out
+
 # ------------------------------------------------------------------------------ PECNet / LBEBM predictors (inference)
 def _mlp_ws(kind, params, n, dev):
     nbytes = getattr(L.lib(), f"et_{kind}_workspace_bytes")(C.byref(params), n)

@@ -758,6 +758,74 @@ int et_agentformer_forward_scenes(const et_agentformer_params *params, const flo
                                   const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *graph_inputs,
                                   void *workspace, size_t workspace_bytes, et_stream_t stream);
 
+/* ---- Graph-TERN predictor, inference (baseline/graphtern: bridge.py pre-hook + graph_tern_light.forward + post-hook) ----
+ * Eval mode only (no drop_edge, no dropout); the network has no BatchNorm.  The parameters are read in place from the
+ * module's own tensors through the pointer tables below (fp32, contiguous).  Field <-> state_dict name (i = st_mrgcn
+ * block, j = epcnn block):
+ *   tp_mrgcns[i].gcn_w / gcn_b      tp_mrgcns.{i}.gcn.conv.weight (64, C_in, 1, 1) / .bias (64): relation r on channel r 16 + c
+ *   tp_mrgcns[i].tcn_prelu          tp_mrgcns.{i}.tcn.0.weight (1)
+ *   tp_mrgcns[i].tcn_w / tcn_b      tp_mrgcns.{i}.tcn.1.weight (16, 16, 3, 1) / .bias (16)
+ *   tp_mrgcns[i].res_w / res_b      tp_mrgcns.{i}.residual.0.weight (16, C_in, 1, 1) / .bias (16); NULL when C_in == 16
+ *   tp_mrgcns[i].prelu              tp_mrgcns.{i}.prelu.weight (1): carried so that the table is complete; the network
+ *                                   (use_mdn) never applies it and the kernel never reads it
+ *   tpcnns[j].tpcn_w / tpcn_b       tpcnns.{j}.tpcns.0.0.weight (k, j == 0 ? T : k, 3, 3) / .bias (k)
+ *   tpcnns[j].tpcn_a                tpcnns.{j}.tpcns.0.1.weight (1)
+ *   tpcnns[j].cpcn_w / cpcn_b       tpcnns.{j}.cpcns.0.0.weight (C_out, 16, 3, 3) / .bias (C_out)
+ *   tpcnns[j].cpcn_a                tpcnns.{j}.cpcns.0.1.weight (1)
+ *   tpcnns[j].rest_w / rest_b       tpcnns.0.restconv.0.weight (k, T, 1, 1) / .bias (k); NULL for j > 0
+ *   tpcnns[j].resc_w / resc_b       tpcnns.{n_epcnn-1}.rescconv.0.weight (S, 16, 1, 1) / .bias (S); NULL for the other
+ *                                   blocks, and for the last one too when S == 16 (identity)
+ * with T = seq_len, k = pred_seq_len, S = n_smpl, C_in = 1 in block 0 and 16 afterwards, C_out = S in the last epcnn block
+ * and 16 before it.
+ * Supported: input_feat = 1, hidden_feat = 16, seq_len = pred_seq_len + 2, 1 <= pred_seq_len <= ET_MAX_K, 1 <= n_smpl <= 64,
+ * 1 <= n_epgcn <= ET_GRAPHTERN_MAX_EPGCN, 2 <= n_epcnn <= ET_GRAPHTERN_MAX_EPCNN; anything else: ET_ERR_UNSUPPORTED.  A
+ * missing pointer (or a residual table that does not fit the shapes): ET_ERR_INVALID_ARG.
+ *
+ * The graphs (model.py:7-15): per time row four relations [A_abs, A_rel, 1 / A_abs, 1 / A_rel], A_abs[i,j] = |u[t,i] -
+ * u[t,j]|, A_rel the same on rel (rel[0] = 0, rel[t] = u[t] - u[t-1]); an inverse is 0 where the distance is EXACTLY 0 (an
+ * fp32 comparison of the fp32 distance, the reference's own decision, no tolerance band); per (r, t): D^-1/2 (A + I)
+ * D^-1/2 with D = rowsum(A + I), in the reference's (D (A + I)) D order.  Division and square root are IEEE.  The epcnn
+ * blocks' 3x3 convolutions pad by replication, clamped at the scene's own first and last pedestrian.
+ *   et_graphtern_forward_graph   one scene as the bridge hands it over: S_obs (1,2,T,N,1) = [abs, rel], both read as given
+ *                                -> out (1,k,N,S), the network's raw output.  N <= ET_SCENE_MAX_N.
+ *   et_graphtern_forward_scenes  a whole split: C_obs (k,N), nrm (4,N) of et_norm_project; per scene u = [C_obs; nrm[0:2] -
+ *                                their mean over the scene], summed in et_scene_project's order; rel, the distances and
+ *                                their inverses are formed where they are used, the (4,T,n,n) stack is never stored ->
+ *                                C_pred_refine (k,N,S).  scene_offsets as et_traj_metrics (NULL = one scene of N rows);
+ *                                n_scenes = 0 takes N = 0 only.  Optional output graph_inputs (T,N) float (may be NULL):
+ *                                the fp32 u the kernel used, scene s at columns [off[s], off[s+1]).  One launch.
+ * Workspace: a scene whose activations fit a workgroup's LDS arena (at S = 20, k = 6: up to 35 pedestrians) needs none;
+ * larger ones use workspace rows [off[s], off[s+1]) of et_graphtern_workspace_bytes(p, N, max_scene_n) bytes (0 when a
+ * scene of max_scene_n pedestrians fits the arena).  A scene larger than ET_SCENE_MAX_N, or one that fits neither, is
+ * not computed: its outputs are NaN.  No host synchronisation, no allocation: the calls can be captured in a graph.
+ * Every sum has a fixed order: a scene's result does not depend on the scenes around it or on where its arena lies. */
+#define ET_GRAPHTERN_MAX_EPGCN 4
+#define ET_GRAPHTERN_MAX_EPCNN 8
+typedef struct et_graphtern_layer {
+    const float *gcn_w, *gcn_b;
+    const float *tcn_prelu;
+    const float *tcn_w, *tcn_b;
+    const float *res_w, *res_b;
+    const float *prelu;
+} et_graphtern_layer;
+typedef struct et_graphtern_epcnn {
+    const float *tpcn_w, *tpcn_b, *tpcn_a;
+    const float *cpcn_w, *cpcn_b, *cpcn_a;
+    const float *rest_w, *rest_b;
+    const float *resc_w, *resc_b;
+} et_graphtern_epcnn;
+typedef struct et_graphtern_params {
+    int n_epgcn, n_epcnn, input_feat, hidden_feat, seq_len, pred_seq_len, n_smpl;
+    et_graphtern_layer tp_mrgcns[ET_GRAPHTERN_MAX_EPGCN];
+    et_graphtern_epcnn tpcnns[ET_GRAPHTERN_MAX_EPCNN];
+} et_graphtern_params;
+size_t et_graphtern_workspace_bytes(const et_graphtern_params *params, int64_t N, int64_t max_scene_n);
+int et_graphtern_forward_graph(const et_graphtern_params *params, const float *S_obs, int64_t N, float *out,
+                               void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_graphtern_forward_scenes(const et_graphtern_params *params, const float *C_obs, const float *nrm, int64_t N,
+                                const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *graph_inputs,
+                                void *workspace, size_t workspace_bytes, et_stream_t stream);
+
 /* ---- fit ----------------------------------------------------------------------------
  * Gram matrices of the normalised trajectories routed to descriptor `which`
  * (1 moving / 0 static) under `mode`:  G_obs (2T_obs,2T_obs), G_pred (2T_pred,2T_pred)
