@@ -109,6 +109,10 @@ SIGNATURES = {
     "et_lbebm_workspace_bytes": (_Z, [_P, _I64]),
     "et_lbebm_predict": (_I, [_P, _P, _P, _I64, _P, _P, _Z, _P]),
     "et_lbebm_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _Z, _P]),
+    # ---- LBEBM predictor, training
+    "et_lbebm_train_workspace_bytes": (_Z, [_P, _I64]),
+    "et_lbebm_train_fwd": (_I, [_P, _P, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _Z, _P]),
+    "et_lbebm_train_bwd": (_I, [_P, _P, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _Z, _P]),
     # ---- AgentFormer predictor, inference
     "et_agentformer_workspace_bytes": (_Z, [_P, _I64, _I64]),
     "et_agentformer_forward_graph": (_I, [_P, _P, _I64, _P, _P, _Z, _P]),
@@ -314,6 +318,16 @@ class MLPParams(C.Structure):
 
 AGENTFORMER_MAX_LAYERS = 4     # ET_AGENTFORMER_MAX_LAYERS
 AGENTFORMER_MAX_SCENE_N = 128  # ET_AGENTFORMER_MAX_SCENE_N
+
+
+class MLPChainGrads(C.Structure):
+    """Mirror of ``et_mlp_chain_grads``: where one chain's weight and bias gradients go (device pointers)."""
+    _fields_ = [("dw", C.c_void_p * MLP_MAX_LAYERS), ("db", C.c_void_p * MLP_MAX_LAYERS)]
+
+
+class LBEBMGrads(C.Structure):
+    """Mirror of ``et_lbebm_grads``."""
+    _fields_ = [(name, MLPChainGrads) for name in ("encoder_past", "encoder_dest", "predictor")]
 
 
 class AgentFormerAttn(C.Structure):

@@ -901,6 +901,75 @@ def lbebm_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False
     return _mlp_forward_scenes("lbebm", model, C_obs, nrm, scene_sizes, want_details)
 
 
+# ------------------------------------------------------------------------------------- LBEBM predictor (training)
+def _mlp_strided(who, dev, width, **tensors):
+    """(N, width_i) float32 tensors on ``dev``, all of one N, as the kernels read them in place: a row-major tensor or the
+    transposed view of one (the bridge's ``C_obs.T``) stays as it is, anything else is copied"""
+    out = []
+    for t in tensors.values():
+        t = t.detach()
+        if t.device != dev or t.dtype != torch.float32:
+            t = t.to(device=dev, dtype=torch.float32)
+        if t.dim() == 2 and not (t.is_contiguous() or t.t().is_contiguous()):
+            t = t.contiguous()
+        out.append(t)
+    n = out[0].shape[0]
+    for name, t, w in zip(tensors, out, width):
+        if t.dim() != 2 or tuple(t.shape) != (n, w):
+            raise ValueError(f"{who}: {name} {tuple(t.shape)} is not ({n}, {w})")
+    return n, out
+
+
+def lbebm_train_fwd(model, past, generated_dest):
+    """``model`` (:class:`eigentrajectory_amd.lbebm.LBEBM`): past (N, 2 past_length), generated_dest (N, 2 sub-goals), read
+    in place through their strides -> (out, saved): out (N, out_width) is :func:`lbebm_predict`'s, bit for bit, in the same
+    2 launches; ``saved`` (float32, flat) holds the activations :func:`lbebm_train_bwd` needs (layout: include/eigentraj.h,
+    "LBEBM predictor, training")."""
+    params, dev = model.et_params()
+    n, (past, dest) = _mlp_strided("lbebm_train_fwd", dev, (params.encoder_past.widths[0], params.encoder_dest.widths[0]),
+                                   past=past, generated_dest=generated_dest)
+    out = torch.empty((n, params.out_width), device=dev)
+    saved = torch.empty((L.lib().et_lbebm_train_workspace_bytes(C.byref(params), n) // 4,), device=dev)
+    L.call("et_lbebm_train_fwd", C.byref(params), L.ptr(past), past.stride(0), past.stride(1), L.ptr(dest), dest.stride(0),
+           dest.stride(1), n, L.ptr(out), L.ptr(saved), None, 0, L.stream(dev))
+    return out, saved
+
+
+def lbebm_train_bwd(model, past, generated_dest, saved, g_out, need_input_grads=False):
+    """The backward pass of :func:`lbebm_train_fwd` in 3 launches: ``saved`` as that call returned it (same ``model``
+    weights, same inputs), ``g_out`` (N, out_width) the gradient at its ``out`` -> a dict keyed by the module's parameter
+    names (``encoder_past.layers.0.weight``, ...) of fresh tensors holding the gradients (nothing is accumulated), plus
+    ``past`` / ``dest``, laid out like the inputs, when ``need_input_grads`` (a bool, or one per input) asks for them."""
+    params, dev = model.et_params()
+    n, (past, dest) = _mlp_strided("lbebm_train_bwd", dev, (params.encoder_past.widths[0], params.encoder_dest.widths[0]),
+                                   past=past, generated_dest=generated_dest)
+    (g_out,) = _dev_args(dev, g_out)
+    nbytes = L.lib().et_lbebm_train_workspace_bytes(C.byref(params), n)
+    if tuple(g_out.shape) != (n, params.out_width):
+        raise ValueError(f"lbebm_train_bwd: g_out {tuple(g_out.shape)} is not ({n}, {params.out_width})")
+    if saved.device != dev or saved.dtype != torch.float32 or not saved.is_contiguous() or saved.numel() * 4 < nbytes:
+        raise ValueError(f"lbebm_train_bwd: saved is not the {nbytes // 4} float32 values lbebm_train_fwd returned for "
+                         f"{n} rows")
+    want_past, want_dest = (need_input_grads if isinstance(need_input_grads, (tuple, list)) else (need_input_grads,) * 2)
+    # one tensor per gradient: autograd's accumulation takes a fresh, unshared tensor over as .grad without a copy
+    out = {name: torch.empty_like(t) for name, t in zip(model.chain_parameter_names(), model.chain_parameters())}
+    grads = L.LBEBMGrads()
+    for chain in model.CHAINS:
+        g = getattr(grads, chain)
+        for i in range(len(getattr(model, chain).layers)):
+            g.dw[i] = out[f"{chain}.layers.{i}.weight"].data_ptr()
+            g.db[i] = out[f"{chain}.layers.{i}.bias"].data_ptr()
+    if want_past:
+        out["past"] = torch.empty_strided(past.shape, past.stride(), device=dev)
+    if want_dest:
+        out["dest"] = torch.empty_strided(dest.shape, dest.stride(), device=dev)
+    ws = torch.empty((nbytes // 4,), device=dev)
+    L.call("et_lbebm_train_bwd", C.byref(params), L.ptr(past), past.stride(0), past.stride(1), L.ptr(dest), dest.stride(0),
+           dest.stride(1), n, L.ptr(saved), L.ptr(g_out), C.byref(grads), L.ptr(out.get("past")), L.ptr(out.get("dest")),
+           L.ptr(ws), nbytes, L.stream(dev))
+    return out
+
+
 # ----------------------------------------------------------------------- curve fitting
 def curve_fit_batch(trajs, bases, steps=100000, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, want_cp=False, want_loss=False):
     """CurveModel/curve_fitting.py for a batch of fits: fit f fits basis ``bases[f]`` (T_f, ncp_f) to every trajectory of

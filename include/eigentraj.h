@@ -684,6 +684,48 @@ int et_lbebm_forward_scenes(const et_mlp_params *params, const float *C_obs, con
                             const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *net_inputs,
                             void *workspace, size_t workspace_bytes, et_stream_t stream);
 
+/* ---- LBEBM predictor, training (what the lbebm bridge runs in training too: LBEBM.predict) -------------------------------
+ * Forward with the activations kept, and the backward pass, of predictor(encoder_past(past) | encoder_dest(dest)).  Notation
+ * for a chain of L layers: a_0 the input, z_i = a_{i-1} W_i^T + b_i, a_i = relu(z_i) for i < L, the output z_L.
+ *   et_lbebm_train_fwd   out (N, out_width) = et_lbebm_predict's, bit for bit, in the same 2 launches; `saved` receives the
+ *                        two encoders' outputs and every a_i, 0 < i < L.  The workspace is not used (NULL / 0 are fine).
+ *   et_lbebm_train_bwd   from g_out (N, out_width), the gradient at `out`: every dW_i (widths[i], widths[i-1]) = g_z(i)^T
+ *                        a_{i-1} and db_i = the column sums of g_z(i), with g_z(L) = g_out, g_a(i-1) = g_z(i) W_i and
+ *                        g_z(i-1) = g_a(i-1) where a_{i-1} > 0, else 0 (an activation of exactly 0 passes nothing); the
+ *                        predictor's input gradient splits at column fdim into the two encoders' output gradients.
+ *                        `grads` names where they go: the buffers are OVERWRITTEN (accumulation is the caller's).  g_past /
+ *                        g_dest (may be NULL: not computed) receive the input gradients, element (row, c) at the input's
+ *                        own offset row * rs + c * cs.  3 launches whatever N and the widths: the
+ *                        predictor's rows, both encoders' rows, every dW / db.
+ * past / dest are read in place through their strides (in elements; element (row, c) at p[row * rs + c * cs], both >= 0):
+ * the bridge hands over transposed views.  `saved` and the workspace have ONE layout and ONE size,
+ * et_lbebm_train_workspace_bytes(params, N) bytes each (0 for parameters outside the family), in floats, every block
+ * starting on a multiple of 4 floats (a block of (N, w) takes N w rounded up to 4):
+ *   encoder_past's output (N, fdim) | encoder_dest's output (N, fdim) | encoder_past a_1 .. a_{L-1}, each (N, widths[i]) |
+ *   encoder_dest a_1 .. a_{L-1} | predictor a_1 .. a_{L-1}
+ * the workspace holding, at the same places, the gradients at those values (g_z(i) for an a_i).  Every dot product is one
+ * fp32 fmaf chain on the f32-input MFMA from a zero accumulator: over a layer's outputs ascending for g_a, over ALL rows 0
+ * .. N-1 ascending for dW and db -- no atomics, no partial sums, so a value is a function of the data alone, two runs agree
+ * bit for bit, and a row's g_z and input gradients do not depend on the other rows or on N.  Rows past N and columns past a
+ * width are taken as zeros; nothing uninitialised is read.  Supported: et_lbebm_predict's family (2 to ET_MLP_MAX_LAYERS
+ * layers, widths 1 to ET_MLP_MAX_WIDTH); anything else ET_ERR_UNSUPPORTED before any launch; a missing pointer
+ * ET_ERR_INVALID_ARG; a short workspace ET_ERR_WORKSPACE.  N = 0: the forward does nothing, the backward writes zeros.  No
+ * host synchronisation, no allocation. */
+typedef struct et_mlp_chain_grads {
+    float *dw[ET_MLP_MAX_LAYERS], *db[ET_MLP_MAX_LAYERS];
+} et_mlp_chain_grads;
+typedef struct et_lbebm_grads {
+    et_mlp_chain_grads encoder_past, encoder_dest, predictor;
+} et_lbebm_grads;
+size_t et_lbebm_train_workspace_bytes(const et_mlp_params *params, int64_t N);
+int et_lbebm_train_fwd(const et_mlp_params *params, const float *past, int64_t past_rs, int64_t past_cs, const float *dest,
+                       int64_t dest_rs, int64_t dest_cs, int64_t N, float *out, float *saved, void *workspace,
+                       size_t workspace_bytes, et_stream_t stream);
+int et_lbebm_train_bwd(const et_mlp_params *params, const float *past, int64_t past_rs, int64_t past_cs, const float *dest,
+                       int64_t dest_rs, int64_t dest_cs, int64_t N, const float *saved, const float *g_out,
+                       const et_lbebm_grads *grads, float *g_past, float *g_dest, void *workspace, size_t workspace_bytes,
+                       et_stream_t stream);
+
 /* ---- AgentFormer predictor, inference (baseline/agentformer: bridge.py hooks + AgentFormerLight.forward) -------------
  * Eval mode, the ET configuration family: input_type = ['pos'], pred_type = 'pos', nz = 0, no learnt prior, pos_concat,
  * no agent encoding, dot-product scores (gaussian_kernel off) with separate same-agent projections (sep_attn on), an
