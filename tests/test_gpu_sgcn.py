@@ -5,7 +5,8 @@ the restatement's, (c) the device's output equals the restatement run with the d
 1e-5 of the largest entry -- and the band may hold at most 0.5 % of a scene's entries (1e-4 of a split's).  Checked: the
 graph form on the reference's recorded scenes (tests/golden/g20_sgcn_net.npz) and on the generic layer counts, the
 identities' broadcast forms, ragged sizes, the scenes form, whole splits end to end against the reference's
-per-pedestrian ADE / FDE, the hook path eagerly and replayed, errors and empty inputs."""
+per-pedestrian ADE / FDE, the hook path eagerly and replayed, errors and empty inputs.
+Other members of the family (T from 3 to 34, 1 to 8 layers, S 1 to 64, scenes up to 512, 300 scenes): tests/test_gpu_sgcn_shapes.py."""
 import numpy as np
 import pytest
 import torch
