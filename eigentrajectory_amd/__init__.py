@@ -13,7 +13,7 @@ from .kmeans import BatchKMeans
 from .stgcnn import SocialSTGCNN
 from .sgcn import SGCN
 from .dmrgcn import SocialDMRGCN
-from .pecnet import PECNet
+from .pecnet import PECNet, enable_native_training
 from .lbebm import LBEBM
 from .implicit import SocialImplicitLight
 from .agentformer import AgentFormerLight
@@ -22,4 +22,4 @@ from .gpgraph import GPGraph, GPGraphSGCN, GPGraphSTGCNN, get_GPGraph_SGCN_model
 
 __all__ = ["EigenTrajectory", "TrajNorm", "ETDescriptor", "ETAnchor", "BatchKMeans", "SocialSTGCNN", "SGCN", "GPGraph",
            "GPGraphSGCN", "get_GPGraph_SGCN_model", "GPGraphSTGCNN", "get_GPGraph_STGCNN_model", "SocialDMRGCN", "PECNet",
-           "LBEBM", "SocialImplicitLight", "AgentFormerLight", "GraphTERNLight"]
+           "LBEBM", "SocialImplicitLight", "AgentFormerLight", "GraphTERNLight", "enable_native_training"]

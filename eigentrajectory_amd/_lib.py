@@ -113,6 +113,12 @@ SIGNATURES = {
     "et_lbebm_train_workspace_bytes": (_Z, [_P, _I64]),
     "et_lbebm_train_fwd": (_I, [_P, _P, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _Z, _P]),
     "et_lbebm_train_bwd": (_I, [_P, _P, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    # ---- PECNet predictor, training
+    "et_pecnet_train_saved_bytes": (_Z, [_P, _I64]),
+    "et_pecnet_train_workspace_bytes": (_Z, [_P, _I64]),
+    "et_pecnet_train_fwd": (_I, [_P, _P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I64, _P, _P, _P, _Z, _P]),
+    "et_pecnet_train_bwd": (_I, [_P, _P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P,
+                                 _Z, _P]),
     # ---- AgentFormer predictor, inference
     "et_agentformer_workspace_bytes": (_Z, [_P, _I64, _I64]),
     "et_agentformer_forward_graph": (_I, [_P, _P, _I64, _P, _P, _Z, _P]),
@@ -328,6 +334,12 @@ class MLPChainGrads(C.Structure):
 class LBEBMGrads(C.Structure):
     """Mirror of ``et_lbebm_grads``."""
     _fields_ = [(name, MLPChainGrads) for name in ("encoder_past", "encoder_dest", "predictor")]
+
+
+class PECNetGrads(C.Structure):
+    """Mirror of ``et_pecnet_grads``."""
+    _fields_ = [(name, MLPChainGrads) for name in ("encoder_past", "encoder_dest", "non_local_theta", "non_local_phi",
+                                                   "non_local_g", "predictor")]
 
 
 class AgentFormerAttn(C.Structure):

@@ -15,7 +15,7 @@
 //   first layer gathers its input from up to three sources side by side (element (row, c) at p[row rs + c cs]).
 //   In the scene form the encoder_dest chain's workgroups form their rows' obs_ori themselves (the scene's mean in
 //   scene_v's summation order), use it as their input and store it for the later launches and the caller.
-// nonlocal_pool_kernel   one wavefront per row: the row's logits against every phi row of its range (fp32 fmaf, ascending),
+// nonlocal_pool_kernel   (et_mlp_chain.inl as well; here its AtLaunch form) one wavefront per row: the row's logits against every phi row of its range (fp32 fmaf, ascending),
 //   softmax over the whole range, times the mask, / max(sum |w|, 1e-12), times g, + feat.  The range is the row's scene
 //   (or all N rows in the module form); a range longer than ET_MLP_MAX_RANGE is not computed: its rows are NaN.
 #include "et_common.h"
@@ -25,70 +25,7 @@ namespace {
 
 #include "et_scene_helpers.inl"  // scene_of_row, up4, kSnThreads
 
-#include "et_mlp_chain.inl"  // the launch structures, mlp_chain_kernel, the parameter checks (shared with et_mlp_train.hip)
-
-constexpr int kAtRows = kMlWaves;  // rows per workgroup of the pooling kernel, one per wavefront
-constexpr int kAtLdsBytes = kAtRows * ET_MLP_MAX_RANGE * 4;
-
-struct AtLaunch {
-    const float *theta, *phi, *g;  // (N, D), (N, D), (N, F)
-    int D, F, n_src;
-    MlSrc src[3];       // feat (N, F), gathered
-    const float *mask;  // (N, N) or null
-    const int32_t *off;
-    int n_scenes;
-    int64_t N;
-    float *out;  // (N, F)
-};
-
-__global__ __launch_bounds__(kMlThreads) void nonlocal_pool_kernel(AtLaunch A) {
-    extern __shared__ float lds[];
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const int64_t N = A.N, row = (int64_t)blockIdx.x * kAtRows + wave;
-    float *lg = lds + wave * ET_MLP_MAX_RANGE;
-    int s = 0;
-    int64_t b = 0, e = 0;
-    if (row < N) range_of_row(A.off, A.n_scenes, N, row, s, b, e);
-    const bool fits = e - b <= ET_MLP_MAX_RANGE;
-    const int n = (row < N && fits) ? (int)(e - b) : 0;
-    const int D = A.D, F = A.F;
-
-    const float *th = A.theta + row * D;
-    float m = -INFINITY;
-    for (int j = lane; j < n; j += kWave) {
-        const float *ph = A.phi + (b + j) * D;
-        float acc = 0.f;
-        for (int c = 0; c < D; ++c) acc = fmaf(th[c], ph[c], acc);
-        lg[j] = acc;
-        m = fmaxf(m, acc);
-    }
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    float z = 0.f;
-    for (int j = lane; j < n; j += kWave) {
-        const float ex = expf(lg[j] - m);
-        lg[j] = ex;
-        z += ex;
-    }
-    for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o);
-    float l1 = 0.f;
-    for (int j = lane; j < n; j += kWave) {
-        float w = lg[j] / z;
-        if (A.mask) w = w * A.mask[row * N + b + j];
-        lg[j] = w;
-        l1 += fabsf(w);
-    }
-    for (int o = 32; o > 0; o >>= 1) l1 += __shfl_xor(l1, o);
-    const float den = fmaxf(l1, 1e-12f);
-    for (int j = lane; j < n; j += kWave) lg[j] = lg[j] / den;
-    __syncthreads();  // (every wavefront gets here: no early exit above) the row's weights are in LDS
-    if (row < N) {
-        for (int c = lane; c < F; c += kWave) {
-            float acc = 0.f;
-            for (int j = 0; j < n; ++j) acc = fmaf(lg[j], A.g[(b + j) * F + c], acc);
-            A.out[row * F + c] = fits ? acc + gather(A.src, A.n_src, row, c) : __builtin_nanf("");
-        }
-    }
-}
+#include "et_mlp_chain.inl"  // the launch structures, both kernels, the parameter checks (shared with et_mlp_train.hip)
 
 // the workspace, in floats: every block starts on a multiple of 4
 struct MlWs {
@@ -124,7 +61,7 @@ static int lds_attributes() {
     if (ok) return ET_OK;
     ET_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(mlp_chain_kernel<MlLaunch>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, kMlLdsBytes));
-    ET_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(nonlocal_pool_kernel),
+    ET_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(nonlocal_pool_kernel<AtLaunch>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, kAtLdsBytes));
     ok = true;
     return ET_OK;
@@ -180,7 +117,7 @@ static int ml_run(const et_mlp_params &p, const float *past, const float *dest, 
         for (int s = 0; s < n_feat; ++s) A.src[s] = feat[s];
         A.mask = mask, A.off = off, A.n_scenes = n_scenes, A.N = N;
         A.out = ws + W.feat[r & 1];
-        hipLaunchKernelGGL(nonlocal_pool_kernel, dim3((unsigned)((N + kAtRows - 1) / kAtRows)), dim3(kMlThreads),
+        hipLaunchKernelGGL(nonlocal_pool_kernel<AtLaunch>, dim3((unsigned)((N + kAtRows - 1) / kAtRows)), dim3(kMlThreads),
                            kAtLdsBytes, stream, A);
         ET_LAUNCH_CHECK();
         feat[0] = rows_of(A.out, F);

@@ -1,8 +1,9 @@
-// et_mlp_chain.inl -- what et_mlp.hip (inference) and et_mlp_train.hip (training) share: the launch structures, the body of
-// the chain kernel and the parameter checks.  #included inside namespace et { namespace { ... } } after
+// et_mlp_chain.inl -- what et_mlp.hip (inference) and et_mlp_train.hip (training) share: the launch structures, the bodies of
+// the chain kernel and of the pooling kernel, and the parameter checks.  #included inside namespace et { namespace { ... } } after
 // et_scene_helpers.inl.  mlp_chain_kernel<MlLaunch> is the inference kernel (et_mlp.hip's header describes it);
 // mlp_chain_kernel<MlTrainLaunch> additionally stores every hidden layer's activations (a compile-time variant: the
-// inference kernel's code has no switch for it).
+// inference kernel's code has no switch for it).  nonlocal_pool_kernel<AtLaunch> / <AtTrainLaunch> likewise: the training form
+// also stores the features it gathered.
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -204,6 +205,83 @@ __global__ __launch_bounds__(kMlThreads) void mlp_chain_kernel(Launch L) {
         float *t = cur;
         cur = nxt;
         nxt = t;
+    }
+}
+
+constexpr int kAtRows = kMlWaves;  // rows per workgroup of the pooling kernel, one per wavefront
+constexpr int kAtLdsBytes = kAtRows * ET_MLP_MAX_RANGE * 4;
+
+struct AtLaunch {
+    static constexpr bool kKeep = false;
+    const float *theta, *phi, *g;  // (N, D), (N, D), (N, F)
+    int D, F, n_src;
+    MlSrc src[3];       // feat (N, F), gathered
+    const float *mask;  // (N, N) or null
+    const int32_t *off;
+    int n_scenes;
+    int64_t N;
+    float *out;  // (N, F)
+};
+
+// the training forward's launch: feat_keep (N, F) or null receives the gathered feat (round 0's concatenation)
+struct AtTrainLaunch : AtLaunch {
+    static constexpr bool kKeep = true;
+    float *feat_keep;
+};
+
+template <class Launch>
+__global__ __launch_bounds__(kMlThreads) void nonlocal_pool_kernel(Launch A) {
+    extern __shared__ float lds[];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const int64_t N = A.N, row = (int64_t)blockIdx.x * kAtRows + wave;
+    float *lg = lds + wave * ET_MLP_MAX_RANGE;
+    int s = 0;
+    int64_t b = 0, e = 0;
+    if (row < N) range_of_row(A.off, A.n_scenes, N, row, s, b, e);
+    const bool fits = e - b <= ET_MLP_MAX_RANGE;
+    const int n = (row < N && fits) ? (int)(e - b) : 0;
+    const int D = A.D, F = A.F;
+
+    const float *th = A.theta + row * D;
+    float m = -INFINITY;
+    for (int j = lane; j < n; j += kWave) {
+        const float *ph = A.phi + (b + j) * D;
+        float acc = 0.f;
+        for (int c = 0; c < D; ++c) acc = fmaf(th[c], ph[c], acc);
+        lg[j] = acc;
+        m = fmaxf(m, acc);
+    }
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    float z = 0.f;
+    for (int j = lane; j < n; j += kWave) {
+        const float ex = expf(lg[j] - m);
+        lg[j] = ex;
+        z += ex;
+    }
+    for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o);
+    float l1 = 0.f;
+    for (int j = lane; j < n; j += kWave) {
+        float w = lg[j] / z;
+        if (A.mask) w = w * A.mask[row * N + b + j];
+        lg[j] = w;
+        l1 += fabsf(w);
+    }
+    for (int o = 32; o > 0; o >>= 1) l1 += __shfl_xor(l1, o);
+    const float den = fmaxf(l1, 1e-12f);
+    for (int j = lane; j < n; j += kWave) lg[j] = lg[j] / den;
+    __syncthreads();  // (every wavefront gets here: no early exit above) the row's weights are in LDS
+    if (row < N) {
+        for (int c = lane; c < F; c += kWave) {
+            float acc = 0.f;
+            for (int j = 0; j < n; ++j) acc = fmaf(lg[j], A.g[(b + j) * F + c], acc);
+            if constexpr (Launch::kKeep) {  // (the training entries refuse a range that does not fit)
+                const float fv = gather(A.src, A.n_src, row, c);
+                A.out[row * F + c] = acc + fv;
+                if (A.feat_keep) A.feat_keep[row * F + c] = fv;
+            } else {
+                A.out[row * F + c] = fits ? acc + gather(A.src, A.n_src, row, c) : __builtin_nanf("");
+            }
+        }
     }
 }
 

@@ -970,6 +970,71 @@ def lbebm_train_bwd(model, past, generated_dest, saved, g_out, need_input_grads=
     return out
 
 
+# ------------------------------------------------------------------------------------- PECNet predictor (training)
+def _pecnet_train_args(who, model, past, generated_dest, mask, initial_pos):
+    params, dev = model.et_params()
+    n, (past, dest, pos) = _mlp_strided(who, dev, (params.encoder_past.widths[0], params.encoder_dest.widths[0], 2),
+                                        past=past, generated_dest=generated_dest, initial_pos=initial_pos)
+    if mask is not None:
+        (mask,) = _dev_args(dev, mask)  # bool -> float32
+        if tuple(mask.shape) != (n, n):
+            raise ValueError(f"{who}: mask {tuple(mask.shape)} is not ({n}, {n})")
+    if params.nonlocal_pools > 0 and n > L.MLP_MAX_RANGE:
+        raise ValueError(f"{who}: {n} rows are beyond the pooling step's range of {L.MLP_MAX_RANGE} (ET_MLP_MAX_RANGE)")
+    strided = []
+    for t in (past, dest, pos):
+        strided += [L.ptr(t), t.stride(0), t.stride(1)]
+    return params, dev, n, (past, dest, pos), mask, strided
+
+
+def pecnet_train_fwd(model, past, generated_dest, mask, initial_pos):
+    """``model`` (:class:`eigentrajectory_amd.pecnet.PECNet`): past (N, 2 past_length), generated_dest (N, 2), initial_pos
+    (N, 2), read in place through their strides; mask (N, N) bool or float32 (None: all ones) -> (out, saved): out
+    (N, out_width) is :func:`pecnet_predict`'s, bit for bit, in the same 2 + 2 nonlocal_pools launches; ``saved`` (float32,
+    flat) holds what :func:`pecnet_train_bwd` needs (layout: csrc/et_mlp_train.hip, "PECNet")."""
+    params, dev, n, _, mask, strided = _pecnet_train_args("pecnet_train_fwd", model, past, generated_dest, mask, initial_pos)
+    out = torch.empty((n, params.out_width), device=dev)
+    saved = torch.empty((L.lib().et_pecnet_train_saved_bytes(C.byref(params), n) // 4,), device=dev)
+    L.call("et_pecnet_train_fwd", C.byref(params), *strided, L.ptr(mask), n, L.ptr(out), L.ptr(saved), None, 0, L.stream(dev))
+    return out, saved
+
+
+def pecnet_train_bwd(model, past, generated_dest, mask, initial_pos, saved, g_out, need_input_grads=False):
+    """The backward pass of :func:`pecnet_train_fwd` in 3 + 3 nonlocal_pools launches: ``saved`` as that call returned it
+    (same ``model`` weights, same inputs, same mask), ``g_out`` (N, out_width) the gradient at its ``out`` -> a dict keyed by
+    the module's parameter names (``encoder_past.layers.0.weight``, ...; the six chains, or without pooling rounds the
+    three that run) of fresh tensors holding the gradients (nothing is accumulated), plus ``past`` / ``dest`` / ``pos``, laid
+    out like the inputs, when ``need_input_grads`` (a bool, or one per input) asks for them.  The mask gets none."""
+    params, dev, n, (past, dest, pos), mask, strided = _pecnet_train_args("pecnet_train_bwd", model, past, generated_dest,
+                                                                          mask, initial_pos)
+    (g_out,) = _dev_args(dev, g_out)
+    if tuple(g_out.shape) != (n, params.out_width):
+        raise ValueError(f"pecnet_train_bwd: g_out {tuple(g_out.shape)} is not ({n}, {params.out_width})")
+    sbytes = L.lib().et_pecnet_train_saved_bytes(C.byref(params), n)
+    if saved.device != dev or saved.dtype != torch.float32 or not saved.is_contiguous() or saved.numel() * 4 < sbytes:
+        raise ValueError(f"pecnet_train_bwd: saved is not the {sbytes // 4} float32 values pecnet_train_fwd returned for "
+                         f"{n} rows")
+    want = need_input_grads if isinstance(need_input_grads, (tuple, list)) else (need_input_grads,) * 3
+    chains = model.CHAINS if params.nonlocal_pools > 0 else model.CHAINS_WITHOUT_POOLING
+    # one tensor per gradient: autograd's accumulation takes a fresh, unshared tensor over as .grad without a copy
+    out = {name: torch.empty_like(t) for name, t in zip(model.chain_parameter_names(), model.chain_parameters())
+           if name.split(".")[0] in chains}
+    grads = L.PECNetGrads()
+    for chain in chains:
+        g = getattr(grads, chain)
+        for i in range(len(getattr(model, chain).layers)):
+            g.dw[i] = out[f"{chain}.layers.{i}.weight"].data_ptr()
+            g.db[i] = out[f"{chain}.layers.{i}.bias"].data_ptr()
+    for key, t, wanted in zip(("past", "dest", "pos"), (past, dest, pos), want):
+        if wanted:
+            out[key] = torch.empty_strided(t.shape, t.stride(), device=dev)
+    nbytes = L.lib().et_pecnet_train_workspace_bytes(C.byref(params), n)
+    ws = torch.empty((nbytes // 4,), device=dev)
+    L.call("et_pecnet_train_bwd", C.byref(params), *strided, L.ptr(mask), n, L.ptr(saved), L.ptr(g_out), C.byref(grads),
+           L.ptr(out.get("past")), L.ptr(out.get("dest")), L.ptr(out.get("pos")), L.ptr(ws), nbytes, L.stream(dev))
+    return out
+
+
 # ----------------------------------------------------------------------- curve fitting
 def curve_fit_batch(trajs, bases, steps=100000, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, want_cp=False, want_loss=False):
     """CurveModel/curve_fitting.py for a batch of fits: fit f fits basis ``bases[f]`` (T_f, ncp_f) to every trajectory of

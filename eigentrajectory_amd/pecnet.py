@@ -1,4 +1,4 @@
-"""PECNet, the predictor of ET-PECNet (baseline/pecnet/model.py), inference on HIP kernels.
+"""PECNet, the predictor of ET-PECNet (baseline/pecnet/model.py), inference and training of ``predict`` on HIP kernels.
 
 Same constructor signature and the same sub-module / parameter names as the reference (``encoder_past.layers.{i}``,
 ``encoder_dest``, ``encoder_latent``, ``decoder``, ``non_local_theta``, ``non_local_phi``, ``non_local_g``, ``predictor``),
@@ -19,6 +19,22 @@ in training mode raise.  A whole split runs in the same fixed number of launches
 :meth:`EigenTrajectory.evaluate_split` / :func:`eigentrajectory_amd.ops.pecnet_forward_scenes`.
 Supported family: ``activation='relu'``, ``discrim=False``, ``dropout=-1``, 1 to 4 hidden layers per MLP, widths 1 to 1024,
 ``nonlocal_pools`` 0 to 8, up to 4096 rows per ``predict`` call with pooling; other shapes construct, but their use raises.
+
+Training (opt-in): the reference's ``pecnet`` bridge calls ``predict`` in training too, so training ET-PECNet differentiates
+exactly what ``predict`` computes (no CVAE, no sampling).  After ``eigentrajectory_amd.enable_native_training(model)`` a
+``predict`` in training mode runs the same ``2 + 2 * nonlocal_pools`` launches with everything the backward needs kept, and
+its backward pass is ``3 + 3 * nonlocal_pools`` launches of csrc/et_mlp_train.hip (12 for the ET configuration): the
+predictor's rows; per pooling round, last to first, the attention step's rows, its column sums, then theta, phi and g side by
+side; both encoders' rows; every dW / db, the shared theta / phi / g weights summed over the rounds.  The gradients reach
+``.grad`` of the tensors of ``encoder_past``, ``encoder_dest``, ``non_local_theta``, ``non_local_phi``, ``non_local_g`` and
+``predictor`` the ordinary autograd way; ``encoder_latent`` and ``decoder`` get none, the mask gets none::
+
+    model = EigenTrajectory(PECNet(...), get_hook_func("pecnet"), hp)
+    eigentrajectory_amd.enable_native_training(model)
+    ETTrainer(model, hp, train_data, val_data).fit(epochs)
+
+The switch is the plain attribute ``native_training`` (no parameter, no buffer, not in the ``state_dict``, default False);
+without the call everything is as before: ``predict`` in training mode raises.
 """
 from __future__ import annotations
 
@@ -69,8 +85,47 @@ def require_eval(module, who):
                            ".eval() first")
 
 
+class _TrainPredict(torch.autograd.Function):
+    """``predict`` with a backward pass (csrc/et_mlp_train.hip).  The tensors of the six chains are inputs, so their gradients
+    accumulate into ``.grad`` like any other parameter's; they, the inputs, the mask and the kept values are saved through
+    ``save_for_backward``: the kernels read the weights in place, and an in-place change between forward and backward (an
+    optimiser step) is caught by autograd's version counters.  ``generated_dest`` and ``initial_pos`` may be one tensor
+    (the bridge's): each gets its own gradient tensor and autograd sums the two."""
+
+    @staticmethod
+    def forward(ctx, model, mask, past, dest, pos, *params):
+        from . import ops
+        out, saved = ops.pecnet_train_fwd(model, past, dest, mask, pos)
+        ctx.model = model
+        ctx.has_mask = mask is not None
+        ctx.save_for_backward(past, dest, pos, saved, *(() if mask is None else (mask,)), *params)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        need = ctx.needs_input_grad
+        if g_out is None:
+            return (None,) * len(need)
+        from . import ops
+        past, dest, pos, saved = ctx.saved_tensors[:4]
+        mask = ctx.saved_tensors[4] if ctx.has_mask else None
+        params = ctx.saved_tensors[4 + ctx.has_mask:]
+        model = ctx.model
+        if any(p.data_ptr() != q.data_ptr() for p, q in zip(params, model.chain_parameters())):
+            raise RuntimeError("PECNet: a parameter tensor of the six chains was replaced between forward and backward")
+        g = ops.pecnet_train_bwd(model, past, dest, mask, pos, saved, g_out, (need[2], need[3], need[4]))
+        return (None, None, g.get("past"), g.get("dest"), g.get("pos"),
+                *(g.get(name) if wanted else None for name, wanted in zip(model.chain_parameter_names(), need[5:])))
+
+
 class PECNet(nn.Module):
-    """baseline/pecnet/model.py's ``PECNet``: ``predict`` natively in eval mode, everything else a tensor holder."""
+    """baseline/pecnet/model.py's ``PECNet``: ``predict`` natively (eval mode; training mode after
+    :func:`eigentrajectory_amd.enable_native_training`), everything else a tensor holder."""
+
+    CHAINS = ("encoder_past", "encoder_dest", "non_local_theta", "non_local_phi", "non_local_g", "predictor")  # of ``predict``
+    CHAINS_WITHOUT_POOLING = ("encoder_past", "encoder_dest", "predictor")  # nonlocal_pools = 0
+    native_training = False  # a plain attribute, set per instance by eigentrajectory_amd.enable_native_training
 
     def __init__(self, enc_past_size, enc_dest_size, enc_latent_size, dec_size, predictor_size, non_local_theta_size,
                  non_local_phi_size, non_local_g_size, fdim, zdim, nonlocal_pools, non_local_dim, sigma, past_length,
@@ -95,6 +150,14 @@ class PECNet(nn.Module):
             getattr(self, name).et_chain(getattr(p, name), f"PECNet.{name}")
         return p, check_tensors(self, "PECNet")
 
+    def chain_parameter_names(self):
+        return [f"{name}.layers.{i}.{kind}" for name in self.CHAINS for i in range(len(getattr(self, name).layers))
+                for kind in ("weight", "bias")]
+
+    def chain_parameters(self):
+        """the tensors of :meth:`chain_parameter_names`, in its order"""
+        return [t for name in self.CHAINS for lin in getattr(self, name).layers for t in (lin.weight, lin.bias)]
+
     def forward(self, *args, **kwargs):
         raise NotImplementedError("PECNet: only predict() is native; forward() (the CVAE path with its random sampling) is "
                                   "not implemented")
@@ -102,6 +165,25 @@ class PECNet(nn.Module):
     def predict(self, past, generated_dest, mask, initial_pos):
         """past (N, 2 past_length), generated_dest (N, 2), mask (N, N) bool or float32, initial_pos (N, 2) ->
         (N, 2 (future_length - 1))"""
+        if self.training and self.native_training:
+            return _TrainPredict.apply(self, mask, past, generated_dest, initial_pos, *self.chain_parameters())
         require_eval(self, "PECNet")
         from . import ops
         return ops.pecnet_predict(self, past, generated_dest, mask, initial_pos)
+
+
+def enable_native_training(model, flag=True):
+    """Let ``predict`` of ``model``'s predictor run in training mode with a native backward pass.  ``model`` is an
+    :class:`eigentrajectory_amd.EigenTrajectory` wrapper or a bare predictor: an ``LBEBM`` (its own
+    ``enable_native_training``) or a ``PECNet`` (the plain attribute ``native_training``); the other eight predictors have no
+    native backward pass and raise.  -> ``model``"""
+    from .lbebm import LBEBM
+    net = getattr(model, "baseline_model", model)
+    if isinstance(net, LBEBM):
+        net.enable_native_training(flag)
+    elif isinstance(net, PECNet):
+        net.native_training = bool(flag)
+    else:
+        raise NotImplementedError(f"enable_native_training: {type(net).__name__} has no native backward pass; only LBEBM and "
+                                  "PECNet train natively")
+    return model

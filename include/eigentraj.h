@@ -726,6 +726,53 @@ int et_lbebm_train_bwd(const et_mlp_params *params, const float *past, int64_t p
                        const et_lbebm_grads *grads, float *g_past, float *g_dest, void *workspace, size_t workspace_bytes,
                        et_stream_t stream);
 
+/* ---- PECNet predictor, training (what the pecnet bridge runs in training too: PECNet.predict) -----------------------------
+ * Forward with everything the backward needs kept, and the backward pass, of et_pecnet_predict: the six chains (notation as
+ * above) and nonlocal_pools rounds of pooling with the SAME theta / phi / g weights.  One round, feat (N, F) -> out (N, F):
+ * f = theta(feat) phi(feat)^T, s = softmax(f) over all N columns, w = s * mask, den = max(sum_j |w_ij|, 1e-12), p = w / den,
+ * out = p g(feat) + feat.  Its backward from G, the gradient at out:  d feat += G;  dp_ij = G_i . g_j;  dw_ij = (dp_ij -
+ * sign(w_ij) sum_k dp_ik p_ik) / den where sum |w| > 1e-12, else dp_ij / 1e-12 (clamp_min's convention);  ds_ij = dw_ij
+ * mask_ij, exactly 0 where mask_ij = 0;  df_ij = s_ij (ds_ij - sum_k ds_ik s_ik);  d theta_i = sum_j df_ij phi_j;  d phi_j =
+ * sum_i df_ij theta_i;  d g_j = sum_i p_ij G_i.  The mask gets no gradient.
+ *   et_pecnet_train_fwd   out (N, out_width) = et_pecnet_predict's, bit for bit, in the same 2 + 2 nonlocal_pools launches;
+ *                         `saved` (et_pecnet_train_saved_bytes) receives the two encoders' outputs, every hidden activation
+ *                         of every chain in every round, theta / phi / g of every round and the features entering every
+ *                         round and the predictor (round 0's [ftraj | dfeat | initial_pos] stored as one block).  The
+ *                         attention weights are NOT kept.  The workspace is not used (NULL / 0 are fine).
+ *   et_pecnet_train_bwd   from g_out (N, out_width): every dW / db of the six chains (`grads`; OVERWRITTEN; with
+ *                         nonlocal_pools = 0 the three non-local chains are neither checked nor written), and, where the
+ *                         pointer is not NULL, the gradients of past, dest and initial_pos at the inputs' own strides.
+ *                         3 + 3 nonlocal_pools launches whatever N: the predictor's rows; per round, last to first: the
+ *                         pooling's rows (one wavefront per row forms s again with the forward's own statements, so with
+ *                         its bits, then p, df and d theta_i), the column sums d phi and d g, then theta, phi and g
+ *                         backward side by side; both encoders' rows; every dW / db.
+ * The gradient at a round's input features is summed in ONE order: the residual G, then the input gradients of theta, of
+ * phi and of g.  After round 0 it splits at columns fdim and 2 fdim into the two encoders' output gradients and g_pos.  A dW
+ * / db element of theta / phi / g is one fp32 fmaf chain over round 0's rows 0 .. N-1, then round 1's, and so on; d phi_j and
+ * d g_j are one chain over i = 0 .. N-1; the row sums (softmax, sum |w|, the two sums over k) are formed by one wavefront,
+ * lane l taking j = l, l + 64, ... ascending, then a fixed butterfly over the 64 lanes.  No atomics, nothing depends on the
+ * grid: two runs agree bit for bit.  A row whose mask row is all zeros has p = 0 and contributes exactly 0 to d theta, d phi
+ * and d g.  past / dest / initial_pos are read in place through their strides (in elements, >= 0); mask (N, N) float32
+ * row-major or NULL (all ones).  The workspace (et_pecnet_train_workspace_bytes) holds the gradients at the kept values and,
+ * with pooling, p and df of ONE round, 2 N^2 floats (128 MB at N = 4096); all sizes are 0 for parameters outside the family.
+ * Supported: et_pecnet_predict's family, N <= ET_MLP_MAX_RANGE with pooling; anything else ET_ERR_UNSUPPORTED before any
+ * launch; a missing pointer ET_ERR_INVALID_ARG; a short workspace ET_ERR_WORKSPACE.  N = 0: the forward does nothing, the
+ * backward writes zeros.  No host synchronisation, no allocation. */
+typedef struct et_pecnet_grads {
+    et_mlp_chain_grads encoder_past, encoder_dest, non_local_theta, non_local_phi, non_local_g, predictor;
+} et_pecnet_grads;
+size_t et_pecnet_train_saved_bytes(const et_mlp_params *params, int64_t N);
+size_t et_pecnet_train_workspace_bytes(const et_mlp_params *params, int64_t N);
+int et_pecnet_train_fwd(const et_mlp_params *params, const float *past, int64_t past_rs, int64_t past_cs, const float *dest,
+                        int64_t dest_rs, int64_t dest_cs, const float *initial_pos, int64_t pos_rs, int64_t pos_cs,
+                        const float *mask, int64_t N, float *out, float *saved, void *workspace, size_t workspace_bytes,
+                        et_stream_t stream);
+int et_pecnet_train_bwd(const et_mlp_params *params, const float *past, int64_t past_rs, int64_t past_cs, const float *dest,
+                        int64_t dest_rs, int64_t dest_cs, const float *initial_pos, int64_t pos_rs, int64_t pos_cs,
+                        const float *mask, int64_t N, const float *saved, const float *g_out, const et_pecnet_grads *grads,
+                        float *g_past, float *g_dest, float *g_pos, void *workspace, size_t workspace_bytes,
+                        et_stream_t stream);
+
 /* ---- AgentFormer predictor, inference (baseline/agentformer: bridge.py hooks + AgentFormerLight.forward) -------------
  * Eval mode, the ET configuration family: input_type = ['pos'], pred_type = 'pos', nz = 0, no learnt prior, pos_concat,
  * no agent encoding, dot-product scores (gaussian_kernel off) with separate same-agent projections (sep_attn on), an
