@@ -500,6 +500,26 @@ def ptr(t):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+def _p(t):
+    """A module tensor's address for a ``c_void_p`` field of the params mirrors: a plain int, which costs less than
+    :func:`ptr`'s ``c_void_p`` object on the per-scene path (a module's tensor is never None)."""
+    return t.data_ptr()
+
+
+def module_device(who, *modules, buffers=False, device=None):
+    """-> the ONE HIP device every parameter of ``modules`` (with ``buffers`` also every floating-point buffer) lives on as
+    a contiguous float32 tensor: the placement check every predictor's ``et_params()`` opens with (``who``: its class
+    name).  ``device``: a device already established (GP-Graph's base model) that they must share."""
+    tensors = [t for m in modules for t in m.parameters()]
+    if buffers:
+        tensors += [b for m in modules for b in m.buffers() if b.is_floating_point()]
+    dev = tensors[0].device if device is None else device
+    if dev.type != "cuda" or any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
+        raise ETLibraryError(f"{who}: every parameter{' and buffer' if buffers else ''} must be a contiguous float32 tensor "
+                             "on ONE HIP device (model.cuda()); there is no CPU path")
+    return dev
+
+
 def stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 

@@ -242,11 +242,7 @@ class AgentFormerLight(nn.Module):
 
     def et_params(self):
         """-> (et_agentformer_params, device): this module's tensors as the kernels read them (include/eigentraj.h)."""
-        tensors = list(self.parameters()) + list(self.buffers())
-        dev = tensors[0].device
-        if dev.type != "cuda" or any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
-            raise L.ETLibraryError("AgentFormerLight: every parameter and buffer must be a contiguous float32 tensor on ONE "
-                                   "HIP device (model.cuda()); there is no CPU path")
+        dev = L.module_device("AgentFormerLight", self, buffers=True)  # (its one buffer: the positional encoding)
         p = L.AgentFormerParams()
         p.motion_dim, p.model_dim, p.ff_dim, p.nhead = self.motion_dim, self.model_dim, self.ff_dim, self.nhead
         p.forecast_dim, p.past_frames, p.future_frames = self.forecast_dim, self.past_frames, self.future_frames

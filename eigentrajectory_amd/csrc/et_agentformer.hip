@@ -644,10 +644,8 @@ extern "C" int et_agentformer_forward_scenes(const et_agentformer_params *params
     const int rc = af_check_params(params);
     if (rc != ET_OK) return rc;
     if (params->past_frames != params->future_frames + 2) return ET_ERR_UNSUPPORTED;  // u = [C_obs; obs_ori]
-    if (N < 0 || N > INT32_MAX / kAfMaxT || n_scenes < 0) return ET_ERR_INVALID_ARG;
-    if (scene_offsets && n_scenes == 0) return N == 0 ? ET_OK : ET_ERR_INVALID_ARG;
-    if (!scene_offsets && N > kAfMaxN) return ET_ERR_INVALID_ARG;
-    if (N == 0) return ET_OK;
+    const int early = scene_args_status(N, INT32_MAX / kAfMaxT, scene_offsets, n_scenes, kAfMaxN);
+    if (early != kSceneArgsGo) return early;
     if (!C_obs || !nrm || !C_pred_refine) return ET_ERR_INVALID_ARG;
     if (!workspace || workspace_bytes < et_agentformer_workspace_bytes(params, N, N)) return ET_ERR_WORKSPACE;
     float *ws = (float *)workspace;

@@ -30,6 +30,19 @@ constexpr int kWave = 64;  // CDNA wavefront width
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 __host__ __device__ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// The row and scene arguments of an et_*_forward_scenes entry point, checked once its parameters have passed (host only):
+// N rows, row_cap the most the predictor's 32-bit indices take, scene_offsets / n_scenes as the caller gave them,
+// one_scene_cap the largest batch that may come without offsets (= as one scene).  -> kSceneArgsGo when there is work to
+// do, else the status to return at once: ET_OK for an empty batch, ET_ERR_INVALID_ARG.  scene_offsets is not read.
+constexpr int kSceneArgsGo = -1;
+static inline int scene_args_status(int64_t N, int64_t row_cap, const int32_t *scene_offsets, int n_scenes,
+                                    int64_t one_scene_cap) {
+    if (N < 0 || N > row_cap || n_scenes < 0) return ET_ERR_INVALID_ARG;
+    if (scene_offsets && n_scenes == 0) return N == 0 ? ET_OK : ET_ERR_INVALID_ARG;
+    if (!scene_offsets && N > one_scene_cap) return ET_ERR_INVALID_ARG;
+    return N == 0 ? ET_OK : kSceneArgsGo;
+}
+
 // A value (or a "done once" flag) of the CURRENT device, zero / default until its first user fills it in: a process may
 // drive several GPUs, and a CU count, a function attribute or a slot counter belongs to one of them.  Declared `static`
 // where it is used.

@@ -148,13 +148,12 @@ extern "C" int et_gpgraph_sgcn_forward_scenes(const et_gpgraph_sgcn_params *para
                                               et_stream_t stream) {
     const int rc = check_gp(params);
     if (rc != ET_OK) return rc;
-    if (N < 0 || 3 * N > INT32_MAX || n_scenes < 0 || 3 * (int64_t)n_scenes > INT32_MAX || sum_n2 < 0 || max_scene_n < 0)
-        return ET_ERR_INVALID_ARG;
-    if (scene_offsets && n_scenes == 0) return N == 0 ? ET_OK : ET_ERR_INVALID_ARG;
-    if (N == 0) return ET_OK;
+    // (the three passes are scenes and rows of their own: 3 N and 3 n_scenes are what has to fit 32 bits)
+    if (3 * N > INT32_MAX || 3 * (int64_t)n_scenes > INT32_MAX || sum_n2 < 0 || max_scene_n < 0) return ET_ERR_INVALID_ARG;
+    const int early = scene_args_status(N, INT32_MAX, scene_offsets, n_scenes, ET_SGCN_MAX_N);
+    if (early != kSceneArgsGo) return early;
     if (!C_obs || !nrm || !C_pred_refine) return ET_ERR_INVALID_ARG;
     if (!scene_offsets) {
-        if (N > ET_SGCN_MAX_N) return ET_ERR_INVALID_ARG;
         n_scenes = 1;
         sum_n2 = N * N;
         max_scene_n = N;

@@ -323,9 +323,7 @@ using namespace et;
 
 extern "C" size_t et_graphtern_workspace_bytes(const et_graphtern_params *params, int64_t N, int64_t max_scene_n) {
     if (gt_check_params(params) != ET_OK || N < 0 || max_scene_n < 0) return 0;
-    const int64_t per = gt_arena_per_ped(gt_dims_of(*params));
-    if (per * max_scene_n * 4 <= kSgLdsBytes) return 0;
-    return (size_t)(per * N * 4);
+    return arena_workspace_bytes(gt_arena_per_ped(gt_dims_of(*params)), N, max_scene_n);
 }
 
 extern "C" int et_graphtern_forward_graph(const et_graphtern_params *params, const float *S_obs, int64_t N, float *out,
@@ -335,13 +333,12 @@ extern "C" int et_graphtern_forward_graph(const et_graphtern_params *params, con
     if (N < 0 || N > ET_SCENE_MAX_N) return ET_ERR_INVALID_ARG;
     if (N == 0) return ET_OK;
     if (!S_obs || !out) return ET_ERR_INVALID_ARG;
-    const int64_t per = gt_arena_per_ped(gt_dims_of(*params));
-    const bool in_lds = per * N * 4 <= kSgLdsBytes;
-    if (!in_lds && (!workspace || workspace_bytes < (size_t)(per * N * 4))) return ET_ERR_WORKSPACE;
+    const ArenaPlace place = arena_place_scene(gt_arena_per_ped(gt_dims_of(*params)), N, workspace, workspace_bytes);
+    if (place.status != ET_OK) return place.status;
     const GraphSrc src{S_obs};
-    hipLaunchKernelGGL((graphtern_kernel<GraphSrc>), dim3(1), dim3(kSgThreads), in_lds ? (unsigned)(per * N * 4) : 0u,
+    hipLaunchKernelGGL((graphtern_kernel<GraphSrc>), dim3(1), dim3(kSgThreads), place.lds_bytes,
                        (hipStream_t)stream, src, *params, nullptr, N, out, nullptr, (float *)workspace,
-                       (int64_t)(workspace ? workspace_bytes / 4 : 0), in_lds ? (int)(per * N) : 0);
+                       (int64_t)(workspace ? workspace_bytes / 4 : 0), place.lds_floats);
     ET_LAUNCH_CHECK();
     return ET_OK;
 }
@@ -351,10 +348,8 @@ extern "C" int et_graphtern_forward_scenes(const et_graphtern_params *params, co
                                            float *graph_inputs, void *workspace, size_t workspace_bytes, et_stream_t stream) {
     const int rc = gt_check_params(params);
     if (rc != ET_OK) return rc;
-    if (N < 0 || N > INT32_MAX || n_scenes < 0) return ET_ERR_INVALID_ARG;
-    if (scene_offsets && n_scenes == 0) return N == 0 ? ET_OK : ET_ERR_INVALID_ARG;
-    if (!scene_offsets && N > ET_SCENE_MAX_N) return ET_ERR_INVALID_ARG;
-    if (N == 0) return ET_OK;
+    const int early = scene_args_status(N, INT32_MAX, scene_offsets, n_scenes, ET_SCENE_MAX_N);
+    if (early != kSceneArgsGo) return early;
     if (!C_obs || !nrm || !C_pred_refine) return ET_ERR_INVALID_ARG;
     const ScenesSrc src{C_obs, nrm, N};
     const unsigned grid = scene_offsets ? (unsigned)n_scenes : 1u;

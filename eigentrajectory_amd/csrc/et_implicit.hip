@@ -374,10 +374,8 @@ extern "C" int et_implicit_forward_scenes(const et_implicit_params *params, cons
     const int rc = im_check_params(params);
     if (rc != ET_OK) return rc;
     if (params->temporal_input < 3) return ET_ERR_UNSUPPORTED;  // v = [C_obs; obs_ori]: one coefficient row at least
-    if (N < 0 || N > INT32_MAX / kImMaxT || n_scenes < 0) return ET_ERR_INVALID_ARG;
-    if (scene_offsets && n_scenes == 0) return N == 0 ? ET_OK : ET_ERR_INVALID_ARG;
-    if (!scene_offsets && N > ET_SCENE_MAX_N) return ET_ERR_INVALID_ARG;
-    if (N == 0) return ET_OK;
+    const int early = scene_args_status(N, INT32_MAX / kImMaxT, scene_offsets, n_scenes, ET_SCENE_MAX_N);
+    if (early != kSceneArgsGo) return early;
     if (!C_obs || !nrm || !C_pred_refine) return ET_ERR_INVALID_ARG;
     if (!workspace || workspace_bytes < et_implicit_workspace_bytes(params, N)) return ET_ERR_WORKSPACE;
     int32_t *tab = (int32_t *)workspace;

@@ -157,10 +157,8 @@ static int ml_scenes(const et_mlp_params *p, bool pecnet, const float *C_obs, co
     const int rc = ml_check_params(p, pecnet);
     if (rc != ET_OK) return rc;
     if (p->encoder_dest.widths[0] != 2 || p->out_width % p->encoder_past.widths[0] != 0) return ET_ERR_UNSUPPORTED;
-    if (N < 0 || N > INT32_MAX || n_scenes < 0) return ET_ERR_INVALID_ARG;
-    if (off && n_scenes == 0) return N == 0 ? ET_OK : ET_ERR_INVALID_ARG;
-    if (!off && N > ET_SCENE_MAX_N) return ET_ERR_INVALID_ARG;
-    if (N == 0) return ET_OK;
+    const int early = scene_args_status(N, INT32_MAX, off, n_scenes, ET_SCENE_MAX_N);
+    if (early != kSceneArgsGo) return early;
     if (!C_obs || !nrm || !out) return ET_ERR_INVALID_ARG;
     return ml_run(*p, nullptr, nullptr, nullptr, nullptr, C_obs, nrm, off, n_scenes, N, out, gin, workspace,
                   workspace_bytes, (hipStream_t)stream);

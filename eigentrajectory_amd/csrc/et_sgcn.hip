@@ -63,12 +63,11 @@ extern "C" int et_sgcn_forward_scenes(const et_sgcn_params *params, const float 
                                       size_t workspace_bytes, et_stream_t stream) {
     const int rc = check_params(params);
     if (rc != ET_OK) return rc;
-    if (N < 0 || N > INT32_MAX || n_scenes < 0 || sum_n2 < 0 || max_scene_n < 0) return ET_ERR_INVALID_ARG;
-    if (scene_offsets && n_scenes == 0) return N == 0 ? ET_OK : ET_ERR_INVALID_ARG;
-    if (N == 0) return ET_OK;
+    if (sum_n2 < 0 || max_scene_n < 0) return ET_ERR_INVALID_ARG;
+    const int early = scene_args_status(N, INT32_MAX, scene_offsets, n_scenes, ET_SGCN_MAX_N);
+    if (early != kSceneArgsGo) return early;
     if (!C_obs || !nrm || !C_pred_refine) return ET_ERR_INVALID_ARG;
     if (!scene_offsets) {
-        if (N > ET_SGCN_MAX_N) return ET_ERR_INVALID_ARG;
         n_scenes = 1;
         sum_n2 = N * N;
         max_scene_n = N;

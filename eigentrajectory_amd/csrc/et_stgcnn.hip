@@ -49,6 +49,7 @@ struct ScenesSrc {
     const float *C_obs, *nrm;
     int64_t N;
     float *out;  // (k,N,S) C_pred_refine
+    // (= scene_v of et_scene_helpers.inl, word for word; calling it instead changes this kernel's --digest: leave it)
     __device__ void load(float *u, int64_t b, int n, int K, float *red) const {
         const int k = K - 2;
         for (int i = threadIdx.x; i < k * n; i += kSgThreads) u[i] = C_obs[(int64_t)(i / n) * N + b + (i % n)];
@@ -103,9 +104,7 @@ using namespace et;
 
 extern "C" size_t et_stgcnn_workspace_bytes(const et_stgcnn_params *params, int64_t N, int64_t max_scene_n) {
     if (check_params(params) != ET_OK || N < 0 || max_scene_n < 0) return 0;
-    const int64_t per = arena_per_ped(dims_of(*params));
-    if (per * max_scene_n * 4 <= kSgLdsBytes) return 0;
-    return (size_t)(per * N * 4);
+    return arena_workspace_bytes(arena_per_ped(dims_of(*params)), N, max_scene_n);
 }
 
 extern "C" int et_stgcnn_forward_scenes(const et_stgcnn_params *params, const float *C_obs, const float *nrm, int64_t N,
@@ -113,10 +112,8 @@ extern "C" int et_stgcnn_forward_scenes(const et_stgcnn_params *params, const fl
                                         void *workspace, size_t workspace_bytes, et_stream_t stream) {
     const int rc = check_params(params);
     if (rc != ET_OK) return rc;
-    if (N < 0 || N > INT32_MAX || n_scenes < 0) return ET_ERR_INVALID_ARG;
-    if (scene_offsets && n_scenes == 0) return N == 0 ? ET_OK : ET_ERR_INVALID_ARG;
-    if (!scene_offsets && N > ET_SCENE_MAX_N) return ET_ERR_INVALID_ARG;
-    if (N == 0) return ET_OK;
+    const int early = scene_args_status(N, INT32_MAX, scene_offsets, n_scenes, ET_SCENE_MAX_N);
+    if (early != kSceneArgsGo) return early;
     if (!C_obs || !nrm || !C_pred_refine) return ET_ERR_INVALID_ARG;
     const ScenesSrc src{C_obs, nrm, N, C_pred_refine};
     const unsigned grid = scene_offsets ? (unsigned)n_scenes : 1u;
@@ -134,13 +131,12 @@ extern "C" int et_stgcnn_forward_graph(const et_stgcnn_params *params, const flo
     if (N < 0 || N > ET_SCENE_MAX_N) return ET_ERR_INVALID_ARG;
     if (N == 0) return ET_OK;
     if (!v || !a || !out) return ET_ERR_INVALID_ARG;
-    const int64_t per = arena_per_ped(dims_of(*params));
-    const bool in_lds = per * N * 4 <= kSgLdsBytes;
-    if (!in_lds && (!workspace || workspace_bytes < (size_t)(per * N * 4))) return ET_ERR_WORKSPACE;
+    const ArenaPlace place = arena_place_scene(arena_per_ped(dims_of(*params)), N, workspace, workspace_bytes);
+    if (place.status != ET_OK) return place.status;
     const GraphSrc src{v, a, out};
-    hipLaunchKernelGGL((stgcnn_kernel<GraphSrc>), dim3(1), dim3(kSgThreads), in_lds ? (unsigned)(per * N * 4) : 0u,
+    hipLaunchKernelGGL((stgcnn_kernel<GraphSrc>), dim3(1), dim3(kSgThreads), place.lds_bytes,
                        (hipStream_t)stream, src, *params, nullptr, N, (float *)workspace,
-                       (int64_t)(workspace ? workspace_bytes / 4 : 0), in_lds ? (int)(per * N) : 0);
+                       (int64_t)(workspace ? workspace_bytes / 4 : 0), place.lds_floats);
     ET_LAUNCH_CHECK();
     return ET_OK;
 }

@@ -15,6 +15,24 @@ constexpr int kSgLdsBytes = 60 * 1024;  // LDS arena of one workgroup (two workg
 constexpr int kSgGroup = 16;            // contraction rows per lane
 constexpr int kSgMaxS = 64;
 
+// Host side of the arena's placement, for the three predictors that keep one of `per` floats per pedestrian (ET-STGCNN,
+// DMRGCN, Graph-TERN).  *_workspace_bytes: none when the largest scene fits the LDS arena, else every scene's rows.
+static inline size_t arena_workspace_bytes(int64_t per, int64_t N, int64_t max_scene_n) {
+    return per * max_scene_n * 4 <= kSgLdsBytes ? 0 : (size_t)(per * N * 4);
+}
+// *_forward_graph's one scene: in LDS, sized for exactly its N pedestrians, else in the caller's workspace (both LDS
+// figures 0), else status = ET_ERR_WORKSPACE
+struct ArenaPlace {
+    int status;
+    unsigned lds_bytes;
+    int lds_floats;
+};
+static inline ArenaPlace arena_place_scene(int64_t per, int64_t N, const void *workspace, size_t workspace_bytes) {
+    if (per * N * 4 <= kSgLdsBytes) return {ET_OK, (unsigned)(per * N * 4), (int)(per * N)};
+    const bool fits = workspace && workspace_bytes >= (size_t)(per * N * 4);
+    return {fits ? ET_OK : ET_ERR_WORKSPACE, 0u, 0};
+}
+
 struct Dims {
     int K, k, S, n_st, n_tp;
     int qpp;  // floats per pedestrian of q

@@ -25,10 +25,10 @@ other shapes construct, but their forward raises.
 """
 from __future__ import annotations
 
-import torch
 import torch.nn as nn
 
 from . import _lib as L
+from ._lib import _p
 
 
 class _MultiRelationalGCN(nn.Module):
@@ -75,10 +75,6 @@ class _TPCNN(nn.Module):
             self.residual = None  # identity
 
 
-def _p(t):
-    return t.data_ptr()
-
-
 class SocialDMRGCN(nn.Module):
     r"""baseline/dmrgcn/predictor.py's ``social_dmrgcn`` (eval-mode inference on the GPU).  ``forward(v, a)``: v (1, 1, K, N),
     a (1, 2, K, N, N) as the dmrgcn bridge's pre-hook builds them -> ``(out (1, S, k, N), a)``; the post-hook takes [0]."""
@@ -102,11 +98,7 @@ class SocialDMRGCN(nn.Module):
         p.n_stgcn, p.n_tpcnn, p.input_feat = self.n_stgcn, self.n_tpcnn, self.input_feat
         p.output_feat, p.seq_len, p.pred_seq_len, p.kernel_size = (self.output_feat, self.seq_len, self.pred_seq_len,
                                                                    self.kernel_size)
-        tensors = list(self.parameters())
-        dev = tensors[0].device
-        if dev.type != "cuda" or any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
-            raise L.ETLibraryError("SocialDMRGCN: every parameter must be a contiguous float32 tensor on ONE HIP device "
-                                   "(model.cuda()); there is no CPU path")
+        dev = L.module_device("SocialDMRGCN", self)
         if len(self.split) != 2 or any(len(s) != L.DMRGCN_BINS for s in self.split):
             raise L.ETLibraryError(f"SocialDMRGCN: the kernel takes two relations of {L.DMRGCN_BINS} split values each")
         for r, s in enumerate(self.split):

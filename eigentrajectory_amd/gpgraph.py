@@ -40,7 +40,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .sgcn import SGCN, _p
+from ._lib import _p
+from .sgcn import SGCN
 from .stgcnn import SocialSTGCNN
 
 
@@ -123,10 +124,7 @@ class GPGraph(nn.Module):
         base, dev = self.baseline_model.et_params()
         p = L.GPGraphSTGCNNParams() if self.stgcnn_base else L.GPGraphSGCNParams()
         p.base = base
-        own = [t for m in (self.group_gen, self.group_mix) for t in m.parameters()]
-        if any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in own):
-            raise L.ETLibraryError("GPGraph: every parameter must be a contiguous float32 tensor on ONE HIP device "
-                                   "(model.cuda()); there is no CPU path")
+        L.module_device("GPGraph", self.group_gen, self.group_mix, device=dev)  # (the base has checked its own)
         if self.stgcnn_base:
             b = self.baseline_model
             if self.in_channels != 1 or self.out_channels != b.output_feat or self.pred_seq_len != b.pred_seq_len \

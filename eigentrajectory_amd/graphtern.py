@@ -28,10 +28,10 @@ by an ulp can move a scene's output by per cent ("Graph-TERN").
 """
 from __future__ import annotations
 
-import torch
 import torch.nn as nn
 
 from . import _lib as L
+from ._lib import _p
 
 HIDDEN_FEAT = 16  # model.py:229
 KERNEL_SIZE = 3   # model.py:230
@@ -83,10 +83,6 @@ class _EPCNN(nn.Module):
             self.restconv = nn.Sequential(nn.Conv2d(obs_seq_len, pred_seq_len, kernel_size=1))
 
 
-def _p(t):
-    return t.data_ptr()
-
-
 class GraphTERNLight(nn.Module):
     r"""baseline/graphtern/model.py's ``graph_tern_light`` (eval-mode inference on the GPU).  ``forward(S_obs)``: S_obs
     (1, 2, T, N, 1) = [abs, rel] as the graphtern bridge's pre-hook builds it -> (1, k, N, S); the post-hook squeezes it."""
@@ -108,11 +104,7 @@ class GraphTERNLight(nn.Module):
         p = L.GraphTERNParams()
         p.n_epgcn, p.n_epcnn, p.input_feat, p.hidden_feat = self.n_epgcn, self.n_epcnn, self.input_feat, HIDDEN_FEAT
         p.seq_len, p.pred_seq_len, p.n_smpl = self.seq_len, self.pred_seq_len, self.n_smpl
-        tensors = list(self.parameters())
-        dev = tensors[0].device
-        if dev.type != "cuda" or any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
-            raise L.ETLibraryError("GraphTERNLight: every parameter must be a contiguous float32 tensor on ONE HIP device "
-                                   "(model.cuda()); there is no CPU path")
+        dev = L.module_device("GraphTERNLight", self)
         if (len(self.tp_mrgcns) != self.n_epgcn or len(self.tpcnns) != self.n_epcnn
                 or self.n_epgcn > L.GRAPHTERN_MAX_EPGCN or self.n_epcnn > L.GRAPHTERN_MAX_EPCNN):
             return p, dev  # the kernel answers ET_ERR_UNSUPPORTED

@@ -91,11 +91,7 @@ class SocialImplicitLight(nn.Module):
         p = L.ImplicitParams()
         p.spatial_input, p.spatial_output = self.spatial_input, self.spatial_output
         p.temporal_input, p.temporal_output = self.temporal_input, self.temporal_output
-        tensors = list(self.parameters())
-        dev = tensors[0].device
-        if dev.type != "cuda" or any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
-            raise L.ETLibraryError("SocialImplicitLight: every parameter must be a contiguous float32 tensor on ONE HIP "
-                                   "device (model.cuda()); there is no CPU path")
+        dev = L.module_device("SocialImplicitLight", self)
         bins = [float(b) for b in self.bins]
         if len(bins) != len(self.implicit_cells):
             raise L.ETLibraryError(f"SocialImplicitLight: {len(bins)} bins for {len(self.implicit_cells)} cells")

@@ -34,7 +34,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .pecnet import MLP, check_tensors, require_eval
+from .pecnet import MLP, require_eval
 
 
 def _arg(args, name):
@@ -116,7 +116,7 @@ class LBEBM(nn.Module):
         p.out_width = self.predictor.layers[-1].out_features
         for name in ("encoder_past", "encoder_dest", "predictor"):
             getattr(self, name).et_chain(getattr(p, name), f"LBEBM.{name}")
-        return p, check_tensors(self, "LBEBM")
+        return p, L.module_device("LBEBM", self)
 
     def forward(self, *args, **kwargs):
         raise NotImplementedError("LBEBM: only predict() is native; forward() (Langevin sampling of the latent, the CVAE "

@@ -9,6 +9,7 @@ device first; without a HIP device every function raises (no CPU fallback).
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import torch
 
@@ -276,12 +277,57 @@ def anchor_reconstruct_metrics_scenes(Cc, gt, A_m, A_s, U_m, U_s, mode, static_d
     return out
 
 
-# ------------------------------------------------------------------------ Social-STGCNN predictor (inference)
-def _stgcnn_ws(params, n, max_n, dev):
-    nbytes = L.lib().et_stgcnn_workspace_bytes(C.byref(params), n, max_n)
+# ------------------------------------------------------------------------ what the ten predictors' wrappers share
+class _SceneBatch(NamedTuple):
+    """A split as an ``et_*_forward_scenes`` entry point takes it (:func:`_scene_batch`)."""
+    C_obs: torch.Tensor       # (k, n) float32 on the device
+    nrm: torch.Tensor         # (>= 2, n) float32 on the device
+    n: int
+    sizes: list               # pedestrians per scene; [n] without scene_sizes
+    off: torch.Tensor | None  # int32 offsets (len(sizes) + 1,) on the device; None without scene_sizes
+    n_scenes: int             # the entry point's n_scenes: len(sizes), 0 without scene_sizes
+    max_n: int                # the largest scene
+
+
+def _scene_batch(who, dev, C_obs, nrm, k, scene_sizes):
+    """The preamble of every ``*_forward_scenes`` wrapper (``who``: its name, for the messages): C_obs (k, N) and nrm
+    (2 or more rows, N) moved to ``dev`` and checked, ``scene_sizes`` (list, integer tensor or None) turned into the
+    offsets and counts the C entry point takes.  None is one scene of all N rows and passes no offsets; an empty list takes
+    N = 0.  What a predictor allows beyond that (a scene limit, a pooling range) is its wrapper's business."""
+    C_obs, nrm = _dev_args(dev, C_obs, nrm)
+    cs, ns = C_obs.shape, nrm.shape
+    if len(cs) != 2 or cs[0] != k or len(ns) != 2 or ns[0] < 2 or ns[1] != cs[1]:
+        raise ValueError(f"{who}: C_obs {tuple(cs)} / nrm {tuple(ns)} are not (k, N) / (2 or more, N) with k = {k}")
+    n = cs[1]
+    if scene_sizes is None:
+        return _SceneBatch(C_obs, nrm, n, [n], None, 0, n)
+    sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
+    if not sizes and n:
+        raise ValueError(f"{who}: no scenes for {n} rows")
+    off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
+    return _SceneBatch(C_obs, nrm, n, sizes, off, len(sizes), max(sizes, default=0))
+
+
+def _workspace(entry_name, dev, params, *args, required=False):
+    """(uint8 tensor on ``dev`` | None, its size) as ``entry_name``, an ``et_*_workspace_bytes``, sizes it for ``params`` and
+    ``args``.  ``required``: the predictor needs a workspace for any input, so a zero answer means that the library
+    refuses ``params`` (status 3)."""
+    nbytes = getattr(L.lib(), entry_name)(C.byref(params), *args)
+    if required and not nbytes:
+        L.check(3, entry_name)  # outside the native family
     return (torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None), nbytes
 
 
+def _read_in_place(who, dev, tensors):
+    """``tensors`` {name: tensor}: ``*_forward_graph`` inputs that the kernels read where they are (nothing is moved or copied
+    for the caller)"""
+    for name, t in tensors.items():
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous float32 tensor on {dev} (got {t.dtype}, {t.device}, "
+                             f"contiguous={t.is_contiguous()})")
+
+
+# ------------------------------------------------------------------------ Social-STGCNN predictor (inference)
 def stgcnn_forward_graph(model, v, a):
     """``model`` (:class:`eigentrajectory_amd.stgcnn.SocialSTGCNN`, eval mode) on one scene as the stgcnn bridge hands it
     over: v (1, 1, K, N), a (K, N, N) -> the raw output (1, S, k, N).  One launch."""
@@ -295,7 +341,7 @@ def stgcnn_forward_graph(model, v, a):
         raise ValueError(f"stgcnn_forward_graph: v {tuple(v.shape)} / a {tuple(a.shape)} are not (1,1,{K},N) / ({K},N,N)")
     v, a = _dev_args(dev, v, a)
     out = torch.empty((1, S, k, n), device=dev)
-    ws, nbytes = _stgcnn_ws(params, n, n, dev)
+    ws, nbytes = _workspace("et_stgcnn_workspace_bytes", dev, params, n, n)
     L.call("et_stgcnn_forward_graph", C.byref(params), L.ptr(v), L.ptr(a), n, L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
     return out
 
@@ -303,37 +349,21 @@ def stgcnn_forward_graph(model, v, a):
 def stgcnn_forward_scenes(model, C_obs, nrm, scene_sizes=None):
     """The stgcnn bridge + ``model`` (eval mode) + the post-hook for every scene of a split in ONE launch: C_obs (k, N) and
     nrm (4, N) of :func:`norm_project` (rows 0-1: the last observed positions, centred here per scene), ``scene_sizes``
-    pedestrians per scene in row order (None = one scene; an empty list takes N = 0) -> C_pred_refine (k, N, S)."""
+    pedestrians per scene in row order as a list or an integer tensor (None = one scene; an empty list takes N = 0) ->
+    C_pred_refine (k, N, S).  The other nine ``*_forward_scenes`` take these three arguments the same way."""
     if getattr(model, "graph_per_time_row", False):
         raise NotImplementedError("stgcnn_forward_scenes: a per-time-row SocialSTGCNN (graph_per_time_row=True) runs only inside "
                                   "GPGraphSTGCNN")
     params, dev = model.et_params()
-    C_obs, nrm = _dev_args(dev, C_obs, nrm)
-    k, n = C_obs.shape
-    if k != params.pred_seq_len or nrm.dim() != 2 or nrm.shape[0] < 2 or nrm.shape[1] != n:
-        raise ValueError(f"stgcnn_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
-                         f"k = {params.pred_seq_len}")
-    if scene_sizes is not None:
-        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
-        if not sizes and n:
-            raise ValueError(f"stgcnn_forward_scenes: no scenes for {n} rows")
-        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
-        max_n = max(sizes, default=0)
-    else:
-        sizes, off, max_n = None, None, n
-    out = torch.empty((k, n, params.output_feat), device=dev)
-    ws, nbytes = _stgcnn_ws(params, n, max_n, dev)
-    L.call("et_stgcnn_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
-           0 if off is None else len(sizes), L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
+    b = _scene_batch("stgcnn_forward_scenes", dev, C_obs, nrm, params.pred_seq_len, scene_sizes)
+    out = torch.empty((params.pred_seq_len, b.n, params.output_feat), device=dev)
+    ws, nbytes = _workspace("et_stgcnn_workspace_bytes", dev, params, b.n, b.max_n)
+    L.call("et_stgcnn_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), b.n, L.ptr(b.off), b.n_scenes,
+           L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
     return out
 
 
 # ------------------------------------------------------------------------------ SGCN predictor (inference)
-def _sgcn_ws(params, n, sum_n2, n_scenes, dev):
-    nbytes = L.lib().et_sgcn_workspace_bytes(C.byref(params), n, sum_n2, int(n_scenes))
-    return (torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None), nbytes
-
-
 def _sgcn_logits(want, T, n, sum_n2, dev):
     if not want:
         return None, None
@@ -356,15 +386,12 @@ def sgcn_forward_graph(model, v, identity, want_logits=False):
             or tuple(id_t.shape) not in ((n, 1, 1), (n, T, T))):
         raise ValueError(f"sgcn_forward_graph: v {tuple(v.shape)} / identity {tuple(id_s.shape)}, {tuple(id_t.shape)} are not "
                          f"(1,{T},N,1) / (1 or {T},N,N), (N,1,1) or (N,{T},{T})")
-    for name, t in (("v", v), ("identity[0]", id_s), ("identity[1]", id_t)):
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"sgcn_forward_graph: {name} must be a contiguous float32 tensor on {dev} (got {t.dtype}, "
-                             f"{t.device}, contiguous={t.is_contiguous()})")
+    _read_in_place("sgcn_forward_graph", dev, {"v": v, "identity[0]": id_s, "identity[1]": id_t})
     if n > L.SGCN_MAX_N:
         raise ValueError(f"sgcn_forward_graph: N = {n} exceeds the {L.SGCN_MAX_N} pedestrians a scene may have")
     out = torch.empty((k, n, S), device=dev)
     ls, lt = _sgcn_logits(want_logits, T, n, n * n, dev)
-    ws, nbytes = _sgcn_ws(params, n, n * n, 1, dev)
+    ws, nbytes = _workspace("et_sgcn_workspace_bytes", dev, params, n, n * n, 1)
     L.call("et_sgcn_forward_graph", C.byref(params), L.ptr(v.detach()), L.ptr(id_s.detach()), int(id_s.shape[0]),
            L.ptr(id_t.detach()), int(id_t.shape[1]), n, L.ptr(out), L.ptr(ls), L.ptr(lt), L.ptr(ws), nbytes, L.stream(dev))
     if want_logits:
@@ -374,45 +401,29 @@ def sgcn_forward_graph(model, v, identity, want_logits=False):
 
 def sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_logits=False):
     """The sgcn bridge + ``model`` (eval mode) + the post-hook for every scene of a split in a fixed number of launches:
-    C_obs (k, N) and nrm (4, N) of :func:`norm_project` (rows 0-1: the last observed positions, centred here per scene),
-    ``scene_sizes`` pedestrians per scene in row order (None = one scene; an empty list takes N = 0) -> C_pred_refine
-    (k, N, S).  With ``want_logits`` also the packed logits: scene s's (T, 4, n, n) block at 4 T (n_0^2 + ... + n_{s-1}^2)
-    of the first and its (n, 4, T, T) block at 4 T T (n_0 + ... + n_{s-1}) of the second."""
+    C_obs, nrm and ``scene_sizes`` as :func:`stgcnn_forward_scenes` -> C_pred_refine (k, N, S).  A scene of more than 512
+    pedestrians raises ValueError.  With ``want_logits`` also the packed logits: scene s's (T, 4, n, n) block at
+    4 T (n_0^2 + ... + n_{s-1}^2) of the first and its (n, 4, T, T) block at 4 T T (n_0 + ... + n_{s-1}) of the second."""
     model._check_mode()
     if getattr(model, "position_channel", False):
         raise NotImplementedError("sgcn_forward_scenes: a two-channel SGCN (position_channel=True) runs only inside GPGraphSGCN")
     params, dev = model.et_params()
-    C_obs, nrm = _dev_args(dev, C_obs, nrm)
-    k, n = C_obs.shape
-    T = params.obs_len
-    if k != params.pred_len or nrm.dim() != 2 or nrm.shape[0] < 2 or nrm.shape[1] != n:
-        raise ValueError(f"sgcn_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
-                         f"k = {params.pred_len}")
-    if scene_sizes is not None:
-        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
-        if not sizes and n:
-            raise ValueError(f"sgcn_forward_scenes: no scenes for {n} rows")
-        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
-    else:
-        sizes, off = [n], None
-    if max(sizes, default=0) > L.SGCN_MAX_N:
-        raise ValueError(f"sgcn_forward_scenes: a scene of {max(sizes)} pedestrians exceeds the {L.SGCN_MAX_N} a scene may have")
-    sum_n2, max_n = sum(s * s for s in sizes), max(sizes, default=0)
-    out = torch.empty((k, n, params.out_dims), device=dev)
-    ls, lt = _sgcn_logits(want_logits, T, n, sum_n2, dev)
-    ws, nbytes = _sgcn_ws(params, n, sum_n2, len(sizes), dev)
-    L.call("et_sgcn_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
-           0 if off is None else len(sizes), sum_n2, max_n, L.ptr(out), L.ptr(ls), L.ptr(lt), L.ptr(ws), nbytes,
-           L.stream(dev))
+    b = _scene_batch("sgcn_forward_scenes", dev, C_obs, nrm, params.pred_len, scene_sizes)
+    n = b.n
+    if b.max_n > L.SGCN_MAX_N:
+        raise ValueError(f"sgcn_forward_scenes: a scene of {b.max_n} pedestrians exceeds the {L.SGCN_MAX_N} a scene may have")
+    sum_n2 = sum(s * s for s in b.sizes)
+    out = torch.empty((params.pred_len, n, params.out_dims), device=dev)
+    ls, lt = _sgcn_logits(want_logits, params.obs_len, n, sum_n2, dev)
+    ws, nbytes = _workspace("et_sgcn_workspace_bytes", dev, params, n, sum_n2, len(b.sizes))
+    L.call("et_sgcn_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), n, L.ptr(b.off), b.n_scenes, sum_n2,
+           b.max_n, L.ptr(out), L.ptr(ls), L.ptr(lt), L.ptr(ws), nbytes, L.stream(dev))
     return (out, ls, lt) if want_logits else out
 
 
 # ------------------------------------------------------------------------ GP-Graph-SGCN predictor (inference)
 def _gpgraph_buffers(params, want, T, n, sum_n2, n_scenes, dev):
-    nbytes = L.lib().et_gpgraph_sgcn_workspace_bytes(C.byref(params), n, sum_n2, int(n_scenes))
-    if not nbytes:
-        L.check(3, "et_gpgraph_sgcn_workspace_bytes")  # outside the native family
-    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    ws, nbytes = _workspace("et_gpgraph_sgcn_workspace_bytes", dev, params, n, sum_n2, n_scenes, required=True)
     gi = torch.empty((n,), device=dev, dtype=torch.int32)
     if not want:
         return ws, nbytes, gi, None, None, None
@@ -433,10 +444,7 @@ def gpgraph_sgcn_forward_graph(model, v_abs, v_rel, want_details=False):
     if tuple(v_abs.shape) != (1, 1, T, n) or tuple(v_rel.shape) != (1, 2, T, n):
         raise ValueError(f"gpgraph_sgcn_forward_graph: v_abs {tuple(v_abs.shape)} / v_rel {tuple(v_rel.shape)} are not "
                          f"(1,1,{T},N) / (1,2,{T},N)")
-    for name, t in (("v_abs", v_abs), ("v_rel", v_rel)):
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"gpgraph_sgcn_forward_graph: {name} must be a contiguous float32 tensor on {dev} (got "
-                             f"{t.dtype}, {t.device}, contiguous={t.is_contiguous()})")
+    _read_in_place("gpgraph_sgcn_forward_graph", dev, {"v_abs": v_abs, "v_rel": v_rel})
     if n > L.SGCN_MAX_N:
         raise ValueError(f"gpgraph_sgcn_forward_graph: N = {n} exceeds the {L.SGCN_MAX_N} pedestrians a scene may have")
     out = torch.empty((1, S, k, n), device=dev)
@@ -462,40 +470,28 @@ def gpgraph_sgcn_forward_graph(model, v_abs, v_rel, want_details=False):
 
 def gpgraph_sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
     """The gpgraphsgcn bridge + ``model`` (eval mode) + the post-hook for every scene of a split in a fixed number of
-    launches (8 + the number of asymmetric convolution layers): C_obs (k, N) and nrm (4, N) of :func:`norm_project`,
-    ``scene_sizes`` as :func:`sgcn_forward_scenes` -> C_pred_refine (k, N, S).  With ``want_details`` also a dict:
+    launches (8 + the number of asymmetric convolution layers): C_obs, nrm and ``scene_sizes`` as
+    :func:`stgcnn_forward_scenes` -> C_pred_refine (k, N, S).  One unlisted scene of more than 512 pedestrians raises
+    ValueError; a listed one is not computed: its rows are NaN.  With ``want_details`` also a dict:
     ``group_index`` (N,) int32 scene-local, ``dist`` packed (scene s's (n, n) block at n_0^2 + ... + n_{s-1}^2), ``logit_s``
     / ``logit_t`` packed as include/eigentraj.h describes (pass m of scene s at 4 T (m sum_n2 + sum_{s'<s} n_s'^2) and at
     4 T T (m N + off[s]))."""
     model._check_mode()
     params, dev = model.et_params()
-    C_obs, nrm = _dev_args(dev, C_obs, nrm)
-    k, n = C_obs.shape
-    T = params.base.obs_len
-    if k != params.base.pred_len or nrm.dim() != 2 or nrm.shape[0] < 2 or nrm.shape[1] != n:
-        raise ValueError(f"gpgraph_sgcn_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
-                         f"k = {params.base.pred_len}")
-    if scene_sizes is not None:
-        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
-        if not sizes and n:
-            raise ValueError(f"gpgraph_sgcn_forward_scenes: no scenes for {n} rows")
-        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
-    else:
-        sizes, off = [n], None
-    if scene_sizes is None and n > L.SGCN_MAX_N:
+    b = _scene_batch("gpgraph_sgcn_forward_scenes", dev, C_obs, nrm, params.base.pred_len, scene_sizes)
+    n = b.n
+    if b.off is None and n > L.SGCN_MAX_N:
         raise ValueError(f"gpgraph_sgcn_forward_scenes: a scene of {n} pedestrians exceeds the {L.SGCN_MAX_N} a scene may have")
     # (a listed scene above the limit is not refused: its rows come back NaN, the other scenes are computed)
-    sum_n2 = sum(s * s for s in sizes if s <= L.SGCN_MAX_N)
-    max_n = max(sizes, default=0)
-    out = torch.empty((k, n, params.base.out_dims), device=dev)
+    sum_n2 = sum(s * s for s in b.sizes if s <= L.SGCN_MAX_N)
+    out = torch.empty((params.base.pred_len, n, params.base.out_dims), device=dev)
     if n == 0:
-        L.call("et_gpgraph_sgcn_forward_scenes", C.byref(params), None, None, 0, L.ptr(off), 0 if off is None else len(sizes),
-               0, 0, None, None, None, None, None, None, 0, L.stream(dev))
+        L.call("et_gpgraph_sgcn_forward_scenes", C.byref(params), None, None, 0, L.ptr(b.off), b.n_scenes, 0, 0, None, None,
+               None, None, None, None, 0, L.stream(dev))
         return (out, {"group_index": torch.empty((0,), device=dev, dtype=torch.int32)}) if want_details else out
-    ws, nbytes, gi, dist, ls, lt = _gpgraph_buffers(params, want_details, T, n, sum_n2, len(sizes), dev)
-    L.call("et_gpgraph_sgcn_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
-           0 if off is None else len(sizes), sum_n2, max_n, L.ptr(out), L.ptr(gi), L.ptr(dist), L.ptr(ls), L.ptr(lt),
-           L.ptr(ws), nbytes, L.stream(dev))
+    ws, nbytes, gi, dist, ls, lt = _gpgraph_buffers(params, want_details, params.base.obs_len, n, sum_n2, len(b.sizes), dev)
+    L.call("et_gpgraph_sgcn_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), n, L.ptr(b.off), b.n_scenes,
+           sum_n2, b.max_n, L.ptr(out), L.ptr(gi), L.ptr(dist), L.ptr(ls), L.ptr(lt), L.ptr(ws), nbytes, L.stream(dev))
     if want_details:
         return out, {"group_index": gi, "dist": dist, "logit_s": ls, "logit_t": lt}
     return out
@@ -503,10 +499,7 @@ def gpgraph_sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_detail
 
 # ---------------------------------------------------------------------- GP-Graph-STGCNN predictor (inference)
 def _gpgraph_stgcnn_buffers(params, want, T, n, sum_n2, n_scenes, dev):
-    nbytes = L.lib().et_gpgraph_stgcnn_workspace_bytes(C.byref(params), n, sum_n2, int(n_scenes))
-    if not nbytes:
-        L.check(3, "et_gpgraph_stgcnn_workspace_bytes")  # outside the native family
-    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    ws, nbytes = _workspace("et_gpgraph_stgcnn_workspace_bytes", dev, params, n, sum_n2, n_scenes, required=True)
     gi = torch.empty((n,), device=dev, dtype=torch.int32)
     if not want:
         return ws, nbytes, gi, None, None
@@ -534,10 +527,7 @@ def gpgraph_stgcnn_forward_graph(model, v_abs, v_rel, want_details=False):
     if tuple(v_abs.shape) != (1, 1, T, n) or tuple(v_rel.shape) != (1, 1, T, n):
         raise ValueError(f"gpgraph_stgcnn_forward_graph: v_abs {tuple(v_abs.shape)} / v_rel {tuple(v_rel.shape)} are not "
                          f"(1,1,{T},N) / (1,1,{T},N)")
-    for name, t in (("v_abs", v_abs), ("v_rel", v_rel)):
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"gpgraph_stgcnn_forward_graph: {name} must be a contiguous float32 tensor on {dev} (got "
-                             f"{t.dtype}, {t.device}, contiguous={t.is_contiguous()})")
+    _read_in_place("gpgraph_stgcnn_forward_graph", dev, {"v_abs": v_abs, "v_rel": v_rel})
     if n > L.SGCN_MAX_N:
         raise ValueError(f"gpgraph_stgcnn_forward_graph: N = {n} exceeds the {L.SGCN_MAX_N} pedestrians a scene may have")
     out = torch.empty((1, S, k, n), device=dev)
@@ -559,44 +549,31 @@ def gpgraph_stgcnn_forward_graph(model, v_abs, v_rel, want_details=False):
 
 
 def gpgraph_stgcnn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
-    """The gpgraphstgcnn bridge + ``model`` (eval mode) + the post-hook for every scene of a split in three launches: C_obs
-    (k, N) and nrm (4, N) of :func:`norm_project`, ``scene_sizes`` as :func:`sgcn_forward_scenes` -> C_pred_refine (k, N, S).
+    """The gpgraphstgcnn bridge + ``model`` (eval mode) + the post-hook for every scene of a split in three launches: C_obs,
+    nrm, ``scene_sizes`` and the scene limit as :func:`gpgraph_sgcn_forward_scenes` -> C_pred_refine (k, N, S).
     With ``want_details`` also a dict: ``group_index`` (N,) int32 scene-local, ``dist`` packed (scene s's (n, n) block at
     n_0^2 + ... + n_{s-1}^2), ``n_groups`` (per scene, int64) and ``graph_inputs`` (3, T N) as include/eigentraj.h describes
     (pass m of scene s a (T, n_m) block at T (m N + off[s]))."""
     _stgcnn_base_of(model, "gpgraph_stgcnn_forward_scenes")
     model._check_mode()
     params, dev = model.et_params()
-    C_obs, nrm = _dev_args(dev, C_obs, nrm)
-    k, n = C_obs.shape
-    T = params.base.seq_len
-    if k != params.base.pred_seq_len or nrm.dim() != 2 or nrm.shape[0] < 2 or nrm.shape[1] != n:
-        raise ValueError(f"gpgraph_stgcnn_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
-                         f"k = {params.base.pred_seq_len}")
-    if scene_sizes is not None:
-        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
-        if not sizes and n:
-            raise ValueError(f"gpgraph_stgcnn_forward_scenes: no scenes for {n} rows")
-        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
-    else:
-        sizes, off = [n], None
-    if scene_sizes is None and n > L.SGCN_MAX_N:
+    b = _scene_batch("gpgraph_stgcnn_forward_scenes", dev, C_obs, nrm, params.base.pred_seq_len, scene_sizes)
+    n, sizes = b.n, b.sizes
+    if b.off is None and n > L.SGCN_MAX_N:
         raise ValueError(f"gpgraph_stgcnn_forward_scenes: a scene of {n} pedestrians exceeds the {L.SGCN_MAX_N} a scene may "
                          "have")
     # (a listed scene above the limit is not refused: its rows come back NaN, the other scenes are computed)
     sum_n2 = sum(s * s for s in sizes if s <= L.SGCN_MAX_N)
-    max_n = max(sizes, default=0)
-    out = torch.empty((k, n, params.base.output_feat), device=dev)
+    out = torch.empty((params.base.pred_seq_len, n, params.base.output_feat), device=dev)
     if n == 0:
-        L.call("et_gpgraph_stgcnn_forward_scenes", C.byref(params), None, None, 0, L.ptr(off), 0 if off is None else len(sizes),
-               0, 0, None, None, None, None, None, 0, L.stream(dev))
+        L.call("et_gpgraph_stgcnn_forward_scenes", C.byref(params), None, None, 0, L.ptr(b.off), b.n_scenes, 0, 0, None, None,
+               None, None, None, 0, L.stream(dev))
         empty = {"group_index": torch.empty((0,), device=dev, dtype=torch.int32), "dist": torch.empty((0,), device=dev),
                  "graph_inputs": torch.empty((3, 0), device=dev), "n_groups": torch.zeros((len(sizes),), dtype=torch.int64)}
         return (out, empty) if want_details else out
-    ws, nbytes, gi, dist, gin = _gpgraph_stgcnn_buffers(params, want_details, T, n, sum_n2, len(sizes), dev)
-    L.call("et_gpgraph_stgcnn_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
-           0 if off is None else len(sizes), sum_n2, max_n, L.ptr(out), L.ptr(gi), L.ptr(dist), L.ptr(gin), L.ptr(ws), nbytes,
-           L.stream(dev))
+    ws, nbytes, gi, dist, gin = _gpgraph_stgcnn_buffers(params, want_details, params.base.seq_len, n, sum_n2, len(sizes), dev)
+    L.call("et_gpgraph_stgcnn_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), n, L.ptr(b.off), b.n_scenes,
+           sum_n2, b.max_n, L.ptr(out), L.ptr(gi), L.ptr(dist), L.ptr(gin), L.ptr(ws), nbytes, L.stream(dev))
     if want_details:
         lo, groups = 0, []
         host = gi.cpu()
@@ -609,11 +586,6 @@ def gpgraph_stgcnn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_deta
 
 
 # ------------------------------------------------------------------------------ DMRGCN predictor (inference)
-def _dmrgcn_ws(params, n, max_n, dev):
-    nbytes = L.lib().et_dmrgcn_workspace_bytes(C.byref(params), n, max_n)
-    return (torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None), nbytes
-
-
 def dmrgcn_forward_graph(model, v, a):
     """``model`` (:class:`eigentrajectory_amd.dmrgcn.SocialDMRGCN`, eval mode) on one scene as the dmrgcn bridge hands it
     over: v (1, 1, K, N), a (1, 2, K, N, N) = [A_disp, A_dist], read as given -> the raw output (1, S, k, N).  One launch."""
@@ -624,44 +596,26 @@ def dmrgcn_forward_graph(model, v, a):
         raise ValueError(f"dmrgcn_forward_graph: v {tuple(v.shape)} / a {tuple(a.shape)} are not (1,1,{K},N) / (1,2,{K},N,N)")
     v, a = _dev_args(dev, v, a)
     out = torch.empty((1, S, k, n), device=dev)
-    ws, nbytes = _dmrgcn_ws(params, n, n, dev)
+    ws, nbytes = _workspace("et_dmrgcn_workspace_bytes", dev, params, n, n)
     L.call("et_dmrgcn_forward_graph", C.byref(params), L.ptr(v), L.ptr(a), n, L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
     return out
 
 
 def dmrgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
-    """The dmrgcn bridge + ``model`` (eval mode) + the post-hook for every scene of a split in ONE launch: C_obs (k, N) and
-    nrm (4, N) of :func:`norm_project` (rows 0-1: the last observed positions, centred here per scene), ``scene_sizes``
-    pedestrians per scene in row order (None = one scene; an empty list takes N = 0) -> C_pred_refine (k, N, S).  With
-    ``want_details`` also a dict: ``graph_inputs`` (K, N), the fp32 v = [C_obs; obs_ori] the kernel used."""
+    """The dmrgcn bridge + ``model`` (eval mode) + the post-hook for every scene of a split in ONE launch: C_obs, nrm and
+    ``scene_sizes`` as :func:`stgcnn_forward_scenes` -> C_pred_refine (k, N, S).  With ``want_details`` also a dict:
+    ``graph_inputs`` (K, N), the fp32 v = [C_obs; obs_ori] the kernel used."""
     params, dev = model.et_params()
-    C_obs, nrm = _dev_args(dev, C_obs, nrm)
-    k, n = C_obs.shape
-    if k != params.pred_seq_len or nrm.dim() != 2 or nrm.shape[0] < 2 or nrm.shape[1] != n:
-        raise ValueError(f"dmrgcn_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
-                         f"k = {params.pred_seq_len}")
-    if scene_sizes is not None:
-        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
-        if not sizes and n:
-            raise ValueError(f"dmrgcn_forward_scenes: no scenes for {n} rows")
-        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
-        max_n = max(sizes, default=0)
-    else:
-        sizes, off, max_n = None, None, n
-    out = torch.empty((k, n, params.output_feat), device=dev)
-    gin = torch.empty((params.seq_len, n), device=dev) if want_details else None
-    ws, nbytes = _dmrgcn_ws(params, n, max_n, dev)
-    L.call("et_dmrgcn_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
-           0 if off is None else len(sizes), L.ptr(out), L.ptr(gin), L.ptr(ws), nbytes, L.stream(dev))
+    b = _scene_batch("dmrgcn_forward_scenes", dev, C_obs, nrm, params.pred_seq_len, scene_sizes)
+    out = torch.empty((params.pred_seq_len, b.n, params.output_feat), device=dev)
+    gin = torch.empty((params.seq_len, b.n), device=dev) if want_details else None
+    ws, nbytes = _workspace("et_dmrgcn_workspace_bytes", dev, params, b.n, b.max_n)
+    L.call("et_dmrgcn_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), b.n, L.ptr(b.off), b.n_scenes,
+           L.ptr(out), L.ptr(gin), L.ptr(ws), nbytes, L.stream(dev))
     return (out, {"graph_inputs": gin}) if want_details else out
 
 
 # ------------------------------------------------------------------------------ Social-Implicit predictor (inference)
-def _implicit_ws(params, n, dev):
-    nbytes = L.lib().et_implicit_workspace_bytes(C.byref(params), n)
-    return (torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None), nbytes
-
-
 def implicit_forward_graph(model, v):
     """``model`` (:class:`eigentrajectory_amd.implicit.SocialImplicitLight`, eval mode) on one scene as the implicit bridge
     hands it over: v (1, 1, T, N) -> the raw output (1, S, T_out, N).  Two launches."""
@@ -672,46 +626,29 @@ def implicit_forward_graph(model, v):
     n = v.shape[-1]
     (v,) = _dev_args(dev, v)
     out = torch.empty((1, S, To, n), device=dev)
-    ws, nbytes = _implicit_ws(params, n, dev)
+    ws, nbytes = _workspace("et_implicit_workspace_bytes", dev, params, n)
     L.call("et_implicit_forward_graph", C.byref(params), L.ptr(v), n, L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
     return out
 
 
 def implicit_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
-    """The implicit bridge + ``model`` (eval mode) + the post-hook for every scene of a split in TWO launches: C_obs (k, N)
-    and nrm (4, N) of :func:`norm_project` (rows 0-1: the last observed positions, centred here per scene), ``scene_sizes``
-    pedestrians per scene in row order (None = one scene; an empty list takes N = 0) -> C_pred_refine (T_out, N, S).  With
+    """The implicit bridge + ``model`` (eval mode) + the post-hook for every scene of a split in TWO launches: C_obs, nrm and
+    ``scene_sizes`` as :func:`stgcnn_forward_scenes`, k = temporal_input - 2 -> C_pred_refine (T_out, N, S).  With
     ``want_details`` also a dict: ``graph_inputs`` (k + 2, N), the fp32 v = [C_obs; obs_ori] the kernel used, and ``zone``
     (N,) int32, every pedestrian's Social-Zone."""
     params, dev = model.et_params()
-    C_obs, nrm = _dev_args(dev, C_obs, nrm)
-    if C_obs.dim() != 2 or C_obs.shape[0] != params.temporal_input - 2 or nrm.dim() != 2 or nrm.shape[0] < 2 \
-            or nrm.shape[1] != C_obs.shape[1]:
-        raise ValueError(f"implicit_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
-                         f"temporal_input - 2 = {params.temporal_input - 2}")
-    n = C_obs.shape[1]
-    if scene_sizes is not None:
-        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
-        if not sizes and n:
-            raise ValueError(f"implicit_forward_scenes: no scenes for {n} rows")
-        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
-    else:
-        sizes, off = None, None
+    b = _scene_batch("implicit_forward_scenes", dev, C_obs, nrm, params.temporal_input - 2, scene_sizes)
+    n = b.n
     out = torch.empty((params.temporal_output, n, params.spatial_output), device=dev)
     gin = torch.empty((params.temporal_input, n), device=dev) if want_details else None
     zone = torch.empty((n,), device=dev, dtype=torch.int32) if want_details else None
-    ws, nbytes = _implicit_ws(params, n, dev)
-    L.call("et_implicit_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
-           0 if off is None else len(sizes), L.ptr(out), L.ptr(gin), L.ptr(zone), L.ptr(ws), nbytes, L.stream(dev))
+    ws, nbytes = _workspace("et_implicit_workspace_bytes", dev, params, n)
+    L.call("et_implicit_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), n, L.ptr(b.off), b.n_scenes,
+           L.ptr(out), L.ptr(gin), L.ptr(zone), L.ptr(ws), nbytes, L.stream(dev))
     return (out, {"graph_inputs": gin, "zone": zone}) if want_details else out
 
 
 # ------------------------------------------------------------------------------ AgentFormer predictor (inference)
-def _agentformer_ws(params, n, max_n, dev):
-    nbytes = L.lib().et_agentformer_workspace_bytes(C.byref(params), n, max_n)
-    return (torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None), nbytes
-
-
 def agentformer_forward_graph(model, pre_motion):
     """``model`` (:class:`eigentrajectory_amd.agentformer.AgentFormerLight`, eval mode) on one scene as the agentformer
     bridge hands it over: pre_motion (T, N, 1) or (T, N) -> ``_seq_out`` (k, N, S).  1 + 2 encoder layers + 4 decoder layers
@@ -728,50 +665,36 @@ def agentformer_forward_graph(model, pre_motion):
                          "scene may have")
     (u,) = _dev_args(dev, pre_motion)
     out = torch.empty((k, n, S), device=dev)
-    ws, nbytes = _agentformer_ws(params, n, n, dev)
+    ws, nbytes = _workspace("et_agentformer_workspace_bytes", dev, params, n, n)
     L.call("et_agentformer_forward_graph", C.byref(params), L.ptr(u), n, L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
     return out
 
 
 def agentformer_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
     """The agentformer bridge + ``model`` (eval mode) + the post-hook for every scene of a split in 2 + 2 encoder layers + 4
-    decoder layers launches: C_obs (k, N) and nrm (4, N) of :func:`norm_project` (rows 0-1: the last observed positions,
-    centred here per scene), ``scene_sizes`` pedestrians per scene in row order (None = one scene; an empty list takes
-    N = 0) -> C_pred_refine (k, N, S).  A scene of more than 128 pedestrians is not computed: its rows are NaN.  With
-    ``want_details`` also a dict: ``graph_inputs`` (k + 2, N), the fp32 pre_motion = [C_obs; obs_ori] the kernels used."""
+    decoder layers launches: C_obs, nrm and ``scene_sizes`` as :func:`stgcnn_forward_scenes`, k = future_frames =
+    past_frames - 2 -> C_pred_refine (k, N, S).  One unlisted scene of more than 128 pedestrians raises ValueError; a listed
+    one is not computed: its rows are NaN.  With ``want_details`` also a dict: ``graph_inputs`` (k + 2, N), the fp32
+    pre_motion = [C_obs; obs_ori] the kernels used."""
     params, dev = model.et_params()
-    C_obs, nrm = _dev_args(dev, C_obs, nrm)
     k = params.future_frames
-    if C_obs.dim() != 2 or C_obs.shape[0] != k or params.past_frames != k + 2 or nrm.dim() != 2 or nrm.shape[0] < 2 \
-            or nrm.shape[1] != C_obs.shape[1]:
-        raise ValueError(f"agentformer_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
-                         f"future_frames = {k}, past_frames = {params.past_frames}")
-    n = C_obs.shape[1]
-    if scene_sizes is not None:
-        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
-        if not sizes and n:
-            raise ValueError(f"agentformer_forward_scenes: no scenes for {n} rows")
-        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
-        max_n = max(sizes, default=0)
-    else:
-        sizes, off, max_n = None, None, n
-        if n > L.AGENTFORMER_MAX_SCENE_N:
-            raise ValueError(f"agentformer_forward_scenes: one scene of {n} pedestrians exceeds the "
-                             f"{L.AGENTFORMER_MAX_SCENE_N} a scene may have")
+    if params.past_frames != k + 2:
+        raise ValueError(f"agentformer_forward_scenes: past_frames = {params.past_frames} is not future_frames + 2 = {k + 2}, "
+                         f"the rows of [C_obs; obs_ori] (C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)})")
+    b = _scene_batch("agentformer_forward_scenes", dev, C_obs, nrm, k, scene_sizes)
+    n = b.n
+    if b.off is None and n > L.AGENTFORMER_MAX_SCENE_N:
+        raise ValueError(f"agentformer_forward_scenes: one scene of {n} pedestrians exceeds the "
+                         f"{L.AGENTFORMER_MAX_SCENE_N} a scene may have")
     out = torch.empty((k, n, params.forecast_dim), device=dev)
     gin = torch.empty((k + 2, n), device=dev) if want_details else None
-    ws, nbytes = _agentformer_ws(params, n, max_n, dev)
-    L.call("et_agentformer_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
-           0 if off is None else len(sizes), L.ptr(out), L.ptr(gin), L.ptr(ws), nbytes, L.stream(dev))
+    ws, nbytes = _workspace("et_agentformer_workspace_bytes", dev, params, n, b.max_n)
+    L.call("et_agentformer_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), n, L.ptr(b.off), b.n_scenes,
+           L.ptr(out), L.ptr(gin), L.ptr(ws), nbytes, L.stream(dev))
     return (out, {"graph_inputs": gin}) if want_details else out
 
 
 # ------------------------------------------------------------------------------ Graph-TERN predictor (inference)
-def _graphtern_ws(params, n, max_n, dev):
-    nbytes = L.lib().et_graphtern_workspace_bytes(C.byref(params), n, max_n)
-    return (torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None), nbytes
-
-
 def graphtern_forward_graph(model, S_obs):
     """``model`` (:class:`eigentrajectory_amd.graphtern.GraphTERNLight`, eval mode) on one scene as the graphtern bridge
     hands it over: S_obs (1, 2, T, N, 1) = [abs, rel], both read as given -> the raw output (1, k, N, S).  One launch."""
@@ -782,43 +705,26 @@ def graphtern_forward_graph(model, S_obs):
         raise ValueError(f"graphtern_forward_graph: S_obs {tuple(S_obs.shape)} is not (1,2,{T},N,1)")
     (S_obs,) = _dev_args(dev, S_obs)
     out = torch.empty((1, k, n, S), device=dev)
-    ws, nbytes = _graphtern_ws(params, n, n, dev)
+    ws, nbytes = _workspace("et_graphtern_workspace_bytes", dev, params, n, n)
     L.call("et_graphtern_forward_graph", C.byref(params), L.ptr(S_obs), n, L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
     return out
 
 
 def graphtern_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
-    """The graphtern bridge + ``model`` (eval mode) + the post-hook for every scene of a split in ONE launch: C_obs (k, N)
-    and nrm (4, N) of :func:`norm_project` (rows 0-1: the last observed positions, centred here per scene), ``scene_sizes``
-    pedestrians per scene in row order (None = one scene; an empty list takes N = 0) -> C_pred_refine (k, N, S).  With
-    ``want_details`` also a dict: ``graph_inputs`` (T, N), the fp32 u = [C_obs; obs_ori] the kernel used."""
+    """The graphtern bridge + ``model`` (eval mode) + the post-hook for every scene of a split in ONE launch: C_obs, nrm and
+    ``scene_sizes`` as :func:`stgcnn_forward_scenes` -> C_pred_refine (k, N, S).  With ``want_details`` also a dict:
+    ``graph_inputs`` (T, N), the fp32 u = [C_obs; obs_ori] the kernel used."""
     params, dev = model.et_params()
-    C_obs, nrm = _dev_args(dev, C_obs, nrm)
-    k, n = C_obs.shape
-    if k != params.pred_seq_len or nrm.dim() != 2 or nrm.shape[0] < 2 or nrm.shape[1] != n:
-        raise ValueError(f"graphtern_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
-                         f"k = {params.pred_seq_len}")
-    if scene_sizes is not None:
-        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
-        if not sizes and n:
-            raise ValueError(f"graphtern_forward_scenes: no scenes for {n} rows")
-        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
-        max_n = max(sizes, default=0)
-    else:
-        sizes, off, max_n = None, None, n
-    out = torch.empty((k, n, params.n_smpl), device=dev)
-    gin = torch.empty((params.seq_len, n), device=dev) if want_details else None
-    ws, nbytes = _graphtern_ws(params, n, max_n, dev)
-    L.call("et_graphtern_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
-           0 if off is None else len(sizes), L.ptr(out), L.ptr(gin), L.ptr(ws), nbytes, L.stream(dev))
+    b = _scene_batch("graphtern_forward_scenes", dev, C_obs, nrm, params.pred_seq_len, scene_sizes)
+    out = torch.empty((params.pred_seq_len, b.n, params.n_smpl), device=dev)
+    gin = torch.empty((params.seq_len, b.n), device=dev) if want_details else None
+    ws, nbytes = _workspace("et_graphtern_workspace_bytes", dev, params, b.n, b.max_n)
+    L.call("et_graphtern_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), b.n, L.ptr(b.off), b.n_scenes,
+           L.ptr(out), L.ptr(gin), L.ptr(ws), nbytes, L.stream(dev))
     return (out, {"graph_inputs": gin}) if want_details else out
 
+
 # ------------------------------------------------------------------------------ PECNet / LBEBM predictors (inference)
-def _mlp_ws(kind, params, n, dev):
-    nbytes = getattr(L.lib(), f"et_{kind}_workspace_bytes")(C.byref(params), n)
-    return (torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None), nbytes
-
-
 def _mlp_rows(who, dev, width, **tensors):
     """(N, width_i) float32 rows on ``dev``, all of one N"""
     out = _dev_args(dev, *tensors.values())
@@ -841,7 +747,7 @@ def pecnet_predict(model, past, generated_dest, mask, initial_pos):
         if tuple(mask.shape) != (n, n):
             raise ValueError(f"pecnet_predict: mask {tuple(mask.shape)} is not ({n}, {n})")
     out = torch.empty((n, params.out_width), device=dev)
-    ws, nbytes = _mlp_ws("pecnet", params, n, dev)
+    ws, nbytes = _workspace("et_pecnet_workspace_bytes", dev, params, n)
     L.call("et_pecnet_predict", C.byref(params), L.ptr(past), L.ptr(dest), L.ptr(mask), L.ptr(pos), n, L.ptr(out), L.ptr(ws),
            nbytes, L.stream(dev))
     return out
@@ -854,42 +760,30 @@ def lbebm_predict(model, past, generated_dest):
     n, (past, dest) = _mlp_rows("lbebm_predict", dev, (params.encoder_past.widths[0], params.encoder_dest.widths[0]),
                                 past=past, generated_dest=generated_dest)
     out = torch.empty((n, params.out_width), device=dev)
-    ws, nbytes = _mlp_ws("lbebm", params, n, dev)
+    ws, nbytes = _workspace("et_lbebm_workspace_bytes", dev, params, n)
     L.call("et_lbebm_predict", C.byref(params), L.ptr(past), L.ptr(dest), n, L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
     return out
 
 
 def _mlp_forward_scenes(kind, model, C_obs, nrm, scene_sizes, want_details):
     params, dev = model.et_params()
-    C_obs, nrm = _dev_args(dev, C_obs, nrm)
-    k, n = C_obs.shape
-    if k != params.encoder_past.widths[0] or nrm.dim() != 2 or nrm.shape[0] < 2 or nrm.shape[1] != n:
-        raise ValueError(f"{kind}_forward_scenes: C_obs {tuple(C_obs.shape)} / nrm {tuple(nrm.shape)} do not match "
-                         f"k = {params.encoder_past.widths[0]}")
-    if scene_sizes is not None:
-        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
-        if not sizes and n:
-            raise ValueError(f"{kind}_forward_scenes: no scenes for {n} rows")
-        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
-    else:
-        sizes, off = None, None
-    largest = n if sizes is None else max(sizes, default=0)
-    if params.nonlocal_pools > 0 and largest > L.MLP_MAX_RANGE:
-        raise ValueError(f"{kind}_forward_scenes: a scene of {largest} pedestrians is beyond the pooling step's range of "
+    k = params.encoder_past.widths[0]
+    b = _scene_batch(f"{kind}_forward_scenes", dev, C_obs, nrm, k, scene_sizes)
+    n = b.n
+    if params.nonlocal_pools > 0 and b.max_n > L.MLP_MAX_RANGE:
+        raise ValueError(f"{kind}_forward_scenes: a scene of {b.max_n} pedestrians is beyond the pooling step's range of "
                          f"{L.MLP_MAX_RANGE} (ET_MLP_MAX_RANGE)")
     out = torch.empty((k, n, params.out_width // max(k, 1)), device=dev)
     gin = torch.empty((k + 2, n), device=dev) if want_details else None
-    ws, nbytes = _mlp_ws(kind, params, n, dev)
-    L.call(f"et_{kind}_forward_scenes", C.byref(params), L.ptr(C_obs), L.ptr(nrm), n, L.ptr(off),
-           0 if off is None else len(sizes), L.ptr(out), L.ptr(gin), L.ptr(ws), nbytes, L.stream(dev))
+    ws, nbytes = _workspace(f"et_{kind}_workspace_bytes", dev, params, n)
+    L.call(f"et_{kind}_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), n, L.ptr(b.off), b.n_scenes,
+           L.ptr(out), L.ptr(gin), L.ptr(ws), nbytes, L.stream(dev))
     return (out, {"net_inputs": gin}) if want_details else out
 
 
 def pecnet_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
     """The pecnet bridge + ``model.predict`` (eval mode) + the post-hook for every scene of a split in 2 + 2 nonlocal_pools
-    launches: C_obs (k, N) and nrm (4, N) of :func:`norm_project` (rows 0-1: the last observed positions, centred here per
-    scene), ``scene_sizes`` pedestrians per scene in row order (None = one scene; an empty list takes N = 0) ->
-    C_pred_refine (k, N, S).  Every scene is its own softmax range under an all-ones mask, as in the reference's test loop
+    launches: C_obs, nrm and ``scene_sizes`` as :func:`stgcnn_forward_scenes` -> C_pred_refine (k, N, S).  Every scene is its own softmax range under an all-ones mask, as in the reference's test loop
     (one scene per call); a scene of more than ET_MLP_MAX_RANGE (4096) pedestrians raises ValueError before any launch.  With
     ``want_details`` also a dict: ``net_inputs`` (k + 2, N), the fp32 [C_obs; obs_ori] used."""
     return _mlp_forward_scenes("pecnet", model, C_obs, nrm, scene_sizes, want_details)

@@ -69,16 +69,6 @@ class MLP(nn.Module):
             chain.w[i], chain.b[i] = lin.weight.data_ptr(), lin.bias.data_ptr()
 
 
-def check_tensors(module, who):
-    """-> the one HIP device every parameter of ``module`` lives on (fp32, contiguous); there is no CPU path"""
-    tensors = list(module.parameters())
-    dev = tensors[0].device
-    if dev.type != "cuda" or any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
-        raise L.ETLibraryError(f"{who}: every parameter must be a contiguous float32 tensor on ONE HIP device "
-                               "(model.cuda()); there is no CPU path")
-    return dev
-
-
 def require_eval(module, who):
     if module.training:
         raise RuntimeError(f"{who}: only predict() in eval mode is native (no CVAE, no sampling, no backward pass) -- call "
@@ -148,7 +138,7 @@ class PECNet(nn.Module):
         p.out_width = self.predictor.layers[-1].out_features
         for name in ("encoder_past", "encoder_dest", "non_local_theta", "non_local_phi", "non_local_g", "predictor"):
             getattr(self, name).et_chain(getattr(p, name), f"PECNet.{name}")
-        return p, check_tensors(self, "PECNet")
+        return p, L.module_device("PECNet", self)
 
     def chain_parameter_names(self):
         return [f"{name}.layers.{i}.{kind}" for name in self.CHAINS for i in range(len(getattr(self, name).layers))

@@ -32,10 +32,10 @@ from __future__ import annotations
 
 import math
 
-import torch
 import torch.nn as nn
 
 from . import _lib as L
+from ._lib import _p
 
 
 class _AsymmetricConvolution(nn.Module):
@@ -106,10 +106,6 @@ class _SparseGraphConvolution(nn.Module):
         self.temporal_spatial_sparse_gcn.append(_GraphConvolution(embedding_dims, embedding_dims))
 
 
-def _p(t):
-    return t.data_ptr()
-
-
 class SGCN(nn.Module):
     r"""baseline/sgcn/model.py's ``TrajectoryModel`` (eval-mode inference on the GPU).  ``forward(graph, identity)``: graph
     (1, T, N, 1) and the two identities as the sgcn bridge's pre-hook builds them -> (pred_len, N, out_dims)."""
@@ -139,11 +135,7 @@ class SGCN(nn.Module):
         p.n_asym, p.embedding_dims, p.n_gcn_layers = self.number_asymmetric_conv_layer, self.embedding_dims, self.number_gcn_layers
         p.obs_len, p.pred_len, p.n_tcn, p.in_dims = self.obs_len, self.pred_len, self.n_tcn, self.in_dims
         p.out_dims, p.num_heads, p.dropout = self.out_dims, self.num_heads, float(self.dropout)
-        tensors = list(self.parameters())
-        dev = tensors[0].device
-        if dev.type != "cuda" or any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
-            raise L.ETLibraryError("SGCN: every parameter must be a contiguous float32 tensor on ONE HIP device "
-                                   "(model.cuda()); there is no CPU path")
+        dev = L.module_device("SGCN", self)
         if (self.number_asymmetric_conv_layer > L.SGCN_MAX_LAYERS or self.n_tcn > L.SGCN_MAX_LAYERS or self.in_dims != 1
                 or self.num_heads != 4 or self.embedding_dims != 64):
             return p, dev  # the kernels answer ET_ERR_UNSUPPORTED

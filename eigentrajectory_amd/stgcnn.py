@@ -24,10 +24,10 @@ only as the three passes of GPGraphSTGCNN's call; its own forward raises.
 """
 from __future__ import annotations
 
-import torch
 import torch.nn as nn
 
 from . import _lib as L
+from ._lib import _p
 
 
 class _GraphConv(nn.Module):
@@ -57,10 +57,6 @@ class _STGCNBlock(nn.Module):
         self.prelu = nn.PReLU()
 
 
-def _p(t):
-    return t.data_ptr()
-
-
 class SocialSTGCNN(nn.Module):
     r"""baseline/stgcnn/model.py's ``social_stgcnn`` (eval-mode inference on the GPU).  ``forward(v, a)``: v (1, 1, K, N),
     a (K, N, N) as the stgcnn bridge's pre-hook builds them -> (1, S, k, N), the raw output the post-hook permutes."""
@@ -85,11 +81,7 @@ class SocialSTGCNN(nn.Module):
         p.n_stgcnn, p.n_txpcnn, p.input_feat = self.n_stgcnn, self.n_txpcnn, self.input_feat
         p.output_feat, p.seq_len, p.pred_seq_len, p.kernel_size = (self.output_feat, self.seq_len, self.pred_seq_len,
                                                                    self.kernel_size)
-        tensors = list(self.parameters()) + [b for b in self.buffers() if b.is_floating_point()]
-        dev = tensors[0].device
-        if dev.type != "cuda" or any(t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
-            raise L.ETLibraryError("SocialSTGCNN: every parameter and buffer must be a contiguous float32 tensor on ONE HIP "
-                                   "device (model.cuda()); there is no CPU path")
+        dev = L.module_device("SocialSTGCNN", self, buffers=True)
         bns = [m for m in self.modules() if isinstance(m, nn.BatchNorm2d)]
         eps = {float(m.eps) for m in bns}
         if len(eps) != 1 or any(m.running_mean is None or m.weight is None for m in bns):

@@ -118,6 +118,139 @@ def test_argument_validation_without_device_work():
     assert lib.et_kmeans_predict(null, z, 6, null, 20, null, null, null) == 1
 
 
+def _fill_pointers(obj, value):
+    """Every pointer field of a ctypes struct (nested structs and arrays included) := value."""
+    if isinstance(obj, ctypes.Array):
+        for i in range(len(obj)):
+            if obj._type_ is ctypes.c_void_p:
+                obj[i] = value
+            elif not issubclass(obj._type_, ctypes._SimpleCData):
+                _fill_pointers(obj[i], value)
+        return
+    for name, typ in obj._fields_:
+        if typ is ctypes.c_void_p:
+            setattr(obj, name, value)
+        elif not issubclass(typ, ctypes._SimpleCData):
+            _fill_pointers(getattr(obj, name), value)
+
+
+def _scene_entry_params(ph):
+    """{predictor: (params struct of a small supported configuration (k = 6, S = 20, one layer of each kind), the field
+    whose value -- second item -- takes it outside the native family)}.  ``ph`` stands for every weight pointer: the host
+    checks them against NULL and never reads through them."""
+    from eigentrajectory_amd import _lib as L
+
+    def stgcnn(n_txpcnn=1):
+        p = L.STGCNNParams(n_stgcnn=1, n_txpcnn=n_txpcnn, input_feat=1, output_feat=20, seq_len=8, pred_seq_len=6,
+                           kernel_size=3, bn_eps=1e-5)
+        _fill_pointers(p, ph)
+        return p
+
+    def sgcn():
+        p = L.SGCNParams(n_asym=1, embedding_dims=64, n_gcn_layers=1, obs_len=8, pred_len=6, n_tcn=1, in_dims=1, out_dims=20,
+                         num_heads=4, dropout=0.0)
+        _fill_pointers(p, ph)
+        return p
+
+    gp_sgcn, gp_stgcnn = L.GPGraphSGCNParams(), L.GPGraphSTGCNNParams()
+    _fill_pointers(gp_sgcn, ph)
+    _fill_pointers(gp_stgcnn, ph)
+    gp_sgcn.base, gp_sgcn.tau, gp_stgcnn.base, gp_stgcnn.tau = sgcn(), 0.1, stgcnn(), 0.1
+
+    dm = L.DMRGCNParams(n_stgcn=1, n_tpcnn=1, input_feat=1, output_feat=20, seq_len=8, pred_seq_len=6, kernel_size=3)
+    _fill_pointers(dm, ph)
+    for r, split in enumerate(([0, 1 / 4, 2 / 4, 3 / 4, 1], [0, 1 / 2, 1, 2, 4])):
+        for b, v in enumerate(split):
+            dm.split[r][b] = v
+
+    im = L.ImplicitParams(spatial_input=1, spatial_output=20, temporal_input=8, temporal_output=6, n_bins=1)
+    _fill_pointers(im, ph)
+
+    af = L.AgentFormerParams(motion_dim=1, model_dim=16, ff_dim=16, nhead=1, forecast_dim=20, past_frames=8, future_frames=6,
+                             n_enc=1, n_dec=1)
+    _fill_pointers(af, ph)
+
+    gt = L.GraphTERNParams(n_epgcn=1, n_epcnn=2, input_feat=1, hidden_feat=16, seq_len=8, pred_seq_len=6, n_smpl=20)
+    _fill_pointers(gt, ph)
+    # the residual convolutions exist only where the widths differ: T != k in the first epcnn block, 16 != S in the last
+    gt.tpcnns[0].resc_w = gt.tpcnns[0].resc_b = gt.tpcnns[1].rest_w = gt.tpcnns[1].rest_b = None
+
+    def mlp(pecnet):
+        p = L.MLPParams(fdim=4, nonlocal_pools=0, non_local_dim=0, out_width=12, pos_width=2 if pecnet else 0)
+        _fill_pointers(p, ph)
+        for chain, widths in ((p.encoder_past, (6, 8, 4)), (p.encoder_dest, (2, 8, 4)),
+                              (p.predictor, (2 * 4 + p.pos_width, 8, 12))):
+            chain.n_layers = 2
+            for i, w in enumerate(widths):
+                chain.widths[i] = w
+        return p
+
+    return {"stgcnn": (stgcnn(), "kernel_size", 5), "sgcn": (sgcn(), "num_heads", 2),
+            "gpgraph_sgcn": (gp_sgcn, "base.num_heads", 2), "gpgraph_stgcnn": (gp_stgcnn, "base.kernel_size", 5),
+            "dmrgcn": (dm, "kernel_size", 5), "implicit": (im, "spatial_input", 2), "agentformer": (af, "motion_dim", 2),
+            "graphtern": (gt, "hidden_feat", 8), "pecnet": (mlp(True), "fdim", 0), "lbebm": (mlp(False), "fdim", 0),
+            "stgcnn_3tpcnn": (stgcnn(3), None, None)}
+
+
+@needs_no_gpu
+def test_scene_entry_points_answer_before_any_launch():
+    """The status every et_*_forward_scenes entry point answers to arguments it refuses, or finishes, on the host: no row
+    gets as far as a launch, and none makes the host read scene_offsets (a placeholder address, like every other
+    pointer here).  Then the workspace sizes of the three predictors that keep a per-scene arena."""
+    from eigentrajectory_amd import _lib as L
+    lib = L.lib()
+    backing = (ctypes.c_char * 64)()
+    ph = ctypes.addressof(backing)
+    params = _scene_entry_params(ph)
+    # predictor: (arguments between n_scenes and C_pred_refine, optional outputs after it, largest unlisted batch)
+    table = {"stgcnn": ((), 0, L.SCENE_MAX_N), "sgcn": ((0, 0), 2, L.SGCN_MAX_N), "gpgraph_sgcn": ((0, 0), 4, L.SGCN_MAX_N),
+             "gpgraph_stgcnn": ((0, 0), 3, L.SGCN_MAX_N), "dmrgcn": ((), 1, L.SCENE_MAX_N), "implicit": ((), 2, L.SCENE_MAX_N),
+             "agentformer": ((), 1, L.AGENTFORMER_MAX_SCENE_N), "graphtern": ((), 1, L.SCENE_MAX_N),
+             "pecnet": ((), 1, L.SCENE_MAX_N), "lbebm": ((), 1, L.SCENE_MAX_N)}
+    assert len(table) == 10
+    for name, (mid, n_optional, one_scene_cap) in table.items():
+        fn = getattr(lib, f"et_{name}_forward_scenes")
+        good, bad_field, bad_value = params[name]
+
+        def status(p, N, off, n_scenes, data=ph, ws=ph, ws_bytes=1 << 20):
+            return fn(p, data, data, N, off, n_scenes, *mid, data, *([None] * n_optional), ws, ws_bytes, None)
+
+        ref = ctypes.byref(good)
+        assert status(None, 3, None, 0) == 1, name                      # no parameters
+        assert status(ref, -1, None, 0) == 1, name                      # N < 0
+        assert status(ref, 3, ph, -1) == 1, name                        # n_scenes < 0
+        assert status(ref, 5, ph, 0) == 1, name                         # offsets without scenes, for 5 rows
+        assert status(ref, 0, ph, 0) == 0, name                         # offsets without scenes, for no rows: nothing to do
+        assert status(ref, one_scene_cap + 1, None, 0) == 1, name       # one unlisted scene above the limit
+        assert status(ref, 0, None, 0) == 0, name                       # N == 0: nothing to do
+        assert status(ref, 3, None, 0, data=None) == 1, name            # no C_obs / nrm / C_pred_refine
+        if name in ("implicit", "agentformer"):
+            assert status(ref, 3, None, 0, ws=None, ws_bytes=0) == 4, name  # these two need a workspace for any N > 0
+        owner, _, field = bad_field.rpartition(".")
+        owner = getattr(good, owner) if owner else good
+        keep = getattr(owner, field)
+        setattr(owner, field, bad_value)
+        assert status(ref, 3, None, 0) == 3, name                       # outside the native family
+        setattr(owner, field, keep)
+        assert status(ref, 0, None, 0) == 0, name                       # (the struct is whole again)
+
+    # arena predictors: floats per pedestrian from the header comment of each source file, K = T = k + 2 = 8, S = 20
+    K, k, S = 8, 6, 20
+    arenas = {"stgcnn": (params["stgcnn_3tpcnn"][0], 2 * K + 2 * S * K + k * S),   # 2K + 2SK + Q, Q = k S with 3 tpcnn layers
+              "dmrgcn": (params["dmrgcn"][0], 2 * K + 10 * K + 3 * S * K),          # 2K + 10K + 3Q, Q = S K
+              "graphtern": (params["graphtern"][0], 6 * K + 3 * 16 * K)}            # 6T + 3Q, Q = 16 T
+    assert [4 * per for _, per in arenas.values()] == [1824, 2304, 1728]           # the bytes those comments state
+    for name, (p, per) in arenas.items():
+        fn = getattr(lib, f"et_{name}_workspace_bytes")
+        ref = ctypes.byref(p)
+        fits = (60 * 1024) // (per * 4)  # the largest scene whose arena fits the 60 KiB of LDS
+        assert fn(None, 100, 10) == 0 and fn(ref, -1, 10) == 0 and fn(ref, 100, -1) == 0, name
+        assert fn(ref, 100, 0) == 0 and fn(ref, 100, fits) == 0 and fn(ref, 10 ** 6, fits) == 0, name
+        assert fn(ref, 100, fits + 1) == per * 100 * 4 and fn(ref, 10 ** 6, fits + 1) == per * 10 ** 6 * 4, name
+        setattr(p, *params[name][1:])
+        assert fn(ref, 100, fits + 1) == 0, name                                   # outside the native family
+
+
 @needs_no_gpu
 def test_product_path_fails_loudly_without_gpu():
     from eigentrajectory_amd import TrajNorm, ops
