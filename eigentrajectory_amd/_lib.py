@@ -102,6 +102,10 @@ SIGNATURES = {
     "et_implicit_workspace_bytes": (_Z, [_P, _I64]),
     "et_implicit_forward_graph": (_I, [_P, _P, _I64, _P, _P, _Z, _P]),
     "et_implicit_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _P, _Z, _P]),
+    # ---- Social-Implicit predictor, training
+    "et_implicit_backward_workspace_bytes": (_Z, [_P, _I64]),
+    "et_implicit_backward_graph": (_I, [_P, _P, _I64, _P, _Z, _P, _I, _P, _P, _Z, _P]),
+    "et_implicit_backward_scenes": (_I, [_P, _I64, _P, _Z, _P, _P, _P, _Z, _P]),
     # ---- PECNet / LBEBM predictors, inference
     "et_pecnet_workspace_bytes": (_Z, [_P, _I64]),
     "et_pecnet_predict": (_I, [_P, _P, _P, _P, _P, _I64, _P, _P, _Z, _P]),
@@ -288,6 +292,7 @@ class DMRGCNParams(C.Structure):
 
 
 IMPLICIT_MAX_BINS = 8  # ET_IMPLICIT_MAX_BINS
+IMPLICIT_BWD_CHUNK = 8  # ET_IMPLICIT_BWD_CHUNK: rows whose gradient terms one workgroup adds, in row order
 
 
 class ImplicitCell(C.Structure):

@@ -7,7 +7,8 @@
 // here.  Two launches, whatever the number of scenes:
 //   implicit_prep_kernel  one workgroup per scene: the scene's v = [C_obs; obs_ori] (scene form), and per pedestrian a
 //                         row of kImTab int32: its zone, the rows of its two predecessors and two successors of the same
-//                         zone within the scene (-1: none), the scene's first row and size
+//                         zone within the scene (-1: none), the scene's first row and size; the eighth entry is 0, or in
+//                         a skipped scene the zone the pedestrian would have had (the backward pass reads it)
 //   implicit_main_kernel  tiles of pedestrians, each pedestrian on its own from its five gathered columns of v:
 //                         u = relu(feat(v)) + highway_input(v) at the compacted positions -1, 0, +1 (S, T each), the local
 //                         stream's (S, T) plane, then the S x T_out outputs.  The zero padding of tpcnn pads u: u of a
@@ -18,6 +19,8 @@
 // The noise term of SocialCellGlobal is noise_w * noise_weights[i] * 0 in the Light form and is left out.  For a finite
 // noise_w it is a zero: adding it could only turn a -0.0 of v into +0.0, i.e. change the sign of a zero product.  A
 // non-finite noise_w (NaN everywhere in the reference) is not reproduced.
+// Training: the forward above is the training-mode forward too; its backward pass (two launches more, the gradients of every
+// cell's tensors) is the second half of this file, "backward".
 #include "et_common.h"
 
 namespace et {
@@ -33,6 +36,7 @@ constexpr int kImMaxBins = ET_IMPLICIT_MAX_BINS;
 constexpr int kImMaxTile = 8;    // pedestrians of one tile
 constexpr int kImMaxGrid = 1024;  // workgroups of the main kernel (they stride over the tiles)
 constexpr int kImTab = 8;  // int32 per pedestrian: zone, rows of the neighbours -2, -1, +1, +2, scene begin, scene size, 0
+                           // (of a skipped scene: the zone it would have had)
 constexpr int kImSkipped = -2;  // zone of a pedestrian whose scene is larger than ET_SCENE_MAX_N (-1: in no zone)
 
 // float offsets of one cell's tensors in the LDS copy (field order of et_implicit_cell)
@@ -107,7 +111,8 @@ __global__ __launch_bounds__(kImThreads) void implicit_prep_kernel(et_implicit_p
         for (int w = tid; w < n; w += kImThreads) {
             int32_t *t = tab + (b + w) * kImTab;
             t[0] = kImSkipped;
-            for (int i = 1; i < kImTab; ++i) t[i] = i < 5 ? -1 : 0;
+            for (int i = 1; i < kImTab - 1; ++i) t[i] = i < 5 ? -1 : 0;
+            t[7] = zone_of(gv ? gv[w] : C_obs[b + w], p);  // read by the backward pass alone: the cell whose gradients it makes NaN
             if (zone_out) zone_out[b + w] = kImSkipped;
         }
         if (gin)
@@ -342,6 +347,301 @@ static int im_launch_main(const et_implicit_params &p, const float *src, const i
     return ET_OK;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------- backward
+// The gradients of the 18 tensors of every cell that the forward reads (noise_w has none to compute: its term is a product
+// with the zero noise), one block of im_layout().size floats per cell in et_implicit_cell's field order.  A pedestrian's
+// output depends on its own five gathered columns alone, so its contribution to every weight gradient is formed on its
+// own, from those columns and its (S, T_out) block G of the upstream gradient; nothing of the forward is kept but the
+// neighbour table.  Two launches whatever N:
+//   implicit_bwd_kernel      one workgroup per (chunk of kImChunk rows, cell).  The chunk's pedestrians of that cell, one
+//                            after the other in row order: u, ul, g, l again with the forward's own statements; du, dul
+//                            from dg = global_w G and dl = local_w G (G read by flat index, the inverse of the local
+//                            stream's reshape); dpre = du where pre > 0 (a NaN pre passes, as torch's relu backward does),
+//                            +0 elsewhere.  Then every gradient element, owned by one thread, CONTINUES its accumulator:
+//                            one fmaf (or addition) per term, ascending over the element's inner index (the position q,
+//                            then t; or s; or the flat index of G for the two scalars).
+//   implicit_bwd_sum_kernel  grad = the chunks' partial blocks added in ascending chunk order.
+// So the summation order of an element is: rows ascending inside chunks of kImChunk rows from a +0 accumulator, then the
+// chunks ascending; it depends on N through the number of chunks only.  No atomics.  Terms that the forward's zero padding
+// of u contributes (a missing neighbour: u = 0) are formed (0 x NaN is a NaN); a missing neighbour carries no gradient to
+// feat / highway_input; taps beyond the T and S edges are not terms, as in the forward.
+constexpr int kImChunk = ET_IMPLICIT_BWD_CHUNK;
+constexpr int kImBwdLdsBytes = 64 * 1024;
+
+__host__ __device__ inline int im_bwd_floats_per_ped(int S, int T, int To) { return 5 * T + 3 * S * To + 12 * T * S; }
+
+struct ImBwdPlan {
+    bool lds;  // the cell's weights and its gradient block in LDS next to the planes
+    int lds_bytes;
+};
+
+inline ImBwdPlan im_bwd_plan(const et_implicit_params &p) {
+    const int per = im_bwd_floats_per_ped(p.spatial_output, p.temporal_input, p.temporal_output);
+    const int wf = 2 * im_layout(p.spatial_output, p.temporal_input, p.temporal_output).size;
+    ImBwdPlan pl;
+    pl.lds = (per + wf) * 4 <= kImBwdLdsBytes - 64;
+    pl.lds_bytes = (per + (pl.lds ? wf : 0)) * 4;
+    return pl;
+}
+
+// src, tab as implicit_main_kernel's; gout: kTns (T_out,N,S), else (1,S,T_out,N); part (chunks, n_bins, L.size)
+template <bool kTns, bool kLds>
+__global__ __launch_bounds__(kImThreads) void implicit_bwd_kernel(et_implicit_params p, const float *__restrict__ src,
+                                                                  const int32_t *__restrict__ tab, int64_t N,
+                                                                  const float *__restrict__ gout, float *part) {
+    extern __shared__ float lds[];
+    const int S = p.spatial_output, T = p.temporal_input, To = p.temporal_output;
+    const int tid = threadIdx.x, z = blockIdx.y;
+    const ImLayout L = im_layout(S, T, To);
+    const int TS = T * S, F = S * To;
+    float *vc = lds;         // (5, T): the columns of the neighbours -2 .. +2
+    float *G = vc + 5 * T;   // (S, T_out), flat f = s T_out + o: the upstream gradient of this pedestrian
+    float *u = G + F;        // (3, T, S): u at the compacted positions -1, 0, +1
+    float *du = u + 3 * TS;  // its gradient through this pedestrian's outputs
+    float *dp = du + 3 * TS;  // du where feat's pre-activation passes the ReLU
+    float *ul = dp + 3 * TS;  // (T, S): the local stream's plane, its gradient, the gradient behind the ReLU
+    float *dul = ul + TS;
+    float *dpl = dul + TS;
+    float *gg = dpl + TS;  // (S, T_out) flat: g and l, for the two scalars' gradients
+    float *ll = gg + F;
+    float *wl = ll + F;  // kLds: the cell's weights, then its gradient block
+    float *blk = part + ((int64_t)blockIdx.x * p.n_bins + z) * L.size;
+    float *acc = kLds ? wl + L.size : blk;
+
+    // the chunk's rows first (the same for all threads): a workgroup none of whose rows is in cell z -- most of them, with
+    // 4 to 8 cells and 8 rows -- writes its block and is done, without staging the weights
+    const int64_t r0 = (int64_t)blockIdx.x * kImChunk;
+    const int rows = (int)(N - r0 < kImChunk ? N - r0 : kImChunk);
+    bool poison = false, any = false;
+    for (int r = 0; r < rows; ++r) {
+        const int32_t *m = tab + (r0 + r) * kImTab;
+        poison = poison || (m[0] == kImSkipped && m[7] == z);
+        any = any || m[0] == z;
+    }
+    if (!any || poison) {
+        for (int e = tid; e < L.size; e += kImThreads) blk[e] = poison ? __builtin_nanf("") : 0.f;
+        return;
+    }
+    for (int e = tid; e < L.size; e += kImThreads) acc[e] = 0.f;
+    if (kLds) {
+        const et_implicit_cell &q = p.cells[z];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int gn = (i < 7 ? L.g[i + 1] : L.l[0]) - L.g[i], ln = (i < 7 ? L.l[i + 1] : L.gw) - L.l[i];
+            for (int j = tid; j < gn; j += kImThreads) wl[L.g[i] + j] = q.global_t[i][j];
+            for (int j = tid; j < ln; j += kImThreads) wl[L.l[i] + j] = q.local_t[i][j];
+        }
+        if (tid == 0) {
+            wl[L.gw] = q.global_w[0];
+            wl[L.lw] = q.local_w[0];
+        }
+    }
+    __syncthreads();
+    const ImCell W = im_cell<kLds>(p, L, wl, kLds ? 0 : z);
+    const float gwv = W.gw[0], lwv = W.lw[0];
+    for (int r = 0; r < rows; ++r) {  // every decision below is the same for all threads
+        const int64_t j = r0 + r;
+        const int32_t *m = tab + j * kImTab;
+        if (m[0] != z) continue;
+        const int64_t b = m[5];
+        const int n = m[6];
+        const int has = (m[2] >= 0 ? 1 : 0) | 2 | (m[3] >= 0 ? 4 : 0);  // bit q: the neighbour at position q - 1 is there
+        for (int it = tid; it < 5 * T; it += kImThreads) {
+            const int t = it % T, c = it / T;
+            const int64_t idx = c == 2 ? j : m[c < 2 ? c + 1 : c];
+            vc[it] = idx >= 0 ? src[b * T + (int64_t)t * n + (idx - b)] : 0.f;
+        }
+        for (int f = tid; f < F; f += kImThreads) {
+            const int s = f / To, o = f - s * To;
+            G[f] = kTns ? gout[((int64_t)o * N + j) * S + s] : gout[(int64_t)f * N + j];
+        }
+        __syncthreads();
+        for (int it = tid; it < 3 * TS; it += kImThreads) {
+            const int s = it % S, t = (it / S) % T, q = it / TS;
+            float val = 0.f, d = 0.f, dpre = 0.f;
+            if ((has >> q) & 1) {
+                const float *col = vc + q * T;
+                float a = W.gfb[s];
+                for (int dt = 0; dt < 3; ++dt) {
+                    const int tt = t + dt - 1;
+                    if (tt < 0 || tt >= T) continue;
+                    for (int dj = 0; dj < 3; ++dj) a = fmaf(W.gfw[s * 9 + dt * 3 + dj], col[dj * T + tt], a);
+                }
+                val = relu(a) + (W.ghiw[s] * col[T + t] + W.ghib[s]);
+                for (int o = 0; o < To; ++o)
+                    for (int ds = 0; ds < 3; ++ds) {
+                        const int sp = s - ds + 1;  // the output row that read u[t, s] through tap ds
+                        if (sp < 0 || sp >= S) continue;
+                        d = fmaf(W.gtw[((o * T + t) * 3 + ds) * 3 + q], gwv * G[sp * To + o], d);
+                    }
+                if (q == 1)
+                    for (int o = 0; o < To; ++o) d = fmaf(W.ghw[o * T + t], gwv * G[s * To + o], d);
+                dpre = a <= 0.f ? 0.f : d;
+            }
+            u[it] = val;
+            du[it] = d;
+            dp[it] = dpre;
+        }
+        for (int it = tid; it < TS; it += kImThreads) {
+            const int s = it % S, t = it / S;
+            const float *col = vc + 2 * T;
+            float a = W.lfb[s];
+            for (int dt = 0; dt < 3; ++dt) {
+                const int tt = t + dt - 1;
+                if (tt >= 0 && tt < T) a = fmaf(W.lfw[s * 3 + dt], col[tt], a);
+            }
+            float d = 0.f;
+            for (int lo = 0; lo < To; ++lo)
+                for (int ds = 0; ds < 3; ++ds) {
+                    const int sp = s - ds + 1;
+                    if (sp >= 0 && sp < S) d = fmaf(W.ltw[(lo * T + t) * 3 + ds], lwv * G[lo * S + sp], d);
+                }
+            for (int lo = 0; lo < To; ++lo) d = fmaf(W.lhw[lo * T + t], lwv * G[lo * S + s], d);
+            ul[it] = relu(a) + (W.lhiw[s] * col[t] + W.lhib[s]);
+            dul[it] = d;
+            dpl[it] = a <= 0.f ? 0.f : d;
+        }
+        __syncthreads();
+        for (int it = tid; it < F; it += kImThreads) {  // g and l: implicit_main_kernel's statements
+            const int s = it % S, o = it / S;
+            float a = W.gtb[o];
+            for (int t = 0; t < T; ++t)
+                for (int ds = 0; ds < 3; ++ds) {
+                    const int ss = s + ds - 1;
+                    if (ss < 0 || ss >= S) continue;
+                    const float *wk = W.gtw + ((o * T + t) * 3 + ds) * 3;
+                    for (int dj = 0; dj < 3; ++dj) a = fmaf(wk[dj], u[(dj * T + t) * S + ss], a);
+                }
+            float res = W.ghb[o];
+            for (int t = 0; t < T; ++t) res = fmaf(W.ghw[o * T + t], u[(T + t) * S + s], res);
+            const int f = s * To + o;
+            const int lo = f / S, ls = f - lo * S;
+            float al = W.ltb[lo];
+            for (int t = 0; t < T; ++t)
+                for (int ds = 0; ds < 3; ++ds) {
+                    const int ss = ls + ds - 1;
+                    if (ss >= 0 && ss < S) al = fmaf(W.ltw[(lo * T + t) * 3 + ds], ul[t * S + ss], al);
+                }
+            float resl = W.lhb[lo];
+            for (int t = 0; t < T; ++t) resl = fmaf(W.lhw[lo * T + t], ul[t * S + ls], resl);
+            gg[f] = a + res;
+            ll[f] = al + resl;
+        }
+        __syncthreads();
+        for (int e = tid; e < L.size; e += kImThreads) {
+            float a = acc[e];
+            if (e < L.l[0]) {
+                if (e < L.g[1]) {  // feat.weight (s, dt, dj)
+                    const int s = e / 9, dt = (e / 3) % 3, dj = e % 3;
+                    for (int q = 0; q < 3; ++q) {
+                        if (!((has >> q) & 1)) continue;
+                        for (int t = 0; t < T; ++t) {
+                            const int tt = t + dt - 1;
+                            if (tt >= 0 && tt < T) a = fmaf(dp[(q * T + t) * S + s], vc[(q + dj) * T + tt], a);
+                        }
+                    }
+                } else if (e < L.g[4]) {  // feat.bias, highway_input.weight, highway_input.bias (s)
+                    const int k = e < L.g[2] ? 1 : e < L.g[3] ? 2 : 3, s = e - L.g[k];
+                    for (int q = 0; q < 3; ++q) {
+                        if (!((has >> q) & 1)) continue;
+                        for (int t = 0; t < T; ++t) {
+                            const int i = (q * T + t) * S + s;
+                            a = k == 1 ? a + dp[i] : k == 2 ? fmaf(du[i], vc[(q + 1) * T + t], a) : a + du[i];
+                        }
+                    }
+                } else if (e < L.g[5]) {  // highway.weight (o, t)
+                    const int i = e - L.g[4], o = i / T, t = i - o * T;
+                    for (int s = 0; s < S; ++s) a = fmaf(gwv * G[s * To + o], u[(T + t) * S + s], a);
+                } else if (e < L.g[6] || e >= L.g[7]) {  // highway.bias, tpcnn.bias (o)
+                    const int o = e - (e < L.g[6] ? L.g[5] : L.g[7]);
+                    for (int s = 0; s < S; ++s) a += gwv * G[s * To + o];
+                } else {  // tpcnn.weight (o, t, ds, dj)
+                    const int i = e - L.g[6], dj = i % 3, ds = (i / 3) % 3, t = (i / 9) % T, o = i / (9 * T);
+                    for (int s = 0; s < S; ++s) {
+                        const int ss = s + ds - 1;
+                        if (ss >= 0 && ss < S) a = fmaf(gwv * G[s * To + o], u[(dj * T + t) * S + ss], a);
+                    }
+                }
+            } else if (e < L.gw) {
+                if (e < L.l[1]) {  // ped.feat.weight (s, dt)
+                    const int i = e - L.l[0], s = i / 3, dt = i - s * 3;
+                    for (int t = 0; t < T; ++t) {
+                        const int tt = t + dt - 1;
+                        if (tt >= 0 && tt < T) a = fmaf(dpl[t * S + s], vc[2 * T + tt], a);
+                    }
+                } else if (e < L.l[4]) {  // ped.feat.bias, ped.highway_input.weight, ped.highway_input.bias (s)
+                    const int k = e < L.l[2] ? 1 : e < L.l[3] ? 2 : 3, s = e - L.l[k];
+                    for (int t = 0; t < T; ++t) {
+                        const int i = t * S + s;
+                        a = k == 1 ? a + dpl[i] : k == 2 ? fmaf(dul[i], vc[2 * T + t], a) : a + dul[i];
+                    }
+                } else if (e < L.l[5]) {  // ped.highway.weight (lo, t)
+                    const int i = e - L.l[4], lo = i / T, t = i - lo * T;
+                    for (int ls = 0; ls < S; ++ls) a = fmaf(lwv * G[lo * S + ls], ul[t * S + ls], a);
+                } else if (e < L.l[6] || e >= L.l[7]) {  // ped.highway.bias, ped.tpcnn.bias (lo)
+                    const int lo = e - (e < L.l[6] ? L.l[5] : L.l[7]);
+                    for (int ls = 0; ls < S; ++ls) a += lwv * G[lo * S + ls];
+                } else {  // ped.tpcnn.weight (lo, t, ds)
+                    const int i = e - L.l[6], ds = i % 3, t = (i / 3) % T, lo = i / (3 * T);
+                    for (int ls = 0; ls < S; ++ls) {
+                        const int ss = ls + ds - 1;
+                        if (ss >= 0 && ss < S) a = fmaf(lwv * G[lo * S + ls], ul[t * S + ss], a);
+                    }
+                }
+            } else {  // global_w, local_w
+                const float *y = e == L.gw ? gg : ll;
+                for (int f = 0; f < F; ++f) a = fmaf(G[f], y[f], a);
+            }
+            acc[e] = a;
+        }
+        __syncthreads();
+    }
+    if (kLds)
+        for (int e = tid; e < L.size; e += kImThreads) blk[e] = acc[e];
+}
+
+// grad (total) = the chunks' blocks part (chunks, total), added in ascending chunk order
+__global__ __launch_bounds__(kImThreads) void implicit_bwd_sum_kernel(const float *__restrict__ part, int64_t chunks,
+                                                                      int total, float *__restrict__ grad) {
+    const int i = blockIdx.x * kImThreads + threadIdx.x;
+    if (i >= total) return;
+    float a = part[i];
+    for (int64_t c = 1; c < chunks; ++c) a += part[c * total + i];
+    grad[i] = a;
+}
+
+static size_t im_bwd_part_bytes(const et_implicit_params &p, int64_t N) {
+    return (size_t)ceil_div(N, kImChunk) * p.n_bins * im_layout(p.spatial_output, p.temporal_input, p.temporal_output).size *
+           sizeof(float);
+}
+
+template <bool kTns>
+static int im_launch_bwd(const et_implicit_params &p, const float *src, const int32_t *tab, int64_t N, const float *gout,
+                         float *grads, float *part, hipStream_t stream) {
+    const ImBwdPlan pl = im_bwd_plan(p);
+    const int64_t chunks = ceil_div(N, kImChunk);
+    const int total = p.n_bins * im_layout(p.spatial_output, p.temporal_input, p.temporal_output).size;
+    const dim3 grid((unsigned)chunks, (unsigned)p.n_bins);
+    if (pl.lds)
+        hipLaunchKernelGGL((implicit_bwd_kernel<kTns, true>), grid, dim3(kImThreads), (unsigned)pl.lds_bytes, stream, p, src,
+                           tab, N, gout, part);
+    else
+        hipLaunchKernelGGL((implicit_bwd_kernel<kTns, false>), grid, dim3(kImThreads), (unsigned)pl.lds_bytes, stream, p,
+                           src, tab, N, gout, part);
+    ET_LAUNCH_CHECK();
+    hipLaunchKernelGGL(implicit_bwd_sum_kernel, dim3((unsigned)ceil_div(total, kImThreads)), dim3(kImThreads), 0, stream, part,
+                       chunks, total, grads);
+    ET_LAUNCH_CHECK();
+    return ET_OK;
+}
+
+static int im_zero_grads(const et_implicit_params &p, float *grads, hipStream_t stream) {
+    const size_t bytes =
+        (size_t)p.n_bins * im_layout(p.spatial_output, p.temporal_input, p.temporal_output).size * sizeof(float);
+    return hipMemsetAsync(grads, 0, bytes, stream) == hipSuccess ? ET_OK : ET_ERR_HIP;
+}
+
 }  // namespace
 }  // namespace et
 
@@ -385,4 +685,45 @@ extern "C" int et_implicit_forward_scenes(const et_implicit_params *params, cons
                        nrm, scene_offsets, N, vbuf, graph_inputs, tab, zone);
     ET_LAUNCH_CHECK();
     return im_launch_main<true>(*params, vbuf, tab, N, C_pred_refine, (hipStream_t)stream);
+}
+
+extern "C" size_t et_implicit_backward_workspace_bytes(const et_implicit_params *params, int64_t N) {
+    if (im_check_params(params) != ET_OK || N <= 0 || N > INT32_MAX / kImMaxT) return 0;
+    return im_bwd_part_bytes(*params, N);
+}
+
+extern "C" int et_implicit_backward_graph(const et_implicit_params *params, const float *v, int64_t N,
+                                          const void *forward_workspace, size_t forward_workspace_bytes, const float *g_out,
+                                          int g_layout, float *grads, void *workspace, size_t workspace_bytes,
+                                          et_stream_t stream) {
+    const int rc = im_check_params(params);
+    if (rc != ET_OK) return rc;
+    if (N < 0 || N > ET_SCENE_MAX_N || !grads || (g_layout != ET_IMPLICIT_G_STN && g_layout != ET_IMPLICIT_G_TNS))
+        return ET_ERR_INVALID_ARG;
+    if (N == 0) return im_zero_grads(*params, grads, (hipStream_t)stream);
+    if (!v || !g_out) return ET_ERR_INVALID_ARG;
+    if (!forward_workspace || forward_workspace_bytes < im_tab_bytes(N) || !workspace ||
+        workspace_bytes < im_bwd_part_bytes(*params, N))
+        return ET_ERR_WORKSPACE;
+    const int32_t *tab = (const int32_t *)forward_workspace;
+    return g_layout == ET_IMPLICIT_G_TNS
+               ? im_launch_bwd<true>(*params, v, tab, N, g_out, grads, (float *)workspace, (hipStream_t)stream)
+               : im_launch_bwd<false>(*params, v, tab, N, g_out, grads, (float *)workspace, (hipStream_t)stream);
+}
+
+extern "C" int et_implicit_backward_scenes(const et_implicit_params *params, int64_t N, const void *forward_workspace,
+                                           size_t forward_workspace_bytes, const float *g, float *grads, void *workspace,
+                                           size_t workspace_bytes, et_stream_t stream) {
+    const int rc = im_check_params(params);
+    if (rc != ET_OK) return rc;
+    if (params->temporal_input < 3) return ET_ERR_UNSUPPORTED;
+    if (N < 0 || N > INT32_MAX / kImMaxT || !grads) return ET_ERR_INVALID_ARG;
+    if (N == 0) return im_zero_grads(*params, grads, (hipStream_t)stream);
+    if (!g) return ET_ERR_INVALID_ARG;
+    if (!forward_workspace || forward_workspace_bytes < et_implicit_workspace_bytes(params, N) || !workspace ||
+        workspace_bytes < im_bwd_part_bytes(*params, N))
+        return ET_ERR_WORKSPACE;
+    const float *vbuf = (const float *)((const char *)forward_workspace + im_tab_bytes(N));
+    return im_launch_bwd<true>(*params, vbuf, (const int32_t *)forward_workspace, N, g, grads, (float *)workspace,
+                               (hipStream_t)stream);
 }

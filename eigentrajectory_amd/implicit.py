@@ -1,4 +1,5 @@
-"""Social-Implicit, the predictor of ET-Implicit (baseline/implicit/model.py: SocialImplicitLight), inference on HIP kernels.
+"""Social-Implicit, the predictor of ET-Implicit (baseline/implicit/model.py: SocialImplicitLight), inference and training on
+HIP kernels.
 
 Same constructor signature and the same sub-module / parameter names as the reference
 (``implicit_cells.{i}.{feat,highway_input,highway,tpcnn}.{weight,bias}``, the same under ``implicit_cells.{i}.ped.``, and
@@ -19,10 +20,26 @@ an in-place edit is seen by the next call, and by a captured graph's next replay
 attributes (constructor constants of the reference, not part of the state_dict); in the Light form the noise is
 identically zero, so the ``noise_w`` term is not computed -- ``noise_w`` is a parameter only so that checkpoints load (a
 non-finite ``noise_w``, whose product with the zero noise is NaN in the reference, is not reproduced).
-Training (the backward pass) is not implemented natively: a forward in training mode raises.  A whole split runs as two
-launches through :meth:`EigenTrajectory.evaluate_split` / :func:`eigentrajectory_amd.ops.implicit_forward_scenes`.
+A whole split runs as two launches through :meth:`EigenTrajectory.evaluate_split` /
+:func:`eigentrajectory_amd.ops.implicit_forward_scenes`.
 Supported family: ``spatial_input = 1``, ``1 <= spatial_output <= 64``, ``temporal_input, temporal_output <= 16``, 1 to 8
 ascending bins; other shapes construct, but their forward raises.
+
+Training (opt-in): the Light form has no dropout, no BatchNorm and no sampling, so its training-mode forward IS its eval
+forward.  After ``eigentrajectory_amd.enable_native_training(model)`` a ``forward(v)`` in training mode runs the same two
+launches as a ``torch.autograd.Function`` whose backward is two launches more (csrc/et_implicit.hip, "backward"): the
+gradients of the 18 tensors of every cell that the forward reads, each pedestrian's contribution formed on its own from its
+five gathered columns and added in a fixed order, no atomics.  They reach ``.grad`` the ordinary autograd way, as views of
+one block; every ``noise_w`` gets an exact zero (the reference's is a sum of products with the zero noise).  ``v`` gets no
+gradient (the bridge detaches it): a ``v`` that requires one raises.  A cell that no pedestrian of the scene is in gets
+exact zeros where the reference leaves ``.grad`` None (DESIGN section 4, "Implicit training")::
+
+    model = EigenTrajectory(SocialImplicitLight(...), get_hook_func("implicit"), hp)
+    eigentrajectory_amd.enable_native_training(model)
+    ETTrainer(model, hp, train_data, val_data, mode="sequenced").fit(epochs)
+
+The switch is the plain attribute ``native_training`` (no parameter, no buffer, not in the ``state_dict``, default False);
+without it a forward in training mode raises, as before.
 """
 from __future__ import annotations
 
@@ -64,9 +81,50 @@ class _SocialCellGlobal(nn.Module):
 _TENSORS = ("feat", "highway_input", "highway", "tpcnn")
 
 
+class _TrainForward(torch.autograd.Function):
+    """``forward(v)`` with a backward pass.  Every parameter of every cell is an input, in :meth:`cell_parameters`' order, so
+    autograd routes the gradients into ``.grad``; they are saved through ``save_for_backward`` with ``v`` and the workspace
+    that holds the neighbour table: the kernels read the weights in place, and an in-place change between forward and
+    backward (an optimiser step) is caught by autograd's version counters."""
+
+    @staticmethod
+    def forward(ctx, model, v, *params):
+        from . import ops
+        et = model.et_params()  # the pointer table once: forward and backward see the same tensors and bins
+        v = L.on_device(v, et[1])
+        ws = ops.implicit_workspace(model, v.shape[-1], et_params=et)
+        out = ops.implicit_forward_graph(model, v, workspace=ws, et_params=et)
+        ctx.model, ctx.et = model, et
+        ctx.has_ws = ws is not None
+        ctx.save_for_backward(v, *(() if ws is None else (ws,)), *params)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        need = ctx.needs_input_grad
+        if g_out is None:
+            return (None,) * len(need)
+        from . import ops
+        model = ctx.model
+        v = ctx.saved_tensors[0]
+        ws = ctx.saved_tensors[1] if ctx.has_ws else None
+        params = ctx.saved_tensors[1 + ctx.has_ws:]
+        if any(p.data_ptr() != q.data_ptr() for p, q in zip(params, model.cell_parameters())):
+            raise RuntimeError("SocialImplicitLight: a parameter tensor was replaced between forward and backward")
+        views = ops.implicit_grad_views(model, ops.implicit_backward_graph(model, v, ws, g_out, et_params=ctx.et))
+        zero = torch.zeros((len(model.implicit_cells), 1), device=v.device)  # noise_w: an exact zero each, one fill
+        grads = [views[name] if name in views else zero[int(name.split(".")[1])]
+                 for name in model.cell_parameter_names()]
+        return (None, None, *(g if wanted else None for g, wanted in zip(grads, need[2:])))
+
+
 class SocialImplicitLight(nn.Module):
-    r"""baseline/implicit/model.py's ``SocialImplicitLight`` (eval-mode inference on the GPU).  ``forward(v)``: v
-    (1, 1, T, N) as the implicit bridge's pre-hook builds it -> (1, S, T_out, N)."""
+    r"""baseline/implicit/model.py's ``SocialImplicitLight`` (inference in eval mode; training mode after
+    :func:`eigentrajectory_amd.enable_native_training`).  ``forward(v)``: v (1, 1, T, N) as the implicit bridge's pre-hook
+    builds it -> (1, S, T_out, N)."""
+
+    native_training = False  # a plain attribute, set per instance by eigentrajectory_amd.enable_native_training
 
     def __init__(self, spatial_input=2, spatial_output=2, temporal_input=8, temporal_output=12,
                  bins=[0, 0.01, 0.1, 1.2], noise_weight=[0.05, 1, 4, 8]):
@@ -109,7 +167,23 @@ class SocialImplicitLight(nn.Module):
             c.noise_w, c.global_w, c.local_w = cell.noise_w.data_ptr(), cell.global_w.data_ptr(), cell.local_w.data_ptr()
         return p, dev
 
+    def cell_parameter_names(self):
+        """the state_dict keys of every cell's 19 tensors: the 8 of the global stream, the 8 of ``ped``, then the scalars"""
+        per_cell = [f"{prefix}{name}.{kind}" for prefix in ("", "ped.") for name in _TENSORS for kind in ("weight", "bias")]
+        return [f"implicit_cells.{i}.{key}" for i in range(len(self.implicit_cells))
+                for key in per_cell + ["noise_w", "global_w", "local_w"]]
+
+    def cell_parameters(self):
+        """the tensors of :meth:`cell_parameter_names`, in its order"""
+        own = dict(self.named_parameters())
+        return [own[name] for name in self.cell_parameter_names()]
+
     def forward(self, v):
+        if self.training and self.native_training:
+            if v.requires_grad:
+                raise RuntimeError("SocialImplicitLight: no input gradient is built (the implicit bridge detaches v); v "
+                                   "requires one")
+            return _TrainForward.apply(self, v, *self.cell_parameters())
         if self.training:
             raise RuntimeError("SocialImplicitLight: only inference is native; training-mode forward and backward are not "
                                "implemented -- call .eval() first")

@@ -616,36 +616,134 @@ def dmrgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=Fals
 
 
 # ------------------------------------------------------------------------------ Social-Implicit predictor (inference)
-def implicit_forward_graph(model, v):
-    """``model`` (:class:`eigentrajectory_amd.implicit.SocialImplicitLight`, eval mode) on one scene as the implicit bridge
-    hands it over: v (1, 1, T, N) -> the raw output (1, S, T_out, N).  Two launches."""
-    params, dev = model.et_params()
+def implicit_workspace(model, n, et_params=None):
+    """A caller-owned workspace for ``n`` pedestrians: pass it as ``workspace=`` to :func:`implicit_forward_graph` /
+    :func:`implicit_forward_scenes`, which fill it with the neighbour table (the scenes form also with every scene's v), and
+    then to :func:`implicit_backward_graph` / :func:`implicit_backward_scenes` (None for ``n`` = 0).  ``et_params``, here
+    and in the graph-form calls: what ``model.et_params()`` returned, for a caller that makes several of these calls on
+    unchanged tensors and bins (the training Function) and builds the pointer table once."""
+    params, dev = et_params or model.et_params()
+    return _workspace("et_implicit_workspace_bytes", dev, params, n)[0]
+
+
+def _implicit_workspace(who, dev, params, n, workspace):
+    """the call's own workspace, or the caller's after a look at it -> (tensor | None, its size in bytes)"""
+    if workspace is None:
+        return _workspace("et_implicit_workspace_bytes", dev, params, n)
+    need = L.lib().et_implicit_workspace_bytes(C.byref(params), n)
+    if workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f"{who}: workspace is not a contiguous uint8 tensor of at least {need} bytes on {dev} "
+                         "(implicit_workspace makes one)")
+    return workspace, workspace.numel()
+
+
+def implicit_forward_graph(model, v, workspace=None, et_params=None):
+    """``model`` (:class:`eigentrajectory_amd.implicit.SocialImplicitLight`) on one scene as the implicit bridge hands it
+    over: v (1, 1, T, N) -> the raw output (1, S, T_out, N).  Two launches.  ``workspace`` (of :func:`implicit_workspace`):
+    the neighbour table is left in it for :func:`implicit_backward_graph`."""
+    params, dev = et_params or model.et_params()
     T, To, S = params.temporal_input, params.temporal_output, params.spatial_output
     if v.dim() != 4 or tuple(v.shape[:3]) != (1, 1, T):
         raise ValueError(f"implicit_forward_graph: v {tuple(v.shape)} is not (1,1,{T},N)")
     n = v.shape[-1]
     (v,) = _dev_args(dev, v)
     out = torch.empty((1, S, To, n), device=dev)
-    ws, nbytes = _workspace("et_implicit_workspace_bytes", dev, params, n)
+    ws, nbytes = _implicit_workspace("implicit_forward_graph", dev, params, n, workspace)
     L.call("et_implicit_forward_graph", C.byref(params), L.ptr(v), n, L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
     return out
 
 
-def implicit_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False):
-    """The implicit bridge + ``model`` (eval mode) + the post-hook for every scene of a split in TWO launches: C_obs, nrm and
+def implicit_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False, workspace=None):
+    """The implicit bridge + ``model`` + the post-hook for every scene of a split in TWO launches: C_obs, nrm and
     ``scene_sizes`` as :func:`stgcnn_forward_scenes`, k = temporal_input - 2 -> C_pred_refine (T_out, N, S).  With
     ``want_details`` also a dict: ``graph_inputs`` (k + 2, N), the fp32 v = [C_obs; obs_ori] the kernel used, and ``zone``
-    (N,) int32, every pedestrian's Social-Zone."""
+    (N,) int32, every pedestrian's Social-Zone.  ``workspace`` (of :func:`implicit_workspace`): the neighbour table and
+    every scene's v are left in it for :func:`implicit_backward_scenes`."""
     params, dev = model.et_params()
     b = _scene_batch("implicit_forward_scenes", dev, C_obs, nrm, params.temporal_input - 2, scene_sizes)
     n = b.n
     out = torch.empty((params.temporal_output, n, params.spatial_output), device=dev)
     gin = torch.empty((params.temporal_input, n), device=dev) if want_details else None
     zone = torch.empty((n,), device=dev, dtype=torch.int32) if want_details else None
-    ws, nbytes = _workspace("et_implicit_workspace_bytes", dev, params, n)
+    ws, nbytes = _implicit_workspace("implicit_forward_scenes", dev, params, n, workspace)
     L.call("et_implicit_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), n, L.ptr(b.off), b.n_scenes,
            L.ptr(out), L.ptr(gin), L.ptr(zone), L.ptr(ws), nbytes, L.stream(dev))
     return (out, {"graph_inputs": gin, "zone": zone}) if want_details else out
+
+
+# ------------------------------------------------------------------------------ Social-Implicit predictor (training)
+def implicit_grad_size(params):
+    """floats of one cell's gradient block (csrc/et_implicit.hip: im_layout().size; noise_w is not in it)"""
+    S, T, To = params.spatial_output, params.temporal_input, params.temporal_output
+    return 18 * S + 14 * To * T + 4 * To + 2
+
+
+def implicit_grad_views(model, grads):
+    """``grads`` (n_bins, G) of :func:`implicit_backward_graph` -> {state_dict key: a view of it shaped like the
+    parameter}, the 18 tensors of every cell the forward reads (``noise_w`` is not among them)."""
+    out = {}
+    for i, cell in enumerate(model.implicit_cells):
+        at = 0
+        for prefix, mod in (("", cell), ("ped.", cell.ped)):
+            for name in ("feat", "highway_input", "highway", "tpcnn"):
+                for kind in ("weight", "bias"):
+                    t = getattr(getattr(mod, name), kind)
+                    out[f"implicit_cells.{i}.{prefix}{name}.{kind}"] = grads[i, at:at + t.numel()].view(t.shape)
+                    at += t.numel()
+        for name in ("global_w", "local_w"):
+            out[f"implicit_cells.{i}.{name}"] = grads[i, at:at + 1]
+            at += 1
+        assert at == grads.shape[1]
+    return out
+
+
+def _implicit_backward(who, entry, model, params, dev, n, workspace, lead, g, tail):
+    """the shared end of the two backward calls: ``lead`` / ``tail`` are the entry's arguments before N / after g"""
+    if n and (workspace is None or workspace.device != dev or workspace.dtype != torch.uint8
+              or not workspace.is_contiguous()):
+        raise ValueError(f"{who}: workspace is not the uint8 tensor the forward call filled")
+    grads = torch.empty((params.n_bins, implicit_grad_size(params)), device=dev)
+    ws, nbytes = _workspace("et_implicit_backward_workspace_bytes", dev, params, n)
+    L.call(entry, C.byref(params), *lead, n, L.ptr(workspace), workspace.numel() if workspace is not None else 0, L.ptr(g),
+           *tail, L.ptr(grads), L.ptr(ws), nbytes, L.stream(dev))
+    return grads
+
+
+def implicit_backward_graph(model, v, workspace, g_out, et_params=None):
+    """The backward pass of :func:`implicit_forward_graph` in TWO launches: ``v`` (1, 1, T, N) and ``workspace`` as that call
+    read / filled them (same weights), ``g_out`` (1, S, T_out, N) the gradient at its output -> grads (n_bins, G) float32,
+    one block per cell in ``et_implicit_cell``'s field order (:func:`implicit_grad_views` names its parts); a cell without
+    pedestrians holds +0.0.  A ``g_out`` that is the permuted view of a contiguous (T_out, N, S) tensor, as the implicit
+    bridge's post-hook makes it, is read where it is."""
+    params, dev = et_params or model.et_params()
+    T, To, S = params.temporal_input, params.temporal_output, params.spatial_output
+    if v.dim() != 4 or tuple(v.shape[:3]) != (1, 1, T):
+        raise ValueError(f"implicit_backward_graph: v {tuple(v.shape)} is not (1,1,{T},N)")
+    n = v.shape[-1]
+    if tuple(g_out.shape) != (1, S, To, n):
+        raise ValueError(f"implicit_backward_graph: g_out {tuple(g_out.shape)} is not (1,{S},{To},{n})")
+    (v,) = _dev_args(dev, v)
+    g_out = g_out.detach()
+    if g_out.device != dev or g_out.dtype != torch.float32:
+        g_out = g_out.to(device=dev, dtype=torch.float32)
+    tns = g_out.permute(0, 2, 3, 1).is_contiguous()  # ET_IMPLICIT_G_TNS: (T_out, N, S) in memory
+    if not tns:
+        g_out = g_out.contiguous()
+    return _implicit_backward("implicit_backward_graph", "et_implicit_backward_graph", model, params, dev, n, workspace,
+                              (L.ptr(v),), g_out, (int(tns),))
+
+
+def implicit_backward_scenes(model, workspace, g):
+    """The backward pass of :func:`implicit_forward_scenes` in TWO launches whatever the number of scenes: ``workspace`` as
+    that call filled it, ``g`` (T_out, N, S) the gradient at C_pred_refine -> grads (n_bins, G) as
+    :func:`implicit_backward_graph`, summed over all scenes."""
+    params, dev = model.et_params()
+    if g.dim() != 3 or (g.shape[0], g.shape[2]) != (params.temporal_output, params.spatial_output):
+        raise ValueError(f"implicit_backward_scenes: g {tuple(g.shape)} is not ({params.temporal_output}, N, "
+                         f"{params.spatial_output})")
+    (g,) = _dev_args(dev, g)
+    return _implicit_backward("implicit_backward_scenes", "et_implicit_backward_scenes", model, params, dev, g.shape[1],
+                              workspace, (), g, ())
 
 
 # ------------------------------------------------------------------------------ AgentFormer predictor (inference)

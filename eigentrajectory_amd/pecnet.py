@@ -163,17 +163,18 @@ class PECNet(nn.Module):
 
 
 def enable_native_training(model, flag=True):
-    """Let ``predict`` of ``model``'s predictor run in training mode with a native backward pass.  ``model`` is an
+    """Let ``model``'s predictor run in training mode with a native backward pass.  ``model`` is an
     :class:`eigentrajectory_amd.EigenTrajectory` wrapper or a bare predictor: an ``LBEBM`` (its own
-    ``enable_native_training``) or a ``PECNet`` (the plain attribute ``native_training``); the other eight predictors have no
-    native backward pass and raise.  -> ``model``"""
+    ``enable_native_training``), a ``PECNet`` or a ``SocialImplicitLight`` (the plain attribute ``native_training``); the
+    other seven predictors have no native backward pass and raise.  -> ``model``"""
+    from .implicit import SocialImplicitLight
     from .lbebm import LBEBM
     net = getattr(model, "baseline_model", model)
     if isinstance(net, LBEBM):
         net.enable_native_training(flag)
-    elif isinstance(net, PECNet):
+    elif isinstance(net, (PECNet, SocialImplicitLight)):
         net.native_training = bool(flag)
     else:
-        raise NotImplementedError(f"enable_native_training: {type(net).__name__} has no native backward pass; only LBEBM and "
-                                  "PECNet train natively")
+        raise NotImplementedError(f"enable_native_training: {type(net).__name__} has no native backward pass; only LBEBM, "
+                                  "PECNet and SocialImplicitLight train natively")
     return model

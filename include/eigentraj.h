@@ -610,6 +610,8 @@ int et_dmrgcn_forward_scenes(const et_dmrgcn_params *params, const float *C_obs,
  *                               only.  Optional outputs (may be NULL): graph_inputs (T,N) float, the fp32 v used, scene
  *                               s at columns [off[s], off[s+1]); zone (N,) int32.  A scene larger than
  *                               ET_SCENE_MAX_N is not computed: its outputs are NaN and its zones -2.
+ *                               (Its rows of the workspace's table keep, in their spare eighth entry, the zone each
+ *                               pedestrian would have had: read by et_implicit_backward_scenes alone.)
  * Two launches per call whatever the number of scenes: one finds every pedestrian's zone and its two predecessors and two
  * successors of the same zone within its scene, one computes every pedestrian on its own from those five columns.
  * Workspace: et_implicit_workspace_bytes(p, N) bytes (0 for N = 0 or parameters outside the family).  No host
@@ -632,6 +634,34 @@ int et_implicit_forward_graph(const et_implicit_params *params, const float *v, 
 int et_implicit_forward_scenes(const et_implicit_params *params, const float *C_obs, const float *nrm, int64_t N,
                                const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *graph_inputs,
                                int32_t *zone, void *workspace, size_t workspace_bytes, et_stream_t stream);
+
+/* ---- Social-Implicit predictor, training: the backward pass of the two calls above (their forward is the training-mode
+ * forward: the Light form has no dropout, no BatchNorm, no sampling).  `grads` (n_bins, G) fp32 with G = 18 S + 14 T_out T
+ * + 4 T_out + 2, the sizes of the 18 tensors below together (1058 in the reference's configuration): per cell, in et_implicit_cell's field order,
+ * the gradients of global_t[0..7], local_t[0..7], global_w, local_w (noise_w multiplies the zero noise: its gradient is
+ * an exact zero and is not stored).  The block is fully overwritten; a cell no pedestrian is in gets +0.0 everywhere (the
+ * reference leaves its .grad None); the cell of a pedestrian of a scene larger than ET_SCENE_MAX_N gets NaN.  No input
+ * gradient is formed (the bridge detaches v).
+ *   et_implicit_backward_graph   one scene: v (T,N) and forward_workspace as et_implicit_forward_graph read / filled them,
+ *                                g_out the gradient at its out: g_layout ET_IMPLICIT_G_STN (1,S,T_out,N), or
+ *                                ET_IMPLICIT_G_TNS the same values as (T_out,N,S), the implicit bridge's post-hook's
+ *                                permute undone by autograd; another value: ET_ERR_INVALID_ARG.
+ *   et_implicit_backward_scenes  a whole batch: forward_workspace as et_implicit_forward_scenes filled it (the table and
+ *                                every scene's v), g (T_out,N,S) the gradient at C_pred_refine.
+ * Two launches whatever N and the number of scenes, no atomics: an element's terms are added rows ascending (within a row
+ * ascending over the element's own inner index) inside chunks of ET_IMPLICIT_BWD_CHUNK rows, then the chunks ascending.
+ * Workspace: et_implicit_backward_workspace_bytes(p, N) (0 for N = 0 or outside the family).  Errors as the forward
+ * entries; N = 0: ET_OK, the block zeroed.  No host synchronisation, no allocation. */
+#define ET_IMPLICIT_BWD_CHUNK 8
+#define ET_IMPLICIT_G_STN 0
+#define ET_IMPLICIT_G_TNS 1
+size_t et_implicit_backward_workspace_bytes(const et_implicit_params *params, int64_t N);
+int et_implicit_backward_graph(const et_implicit_params *params, const float *v, int64_t N, const void *forward_workspace,
+                               size_t forward_workspace_bytes, const float *g_out, int g_layout, float *grads,
+                               void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_implicit_backward_scenes(const et_implicit_params *params, int64_t N, const void *forward_workspace,
+                                size_t forward_workspace_bytes, const float *g, float *grads, void *workspace,
+                                size_t workspace_bytes, et_stream_t stream);
 
 /* ---- PECNet / LBEBM predictors, inference (baseline/pecnet, baseline/lbebm: bridge.py hooks + predict) ---------------
  * Both predict bodies are chains of Linear + ReLU (no activation after a chain's last layer) in exact fp32: every product
