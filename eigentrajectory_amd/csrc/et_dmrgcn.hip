@@ -14,6 +14,8 @@
 //   y[c,t,w] = sum_{r,b} ( sum_ci W_r[b S + c, ci] P[r,b,ci,t,w] + bias_r[b S + c] P[r,b,C_in,t,w] ),
 //   P[r,b,j,t,w] = sum_v L[r,b,t,w,v] X_j[t,v]    (X_j = x[j,t,:], and the ones row j = C_in for the conv bias)
 // so the pair loop runs over 10 (C_in + 1) rows per (t,w) instead of 10 S: 20 rather than 200 in the first block.
+// A pair outside a graph's bin is skipped, where the reference's dense einsum adds 0 x[v]; that product is kept once per
+// contracted row (`zero`), so a NaN or inf in one pedestrian's row reaches every pedestrian of its time row as it does there.
 // L[r,b,t,w,v] = [v == w] - (d_w (A_b[w,v] + [v == w])) d_v, the reference's D (A + I) D order.
 // The bin of a distance is two fp32 comparisons against the split values: the reference's clip_adjacency_matrix decides
 // the same way on the same fp32 number, so there is no tolerance band around a split value.
@@ -153,6 +155,9 @@ __device__ __forceinline__ void dm_run_scene(const Src &src, const et_dmrgcn_par
                 const int t = t0 + tq, j0 = g * kDmRows;
                 const float uw = u[t * n + w], rw = Src::kComputed ? rel[t * n + w] : 0.f;
                 float dw[2][kDmBins], acc[2][kDmBins][kDmRows];
+                float zero[kDmRows];  // 0 x[j,t,v] over all v: the einsum multiplies every column by its (mostly zero) entry
+#pragma unroll
+                for (int jj = 0; jj < kDmRows; ++jj) zero[jj] = 0.f;
 #pragma unroll
                 for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -168,6 +173,7 @@ __device__ __forceinline__ void dm_run_scene(const Src &src, const et_dmrgcn_par
                     for (int jj = 0; jj < kDmRows; ++jj) {
                         const int j = j0 + jj;
                         xv[jj] = j < Cin ? xin[(j * K + t) * n + vv] : j == Cin ? 1.f : 0.f;
+                        zero[jj] = fmaf(xv[jj], 0.f, zero[jj]);  // +0 while x is finite; NaN once a column is not
                     }
 #pragma unroll
                     for (int r = 0; r < 2; ++r) {
@@ -197,7 +203,8 @@ __device__ __forceinline__ void dm_run_scene(const Src &src, const et_dmrgcn_par
                     for (int bb = 0; bb < kDmBins; ++bb)
 #pragma unroll
                         for (int jj = 0; jj < kDmRows; ++jj)
-                            if (j0 + jj < J) q[((tq * kDmRB + r * kDmBins + bb) * J + j0 + jj) * n + w] = acc[r][bb][jj];
+                            if (j0 + jj < J)
+                                q[((tq * kDmRB + r * kDmBins + bb) * J + j0 + jj) * n + w] = acc[r][bb][jj] + zero[jj];
             }
             __syncthreads();
             // the 1x1 convolutions of both relations on the contracted rows, then the tcn's PReLU

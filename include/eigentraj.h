@@ -555,7 +555,8 @@ int et_gpgraph_stgcnn_forward_scenes(const et_gpgraph_stgcnn_params *params, con
  * larger ones use workspace rows [off[s], off[s+1]) of et_dmrgcn_workspace_bytes(p, N, max_scene_n) bytes (0 when a
  * scene of max_scene_n pedestrians fits the arena).  A scene larger than ET_SCENE_MAX_N, or one that fits neither, is
  * not computed: its outputs are NaN.  No host synchronisation, no allocation: the calls can be captured in a graph.
- * Every sum has a fixed order: a scene's result does not depend on the scenes around it or on where its arena lies. */
+ * Every sum has a fixed order: a scene's result does not depend on the scenes around it or on where its arena lies.
+ * A NaN or inf in a scene's v (C_obs, nrm) makes that scene's outputs NaN, as the reference's dense einsum does. */
 #define ET_DMRGCN_MAX_STGCN 4
 #define ET_DMRGCN_MAX_TPCNN 8
 #define ET_DMRGCN_BINS 5

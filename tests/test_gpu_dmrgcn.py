@@ -3,7 +3,9 @@
 kernel reports, moved split values, the scene form against the graph form through the bridge, whole splits end to end
 against the reference's per-pedestrian ADE / FDE, determinism, errors, empty inputs and graph capture.
 
-Measured on the MI355X (figures in DESIGN §4): every comparison below is within its bound."""
+Measured on the MI355X (figures in DESIGN §4): every comparison below is within its bound.
+Other members of the family (K from 3 to 34, S 1 to 64, up to 4 st and 8 tpcnn blocks, scenes up to 512, 300 scenes, a given
+a no bridge builds): tests/test_gpu_dmrgcn_shapes.py."""
 import numpy as np
 import pytest
 import torch
@@ -72,10 +74,12 @@ def _synthetic(n, seed, k=6):
     return C_obs, nrm
 
 
-def _check_scenes(ops, m, C_obs, nrm, sizes, tol=TOL, **fw):
-    """the scene form on (C_obs, nrm, sizes) against the restatement fed the returned graph_inputs; graph_inputs itself:
-    the C_obs rows bit for bit, the obs_ori rows within 2 ulp (at the scale of the scene's positions: both sides are a
-    fp32 mean in their own summation order, subtracted once) of the numpy fp32 value"""
+def _check_scenes(ops, m, C_obs, nrm, sizes, tol=TOL, sd=None, label="scenes", **fw):
+    """the scene form on (C_obs, nrm, sizes) against the restatement (of the state dict ``sd``, default the fixture's ET
+    weights; ``fw``: its block counts and split values) fed the returned graph_inputs; graph_inputs itself: the C_obs rows
+    bit for bit, the obs_ori rows within 2 ulp (at the scale of the scene's positions: both sides are a fp32 mean in their
+    own summation order, subtracted once) of the numpy fp32 value"""
+    sd = SD if sd is None else sd
     dev = next(m.parameters()).device
     out, det = ops.dmrgcn_forward_scenes(m, T(C_obs, dev), T(nrm, dev), scene_sizes=sizes, want_details=True)
     out, gin = N_(out), N_(det["graph_inputs"])
@@ -88,11 +92,11 @@ def _check_scenes(ops, m, C_obs, nrm, sizes, tol=TOL, **fw):
         u = gin[:, lo:lo + n]
         ulp = np.spacing(np.abs(nrm[:2, lo:lo + n]).max().astype(np.float32))
         assert np.abs(u[k:].astype(np.float64) - DN.scene_input(C_obs, nrm, lo, lo + n)[k:]).max() <= 2 * ulp, (lo, n)
-        err = scale_err(out[:, lo:lo + n], DN.c_pred_refine(DN.forward(SD, u, **fw)))
+        err = scale_err(out[:, lo:lo + n], DN.c_pred_refine(DN.forward(sd, u, **fw)))
         worst = max(worst, err)
         assert err <= tol, (lo, n, err)
         lo += n
-    print(f"scenes {sizes}: {worst:.2e}")
+    print(f"{label} {sizes if sizes is None or len(sizes) <= 12 else f'{len(sizes)} scenes'}: {worst:.2e}")
     return out
 
 
