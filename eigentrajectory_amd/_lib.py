@@ -86,6 +86,14 @@ SIGNATURES = {
     "et_sgcn_workspace_bytes": (_Z, [_P, _I64, _I64, _I]),
     "et_sgcn_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _I64, _I64, _P, _P, _P, _P, _Z, _P]),
     "et_sgcn_forward_graph": (_I, [_P, _P, _P, _I, _P, _I, _I64, _P, _P, _P, _P, _Z, _P]),
+    # ---- SGCN predictor, training
+    "et_sgcn_train_workspace_bytes": (_Z, [_P, _I64, _I64, _I]),
+    "et_sgcn_grad_floats": (_I64, [_P]),
+    "et_sgcn_train_layout": (_I, [_P, _I64, _I64, _I, _P, _I]),
+    "et_sgcn_train_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _I64, _I64, _P, _P, _P, _P, _Z, _P]),
+    "et_sgcn_train_forward_graph": (_I, [_P, _P, _P, _I, _P, _I, _I64, _P, _P, _P, _P, _Z, _P]),
+    "et_sgcn_backward_scenes": (_I, [_P, _I64, _P, _I, _I64, _I64, _P, _P, _I64, _P, _Z, _P]),
+    "et_sgcn_backward_graph": (_I, [_P, _P, _I, _P, _I, _I64, _P, _P, _I64, _P, _Z, _P]),
     # ---- GP-Graph-SGCN predictor, inference
     "et_gpgraph_sgcn_workspace_bytes": (_Z, [_P, _I64, _I64, _I]),
     "et_gpgraph_sgcn_forward_graph": (_I, [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _Z, _P]),
@@ -226,6 +234,10 @@ class STGCNNParams(C.Structure):
 
 SGCN_MAX_LAYERS = 8  # ET_SGCN_MAX_LAYERS
 SGCN_MAX_N = 512     # ET_SGCN_MAX_N
+SGCN_TRAIN_LAYOUT_FIELDS = 24  # ET_SGCN_TRAIN_LAYOUT_FIELDS
+SGCN_BWD_CHUNK = 4     # ET_SGCN_BWD_CHUNK: pedestrians whose tail gradients one workgroup adds, in row order
+SGCN_BWD_ROWS = 1024   # ET_SGCN_BWD_ROWS: softmax rows per workgroup of the row kernels
+SGCN_BWD_ITEMS = 4096  # ET_SGCN_BWD_ITEMS: stack positions / entries per workgroup of the asym and fuse kernels
 
 
 class SGCNAttention(C.Structure):

@@ -443,9 +443,15 @@ __global__ __launch_bounds__(kSnThreads) void sgcn_sadj(Ctx c, et_sgcn_params p,
     }
 }
 
-// ---- tail: one wavefront per pedestrian; lane = (h, d) of the (4,16) plane
-template <bool GP>
-__global__ __launch_bounds__(kWave) void sgcn_tail(Ctx c, et_sgcn_params p, float *__restrict__ out) {
+// ---- tail: one wavefront per pedestrian; lane = (h, d) of the (4,16) plane.  KEEP (the training forward,
+// et_sgcn_train.inl): the same statements, and row r's activations are also stored at keep + r * tail_keep_floats(p)
+__host__ __device__ inline int64_t tail_keep_floats(const et_sgcn_params &p) {
+    return (int64_t)(2 * p.obs_len + 2 * p.n_tcn * p.pred_len) * kWave;
+}
+
+template <bool GP, bool KEEP = false>
+__global__ __launch_bounds__(kWave) void sgcn_tail(Ctx c, et_sgcn_params p, float *__restrict__ out,
+                                                   float *__restrict__ keep) {
     extern __shared__ float tail_lds[];  // two (T, 64) buffers
     float *bufA = tail_lds, *bufB = tail_lds + c.T * kWave;
     const int64_t r = blockIdx.x;
@@ -482,6 +488,7 @@ __global__ __launch_bounds__(kWave) void sgcn_tail(Ctx c, et_sgcn_params p, floa
 #pragma unroll
         for (int q = 0; q < kD; ++q) o = fmaf(p.gcn[1].w[d * kD + q], bufA[t * kWave + h * kD + q], o);
         bufB[t * kWave + l] = prelu(o, a1);
+        if constexpr (KEEP) keep[r * tail_keep_floats(p) + t * kWave + l] = o;  // gcn 1 before its PReLU
     }
     __syncthreads();
     // fusion_ (1x1 over heads) of the spatial-temporal features + the temporal-spatial ones -> channels t, plane (h,d)
@@ -490,6 +497,7 @@ __global__ __launch_bounds__(kWave) void sgcn_tail(Ctx c, et_sgcn_params p, floa
 #pragma unroll
         for (int g = 0; g < kH; ++g) o = fmaf(p.fusion_w[h * kH + g], bufB[t * kWave + g * kD + d], o);
         bufA[t * kWave + l] = o + ts[t * kD + d];
+        if constexpr (KEEP) keep[r * tail_keep_floats(p) + (T + t) * kWave + l] = bufA[t * kWave + l];
     }
     __syncthreads();
     float *cur = bufA, *nxt = bufB;
@@ -529,6 +537,11 @@ __global__ __launch_bounds__(kWave) void sgcn_tail(Ctx c, et_sgcn_params p, floa
                 float val = prelu(acc[o], aj);
                 if (j) val += cur[o * kWave + l];
                 nxt[o * kWave + l] = val;
+                if constexpr (KEEP) {  // tcns[j] before its PReLU, then its output
+                    float *kj = keep + r * tail_keep_floats(p) + (int64_t)(2 * T + 2 * j * k) * kWave;
+                    kj[o * kWave + l] = acc[o];
+                    kj[(k + o) * kWave + l] = val;
+                }
             }
         }
         __syncthreads();
@@ -585,10 +598,13 @@ static unsigned chunks(int64_t work_max, int n_scenes) {
 }
 
 // input .. tail on the c.S scenes of c (whoever calls has launched the prep, and for GP the group kernel): 5 +
-// number_asymmetric_conv_layer launches.  out: (k, c.N, S)
+// number_asymmetric_conv_layer launches.  out: (k, c.N, S).  keep (the training forward, GP = false only): layer j reads the
+// stack at c.L.xa / c.L.ta + j x stride and writes the next one instead of the two ping-pong buffers, and the tail stores its
+// activations at keep; the launches and their arithmetic are the same
 template <bool GP>
 static void run_layers(const et_sgcn_params &p, const Ctx &c, const float *gv, const Ident &I, const float *C_obs,
-                       const float *nrm, int64_t max_n, float *out, float *logit_s, float *logit_t, hipStream_t st) {
+                       const float *nrm, int64_t max_n, float *out, float *logit_s, float *logit_t, hipStream_t st,
+                       int64_t s_stride = 0, int64_t t_stride = 0, float *keep = nullptr) {
     const int T = c.T, n_scenes = c.S;
     const dim3 blk(kSnThreads);
     const unsigned S = (unsigned)n_scenes;
@@ -600,13 +616,21 @@ static void run_layers(const et_sgcn_params &p, const Ctx &c, const float *gv, c
     const float *ls = xs[0], *lt = xt[0];
     for (int j = 0; j < p.n_asym; ++j) {
         const bool last = j + 1 == p.n_asym;
-        float *os = last && logit_s ? logit_s : xs[(j + 1) & 1];
-        float *ot = last && logit_t ? logit_t : xt[(j + 1) & 1];
+        float *os = keep ? xs[0] + (j + 1) * s_stride : last && logit_s ? logit_s : xs[(j + 1) & 1];
+        float *ot = keep ? xt[0] + (j + 1) * t_stride : last && logit_t ? logit_t : xt[(j + 1) & 1];
         hipLaunchKernelGGL(sgcn_asym<GP>, dim3(S, by_e), blk, 0, st, c, p.asym_s[j], p.asym_t[j], ls, os, lt, ot);
         ls = os;
         lt = ot;
     }
     hipLaunchKernelGGL(sgcn_tadj<GP>, dim3(S, by_r), blk, 0, st, c, p, I, lt);
     hipLaunchKernelGGL(sgcn_sadj<GP>, dim3(S, by_r), blk, 0, st, c, p, I, ls);
-    hipLaunchKernelGGL(sgcn_tail<GP>, dim3((unsigned)c.N), dim3(kWave), 2 * T * kWave * sizeof(float), st, c, p, out);
+    if constexpr (!GP) {
+        if (keep) {
+            hipLaunchKernelGGL((sgcn_tail<false, true>), dim3((unsigned)c.N), dim3(kWave), 2 * T * kWave * sizeof(float), st, c, p,
+                               out, keep);
+            return;
+        }
+    }
+    hipLaunchKernelGGL(sgcn_tail<GP>, dim3((unsigned)c.N), dim3(kWave), 2 * T * kWave * sizeof(float), st, c, p, out,
+                       (float *)nullptr);
 }

@@ -421,6 +421,181 @@ def sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_logits=False):
     return (out, ls, lt) if want_logits else out
 
 
+# ------------------------------------------------------------------------------ SGCN predictor (training)
+def _sgcn_train_params(who, model, et_params):
+    if getattr(model, "position_channel", False):
+        raise NotImplementedError(f"{who}: a two-channel SGCN (position_channel=True) has no native backward pass")
+    if model.dropout != 0:
+        raise RuntimeError(f"{who}: dropout = {model.dropout} is not implemented natively; construct with dropout=0")
+    return et_params or model.et_params()
+
+
+def sgcn_train_workspace(model, n, sum_n2=None, n_scenes=1, et_params=None):
+    """A training workspace for ``n`` pedestrians in ``n_scenes`` scenes whose squared sizes sum to ``sum_n2`` (one scene:
+    n * n): :func:`sgcn_train_forward_graph` / ``_scenes`` fill it, :func:`sgcn_backward_graph` / ``_scenes`` read it."""
+    params, dev = _sgcn_train_params("sgcn_train_workspace", model, et_params)
+    return _workspace("et_sgcn_train_workspace_bytes", dev, params, n, n * n if sum_n2 is None else sum_n2, n_scenes,
+                      required=n > 0)[0]
+
+
+def _sgcn_check_ws(who, dev, workspace):
+    if workspace is None or workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError(f"{who}: workspace is not a contiguous uint8 tensor on {dev} (sgcn_train_workspace makes one)")
+
+
+def sgcn_train_forward_graph(model, v, identity, workspace, want_logits=False, et_params=None):
+    """:func:`sgcn_forward_graph` with the kept layout (the same kernels; the output is bit-equal): every asymmetric layer's
+    input, the softmax row records, A_t, f1, f2, ts and the tail's activations stay in ``workspace`` (of
+    :func:`sgcn_train_workspace`) for :func:`sgcn_backward_graph`."""
+    params, dev = _sgcn_train_params("sgcn_train_forward_graph", model, et_params)
+    T, k, S = params.obs_len, params.pred_len, params.out_dims
+    id_s, id_t = identity
+    n = v.shape[2] if v.dim() == 4 else -1
+    if (tuple(v.shape) != (1, T, n, 1) or tuple(id_s.shape) not in ((1, n, n), (T, n, n))
+            or tuple(id_t.shape) not in ((n, 1, 1), (n, T, T))):
+        raise ValueError(f"sgcn_train_forward_graph: v {tuple(v.shape)} / identity {tuple(id_s.shape)}, {tuple(id_t.shape)} are "
+                         f"not (1,{T},N,1) / (1 or {T},N,N), (N,1,1) or (N,{T},{T})")
+    _read_in_place("sgcn_train_forward_graph", dev, {"v": v, "identity[0]": id_s, "identity[1]": id_t})
+    if n > L.SGCN_MAX_N:
+        raise ValueError(f"sgcn_train_forward_graph: N = {n} exceeds the {L.SGCN_MAX_N} pedestrians a scene may have")
+    _sgcn_check_ws("sgcn_train_forward_graph", dev, workspace)
+    out = torch.empty((k, n, S), device=dev)
+    ls, lt = _sgcn_logits(want_logits, T, n, n * n, dev)
+    L.call("et_sgcn_train_forward_graph", C.byref(params), L.ptr(v.detach()), L.ptr(id_s.detach()), int(id_s.shape[0]),
+           L.ptr(id_t.detach()), int(id_t.shape[1]), n, L.ptr(out), L.ptr(ls), L.ptr(lt), L.ptr(workspace), workspace.numel(),
+           L.stream(dev))
+    if want_logits:
+        return out, ls.view(T, 4, n, n), lt.view(n, 4, T, T)
+    return out
+
+
+def sgcn_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_logits=False, workspace=None):
+    """:func:`sgcn_forward_scenes` with the kept layout -> (C_pred_refine (k, N, S)[, logit_s, logit_t], workspace); the
+    workspace (made here unless given) goes to :func:`sgcn_backward_scenes` with the same ``scene_sizes``."""
+    params, dev = _sgcn_train_params("sgcn_train_forward_scenes", model, None)
+    b = _scene_batch("sgcn_train_forward_scenes", dev, C_obs, nrm, params.pred_len, scene_sizes)
+    n = b.n
+    if b.max_n > L.SGCN_MAX_N:
+        raise ValueError(f"sgcn_train_forward_scenes: a scene of {b.max_n} pedestrians exceeds the {L.SGCN_MAX_N} a scene may "
+                         "have")
+    sum_n2 = sum(s * s for s in b.sizes)
+    if workspace is None:
+        workspace = sgcn_train_workspace(model, n, sum_n2, len(b.sizes), et_params=(params, dev))
+    if n:
+        _sgcn_check_ws("sgcn_train_forward_scenes", dev, workspace)
+    out = torch.empty((params.pred_len, n, params.out_dims), device=dev)
+    ls, lt = _sgcn_logits(want_logits, params.obs_len, n, sum_n2, dev)
+    L.call("et_sgcn_train_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), n, L.ptr(b.off), b.n_scenes, sum_n2,
+           b.max_n, L.ptr(out), L.ptr(ls), L.ptr(lt), L.ptr(workspace), workspace.numel() if workspace is not None else 0,
+           L.stream(dev))
+    return (out, ls, lt, workspace) if want_logits else (out, workspace)
+
+
+def sgcn_grad_views(model, grads):
+    """``grads``, the flat buffer of :func:`sgcn_backward_graph` / ``_scenes`` -> {state_dict key: a view of it shaped like
+    the parameter}, every parameter of ``model`` (state_dict order)."""
+    out, at = {}, 0
+    for name, t in model.named_parameters():
+        out[name] = grads[at:at + t.numel()].view(t.shape)
+        at += t.numel()
+    if at != grads.numel():
+        raise ValueError(f"sgcn_grad_views: {grads.numel()} floats for parameters of {at}")
+    return out
+
+
+def _sgcn_grads(who, params, dev, d_out, n):
+    k, S = params.pred_len, params.out_dims
+    if tuple(d_out.shape) != (k, n, S):
+        raise ValueError(f"{who}: d_out {tuple(d_out.shape)} is not ({k},{n},{S})")
+    d_out = d_out.detach()
+    if d_out.device != dev or d_out.dtype != torch.float32 or not d_out.is_contiguous():
+        d_out = d_out.to(device=dev, dtype=torch.float32).contiguous()
+    size = int(L.lib().et_sgcn_grad_floats(C.byref(params)))
+    if not size:
+        L.check(3, "et_sgcn_grad_floats")
+    return d_out, torch.empty((size,), device=dev)
+
+
+def sgcn_backward_graph(model, identity, workspace, d_out, et_params=None):
+    """The backward pass of :func:`sgcn_train_forward_graph` in ``number_asymmetric_conv_layer + 8`` launches: ``identity``
+    and ``workspace`` as that call read / filled them (same weights), ``d_out`` (pred_len, N, out_dims) the gradient at its
+    output -> the flat float32 gradient buffer (:func:`sgcn_grad_views` names its parts)."""
+    params, dev = _sgcn_train_params("sgcn_backward_graph", model, et_params)
+    id_s, id_t = identity
+    n = id_s.shape[-1]
+    _read_in_place("sgcn_backward_graph", dev, {"identity[0]": id_s, "identity[1]": id_t})
+    _sgcn_check_ws("sgcn_backward_graph", dev, workspace)
+    d_out, grads = _sgcn_grads("sgcn_backward_graph", params, dev, d_out, n)
+    L.call("et_sgcn_backward_graph", C.byref(params), L.ptr(id_s.detach()), int(id_s.shape[0]), L.ptr(id_t.detach()),
+           int(id_t.shape[1]), n, L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace), workspace.numel(),
+           L.stream(dev))
+    return grads
+
+
+def sgcn_backward_scenes(model, workspace, d_out, scene_sizes=None):
+    """The backward pass of :func:`sgcn_train_forward_scenes`, the same number of launches whatever the number of scenes:
+    ``workspace`` as that call filled it, ``scene_sizes`` as given to it, ``d_out`` (k, N, S) -> the flat gradient buffer,
+    summed over the scenes in ascending order."""
+    params, dev = _sgcn_train_params("sgcn_backward_scenes", model, None)
+    n = d_out.shape[1] if d_out.dim() == 3 else -1
+    d_out, grads = _sgcn_grads("sgcn_backward_scenes", params, dev, d_out, n)
+    if scene_sizes is None:
+        sizes, off, n_scenes = [n], None, 0
+    else:
+        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
+        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
+        n_scenes = len(sizes)
+    if n:
+        _sgcn_check_ws("sgcn_backward_scenes", dev, workspace)
+    L.call("et_sgcn_backward_scenes", C.byref(params), n, L.ptr(off), n_scenes, sum(s * s for s in sizes),
+           max(sizes, default=0), L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace),
+           workspace.numel() if workspace is not None else 0, L.stream(dev))
+    return grads
+
+
+def sgcn_train_views(model, workspace, n, sum_n2=None, n_scenes=1, lo=0, sq=0, scene_n=None):
+    """The values kept in ``workspace`` by name, as views, for the scene of ``scene_n`` pedestrians that starts at row ``lo``
+    and at ``sq`` in the packed n^2 stacks (one scene: the defaults).  Forward: ``v`` (T, n), ``stack_s`` [n_asym + 1] x
+    (T, 4, n, n) and ``stack_t`` [n_asym + 1] x (n, 4, T, T) (every asymmetric layer's input; the last ones are the logits,
+    ``stack_t[0]`` is the temporal attention), ``rows_s`` (T, 4, n, 2) / ``rows_t`` (n, 4, T, 2) (softmax maximum and sum),
+    ``at`` (n, 4, T, T), ``f1`` (T, 4, n, 16), ``f2`` / ``ts`` (n, 4, T, 16), and of the tail per pedestrian ``st_pre``
+    (n, T, 64) (spatial_temporal gcn 1 before its PReLU), ``rep`` (n, T, 64) (the tcns' input), ``tcn_pre`` / ``tcn_out``
+    [n_tcn] x (n, k, 64).  After a backward call also what it left: ``d_ts``, ``d_f2`` (n, 4, T, 16), ``d_f1`` (T, 4, n, 16),
+    ``d_at`` (the tail's part), ``d_accn`` (T, 4, n, 16) (d (A_s f2) per spatial row), ``g_s`` / ``g_t`` (the gradient of every
+    kept stack), ``dir_s`` / ``dir_t`` (the direct parts of d dense) and ``dd_s`` (d dense_s).  The offsets are the library's
+    (``et_sgcn_train_layout``)."""
+    params, _ = model.et_params()
+    T, k, na, nt = params.obs_len, params.pred_len, params.n_asym, params.n_tcn
+    N, n2 = n, n * n if sum_n2 is None else sum_n2
+    m = N if scene_n is None else scene_n
+    f = workspace.view(torch.float32)
+    o = (C.c_int64 * L.SGCN_TRAIN_LAYOUT_FIELDS)()
+    L.call("et_sgcn_train_layout", C.byref(params), N, n2, n_scenes, o, L.SGCN_TRAIN_LAYOUT_FIELDS)
+    (o_v, o_rs, o_rt, o_xs, xs_stride, o_xt, xt_stride, o_at, o_f2, o_f1, o_ts, o_keep, KS, o_dat, o_df1, o_dts, o_df2, o_rrec,
+     o_gs, o_gt, o_dirs, o_dirt, o_dds, _) = (int(x) for x in o)
+    sl = lambda off, cnt, *shape: f[off:off + cnt].view(*shape)
+    rows = lambda off: sl(off + lo * 4 * T * T, m * 4 * T * T, m, 4, T, T)          # (n, 4, T, T) blocks
+    feat = lambda off, *shape: sl(off + lo * 4 * T * 16, m * 4 * T * 16, *shape)     # 64 T floats per pedestrian
+    dense = lambda off: sl(off + 4 * T * sq, 4 * T * m * m, T, 4, m, m)              # (T, 4, n, n) blocks
+    keep = sl(o_keep + lo * KS, m * KS, m, 2 * T + 2 * nt * k, 64)
+    return {
+        "v": sl(o_v + T * lo, T * m, T, m),
+        "stack_s": [dense(o_xs + j * xs_stride) for j in range(na + 1)],
+        "stack_t": [rows(o_xt + j * xt_stride) for j in range(na + 1)],
+        "rows_s": sl(o_rs + 2 * T * 4 * lo, 2 * T * 4 * m, T, 4, m, 2),
+        "rows_t": sl(o_rt + 2 * T * 4 * lo, 2 * T * 4 * m, m, 4, T, 2),
+        "at": rows(o_at), "f1": feat(o_f1, T, 4, m, 16), "f2": feat(o_f2, m, 4, T, 16), "ts": feat(o_ts, m, 4, T, 16),
+        "st_pre": keep[:, :T], "rep": keep[:, T:2 * T],
+        "tcn_pre": [keep[:, 2 * T + 2 * j * k:2 * T + (2 * j + 1) * k] for j in range(nt)],
+        "tcn_out": [keep[:, 2 * T + (2 * j + 1) * k:2 * T + (2 * j + 2) * k] for j in range(nt)],
+        "d_ts": feat(o_dts, m, 4, T, 16), "d_f2": feat(o_df2, m, 4, T, 16), "d_f1": feat(o_df1, T, 4, m, 16), "d_at": rows(o_dat),
+        "d_accn": sl(o_rrec + 4 * T * lo * 17, 4 * T * m * 17, T, 4, m, 17)[..., 1:],
+        "g_s": [dense(o_gs + j * xs_stride) for j in range(na + 1)],
+        "g_t": [rows(o_gt + j * xt_stride) for j in range(na + 1)],
+        "dir_s": dense(o_dirs), "dir_t": rows(o_dirt), "dd_s": dense(o_dds),
+    }
+
+
 # ------------------------------------------------------------------------ GP-Graph-SGCN predictor (inference)
 def _gpgraph_buffers(params, want, T, n, sum_n2, n_scenes, dev):
     ws, nbytes = _workspace("et_gpgraph_sgcn_workspace_bytes", dev, params, n, sum_n2, n_scenes, required=True)

@@ -165,16 +165,25 @@ class PECNet(nn.Module):
 def enable_native_training(model, flag=True):
     """Let ``model``'s predictor run in training mode with a native backward pass.  ``model`` is an
     :class:`eigentrajectory_amd.EigenTrajectory` wrapper or a bare predictor: an ``LBEBM`` (its own
-    ``enable_native_training``), a ``PECNet`` or a ``SocialImplicitLight`` (the plain attribute ``native_training``); the
-    other seven predictors have no native backward pass and raise.  -> ``model``"""
+    ``enable_native_training``), a ``PECNet``, a ``SocialImplicitLight`` or an ``SGCN`` of its native family (``in_dims =
+    1``, four heads, width 64, ``dropout = 0``, no position channel) (the plain attribute ``native_training``); the other
+    six predictors have no native backward pass and raise.  -> ``model``"""
     from .implicit import SocialImplicitLight
     from .lbebm import LBEBM
+    from .sgcn import SGCN
     net = getattr(model, "baseline_model", model)
     if isinstance(net, LBEBM):
         net.enable_native_training(flag)
     elif isinstance(net, (PECNet, SocialImplicitLight)):
         net.native_training = bool(flag)
+    elif isinstance(net, SGCN) and net.outside_native_training() is None:
+        net.native_training = bool(flag)
+    elif isinstance(net, SGCN):
+        raise NotImplementedError(f"enable_native_training: SGCN has no native backward pass outside its native family: "
+                                  f"{net.outside_native_training()}; LBEBM, PECNet, SocialImplicitLight and an SGCN with "
+                                  "in_dims = 1, num_heads = 4, embedding_dims = 64, dropout = 0 and no position channel "
+                                  "train natively")
     else:
         raise NotImplementedError(f"enable_native_training: {type(net).__name__} has no native backward pass; only LBEBM, "
-                                  "PECNet and SocialImplicitLight train natively")
+                                  "PECNet, SocialImplicitLight and SGCN train natively")
     return model

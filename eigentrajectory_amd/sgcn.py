@@ -15,8 +15,13 @@ Same constructor signature and the same sub-module / parameter names as the refe
 list of the spatial (1 or T, N, N) and the temporal (N, 1, 1) or (N, T, T) one -> (pred_len, N, out_dims).  The identities
 are read as given: the bridge's temporal one is all ones, not ``eye(T)``.  The weights are read in place from this module's
 tensors (a ``load_state_dict``, a ``.to()`` or an in-place edit is seen by the next call, and by a captured graph's next
-replay).  Training (the backward pass, the reference's always-active ``F.dropout``) is not implemented natively: a forward
-in training mode, or with ``dropout != 0``, raises.  A whole split runs in a fixed number of launches through
+replay).  A forward in training mode, or with ``dropout != 0`` (the reference's always-active ``F.dropout``), raises -- unless
+the instance was switched by ``eigentrajectory_amd.enable_native_training(model)``: with ``dropout = 0`` the training-mode
+forward *is* the eval forward, and a training-mode ``forward(graph, identity)`` then runs the same kernels on a layout that
+keeps every layer's input (``et_sgcn_train_forward_graph``) and is differentiable with respect to every parameter
+(``et_sgcn_backward_graph``, csrc/et_sgcn_train.inl; no input gradient: the sgcn bridge detaches the graph; ``key.bias`` of
+both attentions gets an exact zero).  The switch is the plain attribute ``native_training`` (no parameter, no buffer, not in
+the ``state_dict``, default False).  A whole split runs in a fixed number of launches through
 :meth:`EigenTrajectory.evaluate_split` / :func:`eigentrajectory_amd.ops.sgcn_forward_scenes`.
 Supported family: ``in_dims = 1``, ``num_heads = 4``, ``embedding_dims = 64``, ``1 <= number_asymmetric_conv_layer, n_tcn <=
 8``, ``pred_len <= 32``, ``obs_len = pred_len + 2``, ``1 <= out_dims <= 64``, ``N <= 512``; other shapes construct, but their
@@ -32,6 +37,7 @@ from __future__ import annotations
 
 import math
 
+import torch
 import torch.nn as nn
 
 from . import _lib as L
@@ -106,9 +112,43 @@ class _SparseGraphConvolution(nn.Module):
         self.temporal_spatial_sparse_gcn.append(_GraphConvolution(embedding_dims, embedding_dims))
 
 
+class _TrainForward(torch.autograd.Function):
+    """``forward(graph, identity)`` with a backward pass.  Every parameter is an input, in ``named_parameters`` order, so
+    autograd routes the gradients into ``.grad``; they are saved through ``save_for_backward`` with the identities and the
+    training workspace: the kernels read the weights in place, and an in-place change between forward and backward (an
+    optimiser step) is caught by autograd's version counters."""
+
+    @staticmethod
+    def forward(ctx, model, graph, id_s, id_t, *params):
+        from . import ops
+        et = model.et_params()  # the pointer table once: forward and backward see the same tensors
+        ws = ops.sgcn_train_workspace(model, graph.shape[2], et_params=et)
+        out = ops.sgcn_train_forward_graph(model, graph, (id_s, id_t), ws, et_params=et)
+        ctx.model, ctx.et = model, et
+        ctx.save_for_backward(id_s, id_t, ws, *params)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        need = ctx.needs_input_grad
+        if g_out is None:
+            return (None,) * len(need)
+        from . import ops
+        model = ctx.model
+        id_s, id_t, ws = ctx.saved_tensors[:3]
+        params = ctx.saved_tensors[3:]
+        if any(p.data_ptr() != q.data_ptr() for p, q in zip(params, model.parameters())):
+            raise RuntimeError("SGCN: a parameter tensor was replaced between forward and backward")
+        views = ops.sgcn_grad_views(model, ops.sgcn_backward_graph(model, (id_s, id_t), ws, g_out, et_params=ctx.et))
+        return (None, None, None, None, *(g if wanted else None for g, wanted in zip(views.values(), need[4:])))
+
+
 class SGCN(nn.Module):
     r"""baseline/sgcn/model.py's ``TrajectoryModel`` (eval-mode inference on the GPU).  ``forward(graph, identity)``: graph
     (1, T, N, 1) and the two identities as the sgcn bridge's pre-hook builds them -> (pred_len, N, out_dims)."""
+
+    native_training = False  # a plain attribute, set per instance by eigentrajectory_amd.enable_native_training
 
     def __init__(self, number_asymmetric_conv_layer=7, embedding_dims=64, number_gcn_layers=1, dropout=0, obs_len=8,
                  pred_len=12, n_tcn=5, in_dims=2, out_dims=5, num_heads=4, position_channel=False):
@@ -160,6 +200,14 @@ class SGCN(nn.Module):
         p.out_w, p.out_b = _p(self.output.weight), _p(self.output.bias)
         return p, dev
 
+    def outside_native_training(self):
+        """-> None, or the field that puts this instance outside the family that trains natively, as text"""
+        for field, want in (("in_dims", 1), ("num_heads", 4), ("embedding_dims", 64), ("dropout", 0),
+                            ("position_channel", False)):
+            if getattr(self, field) != want:
+                return f"{field} = {getattr(self, field)} (native: {want})"
+        return None
+
     def _check_mode(self):
         if self.training:
             raise RuntimeError("SGCN: only inference is native (no dropout, no backward); training-mode forward is not "
@@ -169,6 +217,13 @@ class SGCN(nn.Module):
                                "active even in eval mode); construct with dropout=0")
 
     def forward(self, graph, identity, mask=None):
+        if self.training and self.native_training and not self.position_channel and mask is None and self.dropout == 0:
+            if graph.requires_grad or any(i.requires_grad for i in identity):
+                raise RuntimeError("SGCN: no input gradient is built (the sgcn bridge detaches the graph); an input "
+                                   "requires one")
+            dev = L.module_device("SGCN", self)
+            graph, id_s, id_t = (L.on_device(t, dev) for t in (graph, *identity))
+            return _TrainForward.apply(self, graph, id_s, id_t, *self.parameters())
         self._check_mode()
         if self.position_channel or mask is not None:
             raise NotImplementedError("SGCN: the two-channel base (position_channel=True) and the mask argument run only as "

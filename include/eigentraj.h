@@ -438,6 +438,57 @@ int et_sgcn_forward_graph(const et_sgcn_params *params, const float *v, const fl
                           const float *identity_t, int id_t_t, int64_t N, float *out, float *logit_s, float *logit_t,
                           void *workspace, size_t workspace_bytes, et_stream_t stream);
 
+/* ---- SGCN predictor, training (the family above; dropout = 0 makes the training-mode forward the eval forward) ---------
+ * Gradients of what et_sgcn_forward_graph computes with respect to every parameter; no input gradient (the bridge detaches v).
+ *   et_sgcn_train_workspace_bytes   the training workspace: the eval workspace's values, n_asym + 1 kept stacks of each
+ *                                   kind instead of the two ping-pong ones, the tail's activations, and the backward's
+ *                                   gradient stacks (one per kept stack) and partial sums.  0: outside the family, or N <= 0.
+ *   et_sgcn_train_forward_graph /   et_sgcn_forward_graph / _scenes with the kept layout: the same kernels, the same
+ *   et_sgcn_train_forward_scenes    number of launches, an output that is bit-equal to theirs.  logit_s / logit_t (may be
+ *                                   NULL) are copies of the last kept stacks.
+ *   et_sgcn_backward_graph /        d_out (k, N, S), the gradient at the forward's output, and the workspace as that forward
+ *   et_sgcn_backward_scenes         left it (same parameters, same N, scene_offsets, sum_n2; the graph form also the same
+ *                                   identities) -> grads, grads_floats >= et_sgcn_grad_floats floats: every parameter's
+ *                                   gradient in state_dict order (att[0], att[1]: embedding.weight, .bias, query.weight,
+ *                                   .bias, key.weight, .bias; fus_w, fus_b, fus_a; asym_s[j], then asym_t[j]: conv1.weight,
+ *                                   conv2.weight, conv2.bias, activation.weight; gcn[0..3]: embedding.weight,
+ *                                   activation.weight; fusion_w; tcns j: weight, bias, PReLU weight; out_w, out_b).
+ *                                   number_asymmetric_conv_layer + 8 launches for any number of scenes.
+ * A scene that the forward does not compute (larger than ET_SGCN_MAX_N, or one that does not fit the stacks) contributes
+ * nothing: its rows of d_out are not read.  key.bias of both attentions gets an exact +0.0: it shifts a softmax row by a
+ * constant (autograd leaves rounding noise there).
+ * No atomics.  A weight gradient is the sum of per-workgroup partials over chunks of ET_SGCN_BWD_CHUNK pedestrians (the
+ * tail), ET_SGCN_BWD_ROWS softmax rows or ET_SGCN_BWD_ITEMS stack positions of one scene: ascending inside a chunk (per
+ * lane, then the lanes by a fixed butterfly, then the wavefronts), then the chunks ascending, then the scenes ascending.
+ * Results are bit-identical from run to run.  Host-side checks answer ET_ERR_INVALID_ARG / ET_ERR_WORKSPACE /
+ * ET_ERR_UNSUPPORTED before any launch. */
+#define ET_SGCN_BWD_CHUNK 4
+#define ET_SGCN_BWD_ROWS 1024
+#define ET_SGCN_BWD_ITEMS 4096
+size_t et_sgcn_train_workspace_bytes(const et_sgcn_params *params, int64_t N, int64_t sum_n2, int n_scenes);
+int64_t et_sgcn_grad_floats(const et_sgcn_params *params);
+/* where the training workspace keeps what (host only, no launch), in floats from its start: v, rows_s, rows_t, stack_s,
+ * its stride, stack_t, its stride, at, f2, f1, ts, tail, its floats per row, d_at (the tail's part), d_f1, d_ts, d_f2, the
+ * per-spatial-row record (ZeroSoftmax's denominator and d (A_s f2): 17 floats), g_s, g_t (n_asym + 1 gradient stacks each, the strides of
+ * stack_s / stack_t: d stack j stays for a layer-by-layer check), the direct parts of d dense_s and d dense_t, d dense_s,
+ * the total.  A scene's block starts at T x its first row (v), 4 T x its packed n^2 offset (stack_s, g_s, dense_s parts) or
+ * 4 T T / 64 T x its first row (the rest). */
+#define ET_SGCN_TRAIN_LAYOUT_FIELDS 24
+int et_sgcn_train_layout(const et_sgcn_params *params, int64_t N, int64_t sum_n2, int n_scenes, int64_t *offsets, int n_offsets);
+int et_sgcn_train_forward_scenes(const et_sgcn_params *params, const float *C_obs, const float *nrm, int64_t N,
+                                 const int32_t *scene_offsets, int n_scenes, int64_t sum_n2, int64_t max_scene_n,
+                                 float *C_pred_refine, float *logit_s, float *logit_t, void *workspace,
+                                 size_t workspace_bytes, et_stream_t stream);
+int et_sgcn_train_forward_graph(const et_sgcn_params *params, const float *v, const float *identity_s, int id_s_t,
+                                const float *identity_t, int id_t_t, int64_t N, float *out, float *logit_s, float *logit_t,
+                                void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_sgcn_backward_scenes(const et_sgcn_params *params, int64_t N, const int32_t *scene_offsets, int n_scenes,
+                            int64_t sum_n2, int64_t max_scene_n, const float *d_out, float *grads, int64_t grads_floats,
+                            void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_sgcn_backward_graph(const et_sgcn_params *params, const float *identity_s, int id_s_t, const float *identity_t,
+                           int id_t_t, int64_t N, const float *d_out, float *grads, int64_t grads_floats, void *workspace,
+                           size_t workspace_bytes, et_stream_t stream);
+
 /* ---- GP-Graph-SGCN predictor, inference (baseline/gpgraphsgcn: bridge.py pre-hook + GPGraph.forward around the
  * two-channel SGCN of model_baseline.py + post-hook) --------------------------------------------------------------------
  * The ET configuration: d_type 'learned_l2norm', learned threshold, mix_type 'mlp', all three graphs, shared weights,
