@@ -98,6 +98,14 @@ SIGNATURES = {
     "et_gpgraph_sgcn_workspace_bytes": (_Z, [_P, _I64, _I64, _I]),
     "et_gpgraph_sgcn_forward_graph": (_I, [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "et_gpgraph_sgcn_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _I64, _I64, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    # ---- GP-Graph-SGCN predictor, training
+    "et_gpgraph_sgcn_train_workspace_bytes": (_Z, [_P, _I64, _I64, _I]),
+    "et_gpgraph_sgcn_grad_floats": (_I64, [_P]),
+    "et_gpgraph_sgcn_train_layout": (_I, [_P, _I64, _I64, _I, _P, _I]),
+    "et_gpgraph_sgcn_train_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _I64, _I64, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "et_gpgraph_sgcn_train_forward_graph": (_I, [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "et_gpgraph_sgcn_backward_scenes": (_I, [_P, _I64, _P, _I, _I64, _I64, _P, _P, _I64, _P, _Z, _P]),
+    "et_gpgraph_sgcn_backward_graph": (_I, [_P, _I64, _P, _P, _I64, _P, _Z, _P]),
     # ---- GP-Graph-STGCNN predictor, inference
     "et_gpgraph_stgcnn_workspace_bytes": (_Z, [_P, _I64, _I64, _I]),
     "et_gpgraph_stgcnn_forward_graph": (_I, [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _Z, _P]),
@@ -238,6 +246,8 @@ SGCN_TRAIN_LAYOUT_FIELDS = 24  # ET_SGCN_TRAIN_LAYOUT_FIELDS
 SGCN_BWD_CHUNK = 4     # ET_SGCN_BWD_CHUNK: pedestrians whose tail gradients one workgroup adds, in row order
 SGCN_BWD_ROWS = 1024   # ET_SGCN_BWD_ROWS: softmax rows per workgroup of the row kernels
 SGCN_BWD_ITEMS = 4096  # ET_SGCN_BWD_ITEMS: stack positions / entries per workgroup of the asym and fuse kernels
+GPGRAPH_SGCN_TRAIN_LAYOUT_FIELDS = 49  # ET_GPGRAPH_SGCN_TRAIN_LAYOUT_FIELDS
+GPGRAPH_BWD_ROWS = 64  # ET_GPGRAPH_BWD_ROWS: pedestrians per workgroup partial of the mix weights' gradients
 
 
 class SGCNAttention(C.Structure):

@@ -19,7 +19,8 @@
 // every pedestrian whose label was in {label[r], c1, .., c(m-1)} carries cm.  That is one parallel step per row, n serial
 // steps per scene (rows without a close column are skipped without a barrier).
 // Every sum runs in a fixed order inside one lane, so results are bit-identical from run to run and a scene's result does
-// not depend on the scenes around it.
+// not depend on the scenes around it.  Training (the kept-layout forward and the backward pass to every parameter of the
+// wrapper and of the base) is et_gpgraph_train.inl, on the base's backward of et_sgcn_train.inl.
 #include "et_common.h"
 
 namespace et {
@@ -29,12 +30,16 @@ namespace {
 
 #include "et_gpgraph_core.inl"
 
-struct GLay {  // the workspace behind the base's (floats): v_abs (T,N), conv features (8,T,N), dist and sig_norm (sum n^2),
+struct WLay {  // the workspace behind the base's (floats): v_abs (T,N), conv features (8,T,N), dist and sig_norm (sum n^2),
     int64_t va, feat, dist, sn, po, total;  // the base's output for the 3 N virtual rows (k, 3 N, S)
 };
 
-__host__ __device__ inline GLay glay_of(const Lay &L, int T, int k, int S, int64_t N, int64_t n2) {
-    GLay G;
+struct GpKeep {  // where the training forward keeps sig (sum n^2), its column sums (N) and the group sizes (int32 N); -1: not kept
+    int64_t sig, cs, cnt;
+};
+
+__host__ __device__ inline WLay wlay_of(const Lay &L, int T, int k, int S, int64_t N, int64_t n2) {
+    WLay G;
     G.va = L.total;
     G.feat = up4(G.va + T * N);
     G.dist = up4(G.feat + (int64_t)kGpHid * T * N);
@@ -54,7 +59,7 @@ static GpWeights weights_of(const et_gpgraph_sgcn_params &p) {
 }
 
 // ---- group: one workgroup per real scene (the steps: et_gpgraph_core.inl)
-__global__ __launch_bounds__(kSnThreads) void gp_group(Ctx c, GpTab tab, GpWeights p, GLay G, int64_t n2real,
+__global__ __launch_bounds__(kSnThreads) void gp_group(Ctx c, GpTab tab, GpWeights p, WLay G, GpKeep K, int64_t n2real,
                                                        const float *__restrict__ g_abs, const float *__restrict__ g_rel,
                                                        const float *__restrict__ C_obs, const float *__restrict__ nrm,
                                                        int32_t *__restrict__ group_index, float *__restrict__ dist_out) {
@@ -77,6 +82,11 @@ __global__ __launch_bounds__(kSnThreads) void gp_group(Ctx c, GpTab tab, GpWeigh
     gs.feat = c.ws + G.feat + (int64_t)kGpHid * T * b;
     gs.D = c.ws + G.dist + sq;
     gs.sn = c.ws + G.sn + sq;
+    if (K.sig >= 0) {
+        gs.sig = c.ws + K.sig + sq;
+        gs.cs = c.ws + K.cs + b;
+        gs.cnt = reinterpret_cast<int32_t *>(c.ws + K.cnt) + b;
+    }
     for (int m = 0; m < 3; ++m) {  // the three virtual scenes' rows: pass m at m Nr + b
         gs.in[m][0] = c.ws + c.L.vp + T * (m * Nr + b);
         gs.in[m][1] = c.ws + c.L.v + T * (m * Nr + b);
@@ -95,7 +105,7 @@ static int check_gp(const et_gpgraph_sgcn_params *p) {
 
 static int64_t gp_total(const et_sgcn_params &b, int64_t N, int64_t sum_n2, int n_scenes) {
     const Lay L = lay_of(b.obs_len, 3 * N, 3 * sum_n2, 3 * (int64_t)n_scenes, true);
-    return glay_of(L, b.obs_len, b.pred_len, b.out_dims, N, sum_n2).total;
+    return wlay_of(L, b.obs_len, b.pred_len, b.out_dims, N, sum_n2).total;
 }
 
 static int gp_run(const et_gpgraph_sgcn_params &p, const float *g_abs, const float *g_rel, const float *C_obs,
@@ -114,14 +124,14 @@ static int gp_run(const et_gpgraph_sgcn_params &p, const float *g_abs, const flo
     c.L = lay_of(T, 3 * N, 3 * sum_n2, 3 * (int64_t)n_scenes, true);
     c.Nr = N;
     c.Sr = n_scenes;
-    const GLay G = glay_of(c.L, T, bp.pred_len, bp.out_dims, N, sum_n2);
+    const WLay G = wlay_of(c.L, T, bp.pred_len, bp.out_dims, N, sum_n2);
     if (!workspace || workspace_bytes < (size_t)G.total * 4) return ET_ERR_WORKSPACE;
     const Ident I{nullptr, nullptr, 1, -1};  // eye(n) and eye(T): generate_identity_matrix
     hipLaunchKernelGGL(sgcn_prep<true>, dim3(1), dim3(kSnThreads), 0, st, bp, c.ws);
     const GpTab tab = tab_of(c);
     const GpWeights w = weights_of(p);
-    hipLaunchKernelGGL(gp_group, dim3((unsigned)n_scenes), dim3(kSnThreads), 0, st, c, tab, w, G, sum_n2, g_abs, g_rel, C_obs,
-                       nrm, group_index, dist);
+    hipLaunchKernelGGL(gp_group, dim3((unsigned)n_scenes), dim3(kSnThreads), 0, st, c, tab, w, G, GpKeep{-1, -1, -1}, sum_n2,
+                       g_abs, g_rel, C_obs, nrm, group_index, dist);
     float *po = c.ws + G.po;
     run_layers<true>(bp, c, nullptr, I, nullptr, nullptr, max_n, po, logit_s, logit_t, st);
     hipLaunchKernelGGL(gp_mix, dim3((unsigned)N), dim3(kMixThreads), 6 * bp.out_dims * bp.pred_len * sizeof(float), st, tab, w,
@@ -129,6 +139,10 @@ static int gp_run(const et_gpgraph_sgcn_params &p, const float *g_abs, const flo
     ET_LAUNCH_CHECK();
     return ET_OK;
 }
+
+#include "et_sgcn_train.inl"
+
+#include "et_gpgraph_train.inl"
 
 }  // namespace
 }  // namespace et
@@ -173,4 +187,102 @@ extern "C" int et_gpgraph_sgcn_forward_graph(const et_gpgraph_sgcn_params *param
     if (!v_abs || !v_rel || !out) return ET_ERR_INVALID_ARG;
     return gp_run(*params, v_abs, v_rel, nullptr, nullptr, N, nullptr, 1, N * N, N, out, 1, group_index, dist, logit_s,
                   logit_t, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- training (et_gpgraph_train.inl)
+extern "C" size_t et_gpgraph_sgcn_train_workspace_bytes(const et_gpgraph_sgcn_params *params, int64_t N, int64_t sum_n2,
+                                                        int n_scenes) {
+    if (check_gp(params) != ET_OK || N <= 0 || sum_n2 < 0 || n_scenes < 0) return 0;
+    return (size_t)gtlay_of(params->base, N, sum_n2, n_scenes).total * 4;
+}
+
+extern "C" int64_t et_gpgraph_sgcn_grad_floats(const et_gpgraph_sgcn_params *params) {
+    if (check_gp(params) != ET_OK) return 0;
+    return gp_grad_floats(params->base);
+}
+
+extern "C" int et_gpgraph_sgcn_train_layout(const et_gpgraph_sgcn_params *params, int64_t N, int64_t sum_n2, int n_scenes,
+                                            int64_t *offsets, int n_offsets) {
+    const int rc = check_gp(params);
+    if (rc != ET_OK) return rc;
+    if (N <= 0 || sum_n2 < 0 || n_scenes < 0 || !offsets || n_offsets != ET_GPGRAPH_SGCN_TRAIN_LAYOUT_FIELDS)
+        return ET_ERR_INVALID_ARG;
+    const GTLay g = gtlay_of(params->base, N, sum_n2, n_scenes);
+    const TLay &t = g.t;
+    const int64_t f[ET_GPGRAPH_SGCN_TRAIN_LAYOUT_FIELDS] = {
+        t.L.v, t.L.rs_s, t.L.rs_t, t.xs, t.xs_stride, t.xt, t.xt_stride, t.L.at, t.L.f2, t.L.f1, t.L.ts, t.keep,
+        tail_keep_floats(params->base), t.dat, t.df1, t.dts, t.df2, t.rrec, t.gs, t.gt, t.dir_s, t.dir_t, t.dd_s,
+        t.L.vp, t.L.vn, t.L.gidx, t.dax, t.srec, t.trec, t.dacc_t, t.dx_as, t.dxp, t.dxv,
+        g.W.va, g.W.feat, g.W.dist, g.W.sn, g.W.po, g.sig, g.cs, g.cnt, g.dmix, g.dpo, g.dvp, g.dP, g.dsig, g.dd, g.df, g.total};
+    for (int i = 0; i < ET_GPGRAPH_SGCN_TRAIN_LAYOUT_FIELDS; ++i) offsets[i] = f[i];
+    return ET_OK;
+}
+
+extern "C" int et_gpgraph_sgcn_train_forward_scenes(const et_gpgraph_sgcn_params *params, const float *C_obs, const float *nrm,
+                                                    int64_t N, const int32_t *scene_offsets, int n_scenes, int64_t sum_n2,
+                                                    int64_t max_scene_n, float *C_pred_refine, int32_t *group_index,
+                                                    float *dist, float *logit_s, float *logit_t, void *workspace,
+                                                    size_t workspace_bytes, et_stream_t stream) {
+    const int rc = check_gp(params);
+    if (rc != ET_OK) return rc;
+    if (3 * N > INT32_MAX || 3 * (int64_t)n_scenes > INT32_MAX || sum_n2 < 0 || max_scene_n < 0) return ET_ERR_INVALID_ARG;
+    const int early = scene_args_status(N, INT32_MAX, scene_offsets, n_scenes, ET_SGCN_MAX_N);
+    if (early != kSceneArgsGo) return early;
+    if (!C_obs || !nrm || !C_pred_refine) return ET_ERR_INVALID_ARG;
+    if (!scene_offsets) {
+        n_scenes = 1;
+        sum_n2 = N * N;
+        max_scene_n = N;
+    }
+    if (max_scene_n > ET_SGCN_MAX_N) max_scene_n = ET_SGCN_MAX_N;  // larger scenes are not computed
+    return gp_run_train(*params, nullptr, nullptr, C_obs, nrm, N, scene_offsets, n_scenes, sum_n2, max_scene_n, C_pred_refine,
+                        0, group_index, dist, logit_s, logit_t, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int et_gpgraph_sgcn_train_forward_graph(const et_gpgraph_sgcn_params *params, const float *v_abs,
+                                                   const float *v_rel, int64_t N, float *out, int32_t *group_index,
+                                                   float *dist, float *logit_s, float *logit_t, void *workspace,
+                                                   size_t workspace_bytes, et_stream_t stream) {
+    const int rc = check_gp(params);
+    if (rc != ET_OK) return rc;
+    if (N < 0 || N > ET_SGCN_MAX_N) return ET_ERR_INVALID_ARG;
+    if (N == 0) return ET_OK;
+    if (!v_abs || !v_rel || !out) return ET_ERR_INVALID_ARG;
+    return gp_run_train(*params, v_abs, v_rel, nullptr, nullptr, N, nullptr, 1, N * N, N, out, 1, group_index, dist, logit_s,
+                        logit_t, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int et_gpgraph_sgcn_backward_scenes(const et_gpgraph_sgcn_params *params, int64_t N, const int32_t *scene_offsets,
+                                               int n_scenes, int64_t sum_n2, int64_t max_scene_n, const float *d_out,
+                                               float *grads, int64_t grads_floats, void *workspace, size_t workspace_bytes,
+                                               et_stream_t stream) {
+    const int rc = check_gp(params);
+    if (rc != ET_OK) return rc;
+    if (sum_n2 < 0 || max_scene_n < 0 || !grads || grads_floats < gp_grad_floats(params->base)) return ET_ERR_INVALID_ARG;
+    if (N < 0 || 3 * N > INT32_MAX || n_scenes < 0 || 3 * (int64_t)n_scenes > INT32_MAX ||
+        (scene_offsets && n_scenes == 0 && N != 0) || (!scene_offsets && N > ET_SGCN_MAX_N) || (N > 0 && !d_out))
+        return ET_ERR_INVALID_ARG;
+    if (!scene_offsets) {
+        n_scenes = 1;
+        sum_n2 = N * N;
+        max_scene_n = N;
+    }
+    if (max_scene_n > ET_SGCN_MAX_N) max_scene_n = ET_SGCN_MAX_N;
+    if (N == 0) {  // no scene: every gradient is zero
+        if (hipMemsetAsync(grads, 0, (size_t)gp_grad_floats(params->base) * 4, (hipStream_t)stream) != hipSuccess)
+            return ET_ERR_HIP;
+        return ET_OK;
+    }
+    return gp_run_backward(*params, N, scene_offsets, n_scenes, sum_n2, max_scene_n, d_out, 0, grads, workspace, workspace_bytes,
+                           (hipStream_t)stream);
+}
+
+extern "C" int et_gpgraph_sgcn_backward_graph(const et_gpgraph_sgcn_params *params, int64_t N, const float *d_out, float *grads,
+                                              int64_t grads_floats, void *workspace, size_t workspace_bytes,
+                                              et_stream_t stream) {
+    const int rc = check_gp(params);
+    if (rc != ET_OK) return rc;
+    if (N <= 0 || N > ET_SGCN_MAX_N || !d_out || !grads || grads_floats < gp_grad_floats(params->base))
+        return ET_ERR_INVALID_ARG;
+    return gp_run_backward(*params, N, nullptr, 1, N * N, N, d_out, 1, grads, workspace, workspace_bytes, (hipStream_t)stream);
 }

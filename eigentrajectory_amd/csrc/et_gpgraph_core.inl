@@ -20,6 +20,8 @@ struct GpScene {  // where one real scene's grouping goes (floats in the workspa
     float *va, *feat;   // v_abs (T, n), group_cnn's features (8, T, n)
     float *D, *sn;      // dist and sig_norm (n, n)
     float *in[3][2];    // pass m's input, channel ch: (T, n_m) blocks (CH = 1: [m][0] only)
+    float *sig = nullptr, *cs = nullptr;   // the training forward keeps sig (n, n) and its column sums (n); else NULL
+    int32_t *cnt = nullptr;                // ... and the group sizes (n)
 };
 
 struct GpWeights {
@@ -146,9 +148,14 @@ __device__ __forceinline__ void gp_group_scene(const GpTab &tab, const GpScene &
         float sum = 0.f;
         for (int i = 0; i < n; ++i) sum += sig_of(D[i * n + j], th, tau);
         cs[j] = sum;
+        if (gs.cs) gs.cs[j] = sum;
     }
     __syncthreads();
-    for (int q = tid; q < n * n; q += kSnThreads) sn[q] = sig_of(D[q], th, tau) / cs[q % n];
+    for (int q = tid; q < n * n; q += kSnThreads) {
+        const float sg = sig_of(D[q], th, tau);
+        sn[q] = sg / cs[q % n];
+        if (gs.sig) gs.sig[q] = sg;
+    }
     __syncthreads();
     // v' = (v_rel - v_soft) + v_soft, v_soft = v_rel @ sig_norm: every channel
     for (int q = tid; q < CH * T * n; q += kSnThreads) {
@@ -168,6 +175,8 @@ __device__ __forceinline__ void gp_group_scene(const GpTab &tab, const GpScene &
             if (idx[i] == g) sum += x[i];
         (ch ? v1 : p1)[t * ng + g] = sum / (float)cnt[g];
     }
+    if (gs.cnt)
+        for (int g = tid; g < ng; g += kSnThreads) gs.cnt[g] = cnt[g];
 }
 
 // ---- mix: one workgroup per pedestrian; po (k, 3 Nr, S): the three passes' outputs, pass 1's on the group rows

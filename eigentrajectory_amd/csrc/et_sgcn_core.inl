@@ -598,7 +598,7 @@ static unsigned chunks(int64_t work_max, int n_scenes) {
 }
 
 // input .. tail on the c.S scenes of c (whoever calls has launched the prep, and for GP the group kernel): 5 +
-// number_asymmetric_conv_layer launches.  out: (k, c.N, S).  keep (the training forward, GP = false only): layer j reads the
+// number_asymmetric_conv_layer launches.  out: (k, c.N, S).  keep (the training forward): layer j reads the
 // stack at c.L.xa / c.L.ta + j x stride and writes the next one instead of the two ping-pong buffers, and the tail stores its
 // activations at keep; the launches and their arithmetic are the same
 template <bool GP>
@@ -624,12 +624,10 @@ static void run_layers(const et_sgcn_params &p, const Ctx &c, const float *gv, c
     }
     hipLaunchKernelGGL(sgcn_tadj<GP>, dim3(S, by_r), blk, 0, st, c, p, I, lt);
     hipLaunchKernelGGL(sgcn_sadj<GP>, dim3(S, by_r), blk, 0, st, c, p, I, ls);
-    if constexpr (!GP) {
-        if (keep) {
-            hipLaunchKernelGGL((sgcn_tail<false, true>), dim3((unsigned)c.N), dim3(kWave), 2 * T * kWave * sizeof(float), st, c, p,
-                               out, keep);
-            return;
-        }
+    if (keep) {
+        hipLaunchKernelGGL((sgcn_tail<GP, true>), dim3((unsigned)c.N), dim3(kWave), 2 * T * kWave * sizeof(float), st, c, p,
+                           out, keep);
+        return;
     }
     hipLaunchKernelGGL(sgcn_tail<GP>, dim3((unsigned)c.N), dim3(kWave), 2 * T * kWave * sizeof(float), st, c, p, out,
                        (float *)nullptr);

@@ -1,6 +1,11 @@
 // et_sgcn_train.inl -- SGCN training for the one-channel family (include/eigentraj.h "SGCN predictor, training"): the
 // training forward (the eval kernels of et_sgcn_core.inl on a layout that keeps every asymmetric layer's input and the
-// tail's activations) and the backward pass with respect to every parameter.  #included by et_sgcn.hip after the core.
+// tail's activations) and the backward pass with respect to every parameter.  #included by et_sgcn.hip after the core, and
+// by et_gpgraph.hip: like the forward's, the kernels are templates on GP.  GP = true is the base of GP-Graph-SGCN on its
+// 3 Sr virtual scenes (et_gpgraph_train.inl drives it): a pass has n_m nodes, the temporal score row carries six numbers per
+// head and both channels, the spatial mask of the intra-group pass is multiplied by the same-group matrix, and the kernels
+// also leave what the input gradient needs (d (A_s x) and d (A_t x) per row, A_s^T d (A_s x), the rows' sum dense d dense,
+// d t_i, d a, d b).  The GP = false instantiations keep the arithmetic they had before the template.
 //
 // Backward, number_asymmetric_conv_layer + 8 launches for any number of scenes, in the order the gradient flows:
 //   tail_bwd   per chunk of ET_SGCN_BWD_CHUNK pedestrians   output layer, tcns, fusion_, spatial_temporal gcn 1
@@ -36,6 +41,11 @@ struct TLay {  // training workspace, in floats.  L: the eval layout's names (xa
     int64_t p_tail, p_sadj, p_tadj, p_asym_s, p_asym_t, p_fuse, p_rows;  // partials
     int64_t n_tail, n_rows, n_rows2, n_as, n_at, n_fuse;                 // slots
     int64_t g_tail;                                                       // floats of a tail partial block
+    // GP (the base of GP-Graph-SGCN, three passes as virtual scenes): what the input gradient needs -- per spatial row
+    // d (A_s x), per spatial row (sum dense d dense, d t_i), per temporal row (sum dense d dense, d a, d b), per temporal row
+    // d (A_t x), A_s^T d (A_s x) per (j,h,t), and the input gradient itself, position and coefficient channel (T, n_m)
+    int64_t dax, srec, trec, dacc_t, dx_as, dxp, dxv;
+    int rows_g;                                                           // floats of a rows partial: 16, GP 32
     int64_t total;
 };
 
@@ -48,13 +58,13 @@ struct GLay {
     int64_t att[2], fus, asym_s, asym_t, gcn[4], fusion, tcn[ET_SGCN_MAX_LAYERS], out_w, out_b, total;
 };
 
-__host__ __device__ inline GLay glay_of(const et_sgcn_params &p) {
+__host__ __device__ inline GLay glay_of(const et_sgcn_params &p, bool gp = false) {
     GLay G;
     const int T = p.obs_len;
     int64_t at = 0;
     for (int a = 0; a < 2; ++a) {
         G.att[a] = at;
-        at += 2 * kE + 2 * (kE * kE + kE);
+        at += (gp && a ? 3 : 2) * kE + 2 * (kE * kE + kE);  // GP: the temporal embedding.weight is (64, 2)
     }
     G.fus = at;
     at += T * T + T + 1;
@@ -80,10 +90,10 @@ __host__ __device__ inline GLay glay_of(const et_sgcn_params &p) {
     return G;
 }
 
-__host__ __device__ inline TLay tlay_of(const et_sgcn_params &p, int64_t N, int64_t n2, int64_t S) {
+__host__ __device__ inline TLay tlay_of(const et_sgcn_params &p, int64_t N, int64_t n2, int64_t S, bool gp = false) {
     TLay t;
     const int T = p.obs_len;
-    t.L = lay_of(T, N, n2, S);
+    t.L = lay_of(T, N, n2, S);  // (GP: N, n2, S count the virtual scenes' rows, entries and scenes)
     int64_t at = t.L.xa;
     auto take = [&](int64_t n) {
         const int64_t o = at;
@@ -128,20 +138,36 @@ __host__ __device__ inline TLay tlay_of(const et_sgcn_params &p, int64_t N, int6
     t.p_asym_s = take(t.n_as * kAsymG * p.n_asym);
     t.p_asym_t = take(t.n_at * kAsymG * p.n_asym);
     t.p_fuse = take(t.n_fuse * (T * T + T + 1));
-    t.p_rows = take(t.n_rows2 * 16);
+    t.rows_g = gp ? 32 : 16;
+    t.p_rows = take(t.n_rows2 * t.rows_g);
+    t.dax = t.srec = t.trec = t.dacc_t = t.dx_as = t.dxp = t.dxv = 0;
+    if (gp) {
+        t.L.vp = take(T * N);
+        t.L.vn = take(S);
+        t.L.gidx = take(N / 3);
+        t.dax = take((int64_t)T * kH * N);
+        t.srec = take(2 * (int64_t)T * kH * N);
+        t.trec = take(3 * (int64_t)T * kH * N);
+        t.dacc_t = take((int64_t)T * kH * N);
+        t.dx_as = take((int64_t)T * kH * N);
+        t.dxp = take(T * N);
+        t.dxv = take(T * N);
+        t.L.total = at;  // GP-Graph's wrapper values follow the base's training layout (wlay_of starts at L.total)
+    }
     t.total = at;
     return t;
 }
 
 // slot g of a kernel whose scene of n pedestrians has work(n) items in chunks of `per`: -> scene, chunk (false: no work)
-template <class W>
+template <bool GP, class W>
 __device__ __forceinline__ bool find_slot(const Ctx &c, int64_t g, int64_t per, W work, int64_t &chunk, int64_t &b, int &n,
-                                          int64_t &sq) {
+                                          int64_t &sq, int *scene = nullptr) {
     for (int s = 0; s < c.S; ++s) {
-        if (!scene_at<false>(c, s, b, n, sq)) continue;
+        if (!scene_at<GP>(c, s, b, n, sq)) continue;
         const int64_t nch = ceil_div(work(n), per);
         if (g < nch) {
             chunk = g;
+            if (scene) *scene = s;
             return true;
         }
         g -= nch;
@@ -167,7 +193,25 @@ __device__ __forceinline__ float block_sum(float x, float *red) {
 
 __device__ __forceinline__ float sigmoid_of(float l) { return 1.0f / (1.0f + expf(-l)); }
 
+// the spatial mask of entry (i, j), identity added; GP's intra-group pass (grp: the scene's group index, else NULL): times
+// the same-group matrix, as sgcn_sadj forms it
+template <bool GP>
+__device__ __forceinline__ float smask_of(float l, float ident, const int32_t *grp, int i, int j) {
+    float mk = mask_of(l, ident);
+    if constexpr (GP)
+        if (grp) mk = mk * (grp[i] == grp[j] ? 1.f : 0.f);
+    return mk;
+}
+
+template <bool GP>
+__device__ __forceinline__ const int32_t *group_index_of(const Ctx &c, int s, int64_t b) {
+    if constexpr (GP)
+        if (s >= 2 * c.Sr) return reinterpret_cast<const int32_t *>(c.ws + c.L.gidx) + (b - 2 * c.Nr);
+    return nullptr;
+}
+
 // ---- tail backward
+template <bool GP>
 __global__ __launch_bounds__(kSnThreads) void sgcn_tail_bwd(Ctx c, TLay tl, et_sgcn_params p,
                                                             const float *__restrict__ dout) {
     __shared__ float sdo[ET_MAX_K * kSnMaxS];
@@ -178,7 +222,7 @@ __global__ __launch_bounds__(kSnThreads) void sgcn_tail_bwd(Ctx c, TLay tl, et_s
     float *part = c.ws + tl.p_tail + (int64_t)blockIdx.x * tl.g_tail;
     int64_t chunk, b, sq;
     int n;
-    if (!find_slot(c, blockIdx.x, kBwdChunk, [](int m) { return (int64_t)m; }, chunk, b, n, sq)) {
+    if (!find_slot<GP>(c, blockIdx.x, kBwdChunk, [](int m) { return (int64_t)m; }, chunk, b, n, sq)) {
         for (int64_t q = tid; q < tl.g_tail; q += kSnThreads) part[q] = 0.f;
         return;
     }
@@ -350,6 +394,7 @@ __device__ __forceinline__ void zsm_entry_bwd(float dn, float mk, float l, float
 }
 
 // ---- sadj backward: spatial rows (t,h,i)
+template <bool GP>
 __global__ __launch_bounds__(kSnThreads) void sgcn_sadj_bwd(Ctx c, TLay tl, et_sgcn_params p, Ident I,
                                                             const float *__restrict__ ls, float *__restrict__ gout) {
     __shared__ float s_dz[kD * kSnThreads], s_ac[kD * kSnThreads];
@@ -359,10 +404,12 @@ __global__ __launch_bounds__(kSnThreads) void sgcn_sadj_bwd(Ctx c, TLay tl, et_s
     float *part = c.ws + tl.p_sadj + (int64_t)blockIdx.x * G;
     int64_t chunk, b, sq;
     int n;
-    if (!find_slot(c, blockIdx.x, kBwdRows, [T](int m) { return (int64_t)T * kH * m; }, chunk, b, n, sq)) {
+    int scene = 0;
+    if (!find_slot<GP>(c, blockIdx.x, kBwdRows, [T](int m) { return (int64_t)T * kH * m; }, chunk, b, n, sq, &scene)) {
         for (int q = tid; q < G; q += kSnThreads) part[q] = 0.f;
         return;
     }
+    const int32_t *grp = group_index_of<GP>(c, scene, b);
     const float *hdr = c.ws + tl.L.hdr;
     const float *v = c.ws + tl.L.v + T * b;
     const float *rs_s = c.ws + tl.L.rs_s + 2 * (int64_t)T * kH * b;
@@ -391,7 +438,7 @@ __global__ __launch_bounds__(kSnThreads) void sgcn_sadj_bwd(Ctx c, TLay tl, et_s
             float ssum = 0.f, sx = 0.f;
             for (int j = 0; j < n; ++j) {
                 const float xj = v[t * n + j];
-                const float e = zsm_num(dense(ti, xj, m, sum) * mask_of(lrow[j], ident_s(I, t, i, j, n)));
+                const float e = zsm_num(dense(ti, xj, m, sum) * smask_of<GP>(lrow[j], ident_s(I, t, i, j, n), grp, i, j));
                 ssum += e;
                 sx = fmaf(e, xj, sx);
                 const float *fr = f2 + (((int64_t)j * kH + h) * T + t) * kD;
@@ -432,12 +479,13 @@ __global__ __launch_bounds__(kSnThreads) void sgcn_sadj_bwd(Ctx c, TLay tl, et_s
             rec[0] = den;
 #pragma unroll
             for (int q = 0; q < kD; ++q) rec[1 + q] = dacc[q];
+            if constexpr (GP) c.ws[tl.dax + (int64_t)T * kH * b + r] = dax;
             // d A_s[j] = dax x_j + dacc . f2[j].  d e[j] = (d A_s[j] - sum_j' d A_s[j'] A_s[j']) / den, formed around c0 = d A_s[0]
             // (sum A_s = 1 - 1e-5 / den): the plain form cancels where one entry carries the row, exactly so in a scene of one
             float sdy = 0.f, c0 = 0.f;
             for (int j = 0; j < n; ++j) {
                 const float xj = v[t * n + j];
-                const float e = zsm_num(dense(ti, xj, m, sum) * mask_of(lrow[j], ident_s(I, t, i, j, n)));
+                const float e = zsm_num(dense(ti, xj, m, sum) * smask_of<GP>(lrow[j], ident_s(I, t, i, j, n), grp, i, j));
                 const float *fr = f2 + (((int64_t)j * kH + h) * T + t) * kD;
                 float dy = dax * xj;
 #pragma unroll
@@ -448,7 +496,7 @@ __global__ __launch_bounds__(kSnThreads) void sgcn_sadj_bwd(Ctx c, TLay tl, et_s
             const float tail0 = c0 * (1e-5f / den);
             for (int j = 0; j < n; ++j) {
                 const float xj = v[t * n + j];
-                const float dn = dense(ti, xj, m, sum), mk = mask_of(lrow[j], ident_s(I, t, i, j, n));
+                const float dn = dense(ti, xj, m, sum), mk = smask_of<GP>(lrow[j], ident_s(I, t, i, j, n), grp, i, j);
                 const float *fr = f2 + (((int64_t)j * kH + h) * T + t) * kD;
                 float dy = dax * xj;
 #pragma unroll
@@ -494,40 +542,46 @@ __global__ __launch_bounds__(kSnThreads) void sgcn_sadj_bwd(Ctx c, TLay tl, et_s
 }
 
 // ---- d f2 (n,4,T,16): entry (j,h,t) gathers A_s[t,h,i,j] d (A_s f2)[t,h,i,:] over i ascending
+template <bool GP>
 __global__ __launch_bounds__(kSnThreads) void sgcn_sadj_f2(Ctx c, TLay tl, Ident I, const float *__restrict__ ls) {
     int64_t b, sq;
     int n;
-    if (!scene_at<false>(c, blockIdx.x, b, n, sq)) return;
+    if (!scene_at<GP>(c, blockIdx.x, b, n, sq)) return;
     const int T = c.T;
+    const int32_t *grp = group_index_of<GP>(c, blockIdx.x, b);
     const float *hdr = c.ws + tl.L.hdr;
     const float *v = c.ws + tl.L.v + T * b;
     const float *rs_s = c.ws + tl.L.rs_s + 2 * (int64_t)T * kH * b;
     const float *lg = ls + (int64_t)T * kH * sq;
     const float *rrec = c.ws + tl.rrec + (int64_t)T * kH * b * 17;
+    const float *daxr = c.ws + tl.dax + (int64_t)T * kH * b;  // GP: d (A_s x) per row, for the input gradient
     float *df2 = c.ws + tl.df2 + b * kH * T * kD;
     const int items = n * kH * T;
     for (int it = blockIdx.y * kSnThreads + threadIdx.x; it < items; it += gridDim.y * kSnThreads) {
         const int t = it % T, h = (it / T) % kH, j = it / (T * kH);
         const float xj = v[t * n + j];
-        float acc[kD];
+        float acc[kD], ax = 0.f;
 #pragma unroll
         for (int d = 0; d < kD; ++d) acc[d] = 0.f;
         for (int i = 0; i < n; ++i) {
             const int r = (t * kH + h) * n + i;
             const float ti = fmaf(v[t * n + i], hdr[h], hdr[4 + h]);
             const float e = zsm_num(dense(ti, xj, rs_s[2 * r], rs_s[2 * r + 1]) *
-                                    mask_of(lg[(int64_t)r * n + j], ident_s(I, t, i, j, n)));
+                                    smask_of<GP>(lg[(int64_t)r * n + j], ident_s(I, t, i, j, n), grp, i, j));
             const float *rec = rrec + (int64_t)r * 17;
             const float y = e / rec[0];
 #pragma unroll
             for (int d = 0; d < kD; ++d) acc[d] = fmaf(y, rec[1 + d], acc[d]);
+            if constexpr (GP) ax = fmaf(y, daxr[r], ax);
         }
 #pragma unroll
         for (int d = 0; d < kD; ++d) df2[(int64_t)it * kD + d] = acc[d];
+        if constexpr (GP) c.ws[tl.dx_as + b * kH * T + it] = ax;  // A_s^T d (A_s x) at (j,h,t)
     }
 }
 
 // ---- tadj backward: temporal rows (i,h,t)
+template <bool GP>
 __global__ __launch_bounds__(kSnThreads) void sgcn_tadj_bwd(Ctx c, TLay tl, et_sgcn_params p, Ident I,
                                                             const float *__restrict__ lt, float *__restrict__ gout) {
     __shared__ float red[(kSnThreads / kWave) * (kD + 1)];
@@ -536,12 +590,13 @@ __global__ __launch_bounds__(kSnThreads) void sgcn_tadj_bwd(Ctx c, TLay tl, et_s
     float *part = c.ws + tl.p_tadj + (int64_t)blockIdx.x * G;
     int64_t chunk, b, sq;
     int n;
-    if (!find_slot(c, blockIdx.x, kBwdRows, [T](int m) { return (int64_t)T * kH * m; }, chunk, b, n, sq)) {
+    if (!find_slot<GP>(c, blockIdx.x, kBwdRows, [T](int m) { return (int64_t)T * kH * m; }, chunk, b, n, sq)) {
         if (tid < G) part[tid] = 0.f;
         return;
     }
     const float *hdr = c.ws + tl.L.hdr;
     const float *v = c.ws + tl.L.v + T * b;
+    const float *vp = c.ws + tl.L.vp + T * b;  // (GP only)
     const float *rs_t = c.ws + tl.L.rs_t + 2 * (int64_t)T * kH * b;
     const float *lg = lt + b * kH * T * T;
     const float *dat = c.ws + tl.dat + b * kH * T * T;
@@ -555,16 +610,16 @@ __global__ __launch_bounds__(kSnThreads) void sgcn_tadj_bwd(Ctx c, TLay tl, et_s
     for (int d = 0; d < kD; ++d) gw[d] = 0.f;
     for (int r = r0 + tid; r < r1; r += kSnThreads) {
         const int t = r % T, h = (r / T) % kH, i = r / (T * kH);
-        const TRow<false> tr = trow_of<false>(hdr, v, nullptr, n, t, i, h);
+        const TRow<GP> tr = trow_of<GP>(hdr, v, vp, n, t, i, h);
         const float m = rs_t[2 * r], sum = rs_t[2 * r + 1];
         float ssum = 0.f;
         for (int u = 0; u < T; ++u)
-            ssum += zsm_num(expf(tscore<false>(tr, v, nullptr, n, u, i) - m) / sum *
+            ssum += zsm_num(expf(tscore<GP>(tr, v, vp, n, u, i) - m) / sum *
                             mask_of(lg[(int64_t)r * T + u], ident_t(I, i, t, u, T)));
         const float den = ssum + 1e-5f;
         float acc = 0.f;
         for (int u = 0; u < T; ++u) {
-            const float e = zsm_num(expf(tscore<false>(tr, v, nullptr, n, u, i) - m) / sum *
+            const float e = zsm_num(expf(tscore<GP>(tr, v, vp, n, u, i) - m) / sum *
                                     mask_of(lg[(int64_t)r * T + u], ident_t(I, i, t, u, T)));
             acc = fmaf(e / den, v[u * n + i], acc);
         }
@@ -577,9 +632,10 @@ __global__ __launch_bounds__(kSnThreads) void sgcn_tadj_bwd(Ctx c, TLay tl, et_s
             gw[d] = fmaf(dz, acc, gw[d]);
             dacc = fmaf(dz, w, dacc);
         }
+        if constexpr (GP) c.ws[tl.dacc_t + b * kH * T + r] = dacc;
         float sdy = 0.f, c0 = 0.f;  // around c0 = d A_t[0], as in sgcn_sadj_bwd
         for (int u = 0; u < T; ++u) {
-            const float e = zsm_num(expf(tscore<false>(tr, v, nullptr, n, u, i) - m) / sum *
+            const float e = zsm_num(expf(tscore<GP>(tr, v, vp, n, u, i) - m) / sum *
                                     mask_of(lg[(int64_t)r * T + u], ident_t(I, i, t, u, T)));
             const float dy = fmaf(dacc, v[u * n + i], dat[(int64_t)r * T + u]);
             if (u == 0) c0 = dy;
@@ -587,7 +643,7 @@ __global__ __launch_bounds__(kSnThreads) void sgcn_tadj_bwd(Ctx c, TLay tl, et_s
         }
         const float tail0 = c0 * (1e-5f / den);
         for (int u = 0; u < T; ++u) {
-            const float dn = expf(tscore<false>(tr, v, nullptr, n, u, i) - m) / sum;
+            const float dn = expf(tscore<GP>(tr, v, vp, n, u, i) - m) / sum;
             const float l = lg[(int64_t)r * T + u], mk = mask_of(l, ident_t(I, i, t, u, T));
             const float dy = fmaf(dacc, v[u * n + i], dat[(int64_t)r * T + u]);
             float direct, dl;
@@ -652,6 +708,7 @@ __device__ __forceinline__ void asym_dz(const float *__restrict__ x, const float
     }
 }
 
+template <bool GP>
 __global__ __launch_bounds__(kSnThreads) void sgcn_asym_bwd(Ctx c, TLay tl, et_sgcn_asym As, et_sgcn_asym At, int layer,
                                                             const float *in_s, const float *g_s, float *o_s,
                                                             const float *in_t, const float *g_t, float *o_t) {
@@ -663,8 +720,8 @@ __global__ __launch_bounds__(kSnThreads) void sgcn_asym_bwd(Ctx c, TLay tl, et_s
                                   : tl.p_asym_t + ((int64_t)layer * tl.n_at + slot) * kAsymG);
     int64_t chunk, b, sq;
     int n;
-    const bool found = spatial ? find_slot(c, slot, kBwdItems, [T](int m) { return (int64_t)T * m * m; }, chunk, b, n, sq)
-                               : find_slot(c, slot, kBwdItems, [T](int m) { return (int64_t)m * T * T; }, chunk, b, n, sq);
+    const bool found = spatial ? find_slot<GP>(c, slot, kBwdItems, [T](int m) { return (int64_t)T * m * m; }, chunk, b, n, sq)
+                               : find_slot<GP>(c, slot, kBwdItems, [T](int m) { return (int64_t)m * T * T; }, chunk, b, n, sq);
     if (!found) {
         if (tid < kAsymG) part[tid] = 0.f;
         return;
@@ -738,6 +795,7 @@ __global__ __launch_bounds__(kSnThreads) void sgcn_asym_bwd(Ctx c, TLay tl, et_s
 }
 
 // ---- fuse backward: entries (h,i,j) in tiles of kFuseTile, one thread per entry; then a thread owns pairs (u,t) of d fus_w
+template <bool GP>
 __global__ __launch_bounds__(kFuseTile) void sgcn_fuse_bwd(Ctx c, TLay tl, et_sgcn_params p, const float *__restrict__ g0) {
     __shared__ float s_d[kSnMaxT * kFuseTile], s_da[kSnMaxT * kFuseTile];
     __shared__ float red[kFuseTile / kWave];
@@ -747,7 +805,7 @@ __global__ __launch_bounds__(kFuseTile) void sgcn_fuse_bwd(Ctx c, TLay tl, et_sg
     float *part = c.ws + tl.p_fuse + (int64_t)blockIdx.x * G;
     int64_t chunk, b, sq;
     int n;
-    if (!find_slot(c, blockIdx.x, kBwdItems, [](int m) { return (int64_t)kH * m * m; }, chunk, b, n, sq)) {
+    if (!find_slot<GP>(c, blockIdx.x, kBwdItems, [](int m) { return (int64_t)kH * m * m; }, chunk, b, n, sq)) {
         for (int q = tid; q < G; q += kFuseTile) part[q] = 0.f;
         return;
     }
@@ -814,31 +872,35 @@ __global__ __launch_bounds__(kFuseTile) void sgcn_fuse_bwd(Ctx c, TLay tl, et_sg
 }
 
 // ---- softmax rows: d score = dense (d dense - sum dense d dense); d alpha_h, d beta_h of both attentions
+template <bool GP>
 __global__ __launch_bounds__(kSnThreads) void sgcn_rows_bwd(Ctx c, TLay tl, const float *__restrict__ gt0) {
-    __shared__ float red[(kSnThreads / kWave) * 16];
+    constexpr int kG = GP ? 32 : 16;  // GP: the temporal score row carries six numbers per head, hdr[8 + 4 q + h]
+    __shared__ float red[(kSnThreads / kWave) * kG];
     const int tid = threadIdx.x, T = c.T;
-    float *part = c.ws + tl.p_rows + (int64_t)blockIdx.x * 16;
+    float *part = c.ws + tl.p_rows + (int64_t)blockIdx.x * kG;
     int64_t chunk, b, sq;
     int n;
-    if (!find_slot(c, blockIdx.x, kBwdRows, [T](int m) { return 2 * (int64_t)T * kH * m; }, chunk, b, n, sq)) {
-        if (tid < 16) part[tid] = 0.f;
+    if (!find_slot<GP>(c, blockIdx.x, kBwdRows, [T](int m) { return 2 * (int64_t)T * kH * m; }, chunk, b, n, sq)) {
+        if (tid < kG) part[tid] = 0.f;
         return;
     }
     const float *hdr = c.ws + tl.L.hdr;
     const float *v = c.ws + tl.L.v + T * b;
+    const float *vp = c.ws + tl.L.vp + T * b;  // (GP only)
     const float *rs_s = c.ws + tl.L.rs_s + 2 * (int64_t)T * kH * b;
     const float *dd_s = c.ws + tl.dd_s + (int64_t)T * kH * sq;
     const float *dn_t = c.ws + tl.L.ta + b * kH * T * T;  // the kept temporal attention
     const float *dd_t = c.ws + tl.dir_t + b * kH * T * T, *g_t = gt0 + b * kH * T * T;
     const int rows = T * kH * n;
     const int r0 = (int)chunk * kBwdRows, r1 = r0 + kBwdRows < 2 * rows ? r0 + kBwdRows : 2 * rows;
-    float acc[16];
+    float acc[kG];
 #pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+    for (int e = 0; e < kG; ++e) acc[e] = 0.f;
     for (int rr = r0 + tid; rr < r1; rr += kSnThreads) {
         const bool temporal = rr >= rows;
         int h;
         float xi, dti = 0.f;
+        float pi = 0.f, dtb = 0.f;  // GP, a temporal row: its position, and d b next to d a (dti)
         if (!temporal) {
             const int r = rr, i = r % n, t = r / (n * kH);
             h = (r / n) % kH;
@@ -850,32 +912,62 @@ __global__ __launch_bounds__(kSnThreads) void sgcn_rows_bwd(Ctx c, TLay tl, cons
                 const float xj = v[t * n + j];
                 dti = fmaf(dense(ti, xj, m, sum) * (dd_s[(int64_t)r * n + j] - s), xj, dti);
             }
+            if constexpr (GP) {
+                float *rec = c.ws + tl.srec + 2 * ((int64_t)T * kH * b + r);
+                rec[0] = s;
+                rec[1] = dti;
+            }
         } else {
             const int r = rr - rows, t = r % T, i = r / (T * kH);
             h = (r / T) % kH;
             xi = v[t * n + i];
             float s = 0.f;
             for (int u = 0; u < T; ++u) s = fmaf(dn_t[(int64_t)r * T + u], g_t[(int64_t)r * T + u] + dd_t[(int64_t)r * T + u], s);
-            for (int u = 0; u < T; ++u)
-                dti = fmaf(dn_t[(int64_t)r * T + u] * (g_t[(int64_t)r * T + u] + dd_t[(int64_t)r * T + u] - s), v[u * n + i], dti);
+            if constexpr (GP) {
+                pi = vp[t * n + i];
+                for (int u = 0; u < T; ++u) {
+                    const float ds = dn_t[(int64_t)r * T + u] * (g_t[(int64_t)r * T + u] + dd_t[(int64_t)r * T + u] - s);
+                    dti = fmaf(ds, vp[u * n + i], dti);
+                    dtb = fmaf(ds, v[u * n + i], dtb);
+                }
+                float *rec = c.ws + tl.trec + 3 * (b * kH * T + r);
+                rec[0] = s;
+                rec[1] = dti;
+                rec[2] = dtb;
+            } else {
+                for (int u = 0; u < T; ++u)
+                    dti = fmaf(dn_t[(int64_t)r * T + u] * (g_t[(int64_t)r * T + u] + dd_t[(int64_t)r * T + u] - s), v[u * n + i], dti);
+            }
         }
-        const int base = (temporal ? 8 : 0) + h;
+        if (GP && temporal) {  // a = p h0 + c h1 + h2, b = p h3 + c h4 + h5
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            if (e == base) acc[e] = fmaf(dti, xi, acc[e]);
-            if (e == base + 4) acc[e] += dti;
+            for (int e = 8; e < kG; ++e) {
+                if (e == 8 + h) acc[e] = fmaf(dti, pi, acc[e]);
+                if (e == 12 + h) acc[e] = fmaf(dti, xi, acc[e]);
+                if (e == 16 + h) acc[e] += dti;
+                if (e == 20 + h) acc[e] = fmaf(dtb, pi, acc[e]);
+                if (e == 24 + h) acc[e] = fmaf(dtb, xi, acc[e]);
+                if (e == 28 + h) acc[e] += dtb;
+            }
+        } else {
+            const int base = (temporal ? 8 : 0) + h;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                if (e == base) acc[e] = fmaf(dti, xi, acc[e]);
+                if (e == base + 4) acc[e] += dti;
+            }
         }
     }
     const int wv = tid / kWave;
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
+    for (int e = 0; e < kG; ++e) {
         const float s = wave_sum(acc[e]);
-        if ((tid & (kWave - 1)) == 0) red[wv * 16 + e] = s;
+        if ((tid & (kWave - 1)) == 0) red[wv * kG + e] = s;
     }
     __syncthreads();
-    if (tid < 16) {
+    if (tid < kG) {
         float s = 0.f;
-        for (int w = 0; w < kSnThreads / kWave; ++w) s += red[w * 16 + tid];
+        for (int w = 0; w < kSnThreads / kWave; ++w) s += red[w * kG + tid];
         part[tid] = s;
     }
 }
@@ -937,6 +1029,106 @@ __global__ __launch_bounds__(kSnThreads) void sgcn_prep_bwd(et_sgcn_params p, TL
     }
 }
 
+// GP: the spatial attention as above; the temporal one reads x = (p, c) through a (64, 2) embedding.  Slots as sgcn_prep<true>:
+// 0 spatial, 1 the coefficient column, 2 the position column; d h_q (q = 0..5, per head) at dab[8 + 4 q + h] with
+//   h0 = aq_p.ak_p, h1 = aq_c.ak_p, h2 = cq.ak_p, h3 = aq_p.ak_c, h4 = aq_c.ak_c, h5 = cq.ak_c  (each / 8)
+__global__ __launch_bounds__(kSnThreads) void sgcn_prep_bwd_gp(et_sgcn_params p, TLay tl, const float *ws, float *grads,
+                                                               GLay G) {
+    __shared__ double aq[3][kE], cq[3][kE], ak[3][kE], daq[3][kE], dcq[3][kE], dak[3][kE];
+    __shared__ float dab[32];
+    const int tid = threadIdx.x;
+    if (tid < 32) {
+        float s = 0.f;
+        for (int64_t g = 0; g < tl.n_rows2; ++g) s += ws[tl.p_rows + g * 32 + tid];
+        dab[tid] = s;
+    }
+    if (tid < 3 * kE) {
+        const int slot = tid / kE, a = slot ? 1 : 0, cc = tid % kE;
+        const int stride = a ? 2 : 1, col = slot == 1 ? 1 : 0;
+        const et_sgcn_attention &A = p.att[a];
+        double s_aq = 0, s_cq = (double)A.q_b[cc], s_ak = 0;
+        for (int e = 0; e < kE; ++e) {
+            const double we = A.emb_w[e * stride + col], be = A.emb_b[e];
+            s_aq = fma((double)A.q_w[cc * kE + e], we, s_aq);
+            s_cq = fma((double)A.q_w[cc * kE + e], be, s_cq);
+            s_ak = fma((double)A.k_w[cc * kE + e], we, s_ak);
+        }
+        aq[slot][cc] = s_aq;
+        cq[slot][cc] = s_cq;
+        ak[slot][cc] = s_ak;
+    }
+    __syncthreads();
+    if (tid < 3 * kE) {
+        const int slot = tid / kE, cc = tid % kE, h = cc / kD;
+        if (slot == 0) {
+            const double da = dab[h], db = dab[4 + h];
+            daq[0][cc] = da * ak[0][cc] * 0.125;
+            dcq[0][cc] = db * ak[0][cc] * 0.125;
+            dak[0][cc] = (da * aq[0][cc] + db * cq[0][cc]) * 0.125;
+        } else {
+            const double h0 = dab[8 + h], h1 = dab[12 + h], h2 = dab[16 + h], h3 = dab[20 + h], h4 = dab[24 + h], h5 = dab[28 + h];
+            if (slot == 2) {  // the position column
+                daq[2][cc] = (h0 * ak[2][cc] + h3 * ak[1][cc]) * 0.125;
+                dak[2][cc] = (h0 * aq[2][cc] + h1 * aq[1][cc] + h2 * cq[1][cc]) * 0.125;
+                dcq[2][cc] = 0;
+            } else {  // the coefficient column, and the bias path
+                daq[1][cc] = (h1 * ak[2][cc] + h4 * ak[1][cc]) * 0.125;
+                dak[1][cc] = (h3 * aq[2][cc] + h4 * aq[1][cc] + h5 * cq[1][cc]) * 0.125;
+                dcq[1][cc] = (h2 * ak[2][cc] + h5 * ak[1][cc]) * 0.125;
+            }
+        }
+    }
+    __syncthreads();
+    {  // the spatial attention: emb_w 64, emb_b 64, q_w 4096, q_b 64, k_w 4096, k_b 64
+        const et_sgcn_attention &A = p.att[0];
+        float *g = grads + G.att[0];
+        float *g_qw = g + 2 * kE, *g_qb = g_qw + kE * kE, *g_kw = g_qb + kE, *g_kb = g_kw + kE * kE;
+        for (int q = tid; q < kE * kE; q += kSnThreads) {
+            const int cc = q / kE, e = q % kE;
+            g_qw[q] = (float)(daq[0][cc] * (double)A.emb_w[e] + dcq[0][cc] * (double)A.emb_b[e]);
+            g_kw[q] = (float)(dak[0][cc] * (double)A.emb_w[e]);
+        }
+        if (tid < kE) {
+            g_qb[tid] = (float)dcq[0][tid];
+            g_kb[tid] = 0.f;  // the key bias shifts a softmax row by a constant
+            double sw = 0, sb = 0;
+            for (int cc = 0; cc < kE; ++cc) {
+                sw = fma((double)A.q_w[cc * kE + tid], daq[0][cc], sw);
+                sw = fma((double)A.k_w[cc * kE + tid], dak[0][cc], sw);
+                sb = fma((double)A.q_w[cc * kE + tid], dcq[0][cc], sb);
+            }
+            g[tid] = (float)sw;
+            g[kE + tid] = (float)sb;
+        }
+    }
+    {  // the temporal attention: emb_w (64, 2) 128, emb_b 64, q_w 4096, q_b 64, k_w 4096, k_b 64
+        const et_sgcn_attention &A = p.att[1];
+        float *g = grads + G.att[1];
+        float *g_eb = g + 2 * kE, *g_qw = g_eb + kE, *g_qb = g_qw + kE * kE, *g_kw = g_qb + kE, *g_kb = g_kw + kE * kE;
+        for (int q = tid; q < kE * kE; q += kSnThreads) {
+            const int cc = q / kE, e = q % kE;
+            const double wp = A.emb_w[2 * e], wc = A.emb_w[2 * e + 1];
+            g_qw[q] = (float)(daq[2][cc] * wp + daq[1][cc] * wc + dcq[1][cc] * (double)A.emb_b[e]);
+            g_kw[q] = (float)(dak[2][cc] * wp + dak[1][cc] * wc);
+        }
+        if (tid < kE) {
+            g_qb[tid] = (float)dcq[1][tid];
+            g_kb[tid] = 0.f;
+            double swp = 0, swc = 0, sb = 0;
+            for (int cc = 0; cc < kE; ++cc) {
+                swp = fma((double)A.q_w[cc * kE + tid], daq[2][cc], swp);
+                swp = fma((double)A.k_w[cc * kE + tid], dak[2][cc], swp);
+                swc = fma((double)A.q_w[cc * kE + tid], daq[1][cc], swc);
+                swc = fma((double)A.k_w[cc * kE + tid], dak[1][cc], swc);
+                sb = fma((double)A.q_w[cc * kE + tid], dcq[1][cc], sb);
+            }
+            g[2 * tid] = (float)swp;
+            g[2 * tid + 1] = (float)swc;
+            g_eb[tid] = (float)sb;
+        }
+    }
+}
+
 // ---- reduce: grads[goff + e] = the sum over the slots of part[pbase + slot * pstride + poff + e]
 struct Seg {
     int64_t goff, pbase, pstride, nslots;
@@ -945,7 +1137,7 @@ struct Seg {
 struct Segs {
     int n;
     int64_t total;  // elements over all segments
-    Seg s[2 * ET_SGCN_MAX_LAYERS + 8];
+    Seg s[2 * ET_SGCN_MAX_LAYERS + 8];  // the base's 2 layers + 6, and GP-Graph's two (et_gpgraph_train.inl)
 };
 
 __global__ __launch_bounds__(kSnThreads) void sgcn_grad_reduce(Segs sg, const float *__restrict__ ws, float *__restrict__ grads) {
@@ -997,30 +1189,30 @@ static int run_train(const et_sgcn_params &p, const float *gv, const Ident &I, c
     return ET_OK;
 }
 
-static int run_backward(const et_sgcn_params &p, const Ident &I, int64_t N, const int32_t *off, int n_scenes, int64_t sum_n2,
-                        int64_t max_n, const float *d_out, float *grads, void *workspace, size_t workspace_bytes,
-                        hipStream_t st) {
-    const int T = p.obs_len, na = p.n_asym;
-    const TLay tl = tlay_of(p, N, sum_n2, n_scenes);
-    if (!workspace || workspace_bytes < (size_t)tl.total * 4) return ET_ERR_WORKSPACE;
-    const Ctx c = train_ctx(p, tl, N, off, n_scenes, sum_n2, workspace);
-    const GLay G = glay_of(p);
+// tail_bwd .. prep_bwd on the scenes of c (GP: the 3 Sr virtual scenes; d_out (k, c.N, S)): number_asymmetric_conv_layer + 7
+// launches; and the segments of the base's gradients for the reduce launch, which the caller makes
+template <bool GP>
+static void run_backward_core(const et_sgcn_params &p, const Ident &I, const Ctx &c, const TLay &tl, const GLay &G, int64_t max_n,
+                              const float *d_out, float *grads, hipStream_t st, Segs &sg) {
+    const int T = p.obs_len, na = p.n_asym, n_scenes = c.S;
     const dim3 blk(kSnThreads);
     float *ws = c.ws;
     const float *ls = ws + tl.xs + na * tl.xs_stride, *lt = ws + tl.xt + na * tl.xt_stride;
-    hipLaunchKernelGGL(sgcn_tail_bwd, dim3((unsigned)tl.n_tail), blk, 0, st, c, tl, p, d_out);
-    hipLaunchKernelGGL(sgcn_sadj_bwd, dim3((unsigned)tl.n_rows), blk, 0, st, c, tl, p, I, ls, ws + tl.gs + na * tl.xs_stride);
+    hipLaunchKernelGGL(sgcn_tail_bwd<GP>, dim3((unsigned)tl.n_tail), blk, 0, st, c, tl, p, d_out);
+    hipLaunchKernelGGL(sgcn_sadj_bwd<GP>, dim3((unsigned)tl.n_rows), blk, 0, st, c, tl, p, I, ls, ws + tl.gs + na * tl.xs_stride);
     const unsigned by_r = chunks((int64_t)T * kH * max_n * 4, n_scenes);
-    hipLaunchKernelGGL(sgcn_sadj_f2, dim3((unsigned)n_scenes, by_r), blk, 0, st, c, tl, I, ls);
-    hipLaunchKernelGGL(sgcn_tadj_bwd, dim3((unsigned)tl.n_rows), blk, 0, st, c, tl, p, I, lt, ws + tl.gt + na * tl.xt_stride);
+    hipLaunchKernelGGL(sgcn_sadj_f2<GP>, dim3((unsigned)n_scenes, by_r), blk, 0, st, c, tl, I, ls);
+    hipLaunchKernelGGL(sgcn_tadj_bwd<GP>, dim3((unsigned)tl.n_rows), blk, 0, st, c, tl, p, I, lt, ws + tl.gt + na * tl.xt_stride);
     for (int j = na - 1; j >= 0; --j)  // d stack j + 1 -> d stack j
-        hipLaunchKernelGGL(sgcn_asym_bwd, dim3((unsigned)(tl.n_as + tl.n_at)), blk, 0, st, c, tl, p.asym_s[j], p.asym_t[j], j,
+        hipLaunchKernelGGL(sgcn_asym_bwd<GP>, dim3((unsigned)(tl.n_as + tl.n_at)), blk, 0, st, c, tl, p.asym_s[j], p.asym_t[j], j,
                            ws + tl.xs + j * tl.xs_stride, ws + tl.gs + (j + 1) * tl.xs_stride, ws + tl.gs + j * tl.xs_stride,
                            ws + tl.xt + j * tl.xt_stride, ws + tl.gt + (j + 1) * tl.xt_stride, ws + tl.gt + j * tl.xt_stride);
-    hipLaunchKernelGGL(sgcn_fuse_bwd, dim3((unsigned)tl.n_fuse), dim3(kFuseTile), 0, st, c, tl, p, ws + tl.gs);
-    hipLaunchKernelGGL(sgcn_rows_bwd, dim3((unsigned)tl.n_rows2), blk, 0, st, c, tl, ws + tl.gt);
-    hipLaunchKernelGGL(sgcn_prep_bwd, dim3(1), blk, 0, st, p, tl, ws, grads, G);
-    Segs sg;
+    hipLaunchKernelGGL(sgcn_fuse_bwd<GP>, dim3((unsigned)tl.n_fuse), dim3(kFuseTile), 0, st, c, tl, p, ws + tl.gs);
+    hipLaunchKernelGGL(sgcn_rows_bwd<GP>, dim3((unsigned)tl.n_rows2), blk, 0, st, c, tl, ws + tl.gt);
+    if constexpr (GP)
+        hipLaunchKernelGGL(sgcn_prep_bwd_gp, dim3(1), blk, 0, st, p, tl, ws, grads, G);
+    else
+        hipLaunchKernelGGL(sgcn_prep_bwd, dim3(1), blk, 0, st, p, tl, ws, grads, G);
     sg.n = 0;
     sg.total = 0;
     auto seg = [&](int64_t goff, int len, int64_t pbase, int64_t pstride, int64_t nslots, int poff) {
@@ -1037,7 +1229,17 @@ static int run_backward(const et_sgcn_params &p, const Ident &I, int64_t N, cons
     seg(G.gcn[2], kD + 1, tl.p_tadj, kD + 1, tl.n_rows, 0);
     seg(G.gcn[3], kD * kD + 1, tl.p_sadj, kSadjG, tl.n_rows, kD + 1);
     seg(G.fusion, gt_rest, tl.p_tail, tl.g_tail, tl.n_tail, kD * kD + 1);
-    hipLaunchKernelGGL(sgcn_grad_reduce, dim3((unsigned)ceil_div(sg.total, kSnThreads)), blk, 0, st, sg, ws, grads);
+}
+
+static int run_backward(const et_sgcn_params &p, const Ident &I, int64_t N, const int32_t *off, int n_scenes, int64_t sum_n2,
+                        int64_t max_n, const float *d_out, float *grads, void *workspace, size_t workspace_bytes,
+                        hipStream_t st) {
+    const TLay tl = tlay_of(p, N, sum_n2, n_scenes);
+    if (!workspace || workspace_bytes < (size_t)tl.total * 4) return ET_ERR_WORKSPACE;
+    const Ctx c = train_ctx(p, tl, N, off, n_scenes, sum_n2, workspace);
+    Segs sg;
+    run_backward_core<false>(p, I, c, tl, glay_of(p), max_n, d_out, grads, st, sg);
+    hipLaunchKernelGGL(sgcn_grad_reduce, dim3((unsigned)ceil_div(sg.total, kSnThreads)), dim3(kSnThreads), 0, st, sg, c.ws, grads);
     ET_LAUNCH_CHECK();
     return ET_OK;
 }

@@ -28,9 +28,17 @@ GP-Graph-STGCNN is the same wrapper around the original Social-STGCNN
 inputs (1, 1, T, N); a whole split runs through :func:`eigentrajectory_amd.ops.gpgraph_stgcnn_forward_scenes`.
 
 Native: the ET configuration -- ``d_type='learned_l2norm'``, ``d_th='learned'``, ``mix_type='mlp'``, ``group_type=(True,
-True, True)``, ``weight_share=True`` -- in eval mode with ``dropout = 0``, around either base.  Training and the other
-``d_type`` / ``d_th`` / ``mix_type`` / ``group_type`` / ``weight_share=False`` variants are not: they construct (with the
-reference's parameters), and their forward raises.
+True, True)``, ``weight_share=True`` -- in eval mode with ``dropout = 0``, around either base.  The other ``d_type`` /
+``d_th`` / ``mix_type`` / ``group_type`` / ``weight_share=False`` variants are not: they construct (with the reference's
+parameters), and their forward raises.  A training-mode forward raises too -- unless the instance, around an SGCN base, was
+switched by ``eigentrajectory_amd.enable_native_training(model)``: with ``dropout = 0`` the training-mode forward *is* the
+eval forward, and ``forward(v_abs, v_rel)`` then runs the same kernels on a layout that keeps what the backward pass reads
+(``et_gpgraph_sgcn_train_forward_graph``) and returns ``(v, indices)`` with ``v`` differentiable with respect to every
+parameter of the wrapper and of its base (``et_gpgraph_sgcn_backward_graph``, csrc/et_gpgraph_train.inl; ``indices`` is
+not differentiable, the grouping reaches ``v`` through the straight-through soft assignment; no input gradient: the bridge
+detaches the graph; ``key.bias`` of both attentions gets an exact zero).  The switch is the plain attribute
+``native_training`` (no parameter, no buffer, not in the ``state_dict``, default False).  GP-Graph around Social-STGCNN
+(BatchNorm batch statistics) has no native training.
 """
 from __future__ import annotations
 
@@ -72,12 +80,46 @@ class _GroupIntegrator(nn.Module):
                                                                     padding=(1, 0)))
 
 
+class _TrainForward(torch.autograd.Function):
+    """``forward(v_abs, v_rel)`` with a backward pass, as :class:`eigentrajectory_amd.sgcn._TrainForward`: every parameter of
+    the whole ``GPGraph`` is an input, in ``named_parameters`` order, and is saved with the training workspace; the kernels
+    read the weights in place, and an in-place change between forward and backward is caught by autograd's version
+    counters."""
+
+    @staticmethod
+    def forward(ctx, model, v_abs, v_rel, *params):
+        from . import ops
+        et = model.et_params()  # the pointer table once: forward and backward see the same tensors
+        ws = ops.gpgraph_sgcn_train_workspace(model, v_abs.shape[3], et_params=et)
+        out, idx = ops.gpgraph_sgcn_train_forward_graph(model, v_abs, v_rel, ws, et_params=et)
+        ctx.model, ctx.et = model, et
+        ctx.save_for_backward(ws, *params)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(idx)
+        return out, idx
+
+    @staticmethod
+    def backward(ctx, g_out, _g_idx):
+        need = ctx.needs_input_grad
+        if g_out is None:
+            return (None,) * len(need)
+        from . import ops
+        model = ctx.model
+        ws = ctx.saved_tensors[0]
+        params = ctx.saved_tensors[1:]
+        if any(p.data_ptr() != q.data_ptr() for p, q in zip(params, model.parameters())):
+            raise RuntimeError("GPGraph: a parameter tensor was replaced between forward and backward")
+        views = ops.gpgraph_sgcn_grad_views(model, ops.gpgraph_sgcn_backward_graph(model, ws, g_out, et_params=ctx.et))
+        return (None, None, None, *(g if wanted else None for g, wanted in zip(views.values(), need[3:])))
+
+
 class GPGraph(nn.Module):
     r"""model_groupwrapper.py's ``GPGraph`` (baseline/gpgraphsgcn and baseline/gpgraphstgcnn: the same class) around an
     :class:`SGCN` (``position_channel=True``) or a :class:`SocialSTGCNN` (``graph_per_time_row=True``) base (eval-mode
     inference on the GPU).  ``forward(v_abs, v_rel)`` -> ``(v (1, S, k, N), indices (N,) int64)``."""
 
     TAU = 0.1  # GroupGenerator.forward's default temperature; GPGraph.forward does not pass another
+    native_training = False  # a plain attribute, set per instance by eigentrajectory_amd.enable_native_training
 
     def __init__(self, baseline_model, in_channels=2, out_channels=5, obs_seq_len=8, pred_seq_len=12,
                  d_type="learned_l2norm", d_th="learned", mix_type="mlp", group_type=None, weight_share=True):
@@ -97,6 +139,27 @@ class GPGraph(nn.Module):
     def stgcnn_base(self):
         """True around a Social-STGCNN base (GP-Graph-STGCNN), False around an SGCN base (GP-Graph-SGCN)."""
         return isinstance(self.baseline_model, SocialSTGCNN)
+
+    def outside_native_training(self):
+        """-> None, or what puts this instance outside the family that trains natively, as text"""
+        if self.stgcnn_base:
+            return "the SocialSTGCNN base normalises with BatchNorm batch statistics in training mode"
+        for field, want in (("d_type", "learned_l2norm"), ("mix_type", "mlp"), ("weight_share", True)):
+            if getattr(self, field) != want:
+                return f"{field} = {getattr(self, field)!r} (native: {want!r})"
+        if not isinstance(self.group_gen.th, nn.Parameter):
+            return f"d_th = {self.d_th!r} (native: 'learned')"
+        if not (self.include_original and self.include_inter_group and self.include_intra_group):
+            return (f"group_type = {(self.include_original, self.include_inter_group, self.include_intra_group)} "
+                    "(native: (True, True, True))")
+        base = self.baseline_model
+        if not isinstance(base, SGCN):
+            return f"baseline_model = {type(base).__name__} (native: SGCN)"
+        for field, want in (("in_dims", 1), ("num_heads", 4), ("embedding_dims", 64), ("dropout", 0),
+                            ("position_channel", True)):
+            if getattr(base, field) != want:
+                return f"baseline_model.{field} = {getattr(base, field)} (native: {want})"
+        return None
 
     def _check_mode(self):
         base = self.baseline_model
@@ -142,6 +205,13 @@ class GPGraph(nn.Module):
         return p, dev
 
     def forward(self, v_abs, v_rel):
+        if self.training and self.native_training and self.outside_native_training() is None:
+            if v_abs.requires_grad or v_rel.requires_grad:
+                raise RuntimeError("GPGraph: no input gradient is built (the gpgraphsgcn bridge detaches the graph); an "
+                                   "input requires one")
+            dev = L.module_device("GPGraph", self)
+            v_abs, v_rel = (L.on_device(t, dev) for t in (v_abs, v_rel))
+            return _TrainForward.apply(self, v_abs, v_rel, *self.parameters())
         self._check_mode()
         from . import ops
         if self.stgcnn_base:

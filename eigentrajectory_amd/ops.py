@@ -672,6 +672,218 @@ def gpgraph_sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_detail
     return out
 
 
+# ------------------------------------------------------------------------ GP-Graph-SGCN predictor (training)
+def _gpgraph_train_params(who, model, et_params):
+    if model.stgcnn_base:
+        raise NotImplementedError(f"{who}: GP-Graph around SocialSTGCNN has no native backward pass (BatchNorm batch "
+                                  "statistics)")
+    if model.baseline_model.dropout != 0:
+        raise RuntimeError(f"{who}: dropout = {model.baseline_model.dropout} is not implemented natively; construct the base "
+                           "with dropout=0")
+    return et_params or model.et_params()
+
+
+def gpgraph_sgcn_train_workspace(model, n, sum_n2=None, n_scenes=1, et_params=None):
+    """A training workspace for ``n`` pedestrians in ``n_scenes`` scenes whose squared sizes sum to ``sum_n2`` (one scene:
+    n * n): :func:`gpgraph_sgcn_train_forward_graph` / ``_scenes`` fill it, :func:`gpgraph_sgcn_backward_graph` / ``_scenes``
+    read it."""
+    params, dev = _gpgraph_train_params("gpgraph_sgcn_train_workspace", model, et_params)
+    return _workspace("et_gpgraph_sgcn_train_workspace_bytes", dev, params, n, n * n if sum_n2 is None else sum_n2, n_scenes,
+                      required=n > 0)[0]
+
+
+def _gpgraph_details(want, T, n, sum_n2, dev):
+    gi = torch.empty((n,), device=dev, dtype=torch.int32)
+    if not want:
+        return gi, None, None, None
+    return (gi, torch.empty((sum_n2,), device=dev), torch.empty((3 * 4 * T * sum_n2,), device=dev),
+            torch.empty((3 * n * 4 * T * T,), device=dev))
+
+
+def gpgraph_sgcn_train_forward_graph(model, v_abs, v_rel, workspace, want_details=False, et_params=None):
+    """:func:`gpgraph_sgcn_forward_graph` with the kept layout (the same kernels; ``v`` and ``indices`` are bit-equal): what the
+    backward pass reads stays in ``workspace`` (of :func:`gpgraph_sgcn_train_workspace`) for
+    :func:`gpgraph_sgcn_backward_graph`."""
+    who = "gpgraph_sgcn_train_forward_graph"
+    params, dev = _gpgraph_train_params(who, model, et_params)
+    T, k, S = params.base.obs_len, params.base.pred_len, params.base.out_dims
+    n = v_abs.shape[3] if v_abs.dim() == 4 else -1
+    if tuple(v_abs.shape) != (1, 1, T, n) or tuple(v_rel.shape) != (1, 2, T, n) or n < 1:
+        raise ValueError(f"{who}: v_abs {tuple(v_abs.shape)} / v_rel {tuple(v_rel.shape)} are not (1,1,{T},N) / (1,2,{T},N), "
+                         "N >= 1")
+    _read_in_place(who, dev, {"v_abs": v_abs, "v_rel": v_rel})
+    if n > L.SGCN_MAX_N:
+        raise ValueError(f"{who}: N = {n} exceeds the {L.SGCN_MAX_N} pedestrians a scene may have")
+    _sgcn_check_ws(who, dev, workspace)
+    out = torch.empty((1, S, k, n), device=dev)
+    gi, dist, ls, lt = _gpgraph_details(want_details, T, n, n * n, dev)
+    L.call("et_gpgraph_sgcn_train_forward_graph", C.byref(params), L.ptr(v_abs.detach()), L.ptr(v_rel.detach()), n, L.ptr(out),
+           L.ptr(gi), L.ptr(dist), L.ptr(ls), L.ptr(lt), L.ptr(workspace), workspace.numel(), L.stream(dev))
+    idx = gi.long()
+    if not want_details:
+        return out, idx
+    g = int(idx.max()) + 1
+    sizes = (n, g, n)
+    det = {"dist": dist.view(n, n), "n_groups": g,
+           "logit_s": [ls[4 * T * m * n * n:4 * T * (m * n * n + sizes[m] ** 2)].view(T, 4, sizes[m], sizes[m]) for m in range(3)],
+           "logit_t": [lt[4 * T * T * m * n:4 * T * T * (m * n + sizes[m])].view(sizes[m], 4, T, T) for m in range(3)]}
+    return out, idx, det
+
+
+def _gpgraph_scene_sizes(scene_sizes, n, dev):
+    if scene_sizes is None:
+        return [n], None, 0
+    sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
+    off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
+    return sizes, off, len(sizes)
+
+
+def gpgraph_sgcn_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False, workspace=None):
+    """:func:`gpgraph_sgcn_forward_scenes` with the kept layout -> (C_pred_refine (k, N, S)[, details], workspace); the
+    workspace (made here unless given) goes to :func:`gpgraph_sgcn_backward_scenes` with the same ``scene_sizes``."""
+    who = "gpgraph_sgcn_train_forward_scenes"
+    params, dev = _gpgraph_train_params(who, model, None)
+    b = _scene_batch(who, dev, C_obs, nrm, params.base.pred_len, scene_sizes)
+    n = b.n
+    if b.off is None and n > L.SGCN_MAX_N:
+        raise ValueError(f"{who}: a scene of {n} pedestrians exceeds the {L.SGCN_MAX_N} a scene may have")
+    sum_n2 = sum(s * s for s in b.sizes if s <= L.SGCN_MAX_N)
+    out = torch.empty((params.base.pred_len, n, params.base.out_dims), device=dev)
+    if workspace is None:
+        workspace = gpgraph_sgcn_train_workspace(model, n, sum_n2, len(b.sizes), et_params=(params, dev))
+    if n:
+        _sgcn_check_ws(who, dev, workspace)
+    gi, dist, ls, lt = _gpgraph_details(want_details, params.base.obs_len, n, sum_n2, dev)
+    L.call("et_gpgraph_sgcn_train_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), n, L.ptr(b.off), b.n_scenes,
+           sum_n2, b.max_n, L.ptr(out), L.ptr(gi), L.ptr(dist), L.ptr(ls), L.ptr(lt), L.ptr(workspace),
+           workspace.numel() if workspace is not None else 0, L.stream(dev))
+    if want_details:
+        return out, {"group_index": gi, "dist": dist, "logit_s": ls, "logit_t": lt}, workspace
+    return out, workspace
+
+
+def gpgraph_sgcn_grad_views(model, grads):
+    """``grads``, the flat buffer of :func:`gpgraph_sgcn_backward_graph` / ``_scenes`` -> {state_dict key: a view of it shaped
+    like the parameter}, every parameter of the whole ``GPGraph`` (state_dict order: ``baseline_model.*``, ``group_gen.th``,
+    ``group_gen.group_cnn.0.*``, ``group_mix.st_gcns_mix.{0,1}.*``)."""
+    out, at = {}, 0
+    for name, t in model.named_parameters():
+        out[name] = grads[at:at + t.numel()].view(t.shape)
+        at += t.numel()
+    if at != grads.numel():
+        raise ValueError(f"gpgraph_sgcn_grad_views: {grads.numel()} floats for parameters of {at}")
+    return out
+
+
+def _gpgraph_grads(who, params, dev, d_out, shape):
+    if tuple(d_out.shape) != shape:
+        raise ValueError(f"{who}: d_out {tuple(d_out.shape)} is not {shape}")
+    d_out = d_out.detach()
+    if d_out.device != dev or d_out.dtype != torch.float32 or not d_out.is_contiguous():
+        d_out = d_out.to(device=dev, dtype=torch.float32).contiguous()
+    size = int(L.lib().et_gpgraph_sgcn_grad_floats(C.byref(params)))
+    if not size:
+        L.check(3, "et_gpgraph_sgcn_grad_floats")
+    return d_out, torch.empty((size,), device=dev)
+
+
+def gpgraph_sgcn_backward_graph(model, workspace, d_out, et_params=None):
+    """The backward pass of :func:`gpgraph_sgcn_train_forward_graph` in ``number_asymmetric_conv_layer + 13`` launches:
+    ``workspace`` as that call filled it (same weights), ``d_out`` (1, S, k, N) the gradient at its output -> the flat float32
+    gradient buffer (:func:`gpgraph_sgcn_grad_views` names its parts)."""
+    who = "gpgraph_sgcn_backward_graph"
+    params, dev = _gpgraph_train_params(who, model, et_params)
+    n = d_out.shape[3] if d_out.dim() == 4 else -1
+    _sgcn_check_ws(who, dev, workspace)
+    d_out, grads = _gpgraph_grads(who, params, dev, d_out, (1, params.base.out_dims, params.base.pred_len, n))
+    L.call("et_gpgraph_sgcn_backward_graph", C.byref(params), n, L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace),
+           workspace.numel(), L.stream(dev))
+    return grads
+
+
+def gpgraph_sgcn_backward_scenes(model, workspace, d_out, scene_sizes=None):
+    """The backward pass of :func:`gpgraph_sgcn_train_forward_scenes`, the same number of launches whatever the number of
+    scenes: ``workspace`` as that call filled it, ``scene_sizes`` as given to it, ``d_out`` (k, N, S) -> the flat gradient
+    buffer, summed over the scenes in ascending order."""
+    who = "gpgraph_sgcn_backward_scenes"
+    params, dev = _gpgraph_train_params(who, model, None)
+    n = d_out.shape[1] if d_out.dim() == 3 else -1
+    d_out, grads = _gpgraph_grads(who, params, dev, d_out, (params.base.pred_len, n, params.base.out_dims))
+    sizes, off, n_scenes = _gpgraph_scene_sizes(scene_sizes, n, dev)
+    if n:
+        _sgcn_check_ws(who, dev, workspace)
+    L.call("et_gpgraph_sgcn_backward_scenes", C.byref(params), n, L.ptr(off), n_scenes,
+           sum(s * s for s in sizes if s <= L.SGCN_MAX_N), max(sizes, default=0), L.ptr(d_out), L.ptr(grads), grads.numel(),
+           L.ptr(workspace), workspace.numel() if workspace is not None else 0, L.stream(dev))
+    return grads
+
+
+def gpgraph_sgcn_train_views(model, workspace, n, sum_n2=None, n_scenes=1, lo=0, sq=0, scene_n=None, scene=0):
+    """The values kept in ``workspace`` by name, as views, for scene number ``scene`` of ``scene_n`` pedestrians that starts at
+    row ``lo`` and at ``sq`` in the packed n^2 stacks (one scene: the defaults).  ``n_groups``; ``passes`` [3]: per pass (0
+    pedestrian graph, 1 group means, 2 intra-group, n_m = n, G, n) the names of :func:`sgcn_train_views` and ``vp`` (T, n_m)
+    (the position channel; ``v`` is the coefficient channel), ``out`` (k, n_m, S), and after a backward call ``d_out`` (the
+    base's upstream gradient), ``d_ax`` (T, 4, n_m), ``srec`` (T, 4, n_m, 2), ``trec`` (n_m, 4, T, 3), ``d_acc_t`` (n_m, 4, T),
+    ``dx_as`` (n_m, 4, T), ``dx`` (2, T, n_m) (passes 1 and 2).  The wrapper's: ``v_abs`` (T, n), ``f`` (8, T, n), ``dist``,
+    ``sig``, ``sn`` (sig / colsum) (n, n), ``colsum`` (n,), ``group_index`` (n,), ``group_size`` (G,), and after a backward call
+    ``d_o`` [3] x (k, n, S) (d o_m per pedestrian), ``d_vp`` (2, T, n), ``d_P``, ``d_sig``, ``d_d`` (n, n), ``d_f`` (8, T, n).  The
+    offsets are the library's (``et_gpgraph_sgcn_train_layout``)."""
+    params, _ = model.et_params()
+    bp = params.base
+    T, k, S, na, nt = bp.obs_len, bp.pred_len, bp.out_dims, bp.n_asym, bp.n_tcn
+    N, n2 = n, n * n if sum_n2 is None else sum_n2
+    m0 = N if scene_n is None else scene_n
+    f = workspace.view(torch.float32)
+    i32 = workspace.view(torch.int32)
+    o = (C.c_int64 * L.GPGRAPH_SGCN_TRAIN_LAYOUT_FIELDS)()
+    L.call("et_gpgraph_sgcn_train_layout", C.byref(params), N, n2, n_scenes, o, L.GPGRAPH_SGCN_TRAIN_LAYOUT_FIELDS)
+    (o_v, o_rs, o_rt, o_xs, xs_stride, o_xt, xt_stride, o_at, o_f2, o_f1, o_ts, o_keep, KS, o_dat, o_df1, o_dts, o_df2, o_rrec,
+     o_gs, o_gt, o_dirs, o_dirt, o_dds, o_vp, o_vn, o_gidx, o_dax, o_srec, o_trec, o_dacct, o_dxas, o_dxp, o_dxv, o_va, o_feat,
+     o_dist, o_sn, o_po, o_sig, o_cs, o_cnt, o_dmix, o_dpo, o_dvp, o_dP, o_dsig, o_dd, o_df, _) = (int(x) for x in o)
+    sl = lambda off, cnt, *shape: f[off:off + cnt].view(*shape)
+    G = int(i32[o_vn + n_scenes + scene])
+    passes = []
+    for p_, m in enumerate((m0, G, m0)):
+        r0, q0 = p_ * N + lo, p_ * n2 + sq     # the virtual scene's first row and packed offset
+        rows = lambda off: sl(off + r0 * 4 * T * T, m * 4 * T * T, m, 4, T, T)
+        feat = lambda off, *shape: sl(off + r0 * 4 * T * 16, m * 4 * T * 16, *shape)
+        dense = lambda off: sl(off + 4 * T * q0, 4 * T * m * m, T, 4, m, m)
+        keep = sl(o_keep + r0 * KS, m * KS, m, 2 * T + 2 * nt * k, 64)
+        po = lambda off: f[off:off + k * 3 * N * S].view(k, 3 * N, S)[:, r0:r0 + m]
+        passes.append({
+            "v": sl(o_v + T * r0, T * m, T, m), "vp": sl(o_vp + T * r0, T * m, T, m),
+            "stack_s": [dense(o_xs + j * xs_stride) for j in range(na + 1)],
+            "stack_t": [rows(o_xt + j * xt_stride) for j in range(na + 1)],
+            "rows_s": sl(o_rs + 2 * T * 4 * r0, 2 * T * 4 * m, T, 4, m, 2),
+            "rows_t": sl(o_rt + 2 * T * 4 * r0, 2 * T * 4 * m, m, 4, T, 2),
+            "at": rows(o_at), "f1": feat(o_f1, T, 4, m, 16), "f2": feat(o_f2, m, 4, T, 16), "ts": feat(o_ts, m, 4, T, 16),
+            "st_pre": keep[:, :T], "rep": keep[:, T:2 * T],
+            "tcn_pre": [keep[:, 2 * T + 2 * j * k:2 * T + (2 * j + 1) * k] for j in range(nt)],
+            "tcn_out": [keep[:, 2 * T + (2 * j + 1) * k:2 * T + (2 * j + 2) * k] for j in range(nt)],
+            "out": po(o_po), "d_out": po(o_dpo),
+            "d_ts": feat(o_dts, m, 4, T, 16), "d_f2": feat(o_df2, m, 4, T, 16), "d_f1": feat(o_df1, T, 4, m, 16),
+            "d_at": rows(o_dat), "d_accn": sl(o_rrec + 4 * T * r0 * 17, 4 * T * m * 17, T, 4, m, 17)[..., 1:],
+            "g_s": [dense(o_gs + j * xs_stride) for j in range(na + 1)],
+            "g_t": [rows(o_gt + j * xt_stride) for j in range(na + 1)],
+            "dir_s": dense(o_dirs), "dir_t": rows(o_dirt), "dd_s": dense(o_dds),
+            "d_ax": sl(o_dax + 4 * T * r0, 4 * T * m, T, 4, m), "srec": sl(o_srec + 8 * T * r0, 8 * T * m, T, 4, m, 2),
+            "trec": sl(o_trec + 12 * T * r0, 12 * T * m, m, 4, T, 3), "d_acc_t": sl(o_dacct + 4 * T * r0, 4 * T * m, m, 4, T),
+            "dx_as": sl(o_dxas + 4 * T * r0, 4 * T * m, m, 4, T),
+            "dx": torch.stack([sl(o_dxp + T * r0, T * m, T, m), sl(o_dxv + T * r0, T * m, T, m)]),
+        })
+    m = m0
+    dmix = f[o_dmix:o_dmix + k * 3 * N * S].view(k, 3 * N, S)
+    return {
+        "n_groups": G, "passes": passes,
+        "v_abs": sl(o_va + T * lo, T * m, T, m), "f": sl(o_feat + 8 * T * lo, 8 * T * m, 8, T, m),
+        "dist": sl(o_dist + sq, m * m, m, m), "sn": sl(o_sn + sq, m * m, m, m), "sig": sl(o_sig + sq, m * m, m, m),
+        "colsum": sl(o_cs + lo, m, m), "group_index": i32[o_gidx + lo:o_gidx + lo + m], "group_size": i32[o_cnt + lo:o_cnt + lo + G],
+        "d_o": [dmix[:, p_ * N + lo:p_ * N + lo + m] for p_ in range(3)],
+        "d_vp": sl(o_dvp + 2 * T * lo, 2 * T * m, 2, T, m), "d_P": sl(o_dP + sq, m * m, m, m),
+        "d_sig": sl(o_dsig + sq, m * m, m, m), "d_d": sl(o_dd + sq, m * m, m, m), "d_f": sl(o_df + 8 * T * lo, 8 * T * m, 8, T, m),
+    }
+
+
 # ---------------------------------------------------------------------- GP-Graph-STGCNN predictor (inference)
 def _gpgraph_stgcnn_buffers(params, want, T, n, sum_n2, n_scenes, dev):
     ws, nbytes = _workspace("et_gpgraph_stgcnn_workspace_bytes", dev, params, n, sum_n2, n_scenes, required=True)

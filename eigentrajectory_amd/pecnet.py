@@ -165,17 +165,25 @@ class PECNet(nn.Module):
 def enable_native_training(model, flag=True):
     """Let ``model``'s predictor run in training mode with a native backward pass.  ``model`` is an
     :class:`eigentrajectory_amd.EigenTrajectory` wrapper or a bare predictor: an ``LBEBM`` (its own
-    ``enable_native_training``), a ``PECNet``, a ``SocialImplicitLight`` or an ``SGCN`` of its native family (``in_dims =
-    1``, four heads, width 64, ``dropout = 0``, no position channel) (the plain attribute ``native_training``); the other
-    six predictors have no native backward pass and raise.  -> ``model``"""
+    ``enable_native_training``), a ``PECNet``, a ``SocialImplicitLight``, an ``SGCN`` of its native family (``in_dims =
+    1``, four heads, width 64, ``dropout = 0``, no position channel) or a ``GPGraph`` in the ET configuration around
+    ``SGCN(position_channel=True, dropout=0)`` (the plain attribute ``native_training``); the other five predictors have no
+    native backward pass and raise.  -> ``model``"""
+    from .gpgraph import GPGraph
     from .implicit import SocialImplicitLight
     from .lbebm import LBEBM
     from .sgcn import SGCN
-    net = getattr(model, "baseline_model", model)
+    net = model if isinstance(model, GPGraph) else getattr(model, "baseline_model", model)  # (a GPGraph has a base of its own)
     if isinstance(net, LBEBM):
         net.enable_native_training(flag)
     elif isinstance(net, (PECNet, SocialImplicitLight)):
         net.native_training = bool(flag)
+    elif isinstance(net, GPGraph) and net.outside_native_training() is None:
+        net.native_training = bool(flag)
+    elif isinstance(net, GPGraph):
+        raise NotImplementedError(f"enable_native_training: GPGraph has no native backward pass outside its native family: "
+                                  f"{net.outside_native_training()}; LBEBM, PECNet, SocialImplicitLight, SGCN and a GPGraph "
+                                  "in the ET configuration around SGCN(position_channel=True, dropout=0) train natively")
     elif isinstance(net, SGCN) and net.outside_native_training() is None:
         net.native_training = bool(flag)
     elif isinstance(net, SGCN):
@@ -185,5 +193,5 @@ def enable_native_training(model, flag=True):
                                   "train natively")
     else:
         raise NotImplementedError(f"enable_native_training: {type(net).__name__} has no native backward pass; only LBEBM, "
-                                  "PECNet, SocialImplicitLight and SGCN train natively")
+                                  "PECNet, SocialImplicitLight and SGCN, and GPGraph around SGCN, train natively")
     return model

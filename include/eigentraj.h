@@ -535,6 +535,64 @@ int et_gpgraph_sgcn_forward_scenes(const et_gpgraph_sgcn_params *params, const f
                                    float *C_pred_refine, int32_t *group_index, float *dist, float *logit_s,
                                    float *logit_t, void *workspace, size_t workspace_bytes, et_stream_t stream);
 
+/* ---- GP-Graph-SGCN predictor, training (the configuration above; dropout = 0 makes the training-mode forward the eval
+ * forward) ---------------------------------------------------------------------------------------------------------------
+ * Gradients of what et_gpgraph_sgcn_forward_graph computes with respect to every parameter of the wrapper and of its base;
+ * no gradient for v_abs / v_rel (the bridge builds them from detached tensors).  group_index is not differentiable; the
+ * grouping reaches the output through v' = (v_rel - v_soft).detach() + v_soft alone (the straight-through estimator).
+ *   et_gpgraph_sgcn_train_workspace_bytes  the training workspace: the base's (et_sgcn_train_workspace_bytes' layout for the
+ *                                          3 N virtual rows, 3 sum_n2 entries and 3 n_scenes virtual scenes of the three
+ *                                          passes), the wrapper's eval values, sig, its column sums and the group sizes, and
+ *                                          the backward's intermediate gradients and partial sums.  0: outside the family.
+ *   et_gpgraph_sgcn_train_forward_graph /  et_gpgraph_sgcn_forward_graph / _scenes with the kept layout: the same kernels, the
+ *   et_gpgraph_sgcn_train_forward_scenes   same 8 + number_asymmetric_conv_layer launches, bit-equal outputs.
+ *   et_gpgraph_sgcn_backward_graph /       d_out, laid out as the forward's output ((1,S,k,N) / (k,N,S)), and the workspace as
+ *   et_gpgraph_sgcn_backward_scenes        that forward left it (same parameters, N, scene_offsets, sum_n2) -> grads,
+ *                                          grads_floats >= et_gpgraph_sgcn_grad_floats floats, in the state_dict order of the
+ *                                          whole GPGraph: baseline_model.* as et_sgcn_backward_graph lists them (the temporal
+ *                                          attention's embedding.weight is (64, 2)), group_gen.th, group_gen.group_cnn.0.weight,
+ *                                          .bias, group_mix.st_gcns_mix.0.weight, .1.weight, .1.bias.
+ *                                          number_asymmetric_conv_layer + 13 launches for any number of scenes and any n:
+ *                                          mix_bwd, mixw_bwd, unpool, the base's number_asymmetric_conv_layer + 7 on the
+ *                                          virtual scenes, dx (the base's input gradient of passes 1 and 2), group_bwd, reduce.
+ * The order: mix (d o_m = g / 3 + (W^T g)_m (z > 0 ? 1 : a)), unpool (a group's row: its members' d o_1, ascending), the
+ * base's backward of the three virtual scenes (weight gradients: chunks ascending, then virtual scenes ascending), its input
+ * gradient for passes 1 and 2, pool (d v' = d v'_intra + d pooled[group] / |group|), straight-through (d v_soft = d v'),
+ * d P[i][j] = sum_{c,t} v_rel[c,t,i] d v_soft[c,t,j], d sig = (d P - sum_i' P d P) / colsum, d u = d sig sig (1 - sig),
+ * d d = -d u / tau, d th = sum d u / tau, d f_i = sum_j (d d[i][j] + d d[j][i]) / T (f_i - f_j) / |f_i - f_j| (0 where the norm
+ * is 0: the diagonal and coincident pedestrians), and group_cnn's weight and bias from d f.
+ * A scene that the forward does not compute contributes nothing.  key.bias of both attentions gets an exact +0.0.  No
+ * atomics: the base's partial sums as above; d (mix_a, mix_w, mix_b) per chunk of ET_GPGRAPH_BWD_ROWS pedestrians (rows
+ * ascending), then the chunks ascending; d (th, group_cnn) per scene (a lane's items ascending, the lanes by a fixed
+ * butterfly, the wavefronts ascending), then the scenes ascending.  Bit-identical from run to run. */
+#define ET_GPGRAPH_BWD_ROWS 64
+size_t et_gpgraph_sgcn_train_workspace_bytes(const et_gpgraph_sgcn_params *params, int64_t N, int64_t sum_n2, int n_scenes);
+int64_t et_gpgraph_sgcn_grad_floats(const et_gpgraph_sgcn_params *params);
+/* where the training workspace keeps what (host only, no launch), in floats from its start.  The first 23 fields are
+ * et_sgcn_train_layout's without its total, for the virtual rows (pass m of a scene at rows m N + off[s], at m sum_n2 + its
+ * packed offset in the n^2 stacks); then the position channel (T, 3 N), the virtual scenes' node counts (int32), the group
+ * index (int32 N), per spatial row d (A_s x), per spatial row (sum dense d dense, d t_i), per temporal row (sum dense d
+ * dense, d a, d b), per temporal row d (A_t x), A_s^T d (A_s x) (n,4,T), the input gradient's position and coefficient
+ * channel (T, n_m blocks at T x the virtual row); then the wrapper's: v_abs, f = group_cnn(v_abs) (8,T,n at 8 T off[s]),
+ * dist, sig / colsum, the passes' outputs (k, 3 N, S), sig, its column sums, the group sizes (int32), d o_m per pedestrian
+ * (k, 3 N, S), the base's upstream gradient (k, 3 N, S; pass 1 pooled), d v' (2,T,n at 2 T off[s]), d P, d sig, d d (n,n at
+ * the packed offset), d f (8,T,n), the total. */
+#define ET_GPGRAPH_SGCN_TRAIN_LAYOUT_FIELDS 49
+int et_gpgraph_sgcn_train_layout(const et_gpgraph_sgcn_params *params, int64_t N, int64_t sum_n2, int n_scenes,
+                                 int64_t *offsets, int n_offsets);
+int et_gpgraph_sgcn_train_forward_scenes(const et_gpgraph_sgcn_params *params, const float *C_obs, const float *nrm, int64_t N,
+                                         const int32_t *scene_offsets, int n_scenes, int64_t sum_n2, int64_t max_scene_n,
+                                         float *C_pred_refine, int32_t *group_index, float *dist, float *logit_s,
+                                         float *logit_t, void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_gpgraph_sgcn_train_forward_graph(const et_gpgraph_sgcn_params *params, const float *v_abs, const float *v_rel,
+                                        int64_t N, float *out, int32_t *group_index, float *dist, float *logit_s,
+                                        float *logit_t, void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_gpgraph_sgcn_backward_scenes(const et_gpgraph_sgcn_params *params, int64_t N, const int32_t *scene_offsets,
+                                    int n_scenes, int64_t sum_n2, int64_t max_scene_n, const float *d_out, float *grads,
+                                    int64_t grads_floats, void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_gpgraph_sgcn_backward_graph(const et_gpgraph_sgcn_params *params, int64_t N, const float *d_out, float *grads,
+                                   int64_t grads_floats, void *workspace, size_t workspace_bytes, et_stream_t stream);
+
 /* ---- GP-Graph-STGCNN predictor, inference (baseline/gpgraphstgcnn: bridge.py pre-hook + GPGraph.forward around the
  * social_stgcnn of model_baseline.py + post-hook) ------------------------------------------------------------------------
  * The ET configuration, as for GP-Graph-SGCN; group_w .. mix_b as there.  `base` is the Social-STGCNN table above with ONE
