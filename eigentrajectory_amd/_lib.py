@@ -94,6 +94,14 @@ SIGNATURES = {
     "et_sgcn_train_forward_graph": (_I, [_P, _P, _P, _I, _P, _I, _I64, _P, _P, _P, _P, _Z, _P]),
     "et_sgcn_backward_scenes": (_I, [_P, _I64, _P, _I, _I64, _I64, _P, _P, _I64, _P, _Z, _P]),
     "et_sgcn_backward_graph": (_I, [_P, _P, _I, _P, _I, _I64, _P, _P, _I64, _P, _Z, _P]),
+    # ---- Social-STGCNN predictor, training
+    "et_stgcnn_train_workspace_bytes": (_Z, [_P, _I64, _I]),
+    "et_stgcnn_grad_floats": (_I64, [_P]),
+    "et_stgcnn_train_layout": (_I, [_P, _I64, _I, _P, _I]),
+    "et_stgcnn_train_forward_scenes": (_I, [_P, _P, _P, _P, _I64, _P, _I, _P, _P, _Z, _P]),
+    "et_stgcnn_train_forward_graph": (_I, [_P, _P, _P, _P, _I64, _P, _P, _Z, _P]),
+    "et_stgcnn_backward_scenes": (_I, [_P, _I64, _P, _I, _P, _P, _I64, _P, _Z, _P]),
+    "et_stgcnn_backward_graph": (_I, [_P, _I64, _P, _P, _I64, _P, _Z, _P]),
     # ---- GP-Graph-SGCN predictor, inference
     "et_gpgraph_sgcn_workspace_bytes": (_Z, [_P, _I64, _I64, _I]),
     "et_gpgraph_sgcn_forward_graph": (_I, [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _Z, _P]),
@@ -238,6 +246,17 @@ class STGCNNParams(C.Structure):
                 ("st_gcns", STGCNNLayer * STGCNN_MAX_LAYERS), ("tpcnn_w", C.c_void_p * STGCNN_MAX_LAYERS),
                 ("tpcnn_b", C.c_void_p * STGCNN_MAX_LAYERS), ("prelus", C.c_void_p * STGCNN_MAX_LAYERS),
                 ("out_w", C.c_void_p), ("out_b", C.c_void_p)]
+
+
+STGCNN_TRAIN_LAYOUT_FIELDS = 26  # ET_STGCNN_TRAIN_LAYOUT_FIELDS
+
+
+class STGCNNTrain(C.Structure):
+    """Mirror of ``et_stgcnn_train``: what training adds to ``et_stgcnn_params`` -- the BatchNorm momentum, the writable
+    running statistics of st_gcns.0's three BatchNorms and their num_batches_tracked (int64)."""
+    _fields_ = [("momentum", C.c_float)] + [(name, C.c_void_p) for name in (
+        "bn1_mean", "bn1_var", "bn2_mean", "bn2_var", "res_bn_mean", "res_bn_var", "bn1_batches", "bn2_batches",
+        "res_bn_batches")]
 
 
 SGCN_MAX_LAYERS = 8  # ET_SGCN_MAX_LAYERS

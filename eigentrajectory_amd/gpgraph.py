@@ -38,7 +38,8 @@ parameter of the wrapper and of its base (``et_gpgraph_sgcn_backward_graph``, cs
 not differentiable, the grouping reaches ``v`` through the straight-through soft assignment; no input gradient: the bridge
 detaches the graph; ``key.bias`` of both attentions gets an exact zero).  The switch is the plain attribute
 ``native_training`` (no parameter, no buffer, not in the ``state_dict``, default False).  GP-Graph around Social-STGCNN
-(BatchNorm batch statistics) has no native training.
+has no native training: its per-time-row base (BatchNorm batch statistics in training mode) has no native backward, unlike the
+stand-alone ``SocialSTGCNN`` of ET-STGCNN.
 """
 from __future__ import annotations
 
@@ -143,7 +144,8 @@ class GPGraph(nn.Module):
     def outside_native_training(self):
         """-> None, or what puts this instance outside the family that trains natively, as text"""
         if self.stgcnn_base:
-            return "the SocialSTGCNN base normalises with BatchNorm batch statistics in training mode"
+            return ("the per-time-row SocialSTGCNN base (graph_per_time_row=True, BatchNorm batch statistics in training "
+                    "mode) has no native backward; only the stand-alone SocialSTGCNN of ET-STGCNN trains natively")
         for field, want in (("d_type", "learned_l2norm"), ("mix_type", "mlp"), ("weight_share", True)):
             if getattr(self, field) != want:
                 return f"{field} = {getattr(self, field)!r} (native: {want!r})"

@@ -9,6 +9,7 @@ device first; without a HIP device every function raises (no CPU fallback).
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import NamedTuple
 
 import torch
@@ -363,6 +364,160 @@ def stgcnn_forward_scenes(model, C_obs, nrm, scene_sizes=None):
     return out
 
 
+# ------------------------------------------------------------------------ Social-STGCNN predictor (training)
+def _stgcnn_train_params(who, model, et_params):
+    why = model.outside_native_training()
+    if why is not None:
+        raise NotImplementedError(f"{who}: SocialSTGCNN has no native backward pass outside its native family: {why}")
+    return et_params or model.et_params()
+
+
+def stgcnn_train_workspace(model, n, n_scenes=1, et_params=None):
+    """A training workspace for ``n`` pedestrians in ``n_scenes`` scenes: :func:`stgcnn_train_forward_graph` / ``_scenes``
+    fill it, :func:`stgcnn_backward_graph` / ``_scenes`` read it."""
+    params, dev = _stgcnn_train_params("stgcnn_train_workspace", model, et_params)
+    return _workspace("et_stgcnn_train_workspace_bytes", dev, params, n, max(n_scenes, 1), required=n > 0)[0]
+
+
+def _stgcnn_check_ws(who, dev, workspace):
+    if workspace is None or workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError(f"{who}: workspace is not a contiguous uint8 tensor on {dev} (stgcnn_train_workspace makes one)")
+
+
+def stgcnn_train_forward_graph(model, v, a, workspace, et_params=None):
+    """``model`` in training mode on one scene as the stgcnn bridge hands it over: v (1, 1, K, N), a (K, N, N) -> the raw
+    output (1, S, k, N).  The three BatchNorms use the scene's batch statistics, and their running statistics and
+    ``num_batches_tracked`` are updated in place; every intermediate stays in ``workspace`` (of
+    :func:`stgcnn_train_workspace`) for :func:`stgcnn_backward_graph`.  Two launches."""
+    params, dev = _stgcnn_train_params("stgcnn_train_forward_graph", model, et_params)
+    K, k, S = params.seq_len, params.pred_seq_len, params.output_feat
+    n = v.shape[-1]
+    if tuple(v.shape) != (1, 1, K, n) or tuple(a.shape) != (K, n, n):
+        raise ValueError(f"stgcnn_train_forward_graph: v {tuple(v.shape)} / a {tuple(a.shape)} are not (1,1,{K},N) / "
+                         f"({K},N,N)")
+    v, a = _dev_args(dev, v.detach(), a.detach())
+    out = torch.empty((1, S, k, n), device=dev)
+    if n:
+        _stgcnn_check_ws("stgcnn_train_forward_graph", dev, workspace)
+    train = model.et_train_state()
+    L.call("et_stgcnn_train_forward_graph", C.byref(params), C.byref(train), L.ptr(v), L.ptr(a), n, L.ptr(out),
+           L.ptr(workspace), workspace.numel() if workspace is not None else 0, L.stream(dev))
+    return out
+
+
+def stgcnn_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, workspace=None):
+    """The stgcnn bridge + ``model`` in training mode + the post-hook for every scene of a batch in two launches, one
+    workgroup per scene: each scene is normalised with its own batch statistics, and the running statistics end as after
+    consecutive single-scene calls in row order (an empty scene is no batch).  C_obs, nrm and ``scene_sizes`` as
+    :func:`stgcnn_forward_scenes` -> (C_pred_refine (k, N, S), workspace); the workspace (made here unless given) goes to
+    :func:`stgcnn_backward_scenes` with the same ``scene_sizes``."""
+    params, dev = _stgcnn_train_params("stgcnn_train_forward_scenes", model, None)
+    b = _scene_batch("stgcnn_train_forward_scenes", dev, C_obs, nrm, params.pred_seq_len, scene_sizes)
+    if workspace is None:
+        workspace = stgcnn_train_workspace(model, b.n, len(b.sizes), et_params=(params, dev))
+    if b.n:
+        _stgcnn_check_ws("stgcnn_train_forward_scenes", dev, workspace)
+    out = torch.empty((params.pred_seq_len, b.n, params.output_feat), device=dev)
+    train = model.et_train_state()
+    L.call("et_stgcnn_train_forward_scenes", C.byref(params), C.byref(train), L.ptr(b.C_obs), L.ptr(b.nrm), b.n, L.ptr(b.off),
+           b.n_scenes, L.ptr(out), L.ptr(workspace), workspace.numel() if workspace is not None else 0, L.stream(dev))
+    return out, workspace
+
+
+def stgcnn_grad_views(model, grads):
+    """``grads``, the flat buffer of :func:`stgcnn_backward_graph` / ``_scenes`` -> {state_dict key: a view of it shaped like
+    the parameter}, every parameter of ``model`` (state_dict order; the unused tail ``tpcnns[n_txpcnn-1]`` /
+    ``prelus[n_txpcnn-1]`` holds exact zeros)."""
+    out, at = {}, 0
+    for name, t in model.named_parameters():
+        out[name] = grads[at:at + t.numel()].view(t.shape)
+        at += t.numel()
+    if at != grads.numel():
+        raise ValueError(f"stgcnn_grad_views: {grads.numel()} floats for parameters of {at}")
+    return out
+
+
+def _stgcnn_grads(who, params, dev, d_out, shape):
+    if tuple(d_out.shape) != shape:
+        raise ValueError(f"{who}: d_out {tuple(d_out.shape)} is not {shape}")
+    d_out = d_out.detach()
+    if d_out.device != dev or d_out.dtype != torch.float32 or not d_out.is_contiguous():
+        d_out = d_out.to(device=dev, dtype=torch.float32).contiguous()
+    size = int(L.lib().et_stgcnn_grad_floats(C.byref(params)))
+    if not size:
+        L.check(3, "et_stgcnn_grad_floats")
+    return d_out, torch.empty((size,), device=dev)
+
+
+def stgcnn_backward_graph(model, workspace, d_out, et_params=None):
+    """The backward pass of :func:`stgcnn_train_forward_graph` in two launches: ``workspace`` as that call filled it (same
+    weights), ``d_out`` (1, S, k, N) the gradient at its output -> the flat float32 gradient buffer
+    (:func:`stgcnn_grad_views` names its parts)."""
+    params, dev = _stgcnn_train_params("stgcnn_backward_graph", model, et_params)
+    n = d_out.shape[-1] if d_out.dim() == 4 else -1
+    d_out, grads = _stgcnn_grads("stgcnn_backward_graph", params, dev, d_out, (1, params.output_feat, params.pred_seq_len, n))
+    if n:
+        _stgcnn_check_ws("stgcnn_backward_graph", dev, workspace)
+    L.call("et_stgcnn_backward_graph", C.byref(params), n, L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace),
+           workspace.numel() if workspace is not None else 0, L.stream(dev))
+    return grads
+
+
+def stgcnn_backward_scenes(model, workspace, d_out, scene_sizes=None):
+    """The backward pass of :func:`stgcnn_train_forward_scenes` in two launches whatever the number of scenes:
+    ``workspace`` as that call filled it, ``scene_sizes`` as given to it, ``d_out`` (k, N, S) -> the flat gradient buffer,
+    summed over the scenes in ascending order."""
+    params, dev = _stgcnn_train_params("stgcnn_backward_scenes", model, None)
+    n = d_out.shape[1] if d_out.dim() == 3 else -1
+    d_out, grads = _stgcnn_grads("stgcnn_backward_scenes", params, dev, d_out, (params.pred_seq_len, n, params.output_feat))
+    if scene_sizes is None:
+        off, n_scenes = None, 0
+    else:
+        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
+        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
+        n_scenes = len(sizes)
+    if n:
+        _stgcnn_check_ws("stgcnn_backward_scenes", dev, workspace)
+    L.call("et_stgcnn_backward_scenes", C.byref(params), n, L.ptr(off), n_scenes, L.ptr(d_out), L.ptr(grads), grads.numel(),
+           L.ptr(workspace), workspace.numel() if workspace is not None else 0, L.stream(dev))
+    return grads
+
+
+def stgcnn_train_views(model, workspace, n, n_scenes=1, lo=0, scene=0, scene_n=None):
+    """The values kept in ``workspace`` by name, as views, for scene number ``scene`` of ``scene_n`` pedestrians that starts
+    at row ``lo`` (one scene: the defaults).  Forward: ``u`` (K, n), ``d`` (K, n) (scenes form), ``P`` (K, K + 1, n) (the
+    contraction rows, the ones row last), ``g`` (the gcn output), ``a1`` / ``y`` (tcn.1's input and output), ``t`` (tcn.2's
+    output), ``r`` (residual.0's output), ``s`` (the pre-residual sum, the block PReLU's input), ``x`` -- (S, K, n) each --
+    ``tp_pre`` / ``tp_out`` [applied tpcnns] x (k, S, n), and ``stats`` (3, 5, S): per BatchNorm (tcn.0, tcn.3, residual.1)
+    mean, biased variance, 1/sqrt(var + eps) and, after a backward call, mean(dy), mean(dy x^).  After a backward call also
+    ``d_fin`` (k, S, n), ``d_tp_pre`` / ``d_tp_out``, ``d_x``, ``d_s``, ``d_t``, ``d_r``, ``d_y``, ``d_a1``, ``d_g`` and
+    ``partial``, the scene's own flat gradient.  The offsets are the library's (``et_stgcnn_train_layout``)."""
+    params, _ = model.et_params()
+    K, k, S = params.seq_len, params.pred_seq_len, params.output_feat
+    m = n if scene_n is None else scene_n
+    f = workspace.view(torch.float32)
+    o = (C.c_int64 * L.STGCNN_TRAIN_LAYOUT_FIELDS)()
+    L.call("et_stgcnn_train_layout", C.byref(params), n, n_scenes, o, L.STGCNN_TRAIN_LAYOUT_FIELDS)
+    o = [int(x) for x in o]
+    (o_u, o_d, o_p, o_g, o_a1, o_y, o_t, o_r, o_s, o_x, o_tp, o_dfin, o_dtp, o_dx, o_ds, o_dt, o_dr, o_dy, o_da1, o_dg, per,
+     o_stats, stat_stride, o_part, G, _) = o
+    base = lo * per
+    fld = lambda off, *shape: f[base + off * m:base + off * m + math.prod(shape) * m].view(*shape, m)
+    A = max(1, params.n_txpcnn - 1)
+    views = {"u": fld(o_u, K), "d": fld(o_d, K), "P": fld(o_p, K, K + 1)}
+    for name, off in (("g", o_g), ("a1", o_a1), ("y", o_y), ("t", o_t), ("r", o_r), ("s", o_s), ("x", o_x), ("d_x", o_dx),
+                      ("d_s", o_ds), ("d_t", o_dt), ("d_r", o_dr), ("d_y", o_dy), ("d_a1", o_da1), ("d_g", o_dg)):
+        views[name] = fld(off, S, K)
+    views["tp_pre"] = [fld(o_tp + 2 * j * k * S, k, S) for j in range(A)]
+    views["tp_out"] = [fld(o_tp + (2 * j + 1) * k * S, k, S) for j in range(A)]
+    views["d_tp_pre"] = [fld(o_dtp + 2 * j * k * S, k, S) for j in range(A)]
+    views["d_tp_out"] = [fld(o_dtp + (2 * j + 1) * k * S, k, S) for j in range(A)]
+    views["d_fin"] = fld(o_dfin, k, S)
+    views["stats"] = f[o_stats + scene * stat_stride:o_stats + (scene + 1) * stat_stride].view(3, 5, S)
+    views["partial"] = f[o_part + scene * G:o_part + (scene + 1) * G]
+    return views
+
+
 # ------------------------------------------------------------------------------ SGCN predictor (inference)
 def _sgcn_logits(want, T, n, sum_n2, dev):
     if not want:
@@ -675,8 +830,8 @@ def gpgraph_sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_detail
 # ------------------------------------------------------------------------ GP-Graph-SGCN predictor (training)
 def _gpgraph_train_params(who, model, et_params):
     if model.stgcnn_base:
-        raise NotImplementedError(f"{who}: GP-Graph around SocialSTGCNN has no native backward pass (BatchNorm batch "
-                                  "statistics)")
+        raise NotImplementedError(f"{who}: GP-Graph around SocialSTGCNN has no native backward pass (its per-time-row "
+                                  "base with BatchNorm batch statistics has none)")
     if model.baseline_model.dropout != 0:
         raise RuntimeError(f"{who}: dropout = {model.baseline_model.dropout} is not implemented natively; construct the base "
                            "with dropout=0")

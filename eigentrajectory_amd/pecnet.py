@@ -167,12 +167,15 @@ def enable_native_training(model, flag=True):
     :class:`eigentrajectory_amd.EigenTrajectory` wrapper or a bare predictor: an ``LBEBM`` (its own
     ``enable_native_training``), a ``PECNet``, a ``SocialImplicitLight``, an ``SGCN`` of its native family (``in_dims =
     1``, four heads, width 64, ``dropout = 0``, no position channel) or a ``GPGraph`` in the ET configuration around
-    ``SGCN(position_channel=True, dropout=0)`` (the plain attribute ``native_training``); the other five predictors have no
-    native backward pass and raise.  -> ``model``"""
+    ``SGCN(position_channel=True, dropout=0)``, or a ``SocialSTGCNN`` of its native family (``n_stgcnn = 1``, no per-time-row
+    graph, affine BatchNorms that track running statistics with one float momentum, no dropout; its training-mode forward
+    uses BatchNorm batch statistics and updates the running ones) (the plain attribute ``native_training``); the other four
+    predictors have no native backward pass and raise.  -> ``model``"""
     from .gpgraph import GPGraph
     from .implicit import SocialImplicitLight
     from .lbebm import LBEBM
     from .sgcn import SGCN
+    from .stgcnn import SocialSTGCNN
     net = model if isinstance(model, GPGraph) else getattr(model, "baseline_model", model)  # (a GPGraph has a base of its own)
     if isinstance(net, LBEBM):
         net.enable_native_training(flag)
@@ -191,7 +194,14 @@ def enable_native_training(model, flag=True):
                                   f"{net.outside_native_training()}; LBEBM, PECNet, SocialImplicitLight and an SGCN with "
                                   "in_dims = 1, num_heads = 4, embedding_dims = 64, dropout = 0 and no position channel "
                                   "train natively")
+    elif isinstance(net, SocialSTGCNN) and net.outside_native_training() is None:
+        net.native_training = bool(flag)
+    elif isinstance(net, SocialSTGCNN):
+        raise NotImplementedError(f"enable_native_training: SocialSTGCNN has no native backward pass outside its native "
+                                  f"family: {net.outside_native_training()}; LBEBM, PECNet, SocialImplicitLight, SGCN and a "
+                                  "SocialSTGCNN with n_stgcnn = 1 and graph_per_time_row = False train natively")
     else:
         raise NotImplementedError(f"enable_native_training: {type(net).__name__} has no native backward pass; only LBEBM, "
-                                  "PECNet, SocialImplicitLight and SGCN, and GPGraph around SGCN, train natively")
+                                  "PECNet, SocialImplicitLight, SGCN and SocialSTGCNN, and GPGraph around SGCN, train "
+                                  "natively")
     return model

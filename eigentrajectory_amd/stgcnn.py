@@ -11,9 +11,21 @@ Same constructor signature and the same sub-module / parameter / buffer names as
 
 ``forward(v, a)`` in eval mode is ONE launch of ``et_stgcnn_forward_graph`` (csrc/et_stgcnn.hip): BatchNorm uses its
 running statistics, dropout is off, the weights are read in place from this module's tensors (a ``load_state_dict``, a
-``.to()`` or an in-place edit is seen by the next call, and by a captured graph's next replay).  Training (batch
-statistics, the backward pass) is not implemented natively: a forward in training mode raises.  A whole split runs as one
+``.to()`` or an in-place edit is seen by the next call, and by a captured graph's next replay).  A whole split runs as one
 launch through :meth:`EigenTrajectory.evaluate_split` / :func:`eigentrajectory_amd.ops.stgcnn_forward_scenes`.
+A forward in training mode raises -- unless the instance was switched by
+``eigentrajectory_amd.enable_native_training(model)``.  Then a training-mode ``forward(v, a)`` is
+``et_stgcnn_train_forward_graph`` (csrc/et_stgcnn_train.hip, two launches), which is NOT the eval forward: ``tcn.0``,
+``tcn.3`` and ``residual.1`` normalise with the scene's batch statistics (mean and biased variance per channel over the K N
+values) and update ``running_mean`` / ``running_var`` / ``num_batches_tracked`` as torch does, in the forward, whether or
+not a backward follows.  The output is differentiable with respect to every parameter (``et_stgcnn_backward_graph``, two
+launches; no input gradient: the stgcnn bridge detaches v).  ``tcn.2.bias`` and ``residual.0.bias`` feed a BatchNorm
+directly and get an exact zero; ``tpcnns[n_txpcnn-1]`` / ``prelus[n_txpcnn-1]``, which the forward never reads when
+``n_txpcnn >= 2``, keep ``.grad = None`` as in the reference.  The switch is the plain attribute ``native_training`` (no
+parameter, no buffer, not in the ``state_dict``, default False).  Trained natively: the family below with ``n_stgcnn = 1``
+(the only depth the reference constructs; deeper stacks would send a gradient through the Laplacian contraction),
+``graph_per_time_row=False``, affine BatchNorms that track running statistics with one float momentum and one eps, and
+``tcn[4].p = 0``.
 Supported family: ``input_feat = 1``, ``kernel_size = 3``, ``seq_len = pred_seq_len + 2``, ``1 <= output_feat <= 64``,
 ``pred_seq_len <= 32``, ``1 <= n_stgcnn, n_txpcnn <= 8``; other shapes construct, but their forward raises.
 
@@ -24,6 +36,7 @@ only as the three passes of GPGraphSTGCNN's call; its own forward raises.
 """
 from __future__ import annotations
 
+import torch
 import torch.nn as nn
 
 from . import _lib as L
@@ -57,9 +70,46 @@ class _STGCNBlock(nn.Module):
         self.prelu = nn.PReLU()
 
 
+class _TrainForward(torch.autograd.Function):
+    """``forward(v, a)`` in training mode with a backward pass.  Every parameter is an input, in ``named_parameters`` order,
+    so autograd routes the gradients into ``.grad``; they are saved through ``save_for_backward`` with the training
+    workspace: the kernels read the weights in place, and an in-place change between forward and backward (an optimiser
+    step) is caught by autograd's version counters."""
+
+    @staticmethod
+    def forward(ctx, model, v, a, *params):
+        from . import ops
+        et = model.et_params()  # the pointer table once: forward and backward see the same tensors
+        ws = ops.stgcnn_train_workspace(model, v.shape[-1], et_params=et)
+        out = ops.stgcnn_train_forward_graph(model, v, a, ws, et_params=et)
+        ctx.model, ctx.et = model, et
+        ctx.save_for_backward(*params) if ws is None else ctx.save_for_backward(ws, *params)
+        ctx.has_ws = ws is not None
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        need = ctx.needs_input_grad
+        if g_out is None:
+            return (None,) * len(need)
+        from . import ops
+        model = ctx.model
+        ws = ctx.saved_tensors[0] if ctx.has_ws else None
+        params = ctx.saved_tensors[1 if ctx.has_ws else 0:]
+        if any(p.data_ptr() != q.data_ptr() for p, q in zip(params, model.parameters())):
+            raise RuntimeError("SocialSTGCNN: a parameter tensor was replaced between forward and backward")
+        views = ops.stgcnn_grad_views(model, ops.stgcnn_backward_graph(model, ws, g_out, et_params=ctx.et))
+        unused = model.unused_parameter_names()
+        return (None, None, None, *(g if wanted and name not in unused else None
+                                    for (name, g), wanted in zip(views.items(), need[3:])))
+
+
 class SocialSTGCNN(nn.Module):
     r"""baseline/stgcnn/model.py's ``social_stgcnn`` (eval-mode inference on the GPU).  ``forward(v, a)``: v (1, 1, K, N),
     a (K, N, N) as the stgcnn bridge's pre-hook builds them -> (1, S, k, N), the raw output the post-hook permutes."""
+
+    native_training = False  # a plain attribute, set per instance by eigentrajectory_amd.enable_native_training
 
     def __init__(self, n_stgcnn=1, n_txpcnn=1, input_feat=2, output_feat=5, seq_len=8, pred_seq_len=12, kernel_size=3,
                  graph_per_time_row=False):
@@ -111,7 +161,64 @@ class SocialSTGCNN(nn.Module):
         p.out_w, p.out_b = _p(self.tpcnn_ouput.weight), _p(self.tpcnn_ouput.bias)
         return p, dev
 
+    def outside_native_training(self):
+        """-> None, or the field that puts this instance outside the family that trains natively, as text"""
+        if self.graph_per_time_row:
+            return "graph_per_time_row = True (native: False; the per-time-row base of GPGraphSTGCNN has no native backward)"
+        if self.n_stgcnn != 1:
+            return (f"n_stgcnn = {self.n_stgcnn} (native: 1; deeper stacks send a gradient through the Laplacian "
+                    "contraction and are out of scope)")
+        for field, want in (("input_feat", 1), ("kernel_size", 3), ("seq_len", self.pred_seq_len + 2)):
+            if getattr(self, field) != want:
+                return f"{field} = {getattr(self, field)} (native: {want})"
+        for field, hi in (("n_txpcnn", L.STGCNN_MAX_LAYERS), ("output_feat", 64), ("pred_seq_len", L.MAX_K)):
+            if not 1 <= getattr(self, field) <= hi:
+                return f"{field} = {getattr(self, field)} (native: 1 to {hi})"
+        blk = self.st_gcns[0]
+        bns = {"tcn.0": blk.tcn[0], "tcn.3": blk.tcn[3]}
+        if blk.residual is not None:
+            bns["residual.1"] = blk.residual[1]
+        for name, m in bns.items():
+            if not isinstance(m, nn.BatchNorm2d):
+                return f"st_gcns.0.{name} is {type(m).__name__} (native: BatchNorm2d)"
+            if not m.affine or m.weight is None:
+                return f"st_gcns.0.{name}.affine = False (native: True)"
+            if not m.track_running_stats or m.running_mean is None:
+                return f"st_gcns.0.{name}.track_running_stats = False (native: True)"
+            if not isinstance(m.momentum, float):
+                return f"st_gcns.0.{name}.momentum = {m.momentum} (native: a float)"
+        for field in ("momentum", "eps"):
+            if len({float(getattr(m, field)) for m in bns.values()}) != 1:
+                return f"BatchNorm {field} differs between {', '.join(bns)} (native: one {field})"
+        if getattr(blk.tcn[4], "p", 0) != 0:
+            return f"st_gcns.0.tcn.4.p = {blk.tcn[4].p} (native: 0)"
+        return None
+
+    def unused_parameter_names(self):
+        """the parameters the forward never reads (model.py:140: the last tpcnn / PReLU pair when n_txpcnn >= 2)"""
+        j = self.n_txpcnn - 1
+        return {f"tpcnns.{j}.weight", f"tpcnns.{j}.bias", f"prelus.{j}.weight"} if j >= 1 else set()
+
+    def et_train_state(self):
+        """-> et_stgcnn_train: the momentum, the writable running statistics and num_batches_tracked of st_gcns.0"""
+        t = L.STGCNNTrain()
+        blk = self.st_gcns[0]
+        t.momentum = float(blk.tcn[0].momentum)
+        for name, m in (("bn1", blk.tcn[0]), ("bn2", blk.tcn[3]), ("res_bn", None if blk.residual is None else blk.residual[1])):
+            if m is not None:
+                setattr(t, name + "_mean", _p(m.running_mean))
+                setattr(t, name + "_var", _p(m.running_var))
+                setattr(t, name + "_batches", m.num_batches_tracked.data_ptr())
+        return t
+
     def forward(self, v, a):
+        if self.training and self.native_training and self.outside_native_training() is None:
+            if v.requires_grad or a.requires_grad:
+                raise RuntimeError("SocialSTGCNN: no input gradient is built (the stgcnn bridge detaches v); an input "
+                                   "requires one")
+            dev = L.module_device("SocialSTGCNN", self, buffers=True)
+            v, a = (L.on_device(t, dev) for t in (v, a))
+            return _TrainForward.apply(self, v, a, *self.parameters())
         if self.training:
             raise RuntimeError("SocialSTGCNN: only inference is native (BatchNorm running statistics, no dropout); "
                                "training-mode forward and backward are not implemented -- call .eval() first")

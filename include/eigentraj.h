@@ -489,6 +489,68 @@ int et_sgcn_backward_graph(const et_sgcn_params *params, const float *identity_s
                            int id_t_t, int64_t N, const float *d_out, float *grads, int64_t grads_floats, void *workspace,
                            size_t workspace_bytes, et_stream_t stream);
 
+/* ---- Social-STGCNN predictor, training (the inference family above with n_stgcnn = 1; anything else: ET_ERR_UNSUPPORTED;
+ * deeper stacks would send a gradient through the Laplacian contraction and are out of scope) -------------------------------
+ * The training-mode forward is NOT the eval forward: st_gcns.0.tcn.0, .tcn.3 and .residual.1 (the last only when
+ * output_feat != 1; at output_feat = 1 the residual is the identity) normalise with the statistics of the scene -- mean and
+ * biased variance per channel over its K n values -- and update their running statistics as torch does:
+ * running_mean = (1 - m) running_mean + m mean, running_var = (1 - m) running_var + m var cnt / (cnt - 1), cnt = K n,
+ * num_batches_tracked += 1, per scene, the scenes in ascending order (an empty scene is no batch), whether or not a backward
+ * call follows.  et_stgcnn_params' running statistics are not read.  et_stgcnn_train carries what training adds: the
+ * momentum, the writable running statistics (S floats each) and the three num_batches_tracked (one int64_t each); the
+ * res_bn_* three are NULL exactly when output_feat = 1.
+ *   et_stgcnn_train_workspace_bytes  the training workspace for N pedestrians in n_scenes scenes (graph form: 1): every
+ *                                    intermediate of both passes, the scenes' statistics and gradient partials.  0: outside
+ *                                    the family, N <= 0 or n_scenes < 1.
+ *   et_stgcnn_train_forward_graph /  arguments as et_stgcnn_forward_graph / _scenes, plus `train`; 2 launches (the scene
+ *   et_stgcnn_train_forward_scenes   kernel, one workgroup per scene; the running-statistics kernel) for any N and any
+ *                                    number of scenes.
+ *   et_stgcnn_backward_graph /       d_out laid out as the forward's output ((1,S,k,N) / (k,N,S)) and the workspace as that
+ *   et_stgcnn_backward_scenes        forward left it (same parameters, N, scene_offsets) -> grads, grads_floats >=
+ *                                    et_stgcnn_grad_floats floats: every parameter's gradient in state_dict order
+ *                                    (st_gcns.0: gcn.conv.weight, .bias, tcn.0.weight, .bias, tcn.1.weight, tcn.2.weight,
+ *                                    .bias, tcn.3.weight, .bias, [residual.0.weight, .bias, residual.1.weight, .bias,]
+ *                                    prelu.weight; tpcnns.j.weight, .bias for every j; tpcnn_ouput.weight, .bias;
+ *                                    prelus.j.weight for every j).  2 launches (the scene kernel; the reduction over the
+ *                                    scenes) for any N and any number of scenes.
+ * tcn.2.bias and residual.0.bias feed a training-mode BatchNorm directly: their gradient is an exact +0.0 (autograd leaves
+ * rounding noise there), and so is that of tpcnns[n_txpcnn-1] / prelus[n_txpcnn-1], which the forward never reads when
+ * n_txpcnn >= 2.  No gradient with respect to the input.  No atomics: every per-channel statistic and every gradient element
+ * of a scene is one wavefront's sum over the element's positions (lane l adds positions l, l + 64, ... in ascending order,
+ * then the lanes by the xor butterfly 32, 16, ..., 1), and the scenes' partials are added in ascending order; results are
+ * bit-identical from run to run, and a one-scene scenes call equals the graph call.  A scene of more than ET_SCENE_MAX_N
+ * pedestrians is not computed (NaN outputs, no batch, no gradient).  Host-side checks answer ET_ERR_UNSUPPORTED /
+ * ET_ERR_INVALID_ARG / ET_ERR_WORKSPACE before any launch.  A single scene occupies one CU. */
+typedef struct et_stgcnn_train {
+    float momentum;
+    float *bn1_mean, *bn1_var;
+    float *bn2_mean, *bn2_var;
+    float *res_bn_mean, *res_bn_var;
+    int64_t *bn1_batches, *bn2_batches, *res_bn_batches;
+} et_stgcnn_train;
+size_t et_stgcnn_train_workspace_bytes(const et_stgcnn_params *params, int64_t N, int n_scenes);
+int64_t et_stgcnn_grad_floats(const et_stgcnn_params *params);
+/* where the training workspace keeps what (host only, no launch), in floats.  Per-pedestrian fields first (scene s's block
+ * starts at off[s] x [20]; field f of it at + offsets[f] x the scene's n): u (K,n), d (K,n), P (K,K+1,n), g, a1, y, t, r,
+ * s, x (S,K,n each: gcn output, tcn.1's input and output, tcn.2's output, residual.0's output, the pre-residual sum, the
+ * block's output), tp (per applied tpcnn j < max(1, n_txpcnn - 1): pre-activation, output, (k,S,n) each), dfin (k,S,n), then
+ * the gradients at tp, x, s, t, r, y, a1, g; [20] floats per pedestrian; [21] the statistics (scene s at + s x [22]: per
+ * BatchNorm tcn.0, tcn.3, residual.1 five rows of S: mean, variance, 1/sqrt(var + eps), mean(dy), mean(dy x^)); [23] the
+ * scenes' gradient partials, [24] = et_stgcnn_grad_floats each; [25] the total. */
+#define ET_STGCNN_TRAIN_LAYOUT_FIELDS 26
+int et_stgcnn_train_layout(const et_stgcnn_params *params, int64_t N, int n_scenes, int64_t *offsets, int n_offsets);
+int et_stgcnn_train_forward_scenes(const et_stgcnn_params *params, const et_stgcnn_train *train, const float *C_obs,
+                                   const float *nrm, int64_t N, const int32_t *scene_offsets, int n_scenes,
+                                   float *C_pred_refine, void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_stgcnn_train_forward_graph(const et_stgcnn_params *params, const et_stgcnn_train *train, const float *v,
+                                  const float *a, int64_t N, float *out, void *workspace, size_t workspace_bytes,
+                                  et_stream_t stream);
+int et_stgcnn_backward_scenes(const et_stgcnn_params *params, int64_t N, const int32_t *scene_offsets, int n_scenes,
+                              const float *d_out, float *grads, int64_t grads_floats, void *workspace,
+                              size_t workspace_bytes, et_stream_t stream);
+int et_stgcnn_backward_graph(const et_stgcnn_params *params, int64_t N, const float *d_out, float *grads,
+                             int64_t grads_floats, void *workspace, size_t workspace_bytes, et_stream_t stream);
+
 /* ---- GP-Graph-SGCN predictor, inference (baseline/gpgraphsgcn: bridge.py pre-hook + GPGraph.forward around the
  * two-channel SGCN of model_baseline.py + post-hook) --------------------------------------------------------------------
  * The ET configuration: d_type 'learned_l2norm', learned threshold, mix_type 'mlp', all three graphs, shared weights,
