@@ -122,6 +122,14 @@ SIGNATURES = {
     "et_dmrgcn_workspace_bytes": (_Z, [_P, _I64, _I64]),
     "et_dmrgcn_forward_graph": (_I, [_P, _P, _P, _I64, _P, _P, _Z, _P]),
     "et_dmrgcn_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _Z, _P]),
+    # ---- DMRGCN predictor, training
+    "et_dmrgcn_train_workspace_bytes": (_Z, [_P, _I64, _I]),
+    "et_dmrgcn_grad_floats": (_I64, [_P]),
+    "et_dmrgcn_train_layout": (_I, [_P, _I64, _I, _P, _I]),
+    "et_dmrgcn_train_forward_graph": (_I, [_P, _P, _P, _I64, _P, _P, _P, _Z, _P]),
+    "et_dmrgcn_train_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _P, _Z, _P]),
+    "et_dmrgcn_backward_graph": (_I, [_P, _I64, _P, _P, _I64, _P, _Z, _P]),
+    "et_dmrgcn_backward_scenes": (_I, [_P, _I64, _P, _I, _P, _P, _I64, _P, _Z, _P]),
     # ---- Social-Implicit predictor, inference
     "et_implicit_workspace_bytes": (_Z, [_P, _I64]),
     "et_implicit_forward_graph": (_I, [_P, _P, _I64, _P, _P, _Z, _P]),
@@ -310,6 +318,8 @@ class GPGraphSTGCNNParams(C.Structure):
 DMRGCN_MAX_STGCN = 4  # ET_DMRGCN_MAX_STGCN
 DMRGCN_MAX_TPCNN = 8  # ET_DMRGCN_MAX_TPCNN
 DMRGCN_BINS = 5       # ET_DMRGCN_BINS
+DMRGCN_TRAIN_MAX_N = 512          # ET_DMRGCN_TRAIN_MAX_N
+DMRGCN_TRAIN_LAYOUT_FIELDS = 16   # ET_DMRGCN_TRAIN_LAYOUT_FIELDS
 
 
 class DMRGCNLayer(C.Structure):

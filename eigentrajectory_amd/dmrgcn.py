@@ -16,15 +16,26 @@ as the reference does: v (1, 1, K, N), a (1, 2, K, N, N) = [A_disp, A_dist] as t
 edit is seen by the next call, and by a captured graph's next replay).  ``split`` holds the two disentangling scale sets
 (constructor constants of the reference, not part of the state_dict); bin b of a relation is the open interval
 ``split[r][b] < distance < split[r][b+1]`` (1e10 after the last value), so a distance equal to a split value is in no bin.
-Training (drop_edge, dropout, the backward pass) is not implemented natively: a forward in training mode raises.  A whole
-split runs as one launch through :meth:`EigenTrajectory.evaluate_split` /
+A whole split runs as one launch through :meth:`EigenTrajectory.evaluate_split` /
 :func:`eigentrajectory_amd.ops.dmrgcn_forward_scenes`.
+A forward in training mode raises -- unless the instance was switched by
+``eigentrajectory_amd.enable_native_training(model)``.  Then a training-mode ``forward(v, a, keep=None)`` is
+``et_dmrgcn_train_forward_graph`` (csrc/et_dmrgcn_train.hip, one launch), which is NOT the eval forward: every
+MultiRelationalGCN applies ``drop_edge(A_, 0.8)`` to its clipped 0/1 bin tensor, so each (relation, bin, time row) graph loses
+entries independently per direction and is no longer symmetric.  The draw is :meth:`SocialDMRGCN.draw_keep` -- two
+``torch.rand((1, 5, K, N, N))`` draws, relation 0 (displacement) first, an entry kept where ``~(rand > 0.8)`` -- unless
+``keep`` (uint8, (2, 5, K, N, N), indexed [r, b, t, w, v]) is given.  The output is differentiable with respect to every
+parameter (``et_dmrgcn_backward_graph``, three launches; no input gradient).  The switch is the plain attribute
+``native_training`` (no parameter, no buffer, not in the ``state_dict``, default False).  Trained natively: the family
+below with ``n_stgcn = 1`` (the only depth the reference constructs; deeper stacks would send a gradient through the
+Laplacians), every ``Dropout.p = 0`` and scenes of at most 512 pedestrians.
 Supported family: ``input_feat = 1``, ``kernel_size = 3``, ``seq_len = pred_seq_len + 2``, ``1 <= output_feat <= 64``,
 ``pred_seq_len <= 32``, ``1 <= n_stgcn <= 4``, ``1 <= n_tpcnn <= 8``, five ascending non-negative split values per relation;
 other shapes construct, but their forward raises.
 """
 from __future__ import annotations
 
+import torch
 import torch.nn as nn
 
 from . import _lib as L
@@ -75,9 +86,46 @@ class _TPCNN(nn.Module):
             self.residual = None  # identity
 
 
+class _TrainForward(torch.autograd.Function):
+    """``forward(v, a, keep)`` in training mode with a backward pass.  Every parameter is an input, in ``named_parameters``
+    order, so autograd routes the gradients into ``.grad``; they are saved through ``save_for_backward`` with the training
+    workspace: the kernels read the weights in place, and an in-place change between forward and backward (an optimiser
+    step) is caught by autograd's version counters."""
+
+    @staticmethod
+    def forward(ctx, model, v, a, keep, *params):
+        from . import ops
+        et = model.et_params()  # the pointer table once: forward and backward see the same tensors
+        ws = ops.dmrgcn_train_workspace(model, v.shape[-1], et_params=et)
+        out = ops.dmrgcn_train_forward_graph(model, v, a, ws, keep=keep, et_params=et)
+        ctx.model, ctx.et = model, et
+        ctx.save_for_backward(*params) if ws is None else ctx.save_for_backward(ws, *params)
+        ctx.has_ws = ws is not None
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        need = ctx.needs_input_grad
+        if g_out is None:
+            return (None,) * len(need)
+        from . import ops
+        model = ctx.model
+        ws = ctx.saved_tensors[0] if ctx.has_ws else None
+        params = ctx.saved_tensors[1 if ctx.has_ws else 0:]
+        if any(p.data_ptr() != q.data_ptr() for p, q in zip(params, model.parameters())):
+            raise RuntimeError("SocialDMRGCN: a parameter tensor was replaced between forward and backward")
+        views = ops.dmrgcn_grad_views(model, ops.dmrgcn_backward_graph(model, ws, g_out, et_params=ctx.et))
+        return (None, None, None, None, *(g if wanted else None for g, wanted in zip(views.values(), need[4:])))
+
+
 class SocialDMRGCN(nn.Module):
     r"""baseline/dmrgcn/predictor.py's ``social_dmrgcn`` (eval-mode inference on the GPU).  ``forward(v, a)``: v (1, 1, K, N),
     a (1, 2, K, N, N) as the dmrgcn bridge's pre-hook builds them -> ``(out (1, S, k, N), a)``; the post-hook takes [0]."""
+
+    native_training = False  # a plain attribute, set per instance by eigentrajectory_amd.enable_native_training
+    drop_edge_percent = 0.8  # dmrgcn.py:68: drop_edge(A, 0.8, self.training) keeps an entry where ~(rand > 0.8)
 
     def __init__(self, n_stgcn=1, n_tpcnn=4, input_feat=2, output_feat=5, seq_len=8, pred_seq_len=12, kernel_size=3):
         super().__init__()
@@ -124,7 +172,40 @@ class SocialDMRGCN(nn.Module):
                 t.res_w, t.res_b = _p(blk.residual[0].weight), _p(blk.residual[0].bias)
         return p, dev
 
-    def forward(self, v, a):
+    def outside_native_training(self):
+        """-> None, or the field that puts this instance outside the family that trains natively, as text"""
+        if self.n_stgcn != 1:
+            return (f"n_stgcn = {self.n_stgcn} (native: 1; deeper stacks send a gradient through the Laplacian "
+                    "contraction and are out of scope)")
+        for field, want in (("input_feat", 1), ("kernel_size", 3), ("seq_len", self.pred_seq_len + 2)):
+            if getattr(self, field) != want:
+                return f"{field} = {getattr(self, field)} (native: {want})"
+        for field, hi in (("n_tpcnn", L.DMRGCN_MAX_TPCNN), ("output_feat", 64), ("pred_seq_len", L.MAX_K)):
+            if not 1 <= getattr(self, field) <= hi:
+                return f"{field} = {getattr(self, field)} (native: 1 to {hi})"
+        for name, m in self.named_modules():
+            if isinstance(m, nn.Dropout) and m.p != 0:
+                return f"{name}.p = {m.p} (native: 0)"
+        return None
+
+    def draw_keep(self, n, device, generator=None):
+        """The DropEdge draw of one training-mode forward on ``n`` pedestrians -> uint8 (2, 5, K, n, n), indexed
+        [r, b, t, w, v]: one ``torch.rand((1, 5, K, n, n))`` per relation, r = 0 (displacement) first, as the reference's two
+        MultiRelationalGCNs draw ``rand_like(A_)``; an entry is kept where ``~(rand > drop_edge_percent)``."""
+        shape = (1, L.DMRGCN_BINS, self.seq_len, n, n)
+        draws = [torch.rand(shape, device=device, generator=generator) for _ in range(2)]
+        return torch.cat([~(d > self.drop_edge_percent) for d in draws]).to(torch.uint8)
+
+    def forward(self, v, a, keep=None):
+        if self.training and self.native_training and self.outside_native_training() is None:
+            if v.requires_grad or a.requires_grad:
+                raise RuntimeError("SocialDMRGCN: no input gradient is built (the dmrgcn bridge detaches v); an input "
+                                   "requires one")
+            dev = L.module_device("SocialDMRGCN", self)
+            v, a = (L.on_device(t, dev) for t in (v, a))
+            if keep is None:
+                keep = self.draw_keep(v.shape[-1], dev)
+            return _TrainForward.apply(self, v, a, keep, *self.parameters()), a
         if self.training:
             raise RuntimeError("SocialDMRGCN: only inference is native (no drop_edge, no dropout); training-mode forward and "
                                "backward are not implemented -- call .eval() first")

@@ -1157,6 +1157,186 @@ def dmrgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=Fals
     return (out, {"graph_inputs": gin}) if want_details else out
 
 
+# ------------------------------------------------------------------------------ DMRGCN predictor (training)
+def _dmrgcn_train_params(who, model, et_params):
+    if et_params is not None:   # the training Function's calls: its forward() has looked at the family already
+        return et_params
+    why = model.outside_native_training()
+    if why is not None:
+        raise NotImplementedError(f"{who}: SocialDMRGCN has no native backward pass outside its native family: {why}")
+    return model.et_params()
+
+
+def dmrgcn_train_workspace(model, n, n_scenes=1, et_params=None):
+    """A training workspace for ``n`` pedestrians in ``n_scenes`` scenes: :func:`dmrgcn_train_forward_graph` / ``_scenes``
+    fill it, :func:`dmrgcn_backward_graph` / ``_scenes`` read it (None for ``n`` = 0)."""
+    params, dev = _dmrgcn_train_params("dmrgcn_train_workspace", model, et_params)
+    return _workspace("et_dmrgcn_train_workspace_bytes", dev, params, n, max(n_scenes, 1), required=n > 0)[0]
+
+
+def _dmrgcn_check_ws(who, dev, workspace):
+    if workspace is None or workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError(f"{who}: workspace is not a contiguous uint8 tensor on {dev} (dmrgcn_train_workspace makes one)")
+
+
+def _dmrgcn_keep(who, dev, keep, shape=None, numel=None):
+    """the keep mask as the kernel reads it: contiguous uint8 on ``dev`` of ``shape`` (or of ``numel`` entries); None stays"""
+    if keep is None:
+        return None
+    if keep.dtype != torch.uint8 or (shape is not None and tuple(keep.shape) != shape) or \
+            (numel is not None and keep.numel() != numel):
+        raise ValueError(f"{who}: keep {tuple(keep.shape)} {keep.dtype} is not uint8 "
+                         f"{shape if shape is not None else f'of {numel} entries'}")
+    return keep.to(dev).contiguous()
+
+
+def dmrgcn_train_forward_graph(model, v, a, workspace, keep=None, et_params=None):
+    """``model`` in training mode on one scene as the dmrgcn bridge hands it over: v (1, 1, K, N), a (1, 2, K, N, N),
+    ``keep`` uint8 (2, 5, K, N, N) indexed [r, b, t, w, v] (:meth:`SocialDMRGCN.draw_keep`; None keeps every edge) -> the
+    raw output (1, S, k, N).  What the backward reads stays in ``workspace`` (of :func:`dmrgcn_train_workspace`) for
+    :func:`dmrgcn_backward_graph`.  One launch."""
+    params, dev = _dmrgcn_train_params("dmrgcn_train_forward_graph", model, et_params)
+    K, k, S = params.seq_len, params.pred_seq_len, params.output_feat
+    n = v.shape[-1]
+    if tuple(v.shape) != (1, 1, K, n) or tuple(a.shape) != (1, 2, K, n, n):
+        raise ValueError(f"dmrgcn_train_forward_graph: v {tuple(v.shape)} / a {tuple(a.shape)} are not (1,1,{K},N) / "
+                         f"(1,2,{K},N,N)")
+    if n > L.DMRGCN_TRAIN_MAX_N:
+        raise ValueError(f"dmrgcn_train_forward_graph: N = {n} exceeds the {L.DMRGCN_TRAIN_MAX_N} pedestrians a training scene "
+                         "may have")
+    v, a = _dev_args(dev, v.detach(), a.detach())
+    keep = _dmrgcn_keep("dmrgcn_train_forward_graph", dev, keep, shape=(2, L.DMRGCN_BINS, K, n, n))
+    out = torch.empty((1, S, k, n), device=dev)
+    if n:
+        _dmrgcn_check_ws("dmrgcn_train_forward_graph", dev, workspace)
+    L.call("et_dmrgcn_train_forward_graph", C.byref(params), L.ptr(v), L.ptr(a), n, L.ptr(keep), L.ptr(out),
+           L.ptr(workspace), workspace.numel() if workspace is not None else 0, L.stream(dev))
+    return out
+
+
+def dmrgcn_keep_offsets(scene_sizes, device=None):
+    """-> (int64 tensor (n_scenes + 1,): where each scene's (2, 5, K, n, n) block of a packed keep mask starts, in units of
+    10 K entries (the running sum of n^2; a scene above the training cap takes no room), the total sum of n^2)"""
+    off = [0]
+    for s in scene_sizes:
+        off.append(off[-1] + (int(s) ** 2 if int(s) <= L.DMRGCN_TRAIN_MAX_N else 0))
+    t = torch.tensor(off, dtype=torch.int64)
+    return (t if device is None else t.to(device)), off[-1]
+
+
+def dmrgcn_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, keep=None, workspace=None):
+    """The dmrgcn bridge + ``model`` in training mode + the post-hook for every scene of a batch in ONE launch, one
+    workgroup per scene.  C_obs, nrm and ``scene_sizes`` as :func:`dmrgcn_forward_scenes`; ``keep``: uint8, every scene's
+    (2, 5, K, n, n) block one after the other (:func:`dmrgcn_keep_offsets`), None keeps every edge -> (C_pred_refine
+    (k, N, S), workspace); the workspace (made here unless given) goes to :func:`dmrgcn_backward_scenes` with the same
+    ``scene_sizes``.  A scene of more than 512 pedestrians is not computed (NaN rows)."""
+    params, dev = _dmrgcn_train_params("dmrgcn_train_forward_scenes", model, None)
+    b = _scene_batch("dmrgcn_train_forward_scenes", dev, C_obs, nrm, params.pred_seq_len, scene_sizes)
+    if scene_sizes is None and b.n > L.DMRGCN_TRAIN_MAX_N:
+        raise ValueError(f"dmrgcn_train_forward_scenes: one unlisted scene of {b.n} pedestrians exceeds the "
+                         f"{L.DMRGCN_TRAIN_MAX_N} a training scene may have")
+    if workspace is None:
+        workspace = dmrgcn_train_workspace(model, b.n, len(b.sizes), et_params=(params, dev))
+    if b.n:
+        _dmrgcn_check_ws("dmrgcn_train_forward_scenes", dev, workspace)
+    koff, total = dmrgcn_keep_offsets(b.sizes, dev if keep is not None else None)
+    keep = _dmrgcn_keep("dmrgcn_train_forward_scenes", dev, keep, numel=2 * L.DMRGCN_BINS * params.seq_len * total)
+    out = torch.empty((params.pred_seq_len, b.n, params.output_feat), device=dev)
+    L.call("et_dmrgcn_train_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), b.n, L.ptr(b.off), b.n_scenes,
+           L.ptr(keep), L.ptr(koff if keep is not None else None), L.ptr(out), L.ptr(workspace),
+           workspace.numel() if workspace is not None else 0, L.stream(dev))
+    return out, workspace
+
+
+def dmrgcn_grad_views(model, grads):
+    """``grads``, the flat buffer of :func:`dmrgcn_backward_graph` / ``_scenes`` -> {state_dict key: a view of it shaped like
+    the parameter}, every parameter of ``model`` (state_dict order)."""
+    out, at = {}, 0
+    for name, t in model.named_parameters():
+        out[name] = grads[at:at + t.numel()].view(t.shape)
+        at += t.numel()
+    if at != grads.numel():
+        raise ValueError(f"dmrgcn_grad_views: {grads.numel()} floats for parameters of {at}")
+    return out
+
+
+def _dmrgcn_grads(who, params, dev, d_out, shape):
+    if tuple(d_out.shape) != shape:
+        raise ValueError(f"{who}: d_out {tuple(d_out.shape)} is not {shape}")
+    d_out = d_out.detach()
+    if d_out.device != dev or d_out.dtype != torch.float32 or not d_out.is_contiguous():
+        d_out = d_out.to(device=dev, dtype=torch.float32).contiguous()
+    size = int(L.lib().et_dmrgcn_grad_floats(C.byref(params)))
+    if not size:
+        L.check(3, "et_dmrgcn_grad_floats")
+    return d_out, torch.empty((size,), device=dev)
+
+
+def dmrgcn_backward_graph(model, workspace, d_out, et_params=None):
+    """The backward pass of :func:`dmrgcn_train_forward_graph` in three launches: ``workspace`` as that call filled it (same
+    weights), ``d_out`` (1, S, k, N) the gradient at its output -> the flat float32 gradient buffer
+    (:func:`dmrgcn_grad_views` names its parts)."""
+    params, dev = _dmrgcn_train_params("dmrgcn_backward_graph", model, et_params)
+    n = d_out.shape[-1] if d_out.dim() == 4 else -1
+    d_out, grads = _dmrgcn_grads("dmrgcn_backward_graph", params, dev, d_out, (1, params.output_feat, params.pred_seq_len, n))
+    if n:
+        _dmrgcn_check_ws("dmrgcn_backward_graph", dev, workspace)
+    L.call("et_dmrgcn_backward_graph", C.byref(params), n, L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace),
+           workspace.numel() if workspace is not None else 0, L.stream(dev))
+    return grads
+
+
+def dmrgcn_backward_scenes(model, workspace, d_out, scene_sizes=None):
+    """The backward pass of :func:`dmrgcn_train_forward_scenes` in three launches whatever the number of scenes:
+    ``workspace`` as that call filled it, ``scene_sizes`` as given to it, ``d_out`` (k, N, S) -> the flat gradient buffer,
+    summed over the scenes in ascending order."""
+    params, dev = _dmrgcn_train_params("dmrgcn_backward_scenes", model, None)
+    n = d_out.shape[1] if d_out.dim() == 3 else -1
+    d_out, grads = _dmrgcn_grads("dmrgcn_backward_scenes", params, dev, d_out, (params.pred_seq_len, n, params.output_feat))
+    if scene_sizes is None:
+        off, n_scenes = None, 0
+    else:
+        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
+        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
+        n_scenes = len(sizes)
+    if n:
+        _dmrgcn_check_ws("dmrgcn_backward_scenes", dev, workspace)
+    L.call("et_dmrgcn_backward_scenes", C.byref(params), n, L.ptr(off), n_scenes, L.ptr(d_out), L.ptr(grads), grads.numel(),
+           L.ptr(workspace), workspace.numel() if workspace is not None else 0, L.stream(dev))
+    return grads
+
+
+def dmrgcn_train_views(model, workspace, n, n_scenes=1, lo=0, scene=0, scene_n=None):
+    """The values kept in ``workspace`` by name, as views, for scene number ``scene`` of ``scene_n`` pedestrians that starts
+    at row ``lo`` (one scene: the defaults).  Forward: ``u`` (K, n), ``P`` (2, 5, 2, K, n) (the contraction rows: j = 0 from
+    u, j = 1 from the ones row), ``yp`` (S, K, n) the tcn PReLU's input, ``s`` (S, K, n) the block PReLU's input, ``x``
+    (K, S, n) the block's output, and per tpcnn block the lists ``c0`` / ``y`` / ``c1`` / ``q`` / ``o`` (k, S, n) and ``z``
+    (S, n).  After a backward call also ``d_q`` / ``d_y`` (k, S, n) and ``d_g`` (S, n) per block, ``d_x`` (K, S, n),
+    ``d_yt`` (S, K, n) the gradient at PReLU(yp), and ``partial``, the scene's own flat gradient.  The offsets are the
+    library's (``et_dmrgcn_train_layout``)."""
+    params, _ = model.et_params()
+    K, k, S = params.seq_len, params.pred_seq_len, params.output_feat
+    m = n if scene_n is None else scene_n
+    f = workspace.view(torch.float32)
+    o = (C.c_int64 * L.DMRGCN_TRAIN_LAYOUT_FIELDS)()
+    L.call("et_dmrgcn_train_layout", C.byref(params), n, n_scenes, o, L.DMRGCN_TRAIN_LAYOUT_FIELDS)
+    (o_u, o_p, o_yp, o_s, o_x, o_tp, o_dtp, o_dx, o_dy, _, per, tp_stride, dtp_stride, o_part, G, _) = [int(x) for x in o]
+    base = lo * per
+    fld = lambda off, *shape: f[base + off * m:base + off * m + math.prod(shape) * m].view(*shape, m)
+    kS = k * S
+    views = {"u": fld(o_u, K), "P": fld(o_p, 2, L.DMRGCN_BINS, 2, K), "yp": fld(o_yp, S, K), "s": fld(o_s, S, K),
+             "x": fld(o_x, K, S), "d_x": fld(o_dx, K, S), "d_yt": fld(o_dy, S, K)}
+    blocks = range(params.n_tpcnn)
+    for q, name in enumerate(("c0", "y", "c1", "q", "o")):
+        views[name] = [fld(o_tp + j * tp_stride + q * kS, k, S) for j in blocks]
+    views["z"] = [fld(o_tp + j * tp_stride + 5 * kS, S) for j in blocks]
+    views["d_q"] = [fld(o_dtp + j * dtp_stride, k, S) for j in blocks]
+    views["d_y"] = [fld(o_dtp + j * dtp_stride + kS, k, S) for j in blocks]
+    views["d_g"] = [fld(o_dtp + j * dtp_stride + 2 * kS, S) for j in blocks]
+    views["partial"] = f[o_part + scene * G:o_part + (scene + 1) * G]
+    return views
+
+
 # ------------------------------------------------------------------------------ Social-Implicit predictor (inference)
 def implicit_workspace(model, n, et_params=None):
     """A caller-owned workspace for ``n`` pedestrians: pass it as ``workspace=`` to :func:`implicit_forward_graph` /

@@ -169,8 +169,10 @@ def enable_native_training(model, flag=True):
     1``, four heads, width 64, ``dropout = 0``, no position channel) or a ``GPGraph`` in the ET configuration around
     ``SGCN(position_channel=True, dropout=0)``, or a ``SocialSTGCNN`` of its native family (``n_stgcnn = 1``, no per-time-row
     graph, affine BatchNorms that track running statistics with one float momentum, no dropout; its training-mode forward
-    uses BatchNorm batch statistics and updates the running ones) (the plain attribute ``native_training``); the other four
-    predictors have no native backward pass and raise.  -> ``model``"""
+    uses BatchNorm batch statistics and updates the running ones), or a ``SocialDMRGCN`` of its native family (``n_stgcn =
+    1``, every ``Dropout.p = 0``; its training-mode forward applies DropEdge through a keep mask it draws per call) (the
+    plain attribute ``native_training``); the other three predictors have no native backward pass and raise.  -> ``model``"""
+    from .dmrgcn import SocialDMRGCN
     from .gpgraph import GPGraph
     from .implicit import SocialImplicitLight
     from .lbebm import LBEBM
@@ -200,6 +202,12 @@ def enable_native_training(model, flag=True):
         raise NotImplementedError(f"enable_native_training: SocialSTGCNN has no native backward pass outside its native "
                                   f"family: {net.outside_native_training()}; LBEBM, PECNet, SocialImplicitLight, SGCN and a "
                                   "SocialSTGCNN with n_stgcnn = 1 and graph_per_time_row = False train natively")
+    elif isinstance(net, SocialDMRGCN) and net.outside_native_training() is None:
+        net.native_training = bool(flag)
+    elif isinstance(net, SocialDMRGCN):
+        raise NotImplementedError(f"enable_native_training: SocialDMRGCN has no native backward pass outside its native "
+                                  f"family: {net.outside_native_training()}; LBEBM, PECNet, SocialImplicitLight, SGCN, "
+                                  "SocialSTGCNN and a SocialDMRGCN with n_stgcn = 1 and no dropout train natively")
     else:
         raise NotImplementedError(f"enable_native_training: {type(net).__name__} has no native backward pass; only LBEBM, "
                                   "PECNet, SocialImplicitLight, SGCN and SocialSTGCNN, and GPGraph around SGCN, train "

@@ -756,6 +756,65 @@ int et_dmrgcn_forward_scenes(const et_dmrgcn_params *params, const float *C_obs,
                              const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *graph_inputs,
                              void *workspace, size_t workspace_bytes, et_stream_t stream);
 
+/* ---- DMRGCN predictor, training (social_dmrgcn.forward in training mode + its backward pass) ---------------------------
+ * The training-mode forward is NOT the eval forward: every MultiRelationalGCN applies drop_edge(A_, 0.8) to the clipped 0/1
+ * bin tensor (dropedge.py), so every (relation, bin, time row) graph loses entries independently per direction and is no
+ * longer symmetric.  The draw is the caller's: `keep`, uint8, (2,5,K,N,N) indexed [r,b,t,w,v] (graph form), entry != 0
+ * keeps A_b[w,v]; scenes form: scene s's own (2,5,K,n,n) block starts at 10 K keep_offsets[s], keep_offsets (device,
+ * n_scenes + 1 int64_t) the running sum of n^2 over the scenes (a scene above the cap takes no room); keep = NULL keeps
+ * everything.  cnt[r,b,t,w] = the kept entries of row w, d_w = 1/sqrt(1 + cnt), L[w,v] = [v==w] - (d_w (A'[w,v] + [v==w]))
+ * d_v with d_v the column pedestrian's own row degree; every other statement is et_dmrgcn_forward_*'s in its order, so with
+ * keep = NULL or all ones the output is bit-equal to the inference entry's.
+ * Trained natively: the inference family with n_stgcn = 1 (the only depth the reference builds; deeper stacks send a
+ * gradient through the Laplacians: ET_ERR_UNSUPPORTED) and scenes of at most ET_DMRGCN_TRAIN_MAX_N pedestrians (a larger
+ * scene of the scenes form is not computed: NaN outputs, no gradient; graph form: ET_ERR_INVALID_ARG).
+ *   et_dmrgcn_train_workspace_bytes  the training workspace for N pedestrians in n_scenes scenes (graph form: 1): what the
+ *                                    forward keeps, the activation gradients, an arena for scenes that do not fit LDS and
+ *                                    the scenes' gradient partials.  0: outside the family, N <= 0 or n_scenes < 1.
+ *   et_dmrgcn_train_forward_graph /  arguments as et_dmrgcn_forward_graph / _scenes plus the mask.  ONE launch, one
+ *   et_dmrgcn_train_forward_scenes   workgroup per scene, the live operands in the LDS arena when the scene fits it (at
+ *                                    S = 20, k = 6: up to 24 pedestrians), else in the workspace's arena rows.
+ *   et_dmrgcn_backward_graph /       d_out laid out as the forward's output ((1,S,k,N) / (k,N,S)) and the workspace as that
+ *   et_dmrgcn_backward_scenes        forward left it (same parameters, N, scene_offsets) -> grads, grads_floats >=
+ *                                    et_dmrgcn_grad_floats floats: every parameter's gradient in state_dict order
+ *                                    (st_dmrgcns.0: gcns.0.conv.weight, .bias, gcns.1.conv.weight, .bias, tcn.0.weight,
+ *                                    tcn.1.weight, .bias, [residual.0.weight, .bias,] prelu.weight; tpcnns.j: tpcn.0.0.weight,
+ *                                    .bias, tpcn.0.1.weight, tpcn.1.0.weight, .bias, tpcn.1.1.weight, gtacn.0.0.weight, .bias,
+ *                                    gtacn.0.1.weight, [residual.0.weight, .bias]).  THREE launches for any N and any number
+ *                                    of scenes: the activation gradients (one workgroup per scene, the dependent chain in
+ *                                    the arena), the parameter gradients (16 workgroups per scene: every element is one
+ *                                    wavefront's sum, the scene's 64 wavefronts take them round robin), the reduction.
+ * No gradient with respect to the input.  No atomics: a gradient element of a scene is one wavefront's sum over the
+ * element's positions (lane l adds positions l, l + 64, ... in ascending order, then the lanes by the xor butterfly 32, 16,
+ * ..., 1), and the scenes' partials are added in ascending order, the first one copied; results are bit-identical from run
+ * to run, and a one-scene scenes call equals the graph call.  Host-side checks answer ET_ERR_UNSUPPORTED /
+ * ET_ERR_INVALID_ARG / ET_ERR_WORKSPACE before any launch. */
+#define ET_DMRGCN_TRAIN_MAX_N 512
+size_t et_dmrgcn_train_workspace_bytes(const et_dmrgcn_params *params, int64_t N, int n_scenes);
+int64_t et_dmrgcn_grad_floats(const et_dmrgcn_params *params);
+/* where the training workspace keeps what (host only, no launch), in floats.  Per-pedestrian fields first (scene s's block
+ * starts at off[s] x [10]; field f of it at + offsets[f] x the scene's n): [0] u (K,n), [1] P (2,5,2,K,n) the contraction
+ * rows (j = 0 from u, j = 1 from the ones row), [2] yp (S,K,n) the tcn PReLU's input, [3] s (S,K,n) the block PReLU's
+ * input, [4] x (K,S,n) the block's output, [5] per tpcnn block j at + j x [11]: c0, y, c1, q, o (k,S,n each: tpcn.0's
+ * pre-activation and output, tpcn.1's, the block's output), z (S,n) the GTA pre-activation, [6] per tpcnn block at + j x
+ * [12]: dq, dy (k,S,n), dg (S,n) the gradients at q, y and the GTA row, [7] dx (K,S,n), [8] dy (S,K,n) the gradient at
+ * PReLU(yp), [9] the arena; [10] floats per pedestrian; [13] the scenes' gradient partials, [14] = et_dmrgcn_grad_floats
+ * each; [15] the total. */
+#define ET_DMRGCN_TRAIN_LAYOUT_FIELDS 16
+int et_dmrgcn_train_layout(const et_dmrgcn_params *params, int64_t N, int n_scenes, int64_t *offsets, int n_offsets);
+int et_dmrgcn_train_forward_graph(const et_dmrgcn_params *params, const float *v, const float *a, int64_t N,
+                                  const uint8_t *keep, float *out, void *workspace, size_t workspace_bytes,
+                                  et_stream_t stream);
+int et_dmrgcn_train_forward_scenes(const et_dmrgcn_params *params, const float *C_obs, const float *nrm, int64_t N,
+                                   const int32_t *scene_offsets, int n_scenes, const uint8_t *keep,
+                                   const int64_t *keep_offsets, float *C_pred_refine, void *workspace,
+                                   size_t workspace_bytes, et_stream_t stream);
+int et_dmrgcn_backward_graph(const et_dmrgcn_params *params, int64_t N, const float *d_out, float *grads,
+                             int64_t grads_floats, void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_dmrgcn_backward_scenes(const et_dmrgcn_params *params, int64_t N, const int32_t *scene_offsets, int n_scenes,
+                              const float *d_out, float *grads, int64_t grads_floats, void *workspace,
+                              size_t workspace_bytes, et_stream_t stream);
+
 /* ---- Social-Implicit predictor, inference (baseline/implicit: bridge.py pre-hook + SocialImplicitLight.forward + post-hook)
  * Eval mode, the Light form (its noise is identically zero, so the noise_w term is not computed; noise_w is carried so
  * that the table is complete).  The parameters are read in place from the module's tensors (fp32, contiguous).  Per cell
