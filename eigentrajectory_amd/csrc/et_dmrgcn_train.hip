@@ -23,7 +23,8 @@
 //                                  dg (S), then dx (K,S) and dy (S,K), in the workspace
 //   2. dmrgcn_train_wgrad_kernel   grid (scenes, kDtChunks): every parameter-gradient element of a scene is one wavefront's
 //                                  sum; the scene's 64 wavefronts take the elements round robin -> the scene's partial
-//   3. dmrgcn_grad_reduce_kernel   grads[e] = the scenes' partials in ascending order, the first one copied
+//   3. scene_grad_reduce_kernel    grads[e] = the scenes' partials in ascending order, the first one copied
+//                                  (et_train_sums.inl, shared with et_stgcnn_train.hip)
 // Fixed orders (no atomics; two runs agree bit for bit, a one-scene scenes call equals the graph call): wave_sum of
 // et_train_sums.inl (lane l adds positions l, l + 64, ... ascending from +0, then the xor butterfly 32 .. 1); every other
 // sum is one lane's ascending fmaf chain.  Every PReLU branches on the kept fp32 word in both passes.
@@ -635,32 +636,10 @@ __global__ __launch_bounds__(kSgThreads) void dmrgcn_train_wgrad_kernel(et_dmrgc
     }
 }
 
-// launch 3: grads[e] = the scenes' partials in ascending order, the first one copied; no live scene: +0
-__global__ __launch_bounds__(kSgThreads) void dmrgcn_grad_reduce_kernel(const int32_t *__restrict__ off, int n_scenes,
-                                                                        int64_t N, const float *ws, DtLayout L,
-                                                                        float *grads) {
-    const int64_t i = (int64_t)blockIdx.x * kSgThreads + threadIdx.x;
-    if (i >= L.o[F_GRADS]) return;
-    float acc = 0.f;
-    bool first = true;
-    for (int s = 0; s < n_scenes; ++s) {
-        const int64_t n = off ? (int64_t)off[s + 1] - off[s] : N;
-        if (n < 1 || n > kDtMaxN) continue;
-        const float v = ws[L.o[F_PARTIALS] + s * L.o[F_GRADS] + i];
-        acc = first ? v : acc + v;
-        first = false;
-    }
-    grads[i] = acc;
-}
-
 static int dt_check_params(const et_dmrgcn_params *p) {
     if (!p) return ET_ERR_INVALID_ARG;
     if (p->n_stgcn != 1) return ET_ERR_UNSUPPORTED;  // deeper stacks send a gradient through the Laplacians
     return dm_check_params(p);
-}
-
-static inline bool dt_ws_fits(const DtLayout &L, const void *workspace, size_t workspace_bytes) {
-    return workspace && workspace_bytes >= (size_t)L.o[F_TOTAL] * 4;
 }
 
 template <class Src>
@@ -683,10 +662,7 @@ static int dt_backward(const Src &src, const et_dmrgcn_params *p, const int32_t 
                            *p, off, N, (float *)workspace, L);
         ET_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(dmrgcn_grad_reduce_kernel, dim3((unsigned)ceil_div(L.o[F_GRADS], kSgThreads)), dim3(kSgThreads), 0,
-                       (hipStream_t)stream, off, N > 0 ? ns : 0, N, (const float *)workspace, L, grads);
-    ET_LAUNCH_CHECK();
-    return ET_OK;
+    return scene_grad_reduce((const float *)workspace + L.o[F_PARTIALS], L.o[F_GRADS], kDtMaxN, off, ns, N, grads, stream);
 }
 
 }  // namespace
@@ -726,7 +702,7 @@ extern "C" int et_dmrgcn_train_forward_scenes(const et_dmrgcn_params *params, co
     if (keep && scene_offsets && !keep_offsets) return ET_ERR_INVALID_ARG;  // where each scene's block of the mask starts
     const int ns = scene_offsets ? n_scenes : 1;
     const DtLayout L = dt_layout(dm_dims_of(*params), N, ns);
-    if (!dt_ws_fits(L, workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
+    if (!train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return dt_forward(TrainScenesSrc{{C_obs, nrm, N, C_pred_refine}, nullptr}, params, scene_offsets, ns, N, keep,
                       scene_offsets ? keep_offsets : nullptr, workspace, L, stream);
 }
@@ -740,34 +716,33 @@ extern "C" int et_dmrgcn_train_forward_graph(const et_dmrgcn_params *params, con
     if (N == 0) return ET_OK;
     if (!v || !a || !out) return ET_ERR_INVALID_ARG;
     const DtLayout L = dt_layout(dm_dims_of(*params), N, 1);
-    if (!dt_ws_fits(L, workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
+    if (!train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return dt_forward(TrainGraphSrc{{v, a, out}, nullptr}, params, nullptr, 1, N, keep, nullptr, workspace, L, stream);
 }
 
 extern "C" int et_dmrgcn_backward_scenes(const et_dmrgcn_params *params, int64_t N, const int32_t *scene_offsets,
                                          int n_scenes, const float *d_out, float *grads, int64_t grads_floats,
                                          void *workspace, size_t workspace_bytes, et_stream_t stream) {
-    const int rc = dt_check_params(params);
+    int rc = dt_check_params(params);
     if (rc != ET_OK) return rc;
     const DmDims D = dm_dims_of(*params);
-    if (N < 0 || N > INT32_MAX || n_scenes < 0 || !grads || grads_floats < dt_grad_off(D).total) return ET_ERR_INVALID_ARG;
-    if (scene_offsets ? (n_scenes == 0 && N != 0) : N > kDtMaxN) return ET_ERR_INVALID_ARG;
+    rc = backward_args_status(N, scene_offsets, n_scenes, kDtMaxN, d_out, grads, grads_floats, dt_grad_off(D).total);
+    if (rc != ET_OK) return rc;
     const int ns = scene_offsets ? n_scenes : 1;
     const DtLayout L = dt_layout(D, N, ns);
-    if (N > 0 && !d_out) return ET_ERR_INVALID_ARG;
-    if (N > 0 && !dt_ws_fits(L, workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
+    if (N > 0 && !train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return dt_backward(TrainScenesSrc{{nullptr, nullptr, N, nullptr}, d_out}, params, scene_offsets, ns, N, grads, workspace, L,
                        stream);
 }
 
 extern "C" int et_dmrgcn_backward_graph(const et_dmrgcn_params *params, int64_t N, const float *d_out, float *grads,
                                         int64_t grads_floats, void *workspace, size_t workspace_bytes, et_stream_t stream) {
-    const int rc = dt_check_params(params);
+    int rc = dt_check_params(params);
     if (rc != ET_OK) return rc;
     const DmDims D = dm_dims_of(*params);
-    if (N < 0 || N > kDtMaxN || !grads || grads_floats < dt_grad_off(D).total) return ET_ERR_INVALID_ARG;
+    rc = backward_args_status(N, nullptr, 0, kDtMaxN, d_out, grads, grads_floats, dt_grad_off(D).total);
+    if (rc != ET_OK) return rc;
     const DtLayout L = dt_layout(D, N, 1);
-    if (N > 0 && !d_out) return ET_ERR_INVALID_ARG;
-    if (N > 0 && !dt_ws_fits(L, workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
+    if (N > 0 && !train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return dt_backward(TrainGraphSrc{{nullptr, nullptr, nullptr}, d_out}, params, nullptr, 1, N, grads, workspace, L, stream);
 }

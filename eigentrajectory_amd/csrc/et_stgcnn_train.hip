@@ -519,24 +519,6 @@ __global__ __launch_bounds__(kSgThreads) void stgcnn_train_bwd_kernel(Src src, e
     });
 }
 
-// grads[e] = the scenes' partials in ascending order (header comment: "scenes"); no live scene: +0
-__global__ __launch_bounds__(kSgThreads) void stgcnn_grad_reduce_kernel(const int32_t *__restrict__ off, int n_scenes,
-                                                                        int64_t N, const float *ws, TrainLayout L,
-                                                                        float *grads) {
-    const int64_t i = (int64_t)blockIdx.x * kSgThreads + threadIdx.x;
-    if (i >= L.o[F_GRADS]) return;
-    float acc = 0.f;
-    bool first = true;
-    for (int s = 0; s < n_scenes; ++s) {
-        const int64_t n = off ? (int64_t)off[s + 1] - off[s] : N;
-        if (n < 1 || n > ET_SCENE_MAX_N) continue;
-        const float v = ws[L.o[F_PARTIALS] + s * L.o[F_GRADS] + i];
-        acc = first ? v : acc + v;
-        first = false;
-    }
-    grads[i] = acc;
-}
-
 static int check_train_params(const et_stgcnn_params *p) {
     if (!p) return ET_ERR_INVALID_ARG;
     if (p->n_stgcnn != 1) return ET_ERR_UNSUPPORTED;  // deeper stacks send a gradient through the contraction
@@ -551,10 +533,6 @@ static int check_train_state(const et_stgcnn_params *p, const et_stgcnn_train *t
     if (res != (t->res_bn_mean != nullptr) || res != (t->res_bn_var != nullptr) || res != (t->res_bn_batches != nullptr))
         return ET_ERR_INVALID_ARG;
     return ET_OK;
-}
-
-static inline bool ws_fits(const TrainLayout &L, const void *workspace, size_t workspace_bytes) {
-    return workspace && workspace_bytes >= (size_t)L.o[F_TOTAL] * 4;
 }
 
 template <class Src>
@@ -578,10 +556,8 @@ static int train_backward(const Src &src, const et_stgcnn_params *p, const int32
                            *p, off, N, (float *)workspace, L);
         ET_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(stgcnn_grad_reduce_kernel, dim3((unsigned)ceil_div(L.o[F_GRADS], kSgThreads)), dim3(kSgThreads), 0,
-                       (hipStream_t)stream, off, N > 0 ? ns : 0, N, (const float *)workspace, L, grads);
-    ET_LAUNCH_CHECK();
-    return ET_OK;
+    return scene_grad_reduce((const float *)workspace + L.o[F_PARTIALS], L.o[F_GRADS], ET_SCENE_MAX_N, off, ns, N, grads,
+                             stream);
 }
 
 }  // namespace
@@ -621,7 +597,7 @@ extern "C" int et_stgcnn_train_forward_scenes(const et_stgcnn_params *params, co
     if (!C_obs || !nrm || !C_pred_refine) return ET_ERR_INVALID_ARG;
     const int ns = scene_offsets ? n_scenes : 1;
     const TrainLayout L = train_layout(dims_of(*params), N, ns);
-    if (!ws_fits(L, workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
+    if (!train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return train_forward(TrainScenesSrc{C_obs, nrm, N, C_pred_refine, nullptr}, params, train, scene_offsets, ns, N, workspace,
                          L, stream);
 }
@@ -636,34 +612,33 @@ extern "C" int et_stgcnn_train_forward_graph(const et_stgcnn_params *params, con
     if (N == 0) return ET_OK;
     if (!v || !a || !out) return ET_ERR_INVALID_ARG;
     const TrainLayout L = train_layout(dims_of(*params), N, 1);
-    if (!ws_fits(L, workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
+    if (!train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return train_forward(TrainGraphSrc{v, a, out, nullptr}, params, train, nullptr, 1, N, workspace, L, stream);
 }
 
 extern "C" int et_stgcnn_backward_scenes(const et_stgcnn_params *params, int64_t N, const int32_t *scene_offsets,
                                          int n_scenes, const float *d_out, float *grads, int64_t grads_floats,
                                          void *workspace, size_t workspace_bytes, et_stream_t stream) {
-    const int rc = check_train_params(params);
+    int rc = check_train_params(params);
     if (rc != ET_OK) return rc;
     const Dims D = dims_of(*params);
-    if (N < 0 || N > INT32_MAX || n_scenes < 0 || !grads || grads_floats < grad_off(D).total) return ET_ERR_INVALID_ARG;
-    if (scene_offsets ? (n_scenes == 0 && N != 0) : N > ET_SCENE_MAX_N) return ET_ERR_INVALID_ARG;
+    rc = backward_args_status(N, scene_offsets, n_scenes, ET_SCENE_MAX_N, d_out, grads, grads_floats, grad_off(D).total);
+    if (rc != ET_OK) return rc;
     const int ns = scene_offsets ? n_scenes : 1;
     const TrainLayout L = train_layout(D, N, ns);
-    if (N > 0 && !d_out) return ET_ERR_INVALID_ARG;
-    if (N > 0 && !ws_fits(L, workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
+    if (N > 0 && !train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return train_backward(TrainScenesSrc{nullptr, nullptr, N, nullptr, d_out}, params, scene_offsets, ns, N, grads, workspace,
                           L, stream);
 }
 
 extern "C" int et_stgcnn_backward_graph(const et_stgcnn_params *params, int64_t N, const float *d_out, float *grads,
                                         int64_t grads_floats, void *workspace, size_t workspace_bytes, et_stream_t stream) {
-    const int rc = check_train_params(params);
+    int rc = check_train_params(params);
     if (rc != ET_OK) return rc;
     const Dims D = dims_of(*params);
-    if (N < 0 || N > ET_SCENE_MAX_N || !grads || grads_floats < grad_off(D).total) return ET_ERR_INVALID_ARG;
+    rc = backward_args_status(N, nullptr, 0, ET_SCENE_MAX_N, d_out, grads, grads_floats, grad_off(D).total);
+    if (rc != ET_OK) return rc;
     const TrainLayout L = train_layout(D, N, 1);
-    if (N > 0 && !d_out) return ET_ERR_INVALID_ARG;
-    if (N > 0 && !ws_fits(L, workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
+    if (N > 0 && !train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return train_backward(TrainGraphSrc{nullptr, nullptr, nullptr, d_out}, params, nullptr, 1, N, grads, workspace, L, stream);
 }

@@ -1,7 +1,7 @@
-// et_train_sums.inl -- the fixed-order sums and the small backward pieces that the scene training units share
-// (et_stgcnn_train.hip, et_dmrgcn_train.hip), #included inside their anonymous namespaces after et_stgcnn_core.inl
-// (kSgThreads).  The statements are et_stgcnn_train.hip's, moved here unchanged; its header comment ("wave_sum") gives the
-// order of every sum.
+// et_train_sums.inl -- the fixed-order sums, the small backward pieces and the tail (the scenes' gradient reduce, the
+// backward entries' argument check) that the scene training units share (et_stgcnn_train.hip, et_dmrgcn_train.hip),
+// #included inside their anonymous namespaces after et_stgcnn_core.inl (kSgThreads).  The statements are
+// et_stgcnn_train.hip's, moved here unchanged; its header comment ("wave_sum") gives the order of every sum.
 constexpr int kTrWaves = kSgThreads / kWave;
 
 // header comment: "wave_sum".  Called by all 64 lanes of a wavefront with the same count; every lane gets the sum.
@@ -65,4 +65,47 @@ __device__ __forceinline__ void wave_sum_taps(float *dst, int count, F f) {
         for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
         if ((threadIdx.x & (kWave - 1)) == 0) dst[t] = v;
     }
+}
+
+// grads[e] = the scenes' partials (scene s's G floats at partials + s * G) in ascending order, the first live one copied
+// (et_stgcnn_train.hip's header comment: "scenes"); a scene is live with 1 to max_n pedestrians; no live scene: +0
+__global__ __launch_bounds__(kSgThreads) void scene_grad_reduce_kernel(const float *__restrict__ partials, int64_t G,
+                                                                       int max_n, const int32_t *__restrict__ off,
+                                                                       int n_scenes, int64_t N, float *grads) {
+    const int64_t i = (int64_t)blockIdx.x * kSgThreads + threadIdx.x;
+    if (i >= G) return;
+    float acc = 0.f;
+    bool first = true;
+    for (int s = 0; s < n_scenes; ++s) {
+        const int64_t n = off ? (int64_t)off[s + 1] - off[s] : N;
+        if (n < 1 || n > max_n) continue;
+        const float v = partials[s * G + i];
+        acc = first ? v : acc + v;
+        first = false;
+    }
+    grads[i] = acc;
+}
+
+// the last launch of a backward pass: ns scenes' partials -> grads (no scene when N = 0: every gradient +0)
+static int scene_grad_reduce(const float *partials, int64_t G, int max_n, const int32_t *off, int ns, int64_t N, float *grads,
+                             et_stream_t stream) {
+    hipLaunchKernelGGL(scene_grad_reduce_kernel, dim3((unsigned)ceil_div(G, kSgThreads)), dim3(kSgThreads), 0,
+                       (hipStream_t)stream, partials, G, max_n, off, N > 0 ? ns : 0, N, grads);
+    ET_LAUNCH_CHECK();
+    return ET_OK;
+}
+
+// a training workspace as its layout sizes it, in floats
+static inline bool train_ws_fits(int64_t total_floats, const void *workspace, size_t workspace_bytes) {
+    return workspace && workspace_bytes >= (size_t)total_floats * 4;
+}
+
+// The arguments of an et_*_backward_scenes / _graph entry point (the graph form: no offsets, n_scenes = 0), checked once
+// its parameters have passed: N rows in range, max_n the most that may come as one scene, grads of at least need floats,
+// d_out wherever there is a row.  -> ET_OK or ET_ERR_INVALID_ARG; the workspace is the caller's next check.
+static inline int backward_args_status(int64_t N, const int32_t *scene_offsets, int n_scenes, int max_n, const float *d_out,
+                                       const float *grads, int64_t grads_floats, int64_t need) {
+    if (N < 0 || N > INT32_MAX || n_scenes < 0 || !grads || grads_floats < need) return ET_ERR_INVALID_ARG;
+    if (scene_offsets ? (n_scenes == 0 && N != 0) : N > max_n) return ET_ERR_INVALID_ARG;
+    return N > 0 && !d_out ? ET_ERR_INVALID_ARG : ET_OK;
 }

@@ -40,6 +40,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from ._lib import _p
+from ._native_train import train_forward
 
 
 class _MultiRelationalGCN(nn.Module):
@@ -86,45 +87,14 @@ class _TPCNN(nn.Module):
             self.residual = None  # identity
 
 
-class _TrainForward(torch.autograd.Function):
-    """``forward(v, a, keep)`` in training mode with a backward pass.  Every parameter is an input, in ``named_parameters``
-    order, so autograd routes the gradients into ``.grad``; they are saved through ``save_for_backward`` with the training
-    workspace: the kernels read the weights in place, and an in-place change between forward and backward (an optimiser
-    step) is caught by autograd's version counters."""
-
-    @staticmethod
-    def forward(ctx, model, v, a, keep, *params):
-        from . import ops
-        et = model.et_params()  # the pointer table once: forward and backward see the same tensors
-        ws = ops.dmrgcn_train_workspace(model, v.shape[-1], et_params=et)
-        out = ops.dmrgcn_train_forward_graph(model, v, a, ws, keep=keep, et_params=et)
-        ctx.model, ctx.et = model, et
-        ctx.save_for_backward(*params) if ws is None else ctx.save_for_backward(ws, *params)
-        ctx.has_ws = ws is not None
-        ctx.set_materialize_grads(False)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_out):
-        need = ctx.needs_input_grad
-        if g_out is None:
-            return (None,) * len(need)
-        from . import ops
-        model = ctx.model
-        ws = ctx.saved_tensors[0] if ctx.has_ws else None
-        params = ctx.saved_tensors[1 if ctx.has_ws else 0:]
-        if any(p.data_ptr() != q.data_ptr() for p, q in zip(params, model.parameters())):
-            raise RuntimeError("SocialDMRGCN: a parameter tensor was replaced between forward and backward")
-        views = ops.dmrgcn_grad_views(model, ops.dmrgcn_backward_graph(model, ws, g_out, et_params=ctx.et))
-        return (None, None, None, None, *(g if wanted else None for g, wanted in zip(views.values(), need[4:])))
-
-
 class SocialDMRGCN(nn.Module):
     r"""baseline/dmrgcn/predictor.py's ``social_dmrgcn`` (eval-mode inference on the GPU).  ``forward(v, a)``: v (1, 1, K, N),
     a (1, 2, K, N, N) as the dmrgcn bridge's pre-hook builds them -> ``(out (1, S, k, N), a)``; the post-hook takes [0]."""
 
     native_training = False  # a plain attribute, set per instance by eigentrajectory_amd.enable_native_training
+    #: how enable_native_training ends its refusal of an instance outside the native family
+    trains_natively = ("LBEBM, PECNet, SocialImplicitLight, SGCN, SocialSTGCNN and a SocialDMRGCN with n_stgcn = 1 and no dropout train "
+                       "natively")
     drop_edge_percent = 0.8  # dmrgcn.py:68: drop_edge(A, 0.8, self.training) keeps an entry where ~(rand > 0.8)
 
     def __init__(self, n_stgcn=1, n_tpcnn=4, input_feat=2, output_feat=5, seq_len=8, pred_seq_len=12, kernel_size=3):
@@ -196,6 +166,18 @@ class SocialDMRGCN(nn.Module):
         draws = [torch.rand(shape, device=device, generator=generator) for _ in range(2)]
         return torch.cat([~(d > self.drop_edge_percent) for d in draws]).to(torch.uint8)
 
+    native_parameters = nn.Module.parameters  # what :mod:`._native_train` differentiates: every parameter
+
+    def native_forward(self, et, v, a, keep):
+        from . import ops
+        ws = ops.dmrgcn_train_workspace(self, v.shape[-1], et_params=et)
+        return ops.dmrgcn_train_forward_graph(self, v, a, ws, keep=keep, et_params=et), (() if ws is None else (ws,))
+
+    def native_backward(self, et, kept, g_out):
+        from . import ops
+        ws = kept[0] if kept else None
+        return ops.dmrgcn_grad_views(self, ops.dmrgcn_backward_graph(self, ws, g_out, et_params=et)).values()
+
     def forward(self, v, a, keep=None):
         if self.training and self.native_training and self.outside_native_training() is None:
             if v.requires_grad or a.requires_grad:
@@ -205,7 +187,7 @@ class SocialDMRGCN(nn.Module):
             v, a = (L.on_device(t, dev) for t in (v, a))
             if keep is None:
                 keep = self.draw_keep(v.shape[-1], dev)
-            return _TrainForward.apply(self, v, a, keep, *self.parameters()), a
+            return train_forward(self, v, a, keep), a
         if self.training:
             raise RuntimeError("SocialDMRGCN: only inference is native (no drop_edge, no dropout); training-mode forward and "
                                "backward are not implemented -- call .eval() first")

@@ -50,6 +50,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from ._lib import _p
+from ._native_train import train_forward
 from .sgcn import SGCN
 from .stgcnn import SocialSTGCNN
 
@@ -81,39 +82,6 @@ class _GroupIntegrator(nn.Module):
                                                                     padding=(1, 0)))
 
 
-class _TrainForward(torch.autograd.Function):
-    """``forward(v_abs, v_rel)`` with a backward pass, as :class:`eigentrajectory_amd.sgcn._TrainForward`: every parameter of
-    the whole ``GPGraph`` is an input, in ``named_parameters`` order, and is saved with the training workspace; the kernels
-    read the weights in place, and an in-place change between forward and backward is caught by autograd's version
-    counters."""
-
-    @staticmethod
-    def forward(ctx, model, v_abs, v_rel, *params):
-        from . import ops
-        et = model.et_params()  # the pointer table once: forward and backward see the same tensors
-        ws = ops.gpgraph_sgcn_train_workspace(model, v_abs.shape[3], et_params=et)
-        out, idx = ops.gpgraph_sgcn_train_forward_graph(model, v_abs, v_rel, ws, et_params=et)
-        ctx.model, ctx.et = model, et
-        ctx.save_for_backward(ws, *params)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(idx)
-        return out, idx
-
-    @staticmethod
-    def backward(ctx, g_out, _g_idx):
-        need = ctx.needs_input_grad
-        if g_out is None:
-            return (None,) * len(need)
-        from . import ops
-        model = ctx.model
-        ws = ctx.saved_tensors[0]
-        params = ctx.saved_tensors[1:]
-        if any(p.data_ptr() != q.data_ptr() for p, q in zip(params, model.parameters())):
-            raise RuntimeError("GPGraph: a parameter tensor was replaced between forward and backward")
-        views = ops.gpgraph_sgcn_grad_views(model, ops.gpgraph_sgcn_backward_graph(model, ws, g_out, et_params=ctx.et))
-        return (None, None, None, *(g if wanted else None for g, wanted in zip(views.values(), need[3:])))
-
-
 class GPGraph(nn.Module):
     r"""model_groupwrapper.py's ``GPGraph`` (baseline/gpgraphsgcn and baseline/gpgraphstgcnn: the same class) around an
     :class:`SGCN` (``position_channel=True``) or a :class:`SocialSTGCNN` (``graph_per_time_row=True``) base (eval-mode
@@ -121,6 +89,9 @@ class GPGraph(nn.Module):
 
     TAU = 0.1  # GroupGenerator.forward's default temperature; GPGraph.forward does not pass another
     native_training = False  # a plain attribute, set per instance by eigentrajectory_amd.enable_native_training
+    #: how enable_native_training ends its refusal of an instance outside the native family
+    trains_natively = ("LBEBM, PECNet, SocialImplicitLight, SGCN and a GPGraph in the ET configuration around "
+                       "SGCN(position_channel=True, dropout=0) train natively")
 
     def __init__(self, baseline_model, in_channels=2, out_channels=5, obs_seq_len=8, pred_seq_len=12,
                  d_type="learned_l2norm", d_th="learned", mix_type="mlp", group_type=None, weight_share=True):
@@ -206,6 +177,17 @@ class GPGraph(nn.Module):
         p.mix_a, p.mix_w, p.mix_b = _p(act.weight), _p(mix.weight), _p(mix.bias)
         return p, dev
 
+    native_parameters = nn.Module.parameters  # what :mod:`._native_train` differentiates: every parameter, the base's too
+
+    def native_forward(self, et, v_abs, v_rel):
+        from . import ops
+        ws = ops.gpgraph_sgcn_train_workspace(self, v_abs.shape[3], et_params=et)
+        return ops.gpgraph_sgcn_train_forward_graph(self, v_abs, v_rel, ws, et_params=et), (ws,)  # (v, the indices)
+
+    def native_backward(self, et, kept, g_out):
+        from . import ops
+        return ops.gpgraph_sgcn_grad_views(self, ops.gpgraph_sgcn_backward_graph(self, kept[0], g_out, et_params=et)).values()
+
     def forward(self, v_abs, v_rel):
         if self.training and self.native_training and self.outside_native_training() is None:
             if v_abs.requires_grad or v_rel.requires_grad:
@@ -213,7 +195,7 @@ class GPGraph(nn.Module):
                                    "input requires one")
             dev = L.module_device("GPGraph", self)
             v_abs, v_rel = (L.on_device(t, dev) for t in (v_abs, v_rel))
-            return _TrainForward.apply(self, v_abs, v_rel, *self.parameters())
+            return train_forward(self, v_abs, v_rel)
         self._check_mode()
         from . import ops
         if self.stgcnn_base:

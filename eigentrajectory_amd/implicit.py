@@ -47,6 +47,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from ._native_train import train_forward
 
 
 class _SocialCellLocal(nn.Module):
@@ -79,44 +80,6 @@ class _SocialCellGlobal(nn.Module):
 
 
 _TENSORS = ("feat", "highway_input", "highway", "tpcnn")
-
-
-class _TrainForward(torch.autograd.Function):
-    """``forward(v)`` with a backward pass.  Every parameter of every cell is an input, in :meth:`cell_parameters`' order, so
-    autograd routes the gradients into ``.grad``; they are saved through ``save_for_backward`` with ``v`` and the workspace
-    that holds the neighbour table: the kernels read the weights in place, and an in-place change between forward and
-    backward (an optimiser step) is caught by autograd's version counters."""
-
-    @staticmethod
-    def forward(ctx, model, v, *params):
-        from . import ops
-        et = model.et_params()  # the pointer table once: forward and backward see the same tensors and bins
-        v = L.on_device(v, et[1])
-        ws = ops.implicit_workspace(model, v.shape[-1], et_params=et)
-        out = ops.implicit_forward_graph(model, v, workspace=ws, et_params=et)
-        ctx.model, ctx.et = model, et
-        ctx.has_ws = ws is not None
-        ctx.save_for_backward(v, *(() if ws is None else (ws,)), *params)
-        ctx.set_materialize_grads(False)
-        return out
-
-    @staticmethod
-    def backward(ctx, g_out):
-        need = ctx.needs_input_grad
-        if g_out is None:
-            return (None,) * len(need)
-        from . import ops
-        model = ctx.model
-        v = ctx.saved_tensors[0]
-        ws = ctx.saved_tensors[1] if ctx.has_ws else None
-        params = ctx.saved_tensors[1 + ctx.has_ws:]
-        if any(p.data_ptr() != q.data_ptr() for p, q in zip(params, model.cell_parameters())):
-            raise RuntimeError("SocialImplicitLight: a parameter tensor was replaced between forward and backward")
-        views = ops.implicit_grad_views(model, ops.implicit_backward_graph(model, v, ws, g_out, et_params=ctx.et))
-        zero = torch.zeros((len(model.implicit_cells), 1), device=v.device)  # noise_w: an exact zero each, one fill
-        grads = [views[name] if name in views else zero[int(name.split(".")[1])]
-                 for name in model.cell_parameter_names()]
-        return (None, None, *(g if wanted else None for g, wanted in zip(grads, need[2:])))
 
 
 class SocialImplicitLight(nn.Module):
@@ -178,12 +141,27 @@ class SocialImplicitLight(nn.Module):
         own = dict(self.named_parameters())
         return [own[name] for name in self.cell_parameter_names()]
 
+    native_parameters = cell_parameters  # what :mod:`._native_train` differentiates
+
+    def native_forward(self, et, v):
+        from . import ops
+        v = L.on_device(v, et[1])
+        ws = ops.implicit_workspace(self, v.shape[-1], et_params=et)  # (holds the neighbour table for the backward)
+        return ops.implicit_forward_graph(self, v, workspace=ws, et_params=et), (v, *(() if ws is None else (ws,)))
+
+    def native_backward(self, et, kept, g_out):
+        from . import ops
+        v, ws = kept if len(kept) == 2 else (kept[0], None)
+        views = ops.implicit_grad_views(self, ops.implicit_backward_graph(self, v, ws, g_out, et_params=et))
+        zero = torch.zeros((len(self.implicit_cells), 1), device=v.device)  # noise_w: an exact zero each, one fill
+        return [views[name] if name in views else zero[int(name.split(".")[1])] for name in self.cell_parameter_names()]
+
     def forward(self, v):
         if self.training and self.native_training:
             if v.requires_grad:
                 raise RuntimeError("SocialImplicitLight: no input gradient is built (the implicit bridge detaches v); v "
                                    "requires one")
-            return _TrainForward.apply(self, v, *self.cell_parameters())
+            return train_forward(self, v)
         if self.training:
             raise RuntimeError("SocialImplicitLight: only inference is native; training-mode forward and backward are not "
                                "implemented -- call .eval() first")

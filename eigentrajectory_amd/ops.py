@@ -300,13 +300,21 @@ def _scene_batch(who, dev, C_obs, nrm, k, scene_sizes):
     if len(cs) != 2 or cs[0] != k or len(ns) != 2 or ns[0] < 2 or ns[1] != cs[1]:
         raise ValueError(f"{who}: C_obs {tuple(cs)} / nrm {tuple(ns)} are not (k, N) / (2 or more, N) with k = {k}")
     n = cs[1]
-    if scene_sizes is None:
-        return _SceneBatch(C_obs, nrm, n, [n], None, 0, n)
-    sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
+    sizes, off, n_scenes = _scene_sizes(scene_sizes, n, dev)
     if not sizes and n:
         raise ValueError(f"{who}: no scenes for {n} rows")
+    return _SceneBatch(C_obs, nrm, n, sizes, off, n_scenes, max(sizes, default=0))
+
+
+def _scene_sizes(scene_sizes, n, dev):
+    """``scene_sizes`` (list, integer tensor or None) for ``n`` rows -> (sizes, int32 offsets on ``dev``, n_scenes) as a
+    ``*_scenes`` entry point takes them: the one place that makes them.  None is one scene of all ``n`` rows and passes no
+    offsets: ([n], None, 0); an empty list passes the offsets [0]."""
+    if scene_sizes is None:
+        return [n], None, 0
+    sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
     off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
-    return _SceneBatch(C_obs, nrm, n, sizes, off, len(sizes), max(sizes, default=0))
+    return sizes, off, len(sizes)
 
 
 def _workspace(entry_name, dev, params, *args, required=False):
@@ -328,7 +336,58 @@ def _read_in_place(who, dev, tensors):
                              f"contiguous={t.is_contiguous()})")
 
 
+# ------------------------------------------------------ what the four scene-graph predictors' training wrappers share
+def _numel(t):
+    return 0 if t is None else t.numel()
+
+
+def _check_train_ws(who, dev, workspace, maker):
+    if workspace is None or workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise ValueError(f"{who}: workspace is not a contiguous uint8 tensor on {dev} ({maker} makes one)")
+
+
+def _backward_args(who, grad_floats_entry, params, dev, d_out, shape):
+    """The preamble of a ``*_backward_graph`` / ``_scenes`` wrapper: ``d_out`` checked against ``shape`` and made a contiguous
+    float32 tensor on ``dev`` -> (d_out, the empty flat gradient buffer, sized by ``grad_floats_entry``)."""
+    if tuple(d_out.shape) != shape:
+        raise ValueError(f"{who}: d_out {tuple(d_out.shape)} is not {shape}")
+    d_out = d_out.detach()
+    if d_out.device != dev or d_out.dtype != torch.float32 or not d_out.is_contiguous():
+        d_out = d_out.to(device=dev, dtype=torch.float32).contiguous()
+    size = int(getattr(L.lib(), grad_floats_entry)(C.byref(params)))
+    if not size:
+        L.check(3, grad_floats_entry)
+    return d_out, torch.empty((size,), device=dev)
+
+
+def _grad_views(who, model, grads):
+    out, at, size = {}, 0, grads.numel()
+    for name, t in model.named_parameters():
+        k = t.numel()
+        if at + k <= size:   # (a short buffer is refused below, with the count it should have)
+            out[name] = grads[at:at + k].view(t.shape)
+        at += k
+    if at != size:
+        raise ValueError(f"{who}: {size} floats for parameters of {at}")
+    return out
+
+
+def _layout(entry, n_fields, params, *args):
+    """-> the ``n_fields`` offsets of a training workspace as ``entry``, an ``et_*_train_layout``, gives them for ``args``"""
+    o = (C.c_int64 * n_fields)()
+    L.call(entry, C.byref(params), *args, o, n_fields)
+    return [int(x) for x in o]
+
+
 # ------------------------------------------------------------------------ Social-STGCNN predictor (inference)
+def _stgcnn_graph_args(who, params, dev, v, a):
+    """v (1, 1, K, N) and a (K, N, N) of a graph-form call, checked and on ``dev`` -> (v, a, N)"""
+    K, n = params.seq_len, v.shape[-1]
+    if tuple(v.shape) != (1, 1, K, n) or tuple(a.shape) != (K, n, n):
+        raise ValueError(f"{who}: v {tuple(v.shape)} / a {tuple(a.shape)} are not (1,1,{K},N) / ({K},N,N)")
+    return (*_dev_args(dev, v.detach(), a.detach()), n)
+
+
 def stgcnn_forward_graph(model, v, a):
     """``model`` (:class:`eigentrajectory_amd.stgcnn.SocialSTGCNN`, eval mode) on one scene as the stgcnn bridge hands it
     over: v (1, 1, K, N), a (K, N, N) -> the raw output (1, S, k, N).  One launch."""
@@ -336,12 +395,8 @@ def stgcnn_forward_graph(model, v, a):
         raise NotImplementedError("stgcnn_forward_graph: a per-time-row SocialSTGCNN (graph_per_time_row=True) runs only inside "
                                   "GPGraphSTGCNN")
     params, dev = model.et_params()
-    K, k, S = params.seq_len, params.pred_seq_len, params.output_feat
-    n = v.shape[-1]
-    if tuple(v.shape) != (1, 1, K, n) or tuple(a.shape) != (K, n, n):
-        raise ValueError(f"stgcnn_forward_graph: v {tuple(v.shape)} / a {tuple(a.shape)} are not (1,1,{K},N) / ({K},N,N)")
-    v, a = _dev_args(dev, v, a)
-    out = torch.empty((1, S, k, n), device=dev)
+    v, a, n = _stgcnn_graph_args("stgcnn_forward_graph", params, dev, v, a)
+    out = torch.empty((1, params.output_feat, params.pred_seq_len, n), device=dev)
     ws, nbytes = _workspace("et_stgcnn_workspace_bytes", dev, params, n, n)
     L.call("et_stgcnn_forward_graph", C.byref(params), L.ptr(v), L.ptr(a), n, L.ptr(out), L.ptr(ws), nbytes, L.stream(dev))
     return out
@@ -366,10 +421,12 @@ def stgcnn_forward_scenes(model, C_obs, nrm, scene_sizes=None):
 
 # ------------------------------------------------------------------------ Social-STGCNN predictor (training)
 def _stgcnn_train_params(who, model, et_params):
+    if et_params is not None:   # the training Function's calls: its forward() has looked at the family already
+        return et_params
     why = model.outside_native_training()
     if why is not None:
         raise NotImplementedError(f"{who}: SocialSTGCNN has no native backward pass outside its native family: {why}")
-    return et_params or model.et_params()
+    return model.et_params()
 
 
 def stgcnn_train_workspace(model, n, n_scenes=1, et_params=None):
@@ -379,29 +436,19 @@ def stgcnn_train_workspace(model, n, n_scenes=1, et_params=None):
     return _workspace("et_stgcnn_train_workspace_bytes", dev, params, n, max(n_scenes, 1), required=n > 0)[0]
 
 
-def _stgcnn_check_ws(who, dev, workspace):
-    if workspace is None or workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise ValueError(f"{who}: workspace is not a contiguous uint8 tensor on {dev} (stgcnn_train_workspace makes one)")
-
-
 def stgcnn_train_forward_graph(model, v, a, workspace, et_params=None):
     """``model`` in training mode on one scene as the stgcnn bridge hands it over: v (1, 1, K, N), a (K, N, N) -> the raw
     output (1, S, k, N).  The three BatchNorms use the scene's batch statistics, and their running statistics and
     ``num_batches_tracked`` are updated in place; every intermediate stays in ``workspace`` (of
     :func:`stgcnn_train_workspace`) for :func:`stgcnn_backward_graph`.  Two launches."""
     params, dev = _stgcnn_train_params("stgcnn_train_forward_graph", model, et_params)
-    K, k, S = params.seq_len, params.pred_seq_len, params.output_feat
-    n = v.shape[-1]
-    if tuple(v.shape) != (1, 1, K, n) or tuple(a.shape) != (K, n, n):
-        raise ValueError(f"stgcnn_train_forward_graph: v {tuple(v.shape)} / a {tuple(a.shape)} are not (1,1,{K},N) / "
-                         f"({K},N,N)")
-    v, a = _dev_args(dev, v.detach(), a.detach())
-    out = torch.empty((1, S, k, n), device=dev)
+    v, a, n = _stgcnn_graph_args("stgcnn_train_forward_graph", params, dev, v, a)
+    out = torch.empty((1, params.output_feat, params.pred_seq_len, n), device=dev)
     if n:
-        _stgcnn_check_ws("stgcnn_train_forward_graph", dev, workspace)
+        _check_train_ws("stgcnn_train_forward_graph", dev, workspace, "stgcnn_train_workspace")
     train = model.et_train_state()
     L.call("et_stgcnn_train_forward_graph", C.byref(params), C.byref(train), L.ptr(v), L.ptr(a), n, L.ptr(out),
-           L.ptr(workspace), workspace.numel() if workspace is not None else 0, L.stream(dev))
+           L.ptr(workspace), _numel(workspace), L.stream(dev))
     return out
 
 
@@ -416,11 +463,11 @@ def stgcnn_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, workspace=N
     if workspace is None:
         workspace = stgcnn_train_workspace(model, b.n, len(b.sizes), et_params=(params, dev))
     if b.n:
-        _stgcnn_check_ws("stgcnn_train_forward_scenes", dev, workspace)
+        _check_train_ws("stgcnn_train_forward_scenes", dev, workspace, "stgcnn_train_workspace")
     out = torch.empty((params.pred_seq_len, b.n, params.output_feat), device=dev)
     train = model.et_train_state()
     L.call("et_stgcnn_train_forward_scenes", C.byref(params), C.byref(train), L.ptr(b.C_obs), L.ptr(b.nrm), b.n, L.ptr(b.off),
-           b.n_scenes, L.ptr(out), L.ptr(workspace), workspace.numel() if workspace is not None else 0, L.stream(dev))
+           b.n_scenes, L.ptr(out), L.ptr(workspace), _numel(workspace), L.stream(dev))
     return out, workspace
 
 
@@ -428,25 +475,7 @@ def stgcnn_grad_views(model, grads):
     """``grads``, the flat buffer of :func:`stgcnn_backward_graph` / ``_scenes`` -> {state_dict key: a view of it shaped like
     the parameter}, every parameter of ``model`` (state_dict order; the unused tail ``tpcnns[n_txpcnn-1]`` /
     ``prelus[n_txpcnn-1]`` holds exact zeros)."""
-    out, at = {}, 0
-    for name, t in model.named_parameters():
-        out[name] = grads[at:at + t.numel()].view(t.shape)
-        at += t.numel()
-    if at != grads.numel():
-        raise ValueError(f"stgcnn_grad_views: {grads.numel()} floats for parameters of {at}")
-    return out
-
-
-def _stgcnn_grads(who, params, dev, d_out, shape):
-    if tuple(d_out.shape) != shape:
-        raise ValueError(f"{who}: d_out {tuple(d_out.shape)} is not {shape}")
-    d_out = d_out.detach()
-    if d_out.device != dev or d_out.dtype != torch.float32 or not d_out.is_contiguous():
-        d_out = d_out.to(device=dev, dtype=torch.float32).contiguous()
-    size = int(L.lib().et_stgcnn_grad_floats(C.byref(params)))
-    if not size:
-        L.check(3, "et_stgcnn_grad_floats")
-    return d_out, torch.empty((size,), device=dev)
+    return _grad_views("stgcnn_grad_views", model, grads)
 
 
 def stgcnn_backward_graph(model, workspace, d_out, et_params=None):
@@ -455,11 +484,12 @@ def stgcnn_backward_graph(model, workspace, d_out, et_params=None):
     (:func:`stgcnn_grad_views` names its parts)."""
     params, dev = _stgcnn_train_params("stgcnn_backward_graph", model, et_params)
     n = d_out.shape[-1] if d_out.dim() == 4 else -1
-    d_out, grads = _stgcnn_grads("stgcnn_backward_graph", params, dev, d_out, (1, params.output_feat, params.pred_seq_len, n))
+    d_out, grads = _backward_args("stgcnn_backward_graph", "et_stgcnn_grad_floats", params, dev, d_out,
+                                  (1, params.output_feat, params.pred_seq_len, n))
     if n:
-        _stgcnn_check_ws("stgcnn_backward_graph", dev, workspace)
+        _check_train_ws("stgcnn_backward_graph", dev, workspace, "stgcnn_train_workspace")
     L.call("et_stgcnn_backward_graph", C.byref(params), n, L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace),
-           workspace.numel() if workspace is not None else 0, L.stream(dev))
+           _numel(workspace), L.stream(dev))
     return grads
 
 
@@ -469,17 +499,13 @@ def stgcnn_backward_scenes(model, workspace, d_out, scene_sizes=None):
     summed over the scenes in ascending order."""
     params, dev = _stgcnn_train_params("stgcnn_backward_scenes", model, None)
     n = d_out.shape[1] if d_out.dim() == 3 else -1
-    d_out, grads = _stgcnn_grads("stgcnn_backward_scenes", params, dev, d_out, (params.pred_seq_len, n, params.output_feat))
-    if scene_sizes is None:
-        off, n_scenes = None, 0
-    else:
-        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
-        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
-        n_scenes = len(sizes)
+    d_out, grads = _backward_args("stgcnn_backward_scenes", "et_stgcnn_grad_floats", params, dev, d_out,
+                                  (params.pred_seq_len, n, params.output_feat))
+    _, off, n_scenes = _scene_sizes(scene_sizes, n, dev)
     if n:
-        _stgcnn_check_ws("stgcnn_backward_scenes", dev, workspace)
+        _check_train_ws("stgcnn_backward_scenes", dev, workspace, "stgcnn_train_workspace")
     L.call("et_stgcnn_backward_scenes", C.byref(params), n, L.ptr(off), n_scenes, L.ptr(d_out), L.ptr(grads), grads.numel(),
-           L.ptr(workspace), workspace.numel() if workspace is not None else 0, L.stream(dev))
+           L.ptr(workspace), _numel(workspace), L.stream(dev))
     return grads
 
 
@@ -496,11 +522,8 @@ def stgcnn_train_views(model, workspace, n, n_scenes=1, lo=0, scene=0, scene_n=N
     K, k, S = params.seq_len, params.pred_seq_len, params.output_feat
     m = n if scene_n is None else scene_n
     f = workspace.view(torch.float32)
-    o = (C.c_int64 * L.STGCNN_TRAIN_LAYOUT_FIELDS)()
-    L.call("et_stgcnn_train_layout", C.byref(params), n, n_scenes, o, L.STGCNN_TRAIN_LAYOUT_FIELDS)
-    o = [int(x) for x in o]
     (o_u, o_d, o_p, o_g, o_a1, o_y, o_t, o_r, o_s, o_x, o_tp, o_dfin, o_dtp, o_dx, o_ds, o_dt, o_dr, o_dy, o_da1, o_dg, per,
-     o_stats, stat_stride, o_part, G, _) = o
+     o_stats, stat_stride, o_part, G, _) = _layout("et_stgcnn_train_layout", L.STGCNN_TRAIN_LAYOUT_FIELDS, params, n, n_scenes)
     base = lo * per
     fld = lambda off, *shape: f[base + off * m:base + off * m + math.prod(shape) * m].view(*shape, m)
     A = max(1, params.n_txpcnn - 1)
@@ -525,6 +548,21 @@ def _sgcn_logits(want, T, n, sum_n2, dev):
     return torch.empty((4 * T * sum_n2,), device=dev), torch.empty((n * 4 * T * T,), device=dev)
 
 
+def _sgcn_graph_args(who, params, dev, v, identity):
+    """v (1, T, N, 1) and the two identities of a graph-form call, checked (they are read in place) -> (id_s, id_t, N)"""
+    T = params.obs_len
+    id_s, id_t = identity
+    n = v.shape[2] if v.dim() == 4 else -1
+    if (tuple(v.shape) != (1, T, n, 1) or tuple(id_s.shape) not in ((1, n, n), (T, n, n))
+            or tuple(id_t.shape) not in ((n, 1, 1), (n, T, T))):
+        raise ValueError(f"{who}: v {tuple(v.shape)} / identity {tuple(id_s.shape)}, {tuple(id_t.shape)} are not "
+                         f"(1,{T},N,1) / (1 or {T},N,N), (N,1,1) or (N,{T},{T})")
+    _read_in_place(who, dev, {"v": v, "identity[0]": id_s, "identity[1]": id_t})
+    if n > L.SGCN_MAX_N:
+        raise ValueError(f"{who}: N = {n} exceeds the {L.SGCN_MAX_N} pedestrians a scene may have")
+    return id_s, id_t, n
+
+
 def sgcn_forward_graph(model, v, identity, want_logits=False):
     """``model`` (:class:`eigentrajectory_amd.sgcn.SGCN`, eval mode) on one scene as the sgcn bridge hands it over: v
     (1, T, N, 1), identity = [spatial (1 or T, N, N), temporal (N, 1, 1) or (N, T, T)] -> (pred_len, N, out_dims); with
@@ -535,15 +573,7 @@ def sgcn_forward_graph(model, v, identity, want_logits=False):
         raise NotImplementedError("sgcn_forward_graph: a two-channel SGCN (position_channel=True) runs only inside GPGraphSGCN")
     params, dev = model.et_params()
     T, k, S = params.obs_len, params.pred_len, params.out_dims
-    id_s, id_t = identity
-    n = v.shape[2] if v.dim() == 4 else -1
-    if (tuple(v.shape) != (1, T, n, 1) or tuple(id_s.shape) not in ((1, n, n), (T, n, n))
-            or tuple(id_t.shape) not in ((n, 1, 1), (n, T, T))):
-        raise ValueError(f"sgcn_forward_graph: v {tuple(v.shape)} / identity {tuple(id_s.shape)}, {tuple(id_t.shape)} are not "
-                         f"(1,{T},N,1) / (1 or {T},N,N), (N,1,1) or (N,{T},{T})")
-    _read_in_place("sgcn_forward_graph", dev, {"v": v, "identity[0]": id_s, "identity[1]": id_t})
-    if n > L.SGCN_MAX_N:
-        raise ValueError(f"sgcn_forward_graph: N = {n} exceeds the {L.SGCN_MAX_N} pedestrians a scene may have")
+    id_s, id_t, n = _sgcn_graph_args("sgcn_forward_graph", params, dev, v, identity)
     out = torch.empty((k, n, S), device=dev)
     ls, lt = _sgcn_logits(want_logits, T, n, n * n, dev)
     ws, nbytes = _workspace("et_sgcn_workspace_bytes", dev, params, n, n * n, 1)
@@ -578,11 +608,13 @@ def sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_logits=False):
 
 # ------------------------------------------------------------------------------ SGCN predictor (training)
 def _sgcn_train_params(who, model, et_params):
+    if et_params is not None:   # the training Function's calls: its forward() has looked at the family already
+        return et_params
     if getattr(model, "position_channel", False):
         raise NotImplementedError(f"{who}: a two-channel SGCN (position_channel=True) has no native backward pass")
     if model.dropout != 0:
         raise RuntimeError(f"{who}: dropout = {model.dropout} is not implemented natively; construct with dropout=0")
-    return et_params or model.et_params()
+    return model.et_params()
 
 
 def sgcn_train_workspace(model, n, sum_n2=None, n_scenes=1, et_params=None):
@@ -593,27 +625,14 @@ def sgcn_train_workspace(model, n, sum_n2=None, n_scenes=1, et_params=None):
                       required=n > 0)[0]
 
 
-def _sgcn_check_ws(who, dev, workspace):
-    if workspace is None or workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise ValueError(f"{who}: workspace is not a contiguous uint8 tensor on {dev} (sgcn_train_workspace makes one)")
-
-
 def sgcn_train_forward_graph(model, v, identity, workspace, want_logits=False, et_params=None):
     """:func:`sgcn_forward_graph` with the kept layout (the same kernels; the output is bit-equal): every asymmetric layer's
     input, the softmax row records, A_t, f1, f2, ts and the tail's activations stay in ``workspace`` (of
     :func:`sgcn_train_workspace`) for :func:`sgcn_backward_graph`."""
     params, dev = _sgcn_train_params("sgcn_train_forward_graph", model, et_params)
     T, k, S = params.obs_len, params.pred_len, params.out_dims
-    id_s, id_t = identity
-    n = v.shape[2] if v.dim() == 4 else -1
-    if (tuple(v.shape) != (1, T, n, 1) or tuple(id_s.shape) not in ((1, n, n), (T, n, n))
-            or tuple(id_t.shape) not in ((n, 1, 1), (n, T, T))):
-        raise ValueError(f"sgcn_train_forward_graph: v {tuple(v.shape)} / identity {tuple(id_s.shape)}, {tuple(id_t.shape)} are "
-                         f"not (1,{T},N,1) / (1 or {T},N,N), (N,1,1) or (N,{T},{T})")
-    _read_in_place("sgcn_train_forward_graph", dev, {"v": v, "identity[0]": id_s, "identity[1]": id_t})
-    if n > L.SGCN_MAX_N:
-        raise ValueError(f"sgcn_train_forward_graph: N = {n} exceeds the {L.SGCN_MAX_N} pedestrians a scene may have")
-    _sgcn_check_ws("sgcn_train_forward_graph", dev, workspace)
+    id_s, id_t, n = _sgcn_graph_args("sgcn_train_forward_graph", params, dev, v, identity)
+    _check_train_ws("sgcn_train_forward_graph", dev, workspace, "sgcn_train_workspace")
     out = torch.empty((k, n, S), device=dev)
     ls, lt = _sgcn_logits(want_logits, T, n, n * n, dev)
     L.call("et_sgcn_train_forward_graph", C.byref(params), L.ptr(v.detach()), L.ptr(id_s.detach()), int(id_s.shape[0]),
@@ -637,38 +656,18 @@ def sgcn_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_logits=F
     if workspace is None:
         workspace = sgcn_train_workspace(model, n, sum_n2, len(b.sizes), et_params=(params, dev))
     if n:
-        _sgcn_check_ws("sgcn_train_forward_scenes", dev, workspace)
+        _check_train_ws("sgcn_train_forward_scenes", dev, workspace, "sgcn_train_workspace")
     out = torch.empty((params.pred_len, n, params.out_dims), device=dev)
     ls, lt = _sgcn_logits(want_logits, params.obs_len, n, sum_n2, dev)
     L.call("et_sgcn_train_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), n, L.ptr(b.off), b.n_scenes, sum_n2,
-           b.max_n, L.ptr(out), L.ptr(ls), L.ptr(lt), L.ptr(workspace), workspace.numel() if workspace is not None else 0,
-           L.stream(dev))
+           b.max_n, L.ptr(out), L.ptr(ls), L.ptr(lt), L.ptr(workspace), _numel(workspace), L.stream(dev))
     return (out, ls, lt, workspace) if want_logits else (out, workspace)
 
 
 def sgcn_grad_views(model, grads):
     """``grads``, the flat buffer of :func:`sgcn_backward_graph` / ``_scenes`` -> {state_dict key: a view of it shaped like
     the parameter}, every parameter of ``model`` (state_dict order)."""
-    out, at = {}, 0
-    for name, t in model.named_parameters():
-        out[name] = grads[at:at + t.numel()].view(t.shape)
-        at += t.numel()
-    if at != grads.numel():
-        raise ValueError(f"sgcn_grad_views: {grads.numel()} floats for parameters of {at}")
-    return out
-
-
-def _sgcn_grads(who, params, dev, d_out, n):
-    k, S = params.pred_len, params.out_dims
-    if tuple(d_out.shape) != (k, n, S):
-        raise ValueError(f"{who}: d_out {tuple(d_out.shape)} is not ({k},{n},{S})")
-    d_out = d_out.detach()
-    if d_out.device != dev or d_out.dtype != torch.float32 or not d_out.is_contiguous():
-        d_out = d_out.to(device=dev, dtype=torch.float32).contiguous()
-    size = int(L.lib().et_sgcn_grad_floats(C.byref(params)))
-    if not size:
-        L.check(3, "et_sgcn_grad_floats")
-    return d_out, torch.empty((size,), device=dev)
+    return _grad_views("sgcn_grad_views", model, grads)
 
 
 def sgcn_backward_graph(model, identity, workspace, d_out, et_params=None):
@@ -679,8 +678,9 @@ def sgcn_backward_graph(model, identity, workspace, d_out, et_params=None):
     id_s, id_t = identity
     n = id_s.shape[-1]
     _read_in_place("sgcn_backward_graph", dev, {"identity[0]": id_s, "identity[1]": id_t})
-    _sgcn_check_ws("sgcn_backward_graph", dev, workspace)
-    d_out, grads = _sgcn_grads("sgcn_backward_graph", params, dev, d_out, n)
+    _check_train_ws("sgcn_backward_graph", dev, workspace, "sgcn_train_workspace")
+    d_out, grads = _backward_args("sgcn_backward_graph", "et_sgcn_grad_floats", params, dev, d_out,
+                                  (params.pred_len, n, params.out_dims))
     L.call("et_sgcn_backward_graph", C.byref(params), L.ptr(id_s.detach()), int(id_s.shape[0]), L.ptr(id_t.detach()),
            int(id_t.shape[1]), n, L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace), workspace.numel(),
            L.stream(dev))
@@ -693,18 +693,14 @@ def sgcn_backward_scenes(model, workspace, d_out, scene_sizes=None):
     summed over the scenes in ascending order."""
     params, dev = _sgcn_train_params("sgcn_backward_scenes", model, None)
     n = d_out.shape[1] if d_out.dim() == 3 else -1
-    d_out, grads = _sgcn_grads("sgcn_backward_scenes", params, dev, d_out, n)
-    if scene_sizes is None:
-        sizes, off, n_scenes = [n], None, 0
-    else:
-        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
-        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
-        n_scenes = len(sizes)
+    d_out, grads = _backward_args("sgcn_backward_scenes", "et_sgcn_grad_floats", params, dev, d_out,
+                                  (params.pred_len, n, params.out_dims))
+    sizes, off, n_scenes = _scene_sizes(scene_sizes, n, dev)
     if n:
-        _sgcn_check_ws("sgcn_backward_scenes", dev, workspace)
+        _check_train_ws("sgcn_backward_scenes", dev, workspace, "sgcn_train_workspace")
     L.call("et_sgcn_backward_scenes", C.byref(params), n, L.ptr(off), n_scenes, sum(s * s for s in sizes),
-           max(sizes, default=0), L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace),
-           workspace.numel() if workspace is not None else 0, L.stream(dev))
+           max(sizes, default=0), L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace), _numel(workspace),
+           L.stream(dev))
     return grads
 
 
@@ -724,10 +720,8 @@ def sgcn_train_views(model, workspace, n, sum_n2=None, n_scenes=1, lo=0, sq=0, s
     N, n2 = n, n * n if sum_n2 is None else sum_n2
     m = N if scene_n is None else scene_n
     f = workspace.view(torch.float32)
-    o = (C.c_int64 * L.SGCN_TRAIN_LAYOUT_FIELDS)()
-    L.call("et_sgcn_train_layout", C.byref(params), N, n2, n_scenes, o, L.SGCN_TRAIN_LAYOUT_FIELDS)
     (o_v, o_rs, o_rt, o_xs, xs_stride, o_xt, xt_stride, o_at, o_f2, o_f1, o_ts, o_keep, KS, o_dat, o_df1, o_dts, o_df2, o_rrec,
-     o_gs, o_gt, o_dirs, o_dirt, o_dds, _) = (int(x) for x in o)
+     o_gs, o_gt, o_dirs, o_dirt, o_dds, _) = _layout("et_sgcn_train_layout", L.SGCN_TRAIN_LAYOUT_FIELDS, params, N, n2, n_scenes)
     sl = lambda off, cnt, *shape: f[off:off + cnt].view(*shape)
     rows = lambda off: sl(off + lo * 4 * T * T, m * 4 * T * T, m, 4, T, T)          # (n, 4, T, T) blocks
     feat = lambda off, *shape: sl(off + lo * 4 * T * 16, m * 4 * T * 16, *shape)     # 64 T floats per pedestrian
@@ -829,13 +823,15 @@ def gpgraph_sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_detail
 
 # ------------------------------------------------------------------------ GP-Graph-SGCN predictor (training)
 def _gpgraph_train_params(who, model, et_params):
+    if et_params is not None:   # the training Function's calls: its forward() has looked at the family already
+        return et_params
     if model.stgcnn_base:
         raise NotImplementedError(f"{who}: GP-Graph around SocialSTGCNN has no native backward pass (its per-time-row "
                                   "base with BatchNorm batch statistics has none)")
     if model.baseline_model.dropout != 0:
         raise RuntimeError(f"{who}: dropout = {model.baseline_model.dropout} is not implemented natively; construct the base "
                            "with dropout=0")
-    return et_params or model.et_params()
+    return model.et_params()
 
 
 def gpgraph_sgcn_train_workspace(model, n, sum_n2=None, n_scenes=1, et_params=None):
@@ -869,7 +865,7 @@ def gpgraph_sgcn_train_forward_graph(model, v_abs, v_rel, workspace, want_detail
     _read_in_place(who, dev, {"v_abs": v_abs, "v_rel": v_rel})
     if n > L.SGCN_MAX_N:
         raise ValueError(f"{who}: N = {n} exceeds the {L.SGCN_MAX_N} pedestrians a scene may have")
-    _sgcn_check_ws(who, dev, workspace)
+    _check_train_ws(who, dev, workspace, "gpgraph_sgcn_train_workspace")
     out = torch.empty((1, S, k, n), device=dev)
     gi, dist, ls, lt = _gpgraph_details(want_details, T, n, n * n, dev)
     L.call("et_gpgraph_sgcn_train_forward_graph", C.byref(params), L.ptr(v_abs.detach()), L.ptr(v_rel.detach()), n, L.ptr(out),
@@ -883,14 +879,6 @@ def gpgraph_sgcn_train_forward_graph(model, v_abs, v_rel, workspace, want_detail
            "logit_s": [ls[4 * T * m * n * n:4 * T * (m * n * n + sizes[m] ** 2)].view(T, 4, sizes[m], sizes[m]) for m in range(3)],
            "logit_t": [lt[4 * T * T * m * n:4 * T * T * (m * n + sizes[m])].view(sizes[m], 4, T, T) for m in range(3)]}
     return out, idx, det
-
-
-def _gpgraph_scene_sizes(scene_sizes, n, dev):
-    if scene_sizes is None:
-        return [n], None, 0
-    sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
-    off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
-    return sizes, off, len(sizes)
 
 
 def gpgraph_sgcn_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=False, workspace=None):
@@ -907,11 +895,11 @@ def gpgraph_sgcn_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_
     if workspace is None:
         workspace = gpgraph_sgcn_train_workspace(model, n, sum_n2, len(b.sizes), et_params=(params, dev))
     if n:
-        _sgcn_check_ws(who, dev, workspace)
+        _check_train_ws(who, dev, workspace, "gpgraph_sgcn_train_workspace")
     gi, dist, ls, lt = _gpgraph_details(want_details, params.base.obs_len, n, sum_n2, dev)
     L.call("et_gpgraph_sgcn_train_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), n, L.ptr(b.off), b.n_scenes,
-           sum_n2, b.max_n, L.ptr(out), L.ptr(gi), L.ptr(dist), L.ptr(ls), L.ptr(lt), L.ptr(workspace),
-           workspace.numel() if workspace is not None else 0, L.stream(dev))
+           sum_n2, b.max_n, L.ptr(out), L.ptr(gi), L.ptr(dist), L.ptr(ls), L.ptr(lt), L.ptr(workspace), _numel(workspace),
+           L.stream(dev))
     if want_details:
         return out, {"group_index": gi, "dist": dist, "logit_s": ls, "logit_t": lt}, workspace
     return out, workspace
@@ -921,25 +909,7 @@ def gpgraph_sgcn_grad_views(model, grads):
     """``grads``, the flat buffer of :func:`gpgraph_sgcn_backward_graph` / ``_scenes`` -> {state_dict key: a view of it shaped
     like the parameter}, every parameter of the whole ``GPGraph`` (state_dict order: ``baseline_model.*``, ``group_gen.th``,
     ``group_gen.group_cnn.0.*``, ``group_mix.st_gcns_mix.{0,1}.*``)."""
-    out, at = {}, 0
-    for name, t in model.named_parameters():
-        out[name] = grads[at:at + t.numel()].view(t.shape)
-        at += t.numel()
-    if at != grads.numel():
-        raise ValueError(f"gpgraph_sgcn_grad_views: {grads.numel()} floats for parameters of {at}")
-    return out
-
-
-def _gpgraph_grads(who, params, dev, d_out, shape):
-    if tuple(d_out.shape) != shape:
-        raise ValueError(f"{who}: d_out {tuple(d_out.shape)} is not {shape}")
-    d_out = d_out.detach()
-    if d_out.device != dev or d_out.dtype != torch.float32 or not d_out.is_contiguous():
-        d_out = d_out.to(device=dev, dtype=torch.float32).contiguous()
-    size = int(L.lib().et_gpgraph_sgcn_grad_floats(C.byref(params)))
-    if not size:
-        L.check(3, "et_gpgraph_sgcn_grad_floats")
-    return d_out, torch.empty((size,), device=dev)
+    return _grad_views("gpgraph_sgcn_grad_views", model, grads)
 
 
 def gpgraph_sgcn_backward_graph(model, workspace, d_out, et_params=None):
@@ -949,8 +919,9 @@ def gpgraph_sgcn_backward_graph(model, workspace, d_out, et_params=None):
     who = "gpgraph_sgcn_backward_graph"
     params, dev = _gpgraph_train_params(who, model, et_params)
     n = d_out.shape[3] if d_out.dim() == 4 else -1
-    _sgcn_check_ws(who, dev, workspace)
-    d_out, grads = _gpgraph_grads(who, params, dev, d_out, (1, params.base.out_dims, params.base.pred_len, n))
+    _check_train_ws(who, dev, workspace, "gpgraph_sgcn_train_workspace")
+    d_out, grads = _backward_args(who, "et_gpgraph_sgcn_grad_floats", params, dev, d_out,
+                                  (1, params.base.out_dims, params.base.pred_len, n))
     L.call("et_gpgraph_sgcn_backward_graph", C.byref(params), n, L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace),
            workspace.numel(), L.stream(dev))
     return grads
@@ -963,13 +934,14 @@ def gpgraph_sgcn_backward_scenes(model, workspace, d_out, scene_sizes=None):
     who = "gpgraph_sgcn_backward_scenes"
     params, dev = _gpgraph_train_params(who, model, None)
     n = d_out.shape[1] if d_out.dim() == 3 else -1
-    d_out, grads = _gpgraph_grads(who, params, dev, d_out, (params.base.pred_len, n, params.base.out_dims))
-    sizes, off, n_scenes = _gpgraph_scene_sizes(scene_sizes, n, dev)
+    d_out, grads = _backward_args(who, "et_gpgraph_sgcn_grad_floats", params, dev, d_out,
+                                  (params.base.pred_len, n, params.base.out_dims))
+    sizes, off, n_scenes = _scene_sizes(scene_sizes, n, dev)
     if n:
-        _sgcn_check_ws(who, dev, workspace)
+        _check_train_ws(who, dev, workspace, "gpgraph_sgcn_train_workspace")
     L.call("et_gpgraph_sgcn_backward_scenes", C.byref(params), n, L.ptr(off), n_scenes,
            sum(s * s for s in sizes if s <= L.SGCN_MAX_N), max(sizes, default=0), L.ptr(d_out), L.ptr(grads), grads.numel(),
-           L.ptr(workspace), workspace.numel() if workspace is not None else 0, L.stream(dev))
+           L.ptr(workspace), _numel(workspace), L.stream(dev))
     return grads
 
 
@@ -990,11 +962,10 @@ def gpgraph_sgcn_train_views(model, workspace, n, sum_n2=None, n_scenes=1, lo=0,
     m0 = N if scene_n is None else scene_n
     f = workspace.view(torch.float32)
     i32 = workspace.view(torch.int32)
-    o = (C.c_int64 * L.GPGRAPH_SGCN_TRAIN_LAYOUT_FIELDS)()
-    L.call("et_gpgraph_sgcn_train_layout", C.byref(params), N, n2, n_scenes, o, L.GPGRAPH_SGCN_TRAIN_LAYOUT_FIELDS)
     (o_v, o_rs, o_rt, o_xs, xs_stride, o_xt, xt_stride, o_at, o_f2, o_f1, o_ts, o_keep, KS, o_dat, o_df1, o_dts, o_df2, o_rrec,
      o_gs, o_gt, o_dirs, o_dirt, o_dds, o_vp, o_vn, o_gidx, o_dax, o_srec, o_trec, o_dacct, o_dxas, o_dxp, o_dxv, o_va, o_feat,
-     o_dist, o_sn, o_po, o_sig, o_cs, o_cnt, o_dmix, o_dpo, o_dvp, o_dP, o_dsig, o_dd, o_df, _) = (int(x) for x in o)
+     o_dist, o_sn, o_po, o_sig, o_cs, o_cnt, o_dmix, o_dpo, o_dvp, o_dP, o_dsig, o_dd, o_df, _) = _layout(
+         "et_gpgraph_sgcn_train_layout", L.GPGRAPH_SGCN_TRAIN_LAYOUT_FIELDS, params, N, n2, n_scenes)
     sl = lambda off, cnt, *shape: f[off:off + cnt].view(*shape)
     G = int(i32[o_vn + n_scenes + scene])
     passes = []
@@ -1174,11 +1145,6 @@ def dmrgcn_train_workspace(model, n, n_scenes=1, et_params=None):
     return _workspace("et_dmrgcn_train_workspace_bytes", dev, params, n, max(n_scenes, 1), required=n > 0)[0]
 
 
-def _dmrgcn_check_ws(who, dev, workspace):
-    if workspace is None or workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise ValueError(f"{who}: workspace is not a contiguous uint8 tensor on {dev} (dmrgcn_train_workspace makes one)")
-
-
 def _dmrgcn_keep(who, dev, keep, shape=None, numel=None):
     """the keep mask as the kernel reads it: contiguous uint8 on ``dev`` of ``shape`` (or of ``numel`` entries); None stays"""
     if keep is None:
@@ -1208,9 +1174,9 @@ def dmrgcn_train_forward_graph(model, v, a, workspace, keep=None, et_params=None
     keep = _dmrgcn_keep("dmrgcn_train_forward_graph", dev, keep, shape=(2, L.DMRGCN_BINS, K, n, n))
     out = torch.empty((1, S, k, n), device=dev)
     if n:
-        _dmrgcn_check_ws("dmrgcn_train_forward_graph", dev, workspace)
+        _check_train_ws("dmrgcn_train_forward_graph", dev, workspace, "dmrgcn_train_workspace")
     L.call("et_dmrgcn_train_forward_graph", C.byref(params), L.ptr(v), L.ptr(a), n, L.ptr(keep), L.ptr(out),
-           L.ptr(workspace), workspace.numel() if workspace is not None else 0, L.stream(dev))
+           L.ptr(workspace), _numel(workspace), L.stream(dev))
     return out
 
 
@@ -1238,38 +1204,20 @@ def dmrgcn_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, keep=None, 
     if workspace is None:
         workspace = dmrgcn_train_workspace(model, b.n, len(b.sizes), et_params=(params, dev))
     if b.n:
-        _dmrgcn_check_ws("dmrgcn_train_forward_scenes", dev, workspace)
+        _check_train_ws("dmrgcn_train_forward_scenes", dev, workspace, "dmrgcn_train_workspace")
     koff, total = dmrgcn_keep_offsets(b.sizes, dev if keep is not None else None)
     keep = _dmrgcn_keep("dmrgcn_train_forward_scenes", dev, keep, numel=2 * L.DMRGCN_BINS * params.seq_len * total)
     out = torch.empty((params.pred_seq_len, b.n, params.output_feat), device=dev)
     L.call("et_dmrgcn_train_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), b.n, L.ptr(b.off), b.n_scenes,
-           L.ptr(keep), L.ptr(koff if keep is not None else None), L.ptr(out), L.ptr(workspace),
-           workspace.numel() if workspace is not None else 0, L.stream(dev))
+           L.ptr(keep), L.ptr(koff if keep is not None else None), L.ptr(out), L.ptr(workspace), _numel(workspace),
+           L.stream(dev))
     return out, workspace
 
 
 def dmrgcn_grad_views(model, grads):
     """``grads``, the flat buffer of :func:`dmrgcn_backward_graph` / ``_scenes`` -> {state_dict key: a view of it shaped like
     the parameter}, every parameter of ``model`` (state_dict order)."""
-    out, at = {}, 0
-    for name, t in model.named_parameters():
-        out[name] = grads[at:at + t.numel()].view(t.shape)
-        at += t.numel()
-    if at != grads.numel():
-        raise ValueError(f"dmrgcn_grad_views: {grads.numel()} floats for parameters of {at}")
-    return out
-
-
-def _dmrgcn_grads(who, params, dev, d_out, shape):
-    if tuple(d_out.shape) != shape:
-        raise ValueError(f"{who}: d_out {tuple(d_out.shape)} is not {shape}")
-    d_out = d_out.detach()
-    if d_out.device != dev or d_out.dtype != torch.float32 or not d_out.is_contiguous():
-        d_out = d_out.to(device=dev, dtype=torch.float32).contiguous()
-    size = int(L.lib().et_dmrgcn_grad_floats(C.byref(params)))
-    if not size:
-        L.check(3, "et_dmrgcn_grad_floats")
-    return d_out, torch.empty((size,), device=dev)
+    return _grad_views("dmrgcn_grad_views", model, grads)
 
 
 def dmrgcn_backward_graph(model, workspace, d_out, et_params=None):
@@ -1278,11 +1226,12 @@ def dmrgcn_backward_graph(model, workspace, d_out, et_params=None):
     (:func:`dmrgcn_grad_views` names its parts)."""
     params, dev = _dmrgcn_train_params("dmrgcn_backward_graph", model, et_params)
     n = d_out.shape[-1] if d_out.dim() == 4 else -1
-    d_out, grads = _dmrgcn_grads("dmrgcn_backward_graph", params, dev, d_out, (1, params.output_feat, params.pred_seq_len, n))
+    d_out, grads = _backward_args("dmrgcn_backward_graph", "et_dmrgcn_grad_floats", params, dev, d_out,
+                                  (1, params.output_feat, params.pred_seq_len, n))
     if n:
-        _dmrgcn_check_ws("dmrgcn_backward_graph", dev, workspace)
+        _check_train_ws("dmrgcn_backward_graph", dev, workspace, "dmrgcn_train_workspace")
     L.call("et_dmrgcn_backward_graph", C.byref(params), n, L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace),
-           workspace.numel() if workspace is not None else 0, L.stream(dev))
+           _numel(workspace), L.stream(dev))
     return grads
 
 
@@ -1292,17 +1241,13 @@ def dmrgcn_backward_scenes(model, workspace, d_out, scene_sizes=None):
     summed over the scenes in ascending order."""
     params, dev = _dmrgcn_train_params("dmrgcn_backward_scenes", model, None)
     n = d_out.shape[1] if d_out.dim() == 3 else -1
-    d_out, grads = _dmrgcn_grads("dmrgcn_backward_scenes", params, dev, d_out, (params.pred_seq_len, n, params.output_feat))
-    if scene_sizes is None:
-        off, n_scenes = None, 0
-    else:
-        sizes = [int(s) for s in (scene_sizes.tolist() if torch.is_tensor(scene_sizes) else scene_sizes)]
-        off = scene_offsets(sizes, n, dev) if sizes else torch.zeros((1,), device=dev, dtype=torch.int32)
-        n_scenes = len(sizes)
+    d_out, grads = _backward_args("dmrgcn_backward_scenes", "et_dmrgcn_grad_floats", params, dev, d_out,
+                                  (params.pred_seq_len, n, params.output_feat))
+    _, off, n_scenes = _scene_sizes(scene_sizes, n, dev)
     if n:
-        _dmrgcn_check_ws("dmrgcn_backward_scenes", dev, workspace)
+        _check_train_ws("dmrgcn_backward_scenes", dev, workspace, "dmrgcn_train_workspace")
     L.call("et_dmrgcn_backward_scenes", C.byref(params), n, L.ptr(off), n_scenes, L.ptr(d_out), L.ptr(grads), grads.numel(),
-           L.ptr(workspace), workspace.numel() if workspace is not None else 0, L.stream(dev))
+           L.ptr(workspace), _numel(workspace), L.stream(dev))
     return grads
 
 
@@ -1318,9 +1263,8 @@ def dmrgcn_train_views(model, workspace, n, n_scenes=1, lo=0, scene=0, scene_n=N
     K, k, S = params.seq_len, params.pred_seq_len, params.output_feat
     m = n if scene_n is None else scene_n
     f = workspace.view(torch.float32)
-    o = (C.c_int64 * L.DMRGCN_TRAIN_LAYOUT_FIELDS)()
-    L.call("et_dmrgcn_train_layout", C.byref(params), n, n_scenes, o, L.DMRGCN_TRAIN_LAYOUT_FIELDS)
-    (o_u, o_p, o_yp, o_s, o_x, o_tp, o_dtp, o_dx, o_dy, _, per, tp_stride, dtp_stride, o_part, G, _) = [int(x) for x in o]
+    (o_u, o_p, o_yp, o_s, o_x, o_tp, o_dtp, o_dx, o_dy, _, per, tp_stride, dtp_stride, o_part, G, _) = _layout(
+        "et_dmrgcn_train_layout", L.DMRGCN_TRAIN_LAYOUT_FIELDS, params, n, n_scenes)
     base = lo * per
     fld = lambda off, *shape: f[base + off * m:base + off * m + math.prod(shape) * m].view(*shape, m)
     kS = k * S
@@ -1426,8 +1370,8 @@ def _implicit_backward(who, entry, model, params, dev, n, workspace, lead, g, ta
         raise ValueError(f"{who}: workspace is not the uint8 tensor the forward call filled")
     grads = torch.empty((params.n_bins, implicit_grad_size(params)), device=dev)
     ws, nbytes = _workspace("et_implicit_backward_workspace_bytes", dev, params, n)
-    L.call(entry, C.byref(params), *lead, n, L.ptr(workspace), workspace.numel() if workspace is not None else 0, L.ptr(g),
-           *tail, L.ptr(grads), L.ptr(ws), nbytes, L.stream(dev))
+    L.call(entry, C.byref(params), *lead, n, L.ptr(workspace), _numel(workspace), L.ptr(g), *tail, L.ptr(grads), L.ptr(ws),
+           nbytes, L.stream(dev))
     return grads
 
 

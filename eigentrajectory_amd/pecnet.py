@@ -172,44 +172,23 @@ def enable_native_training(model, flag=True):
     uses BatchNorm batch statistics and updates the running ones), or a ``SocialDMRGCN`` of its native family (``n_stgcn =
     1``, every ``Dropout.p = 0``; its training-mode forward applies DropEdge through a keep mask it draws per call) (the
     plain attribute ``native_training``); the other three predictors have no native backward pass and raise.  -> ``model``"""
-    from .dmrgcn import SocialDMRGCN
+    from ._native_train import family_name
     from .gpgraph import GPGraph
     from .implicit import SocialImplicitLight
     from .lbebm import LBEBM
-    from .sgcn import SGCN
-    from .stgcnn import SocialSTGCNN
     net = model if isinstance(model, GPGraph) else getattr(model, "baseline_model", model)  # (a GPGraph has a base of its own)
     if isinstance(net, LBEBM):
         net.enable_native_training(flag)
     elif isinstance(net, (PECNet, SocialImplicitLight)):
         net.native_training = bool(flag)
-    elif isinstance(net, GPGraph) and net.outside_native_training() is None:
+    elif hasattr(net, "outside_native_training"):  # SGCN, GPGraph, SocialSTGCNN, SocialDMRGCN: a native family each
+        why = net.outside_native_training()
+        if why is not None:
+            raise NotImplementedError(f"enable_native_training: {family_name(net)} has no native backward pass outside its "
+                                      f"native family: {why}; {net.trains_natively}")
         net.native_training = bool(flag)
-    elif isinstance(net, GPGraph):
-        raise NotImplementedError(f"enable_native_training: GPGraph has no native backward pass outside its native family: "
-                                  f"{net.outside_native_training()}; LBEBM, PECNet, SocialImplicitLight, SGCN and a GPGraph "
-                                  "in the ET configuration around SGCN(position_channel=True, dropout=0) train natively")
-    elif isinstance(net, SGCN) and net.outside_native_training() is None:
-        net.native_training = bool(flag)
-    elif isinstance(net, SGCN):
-        raise NotImplementedError(f"enable_native_training: SGCN has no native backward pass outside its native family: "
-                                  f"{net.outside_native_training()}; LBEBM, PECNet, SocialImplicitLight and an SGCN with "
-                                  "in_dims = 1, num_heads = 4, embedding_dims = 64, dropout = 0 and no position channel "
-                                  "train natively")
-    elif isinstance(net, SocialSTGCNN) and net.outside_native_training() is None:
-        net.native_training = bool(flag)
-    elif isinstance(net, SocialSTGCNN):
-        raise NotImplementedError(f"enable_native_training: SocialSTGCNN has no native backward pass outside its native "
-                                  f"family: {net.outside_native_training()}; LBEBM, PECNet, SocialImplicitLight, SGCN and a "
-                                  "SocialSTGCNN with n_stgcnn = 1 and graph_per_time_row = False train natively")
-    elif isinstance(net, SocialDMRGCN) and net.outside_native_training() is None:
-        net.native_training = bool(flag)
-    elif isinstance(net, SocialDMRGCN):
-        raise NotImplementedError(f"enable_native_training: SocialDMRGCN has no native backward pass outside its native "
-                                  f"family: {net.outside_native_training()}; LBEBM, PECNet, SocialImplicitLight, SGCN, "
-                                  "SocialSTGCNN and a SocialDMRGCN with n_stgcn = 1 and no dropout train natively")
     else:
         raise NotImplementedError(f"enable_native_training: {type(net).__name__} has no native backward pass; only LBEBM, "
-                                  "PECNet, SocialImplicitLight, SGCN and SocialSTGCNN, and GPGraph around SGCN, train "
-                                  "natively")
+                                  "PECNet, SocialImplicitLight, SGCN, SocialSTGCNN and SocialDMRGCN, and GPGraph around SGCN, "
+                                  "train natively")
     return model

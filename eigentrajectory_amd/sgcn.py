@@ -37,11 +37,11 @@ from __future__ import annotations
 
 import math
 
-import torch
 import torch.nn as nn
 
 from . import _lib as L
 from ._lib import _p
+from ._native_train import train_forward
 
 
 class _AsymmetricConvolution(nn.Module):
@@ -112,43 +112,14 @@ class _SparseGraphConvolution(nn.Module):
         self.temporal_spatial_sparse_gcn.append(_GraphConvolution(embedding_dims, embedding_dims))
 
 
-class _TrainForward(torch.autograd.Function):
-    """``forward(graph, identity)`` with a backward pass.  Every parameter is an input, in ``named_parameters`` order, so
-    autograd routes the gradients into ``.grad``; they are saved through ``save_for_backward`` with the identities and the
-    training workspace: the kernels read the weights in place, and an in-place change between forward and backward (an
-    optimiser step) is caught by autograd's version counters."""
-
-    @staticmethod
-    def forward(ctx, model, graph, id_s, id_t, *params):
-        from . import ops
-        et = model.et_params()  # the pointer table once: forward and backward see the same tensors
-        ws = ops.sgcn_train_workspace(model, graph.shape[2], et_params=et)
-        out = ops.sgcn_train_forward_graph(model, graph, (id_s, id_t), ws, et_params=et)
-        ctx.model, ctx.et = model, et
-        ctx.save_for_backward(id_s, id_t, ws, *params)
-        ctx.set_materialize_grads(False)
-        return out
-
-    @staticmethod
-    def backward(ctx, g_out):
-        need = ctx.needs_input_grad
-        if g_out is None:
-            return (None,) * len(need)
-        from . import ops
-        model = ctx.model
-        id_s, id_t, ws = ctx.saved_tensors[:3]
-        params = ctx.saved_tensors[3:]
-        if any(p.data_ptr() != q.data_ptr() for p, q in zip(params, model.parameters())):
-            raise RuntimeError("SGCN: a parameter tensor was replaced between forward and backward")
-        views = ops.sgcn_grad_views(model, ops.sgcn_backward_graph(model, (id_s, id_t), ws, g_out, et_params=ctx.et))
-        return (None, None, None, None, *(g if wanted else None for g, wanted in zip(views.values(), need[4:])))
-
-
 class SGCN(nn.Module):
     r"""baseline/sgcn/model.py's ``TrajectoryModel`` (eval-mode inference on the GPU).  ``forward(graph, identity)``: graph
     (1, T, N, 1) and the two identities as the sgcn bridge's pre-hook builds them -> (pred_len, N, out_dims)."""
 
     native_training = False  # a plain attribute, set per instance by eigentrajectory_amd.enable_native_training
+    #: how enable_native_training ends its refusal of an instance outside the native family
+    trains_natively = ("LBEBM, PECNet, SocialImplicitLight and an SGCN with in_dims = 1, num_heads = 4, embedding_dims = 64, dropout = 0 "
+                       "and no position channel train natively")
 
     def __init__(self, number_asymmetric_conv_layer=7, embedding_dims=64, number_gcn_layers=1, dropout=0, obs_len=8,
                  pred_len=12, n_tcn=5, in_dims=2, out_dims=5, num_heads=4, position_channel=False):
@@ -216,6 +187,18 @@ class SGCN(nn.Module):
             raise RuntimeError(f"SGCN: dropout = {self.dropout} is not implemented natively (the reference's F.dropout is "
                                "active even in eval mode); construct with dropout=0")
 
+    native_parameters = nn.Module.parameters  # what :mod:`._native_train` differentiates: every parameter
+
+    def native_forward(self, et, graph, id_s, id_t):
+        from . import ops
+        ws = ops.sgcn_train_workspace(self, graph.shape[2], et_params=et)
+        return ops.sgcn_train_forward_graph(self, graph, (id_s, id_t), ws, et_params=et), (id_s, id_t, ws)
+
+    def native_backward(self, et, kept, g_out):
+        from . import ops
+        id_s, id_t, ws = kept
+        return ops.sgcn_grad_views(self, ops.sgcn_backward_graph(self, (id_s, id_t), ws, g_out, et_params=et)).values()
+
     def forward(self, graph, identity, mask=None):
         if self.training and self.native_training and not self.position_channel and mask is None and self.dropout == 0:
             if graph.requires_grad or any(i.requires_grad for i in identity):
@@ -223,7 +206,7 @@ class SGCN(nn.Module):
                                    "requires one")
             dev = L.module_device("SGCN", self)
             graph, id_s, id_t = (L.on_device(t, dev) for t in (graph, *identity))
-            return _TrainForward.apply(self, graph, id_s, id_t, *self.parameters())
+            return train_forward(self, graph, id_s, id_t)
         self._check_mode()
         if self.position_channel or mask is not None:
             raise NotImplementedError("SGCN: the two-channel base (position_channel=True) and the mask argument run only as "

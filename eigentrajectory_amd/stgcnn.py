@@ -36,11 +36,11 @@ only as the three passes of GPGraphSTGCNN's call; its own forward raises.
 """
 from __future__ import annotations
 
-import torch
 import torch.nn as nn
 
 from . import _lib as L
 from ._lib import _p
+from ._native_train import train_forward
 
 
 class _GraphConv(nn.Module):
@@ -70,46 +70,14 @@ class _STGCNBlock(nn.Module):
         self.prelu = nn.PReLU()
 
 
-class _TrainForward(torch.autograd.Function):
-    """``forward(v, a)`` in training mode with a backward pass.  Every parameter is an input, in ``named_parameters`` order,
-    so autograd routes the gradients into ``.grad``; they are saved through ``save_for_backward`` with the training
-    workspace: the kernels read the weights in place, and an in-place change between forward and backward (an optimiser
-    step) is caught by autograd's version counters."""
-
-    @staticmethod
-    def forward(ctx, model, v, a, *params):
-        from . import ops
-        et = model.et_params()  # the pointer table once: forward and backward see the same tensors
-        ws = ops.stgcnn_train_workspace(model, v.shape[-1], et_params=et)
-        out = ops.stgcnn_train_forward_graph(model, v, a, ws, et_params=et)
-        ctx.model, ctx.et = model, et
-        ctx.save_for_backward(*params) if ws is None else ctx.save_for_backward(ws, *params)
-        ctx.has_ws = ws is not None
-        ctx.set_materialize_grads(False)
-        return out
-
-    @staticmethod
-    def backward(ctx, g_out):
-        need = ctx.needs_input_grad
-        if g_out is None:
-            return (None,) * len(need)
-        from . import ops
-        model = ctx.model
-        ws = ctx.saved_tensors[0] if ctx.has_ws else None
-        params = ctx.saved_tensors[1 if ctx.has_ws else 0:]
-        if any(p.data_ptr() != q.data_ptr() for p, q in zip(params, model.parameters())):
-            raise RuntimeError("SocialSTGCNN: a parameter tensor was replaced between forward and backward")
-        views = ops.stgcnn_grad_views(model, ops.stgcnn_backward_graph(model, ws, g_out, et_params=ctx.et))
-        unused = model.unused_parameter_names()
-        return (None, None, None, *(g if wanted and name not in unused else None
-                                    for (name, g), wanted in zip(views.items(), need[3:])))
-
-
 class SocialSTGCNN(nn.Module):
     r"""baseline/stgcnn/model.py's ``social_stgcnn`` (eval-mode inference on the GPU).  ``forward(v, a)``: v (1, 1, K, N),
     a (K, N, N) as the stgcnn bridge's pre-hook builds them -> (1, S, k, N), the raw output the post-hook permutes."""
 
     native_training = False  # a plain attribute, set per instance by eigentrajectory_amd.enable_native_training
+    #: how enable_native_training ends its refusal of an instance outside the native family
+    trains_natively = ("LBEBM, PECNet, SocialImplicitLight, SGCN and a SocialSTGCNN with n_stgcnn = 1 and graph_per_time_row = False "
+                       "train natively")
 
     def __init__(self, n_stgcnn=1, n_txpcnn=1, input_feat=2, output_feat=5, seq_len=8, pred_seq_len=12, kernel_size=3,
                  graph_per_time_row=False):
@@ -211,6 +179,19 @@ class SocialSTGCNN(nn.Module):
                 setattr(t, name + "_batches", m.num_batches_tracked.data_ptr())
         return t
 
+    native_parameters = nn.Module.parameters  # what :mod:`._native_train` differentiates: every parameter
+
+    def native_forward(self, et, v, a):
+        from . import ops
+        ws = ops.stgcnn_train_workspace(self, v.shape[-1], et_params=et)
+        return ops.stgcnn_train_forward_graph(self, v, a, ws, et_params=et), (() if ws is None else (ws,))
+
+    def native_backward(self, et, kept, g_out):
+        from . import ops
+        views = ops.stgcnn_grad_views(self, ops.stgcnn_backward_graph(self, kept[0] if kept else None, g_out, et_params=et))
+        unused = self.unused_parameter_names()
+        return [None if name in unused else g for name, g in views.items()]
+
     def forward(self, v, a):
         if self.training and self.native_training and self.outside_native_training() is None:
             if v.requires_grad or a.requires_grad:
@@ -218,7 +199,7 @@ class SocialSTGCNN(nn.Module):
                                    "requires one")
             dev = L.module_device("SocialSTGCNN", self, buffers=True)
             v, a = (L.on_device(t, dev) for t in (v, a))
-            return _TrainForward.apply(self, v, a, *self.parameters())
+            return train_forward(self, v, a)
         if self.training:
             raise RuntimeError("SocialSTGCNN: only inference is native (BatchNorm running statistics, no dropout); "
                                "training-mode forward and backward are not implemented -- call .eval() first")
