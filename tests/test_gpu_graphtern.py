@@ -12,7 +12,10 @@ shows against itself; there is no per-pedestrian comparison against the referenc
 Measured on the MI355X (figures in DESIGN §4 "Graph-TERN"): graph form against the reference <= 3.8e-7 of the largest
 entry, scene form against the restatement <= 7.3e-7, scene form against graph form bit-equal; the device's C_obs is within
 2.0 of the draws' units of the reference's on eth; the split means are within 1.4e-8 / 5.9e-9 (eth ADE / FDE), 1.3e-8 /
-2.9e-8 (zara1), 3.6e-6 / 2.8e-5 (zara2) of the reference's."""
+2.9e-8 (zara1), 3.6e-6 / 2.8e-5 (zara2) of the reference's.
+
+Other members of the supported family (ranks 1 to 32, S 1 to 64, the block counts' limits, chunked later blocks, a rel no
+bridge builds, guard bands, the "fits nowhere" branch): tests/test_gpu_graphtern_shapes.py."""
 import numpy as np
 import pytest
 import torch
@@ -73,17 +76,7 @@ def split(scene, dev):
     return T(obs, dev), T(pred, dev), np.asarray(sse)
 
 
-def _synthetic(n, seed, k=6):
-    """coefficients with equal (rounded) values in every row, a few identical columns and a few all-zero ones (static
-    pedestrians), positions around the origin: exact zeros occur off the diagonal in both relations"""
-    rng = np.random.default_rng(seed)
-    C_obs = rng.normal(0, 1, (k, n)).astype(np.float32)
-    C_obs[:, : max(n // 4, 1)] = np.round(C_obs[:, : max(n // 4, 1)], 1)
-    nrm = rng.normal(0, 5, (4, n)).astype(np.float32)
-    for i in range(0, n - 1, 5):  # coincident columns: the same pedestrian twice
-        C_obs[:, i + 1], nrm[:, i + 1] = C_obs[:, i], nrm[:, i]
-    C_obs[:, 3::11] = 0.0
-    return C_obs, nrm
+_synthetic = GN.synthetic_split  # (n or the scene sizes, seed, k = 6): the split generator, shared with the shapes file
 
 
 def _check_scenes(ops, m, sd, C_obs, nrm, sizes, tol=TOL):
@@ -218,6 +211,9 @@ def test_nan_stays_in_its_scene(dev, ops):
     out = N_(ops.graphtern_forward_scenes(m, T(bad, dev), T(nrm, dev), scene_sizes=sizes))
     torch.cuda.synchronize()
     assert np.isnan(out[:, 4:13]).any() and np.isnan(out[:, 6]).all()
+    with np.errstate(invalid="ignore"):  # the restatement (and the reference's arithmetic): the whole scene is NaN
+        ref = GN.forward(SD, GN.scene_input(bad, nrm, 4, 13))
+    assert np.isnan(ref).all() and np.array_equal(np.isnan(out[:, 4:13]), np.isnan(ref))
     keep = np.r_[0:4, 13:56]
     assert np.array_equal(out[:, keep], clean[:, keep]) and np.isfinite(clean).all()
 

@@ -2,7 +2,10 @@
 restatement (tests/_graphtern_np.py) against the reference's recorded network outputs (tests/golden/g27_graphtern.npz,
 tools/make_golden_graphtern.py), what the fixture covers, the module's state_dict against the reference's, the
 evaluate_split dispatch, the entry points' argument validation (host side, before any device work) and the refusal to run
-in training mode."""
+in training mode; and what tests/test_gpu_graphtern_shapes.py relies on: the path each configuration of GN.CONFIGS reaches
+(the kernel's arena figures restated), its seeded weights, the restatement against the reference at those shapes
+(tests/golden/g33_graphtern_family.npz), the restatement's own float32 mode on every input compared on the GPU, the exact
+zeros of every layout, the NaN mask and the refusals one step outside every limit."""
 import ctypes as C
 import re
 
@@ -232,6 +235,7 @@ def test_arguments_are_validated_on_the_host():
 
     for call in (graph, scenes):
         for bad in (dict(n_smpl=65), dict(n_smpl=0), dict(seq_len=9), dict(pred_seq_len=33, seq_len=35), dict(input_feat=2),
+                    dict(pred_seq_len=1, seq_len=4), dict(pred_seq_len=32, seq_len=33), dict(pred_seq_len=0, seq_len=2),
                     dict(hidden_feat=32), dict(n_epgcn=0), dict(n_epgcn=_lib.GRAPHTERN_MAX_EPGCN + 1), dict(n_epcnn=1),
                     dict(n_epcnn=_lib.GRAPHTERN_MAX_EPCNN + 1)):
             assert call(_params(**bad)) == UNSUPPORTED, bad
@@ -279,3 +283,237 @@ def test_graphtern_abi_names_declared_and_mirrored():
     assert d["ET_GRAPHTERN_MAX_EPGCN"] >= 2 and d["ET_GRAPHTERN_MAX_EPCNN"] >= 6 and d["ET_ABI_VERSION"] == 3
     assert C.sizeof(_lib.GraphTERNLayer) == 8 * 8 and C.sizeof(_lib.GraphTERNEpcnn) == 10 * 8
     assert C.sizeof(_lib.GraphTERNParams) == 7 * 4 + 4 + 4 * 8 * 8 + 8 * 10 * 8  # ints, padding, pointer tables
+
+
+# ------------------------------------------------- the configurations of tests/test_gpu_graphtern_shapes.py (GN.CONFIGS)
+G33 = G.load("g33_graphtern_family.npz")
+# name: T, qpp, floats per pedestrian, the largest scene in LDS, the chunks of a later st_mrgcn block (None: one block)
+FIGURES = {
+    "k1": (3, 68, 222, 69, [1, 1, 1]),
+    "k2s16": (4, 68, 228, 67, [1, 1, 1, 1]),
+    "deep": (8, 128, 432, 35, [1] * 8),
+    "wide": (8, 384, 1200, 12, [5, 3]),
+    "kmax": (34, 2048, 6348, 2, [30, 4]),
+    "tall": (34, 544, 1836, 8, [8, 8, 8, 8, 2]),
+    "et": (8, 128, 432, 35, None),
+}
+
+
+def _cfg_params(name):
+    c = GN.CONFIGS[name]
+    return _params(n_epgcn=c["st"], n_epcnn=c["epcnn"], n_smpl=c["S"], seq_len=c["k"] + 2, pred_seq_len=c["k"])
+
+
+def test_configs_reach_the_paths_they_are_for():
+    """gt_dims_of / gt_arena_per_ped / the chunking of gt_run_scene restated (GN.dims) give the figures each configuration
+    was chosen for, and the library sizes the workspace by the same rule on either side of every configuration's switch"""
+    from eigentrajectory_amd import _lib
+    assert {n: (c["k"], c["S"], c["st"], c["epcnn"]) for n, c in GN.CONFIGS.items()} == {
+        "k1": (1, 1, 2, 2), "k2s16": (2, 16, 3, 2), "deep": (6, 9, 4, 8), "wide": (6, 64, 2, 3), "kmax": (32, 64, 2, 2),
+        "tall": (32, 1, 3, 2), "et": (6, 20, 1, 6)}
+    assert set(FIGURES) == set(GN.CONFIGS) and GN.LDS_BYTES // 4 == 15360
+    ws = lambda name, n, mx: int(_lib.lib().et_graphtern_workspace_bytes(C.byref(_cfg_params(name)), n, mx))
+    for name, (T, qpp, per, lim, later) in FIGURES.items():
+        c = GN.CONFIGS[name]
+        assert GN.config_dims(name) == (T, qpp, per, lim, later), name
+        assert (later is None) == (c["st"] == 1) and (later is None or sum(later) == T), name
+        assert per == 6 * T + 3 * qpp and per * lim * 4 <= GN.LDS_BYTES < per * (lim + 1) * 4
+        assert GN.workspace_bytes(per, 1000, lim) == 0 and GN.workspace_bytes(per, 1000, lim + 1) == per * 1000 * 4
+        assert GN.layout_sizes(name, "edge") == (1, 2, 3, 0, 63, 64, 65, lim, lim + 1)
+        for n, mx in ((1000, lim), (1000, lim + 1), (lim, lim), (lim + 1, lim + 1), (7, 1), (16390, 16385)):
+            assert ws(name, n, mx) == GN.workspace_bytes(per, n, mx), (name, n, mx)
+        assert ws(name, sum(GN.layout_sizes(name, "edge")), lim + 1) == per * sum(GN.layout_sizes(name, "edge")) * 4
+    floor = GN.REL * (GN.HIDDEN + 1)
+    assert FIGURES["k1"][1] == FIGURES["k2s16"][1] == floor == 68 > 16 * 4 > 2 * 16          # the floor, above 16 T and k S
+    assert FIGURES["wide"][1] == 6 * 64 > 16 * 8 and FIGURES["kmax"][1] == 32 * 64 > 16 * 34  # qpp from k S
+    assert FIGURES["tall"][1] == 16 * 34 > 32 * 1 and FIGURES["deep"][1] == 16 * 8 > 6 * 9    # qpp from 16 T
+    assert {n for n, f in FIGURES.items() if f[4] and max(f[4]) > 1} == {"wide", "kmax", "tall"}   # tq > 0 somewhere
+    assert all(f[4][-1] < f[4][0] for n, f in FIGURES.items() if n in ("wide", "kmax", "tall"))     # a ragged last chunk
+    assert GN.CONFIGS["k2s16"]["S"] == GN.HIDDEN                      # the last epcnn block's residual is the identity
+    assert GN.CONFIGS["deep"]["st"] == _lib.GRAPHTERN_MAX_EPGCN and GN.CONFIGS["deep"]["epcnn"] == _lib.GRAPHTERN_MAX_EPCNN
+    assert GN.CONFIGS["kmax"]["k"] == H.defines()["ET_MAX_K"] and FIGURES["kmax"][3] + 1 == 3  # the workspace from n = 3 on
+    assert GN.BIG == (257, 512) and len(GN.MANY) == 300 and set(GN.MANY) == {0, 1, 2, 3, 4, 5}
+    assert GN.NAN_SIZES == (4, 70, 40, 3, 9) and GN.FIXTURE_SIZES == (3, 13)
+    assert {n for n, u in GN.USED.items() if "big" in u} == {"k1", "wide"}
+    assert {n for n, u in GN.USED.items() if "many" in u} == {"k1", "et"}
+    assert {n for n, u in GN.USED.items() if "nan" in u} == {"deep", "wide"}
+    assert all({"edge", "g3", "g65"} <= set(u) for u in GN.USED.values()) and set(GN.USED) == set(GN.CONFIGS)
+    assert set(GN.SEEDS) == {(n, l) for n, u in GN.USED.items() for l in u}
+
+
+@pytest.mark.parametrize("name", list(GN.CONFIGS))
+def test_config_loads_strictly_and_leaves_no_default(name):
+    from eigentrajectory_amd.graphtern import GraphTERNLight
+    sd = GN.random_state(name)
+    net = GraphTERNLight(**GN.module_cfg(name))
+    mine = net.state_dict()
+    assert list(mine) == list(sd) == list(GN.state_shapes(name))
+    assert all(tuple(mine[k].shape) == sd[k].shape == GN.state_shapes(name)[k] for k in sd)
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+    c = GN.CONFIGS[name]
+    assert GN.counts(sd) == (c["st"], c["epcnn"]) and all(v.dtype == np.float32 for v in sd.values())
+    slopes = [float(v[0]) for k, v in sd.items() if GN.is_slope(k)]
+    assert all(sd[k].shape == (1,) for k in sd if GN.is_slope(k)) and len(slopes) == 2 * c["st"] + 2 * c["epcnn"]
+    assert len(set(slopes)) == len(slopes) and all(abs(a - 0.25) > 0.02 and a > 0.04 for a in slopes)
+    assert all(f"tp_mrgcns.{i}.prelu.weight" in sd for i in range(c["st"]))  # the slope the network never applies
+    assert all(np.abs(v).min() > 0 for k, v in sd.items() if k.endswith("bias"))
+    assert "tp_mrgcns.0.residual.0.weight" in sd and not any(f"tp_mrgcns.{i}.residual.0.weight" in sd for i in range(1, 4))
+    last = c["epcnn"] - 1
+    assert "tpcnns.0.restconv.0.weight" in sd and (f"tpcnns.{last}.rescconv.0.weight" in sd) == (c["S"] != 16)
+    assert sum("rescconv" in k or "restconv" in k for k in sd) == (4 if c["S"] != 16 else 2)
+    for other in GN.CONFIGS:  # no two configurations share a draw
+        if other != name:
+            assert not np.array_equal(GN.random_state(other)["tpcnns.0.cpcns.0.1.weight"], sd["tpcnns.0.cpcns.0.1.weight"])
+    assert all(np.array_equal(v, GN.random_state(name)[k]) for k, v in sd.items())  # seeded
+
+
+def test_the_split_generator_keeps_its_bits_and_the_float64_default_too():
+    """GN.synthetic_split is tests/test_gpu_graphtern.py's former _synthetic (an int or the scene sizes, any k), and the
+    restatement's default is fp64 as before the dtype argument"""
+    a, b = GN.synthetic_split(65, 1), GN.synthetic_split((1, 0, 64), 1, 6)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[0].shape == (6, 65) and a[1].shape == (4, 65)
+    assert np.array_equal(a[0][:, 21], a[0][:, 20]) and np.array_equal(a[1][:, 21], a[1][:, 20])  # the same pedestrian twice
+    assert np.array_equal(a[0][:, 22], np.random.default_rng(1).normal(0, 1, (6, 65)).astype(np.float32)[:, 22])
+    assert GN.synthetic_split((3, 4), 2, 1)[0].shape == (1, 7) and GN.synthetic_split((3, 4), 2, 32)[0].shape == (32, 7)
+    sd = net_state()
+    u = Z["grid.s_obs"][0, 0, :, :, 0]
+    o = GN.forward(sd, u)
+    assert o.dtype == np.float64 and np.array_equal(o, GN.forward(sd, u, dtype=np.float64))
+    assert GN.graphs(u, GN.rel_of(u)).dtype == np.float64 and GN.graphs(u, GN.rel_of(u), np.float32).dtype == np.float32
+
+
+def test_the_restatement_reproduces_the_reference_across_the_family():
+    """g33: the reference's graph_tern_light at every configuration under GN.random_state, on the bridge's S_obs of the
+    scenes of 3 and 13 (tools/make_golden_graphtern.py --family; no configuration was refused): the inputs are regenerated
+    bit for bit, the fp64 restatement is within TOL of every output.  Measured: k1 2.0e-7, k2s16 1.8e-7, deep 3.2e-7, wide
+    3.8e-7, kmax 3.1e-7, tall 6.8e-7, et 3.3e-7"""
+    assert sorted(G33.files) == sorted(f"{name}.{what}{n}" for name in GN.CONFIGS for what in ("s_obs", "net_out")
+                                       for n in GN.FIXTURE_SIZES)
+    for name, c in GN.CONFIGS.items():
+        sd = GN.random_state(name)
+        sizes, C_obs, nrm = GN.fixture_inputs(name)
+        worst = 0.0
+        for _, lo, n, u in GN.scenes_of(sizes, C_obs, nrm):
+            s_obs, ref = G33[f"{name}.s_obs{n}"], G33[f"{name}.net_out{n}"]
+            assert s_obs.shape == (2, c["k"] + 2, n) and ref.shape == (c["k"], n, c["S"]) and ref.dtype == np.float32
+            assert np.array_equal(GN.s_obs_of(u)[0, :, :, :, 0], s_obs), (name, n)
+            errs = (scale_err(GN.forward(sd, s_obs[0], s_obs[1]), ref), scale_err(GN.forward(sd, u), ref))
+            worst = max(worst, *errs)
+            assert max(errs) <= TOL, (name, n, errs)
+        print(f"graphtern {name}: restatement against the reference {worst:.2e} of the largest entry")
+
+
+def _compared_inputs(name):
+    """yields (label, u, rel or None) of every network input tests/test_gpu_graphtern_shapes.py compares at ``name``: the
+    non-empty scenes of its layouts, the g33 scenes, and the graph-form scenes of 3 and 65 with GN.odd_rel"""
+    for layout in GN.USED[name]:
+        sizes, C_obs, nrm = GN.layout_inputs(name, layout)
+        got = 0
+        for s, _, n, u in GN.scenes_of(sizes, C_obs, nrm):
+            got += 1
+            yield layout, u, None
+            if layout in ("g3", "g65"):
+                yield layout + " odd rel", u, GN.odd_rel(u)
+        assert got == sum(1 for n in sizes if n)  # no scene left out
+    sizes, C_obs, nrm = GN.fixture_inputs(name)
+    for _, _, n, u in GN.scenes_of(sizes, C_obs, nrm):
+        yield "g33", u, None
+
+
+@pytest.mark.parametrize("name", list(GN.CONFIGS))
+def test_float32_mode_is_within_a_quarter_of_the_tolerance(name):
+    """the restatement in numpy fp32 after the fp32 distances (the same statements, the arithmetic's own error) against
+    itself in fp64 on every network input the GPU file compares: within TOL / 4 of the largest entry.  Measured (edge, g3,
+    g65, then the others; the odd rel among g3 / g65): k1 8.3e-7, 8.7e-7, 3.6e-7, big 3.3e-7, many 1.3e-6; k2s16 1.9e-7,
+    1.5e-7, 2.3e-7; deep 2.8e-7, 2.7e-7, 2.6e-7, nan 2.7e-7; wide 2.5e-7, 2.2e-7, 2.1e-7, big 2.3e-7, nan 2.2e-7; kmax
+    2.5e-7, 1.9e-7, 1.8e-7; tall 3.8e-7, 3.6e-7, 2.9e-7; et 2.2e-7, 2.2e-7, 1.5e-7, many 3.6e-7"""
+    sd, c = GN.random_state(name), GN.CONFIGS[name]
+    worst = {}
+    for label, u, rel in _compared_inputs(name):
+        o64, o32 = GN.forward(sd, u, rel), GN.forward(sd, u, rel, dtype=np.float32)
+        assert o32.dtype == np.float32 and o64.dtype == np.float64 and o64.shape == (c["k"], u.shape[1], c["S"])
+        assert np.isfinite(o64).all()
+        key = label.split()[0]
+        worst[key] = max(worst.get(key, 0.0), scale_err(o32, o64))
+    assert set(worst) == set(GN.USED[name]) | {"g33"}
+    for key, err in worst.items():
+        print(f"graphtern {name} {key}: float32 mode {err:.2e} of the largest entry (bound {GN.TOL / 4:.1e})")
+        assert err <= GN.TOL / 4, (name, key, err)
+
+
+def test_every_layout_has_exact_zeros_off_the_diagonal():
+    """in both relations, in every time row (of rel: every row but the all-zero first), in some scene of every layout of
+    every configuration -- coincident columns, rounded values, all-zero columns; and GN.odd_rel is what it says"""
+    for name, used in GN.USED.items():
+        k = GN.CONFIGS[name]["k"]
+        for layout in used:
+            sizes, C_obs, nrm = GN.layout_inputs(name, layout)
+            both, tied_values = 0, False
+            for _, lo, n, u in GN.scenes_of(sizes, C_obs, nrm):
+                off = ~np.eye(n, dtype=bool)
+                za, zr = (GN.distances(u) == 0) & off, (GN.distances(GN.rel_of(u)) == 0) & off
+                both += bool(za.any(axis=(1, 2)).all() and zr.any(axis=(1, 2))[1:].all())
+                pair = za.all(axis=0)  # the same pedestrian twice: zero in every row
+                tied_values |= bool((za[:k] & ~pair).any())
+            assert both >= 1, (name, layout)
+            assert tied_values or max(sizes) < 8 or k > 6, (name, layout)  # equal rounded values beyond the repeated columns
+            assert (C_obs == 0).all(axis=0).any() or C_obs.shape[1] <= 3
+    for name, n in (("k1", 3), ("deep", 65), ("kmax", 13)):
+        C_obs, nrm = GN.synthetic_split((n,), 1, GN.CONFIGS[name]["k"])
+        u = GN.scene_input(C_obs, nrm, 0, n)
+        rel = GN.odd_rel(u)
+        assert rel.dtype == np.float32 and rel.shape == u.shape and rel[0].any()
+        assert not np.array_equal(rel, GN.rel_of(u)) and np.abs(rel - GN.rel_of(u)).max() > 0.1
+        if n >= 4:
+            off = ~np.eye(n, dtype=bool)
+            new = (GN.distances(rel) == 0) & off & ~((GN.distances(u) == 0) & off)
+            assert new[:, 2, 3].all() and new[1::2, 0, n - 1].all() and not new[0::2, 0, n - 1].any()
+        sd = GN.random_state(name)
+        assert scale_err(GN.forward(sd, u, rel), GN.forward(sd, u)) > 1e-3  # rel is read as given
+
+
+@pytest.mark.parametrize("value", [np.nan, np.inf], ids=["nan", "inf"])
+@pytest.mark.parametrize("name", ["deep", "wide", "et"])
+def test_a_nan_coefficient_poisons_the_whole_scene_in_the_restatement(name, value):
+    """the reference's arithmetic, restated: a NaN (or inf: |inf - inf|) coefficient makes its pedestrian's row and column
+    of A, every degree of that time row and so the whole time row NaN; the tcn carries it to the rows next to it and the
+    first epcnn convolution, which sums over all rows, to the whole scene.  tests/test_gpu_graphtern_shapes.py and
+    tests/test_gpu_graphtern.py hold the device to this mask"""
+    sd = GN.random_state(name)
+    C_obs, nrm = GN.synthetic_split((40,), 3, GN.CONFIGS[name]["k"])
+    C_obs[3, 17] = value
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out = GN.forward(sd, GN.scene_input(C_obs, nrm, 0, 40))
+    assert np.isnan(out).all()
+
+
+def test_one_step_outside_every_limit_is_refused_on_the_host():
+    """the refusals test_arguments_are_validated_on_the_host leaves out, at ranks other than 6 too: k = 0 and 33, S = 0 and
+    65, no st_mrgcn block and five, one epcnn block and nine, seq_len one off k + 2 on either side at k = 1, 2 and 32; the
+    accepted side of each limit is a member of GN.CONFIGS.  Both entry points, before any launch (the calls run without a
+    device); the workspace size of each is 0"""
+    from eigentrajectory_amd import _lib
+    lib = _lib.lib()
+    UNSUPPORTED = H.defines()["ET_ERR_UNSUPPORTED"]
+    bad = {"k = 0": dict(pred_seq_len=0, seq_len=2), "k = 33": dict(pred_seq_len=33, seq_len=35),
+           "S = 0": dict(n_smpl=0), "S = 65": dict(n_smpl=65), "n_epgcn = 0": dict(n_epgcn=0),
+           "n_epgcn = 5": dict(n_epgcn=_lib.GRAPHTERN_MAX_EPGCN + 1), "n_epcnn = 1": dict(n_epcnn=1),
+           "n_epcnn = 9": dict(n_epcnn=_lib.GRAPHTERN_MAX_EPCNN + 1)}
+    for k in (1, 2, 32):
+        bad[f"seq_len = k + 1, k = {k}"] = dict(pred_seq_len=k, seq_len=k + 1)
+        bad[f"seq_len = k + 3, k = {k}"] = dict(pred_seq_len=k, seq_len=k + 3)
+    bad["k = 32 under seq_len 8"] = dict(pred_seq_len=32)
+    for name, c in GN.CONFIGS.items():  # every configuration one step outside in S and in the block counts
+        base = dict(n_epgcn=c["st"], n_epcnn=c["epcnn"], n_smpl=c["S"], seq_len=c["k"] + 2, pred_seq_len=c["k"])
+        bad[f"{name} S = 65"] = dict(base, n_smpl=65)
+        bad[f"{name} n_epgcn = 0"] = dict(base, n_epgcn=0)
+        bad[f"{name} seq_len = k + 1"] = dict(base, seq_len=c["k"] + 1)
+    for what, kw in bad.items():
+        p = _params(**kw)
+        assert lib.et_graphtern_forward_graph(C.byref(p), 8, 3, 8, None, 0, None) == UNSUPPORTED, what
+        assert lib.et_graphtern_forward_scenes(C.byref(p), 8, 8, 3, None, 0, 8, None, None, 0, None) == UNSUPPORTED, what
+        assert int(lib.et_graphtern_workspace_bytes(C.byref(p), 5000, 100)) == 0, what
+    for name in GN.CONFIGS:  # the accepted side: N = 0 is answered ET_OK once the parameters have passed
+        assert lib.et_graphtern_forward_graph(C.byref(_cfg_params(name)), None, 0, None, None, 0, None) == 0, name
+        assert lib.et_graphtern_forward_scenes(C.byref(_cfg_params(name)), None, None, 0, None, 0, None, None, None, 0,
+                                               None) == 0, name

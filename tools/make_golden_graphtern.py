@@ -4,6 +4,7 @@ ET constructor arguments (utils/trainer.py:540: n_epgcn=1, n_epcnn=6, input_feat
 n_smpl=S), seeded, run on CPU in the build container.
 
     python tools/make_golden_graphtern.py --ref /root/reference --out tests/golden
+    python tools/make_golden_graphtern.py --family [--ref ... --out ...]    # G33 only, see family(); G27 is left alone
 
 The reference's normalizer moves its identity matrices to the GPU (`torch.eye(...).cuda()`, baseline/graphtern/
 normalizer.py); there is no GPU here, so for the duration of this script `Tensor.cuda` / `Module.cuda` are the identity --
@@ -88,11 +89,82 @@ def tied_zero(u):
     return False
 
 
+def family(args):
+    """G33 (--family): the reference's graph_tern_light at every member of tests/_graphtern_np.py: CONFIGS, under that
+    configuration's seeded weights (GN.random_state, loaded with strict=True), on the bridge's S_obs of the two scenes of
+    GN.fixture_inputs (3 and 13 pedestrians from the edge generator).  Stored per configuration and scene size n:
+      <name>.s_obs<n>     the bridge's S_obs as (2, T, n) = [abs, rel]
+      <name>.net_out<n>   the raw network output (k, n, S)
+    The weights are not stored: the tests regenerate them from the seed.  Asserted before anything is written: S_obs is
+    GN.s_obs_of(u) bit for bit, the fp64 restatement reproduces every output within 1e-5 of its largest entry, and the
+    reference's fp32 run is within 1e-5 of its own fp64 run.  A configuration the reference refuses to build or run is left
+    out and named in the manifest (MANIFEST_g33_graphtern_family.json).  Only data is written."""
+    import json
+    from tests import _graphtern_np as GN
+    sys.path.insert(0, args.ref)
+    os.chdir(args.ref)
+    torch.Tensor.cuda = lambda self, *a, **k: self  # no GPU in the build container (see the module docstring)
+    torch.nn.Module.cuda = lambda self, *a, **k: self
+    from baseline.graphtern import TrajectoryPredictor, model_forward, model_forward_pre_hook
+    torch.set_num_threads(1)
+    out, per_case, refused = {}, {}, {}
+    for name in GN.CONFIGS:
+        sd = GN.random_state(name)
+        try:
+            nets = []
+            for _ in range(2):  # (the residuals are lambdas closing over the instance: the fp64 copy is built afresh)
+                net = TrajectoryPredictor(**GN.module_cfg(name))
+                net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+                nets.append(net.eval())
+            nets[1].double()
+            sizes, C_obs, nrm = GN.fixture_inputs(name)
+            case = {}
+            for _, lo, n, u in GN.scenes_of(sizes, C_obs, nrm):
+                k = C_obs.shape[0]
+                with torch.no_grad():
+                    inp = model_forward_pre_hook(torch.from_numpy(u[:k]), torch.from_numpy(u[k:]))
+                    res = model_forward(inp, nets[0])
+                    r64 = nets[1](inp[0].double())
+                case[n] = (inp[0].numpy(), res[0].numpy(), r64[0].numpy(), u)
+        except Exception as exc:  # noqa: BLE001 -- the reference's own refusal of a shape
+            refused[name] = f"{type(exc).__name__}: {exc}"
+            print(f"{name}: the reference refuses this shape ({refused[name]}); left out", flush=True)
+            continue
+        c = GN.CONFIGS[name]
+        for n, (s_obs, ref, r64, u) in case.items():
+            assert s_obs.shape == (1, 2, c["k"] + 2, n, 1) and ref.shape == (c["k"], n, c["S"]) and ref.dtype == np.float32
+            assert np.array_equal(s_obs, GN.s_obs_of(u)), (name, n)
+            scale = np.abs(ref).max()
+            e_np = float(np.abs(GN.forward(sd, s_obs[0, 0, :, :, 0], s_obs[0, 1, :, :, 0]) - ref).max() / scale)
+            e_64 = float(np.abs(r64 - ref).max() / scale)
+            assert e_np <= 1e-5 and e_64 <= 1e-5, (name, n, e_np, e_64)
+            out[f"{name}.s_obs{n}"], out[f"{name}.net_out{n}"] = s_obs[0, :, :, :, 0], ref
+            per_case[f"{name}.{n}"] = {"restatement_vs_reference": e_np, "reference_fp32_vs_fp64": e_64,
+                                       "largest_entry": float(scale)}
+            print(f"{name} n = {n}: restatement {e_np:.2e}, the reference's fp32 against its fp64 run {e_64:.2e}", flush=True)
+    path = os.path.join(args.out, "g33_graphtern_family.npz")
+    np.savez_compressed(path, **out)
+    size = os.path.getsize(path)
+    assert size < 1024 * 1024
+    manifest = {"g33_graphtern_family": {
+        "cases": sorted(per_case), "refused_by_the_reference": refused, "state_seed": GN.STATE_SEED,
+        "configs": {n: {k: v for k, v in c.items()} for n, c in GN.CONFIGS.items()}, "scene_sizes": list(GN.FIXTURE_SIZES),
+        "numpy": np.__version__, "torch": torch.__version__, "bytes": size, "per_case": per_case}}
+    with open(os.path.join(args.out, "MANIFEST_g33_graphtern_family.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+        f.write("\n")
+    print("wrote", path, size)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
+    ap.add_argument("--family", action="store_true",
+                    help="write g33_graphtern_family.npz (the members of tests/_graphtern_np.py: CONFIGS) and leave g27 alone")
     args = ap.parse_args()
+    if args.family:
+        return family(args)
     from tests import _golden as G
     from tests import _graphtern_np as GN
     sys.path.insert(0, args.ref)
