@@ -2,7 +2,10 @@
 fp64 numpy restatement (tests/_gpgraph_stgcnn_np.py) against the reference's recorded distances, group indices, pass inputs
 and outputs (tests/golden/g22_gpgraph_stgcnn_net.npz, tools/make_golden_gpgraph_stgcnn.py), the fp32 bounds on the inputs of
 passes 1 and 2 on the reference's own values, the module's state_dict against the reference's, the refusals, and the ABI's
-names."""
+names; and, across the family (tests/_gpgraph_stgcnn_np.py: CONFIGS), the conditions on the seeded inputs of
+tests/test_gpu_gpgraph_stgcnn_shapes.py: the restated arena and workspace figures, no undecided pair, 1 < G < n, merges that
+are not the connected components, the restatement's own fp32 error, weights that show a wrong statement, and fixture G34
+(tests/golden/g34_gpgraph_stgcnn_family.npz) reproduced."""
 import os
 import re
 
@@ -231,3 +234,148 @@ def test_gpgraph_stgcnn_abi_names_declared_and_listed():
         # a base outside the STGCNN family: status 3, before any pointer is looked at
         assert _lib.lib().et_gpgraph_stgcnn_forward_graph(_lib.C.byref(p), None, None, _lib.i64(3), None, None, None, None,
                                                           None, 0, None) == 3
+
+
+# ------------------------------------------------------------------------------------------------- across the family
+# The conditions that keep tests/test_gpu_gpgraph_stgcnn_shapes.py from hiding behind its inputs, on the restatement alone.
+Z34 = G.load("g34_gpgraph_stgcnn_family.npz")
+_CASES = {}
+
+
+def family_cases():
+    """every scene the GPU file compares -> {tag: (name, v_abs, v_rel, th, kind)}; kind: layout name, "graph" or "extreme\""""
+    if _CASES:
+        return _CASES
+    for name in GS.CONFIGS:
+        layouts = [(layout, GS.layout_case(name, layout)) for layout in GS.USED[name]]
+        if "limit" in GS.USED[name]:
+            layouts.append(("around", GS.around_case(name)))
+        if name == "j17":
+            layouts.append(("nan", GS.layout_case(name, "nan")))
+        for layout, (sizes, C_obs, nrm, th) in layouts:
+            for s, lo, n, v in GS.scenes_of(sizes, C_obs, nrm):
+                if layout != "around" or n < GS.MAX_N:  # (the scene of 512 is layout limit's, bit for bit)
+                    _CASES[f"{name}.{layout}[{s}]"] = (name, v, v, th, layout)
+        for which, odd in GS.graph_cases(name):
+            va, vr, th = GS.graph_case(name, which, odd)
+            _CASES[f"{name}.{which}{'odd' if odd else ''}"] = (name, va, vr, th, "graph")
+        for above in (False, True) if name in GS.EXTREMES else ():
+            sizes, C_obs, nrm, th = GS.extreme_case(name, above)
+            v = GS.scenes_of(sizes, C_obs, nrm)[0][3]
+            _CASES[f"{name}.{'above' if above else 'below'}"] = (name, v, v, th, "extreme")
+    return _CASES
+
+
+def test_family_arena_and_workspace_figures():
+    for name, cfg in GS.CONFIGS.items():
+        assert (GS.arena_per_ped(*cfg), GS.lds_max_n(*cfg)) == GS.ARENA[name], name
+        L = GS.ARENA[name][1]
+        sizes = GS.layout_sizes(name, "edge")
+        assert sizes[3] == 0 and sizes[:3] == (1, 2, 3)
+        if name not in ("s1", "max"):
+            assert L - 1 in sizes and L in sizes and L + 1 in sizes and L + 1 <= GS.MAX_N
+        assert max(sizes) <= GS.MAX_SCENE.get(name, GS.MAX_N)
+    assert GS.ARENA["s1"][1] > GS.MAX_N  # no scene ever leaves LDS
+    # by hand, et (T = 8, k = 6, S = 20), one scene of 3: 6 -> 8, + 3 -> 12, + 3 -> 16, + 24 = 40, + 192 = 232, + 9 -> 244,
+    # + 9 -> 256, + 72 = 328, + 6 * 9 * 20 = 1408, no arena
+    et = GS.CONFIGS["et"]
+    assert GS.workspace_floats(et, 3, 9, 1) == 1408
+    where, total = GS.workspace_offsets(et, 34, 34 * 34, 1)   # a scene of 34 may be there: 456 floats for each of 3 N rows
+    assert total - where["arena"] == 456 * 3 * 34 and GS.workspace_floats(et, 34, 34 * 34 - 1, 1) == where["arena"]
+    for name in GS.CONFIGS:  # in the scene of L + 1 the group pass sits in LDS while passes 0 and 2 sit in the workspace
+        which = "g3" if name == "max" else "gL1"
+        if GS.graph_n(name, which) is None:
+            assert name == "s1"
+            continue
+        va, vr, th = GS.graph_case(name, which)
+        n = va.shape[1]
+        assert n == GS.ARENA[name][1] + 1
+        G_ = int(GS.grouping(GN.split_state(GS.with_threshold(name, th))[1], va)[1].max()) + 1
+        assert G_ <= GS.ARENA[name][1] < n, (name, G_)
+
+
+def test_family_seed_conditions():
+    """no undecided pair; 1 < G < n for n >= 3 (the extreme thresholds: G = n and G = 1); the merge is not the connected
+    components on at least three scenes, one of them above 256; in the scenes above 256 a group with members on both sides
+    of index 256 and a surviving label >= 256 (a scene of 257 can have only one of the two: both occur among the scenes of
+    257, and both in every scene of 512); the restatement's fp32 mode, fed its own fp32-rounded inputs of passes 1
+    and 2, within TOL / 4 of its fp64 mode"""
+    differs, differs_big, worst, large = 0, 0, {}, []
+    for tag, (name, va, vr, th, kind) in family_cases().items():
+        sd = GS.with_threshold(name, th)
+        rel = None if vr is va else vr
+        own = GS.forward(sd, va, v_rel=rel)
+        n, g = va.shape[1], own["n_groups"]
+        assert GN.pair_margin(own["dist"], float(th)) > GS.BAND_D, tag
+        close = own["dist"] <= float(th)
+        raw = GN.merge_literal(close)
+        assert np.array_equal(GN.compact(raw), own["indices"]), tag
+        if kind == "extreme":
+            assert g == (1 if tag.endswith("above") else n), (tag, g)
+        elif n >= 3:
+            assert 1 < g < n, (tag, g, n)
+            if len(np.unique(GN.merge_union_find(close))) != g:
+                differs += 1
+                differs_big += int(n > 256)
+        if n > 256 and kind != "extreme":
+            idx = own["indices"]
+            straddles = bool(np.isin(idx[256:], idx[:256]).any())
+            survives = bool(raw.max() >= 256)
+            # (a scene of 257 has one pedestrian above 255: merged, its group straddles; alone, its label survives)
+            assert (straddles and survives) if n > 257 else (straddles or survives), (tag, straddles, survives)
+            large.append((n, straddles, survives))
+        given = tuple(np.asarray(x, np.float32) for x in own["inputs"])
+        a = GS.forward(sd, va, inputs=given, indices=own["indices"], v_rel=rel)
+        b = GS.forward(sd, va, inputs=given, indices=own["indices"], v_rel=rel, dtype=np.float32)
+        err = GS.rel_err(b["out"], a["out"])
+        worst[name] = max(worst.get(name, 0.0), err)
+        assert err <= GS.TOL / 4, (tag, err)
+    print("gpgraph-stgcnn family: the restatement's fp32 mode against its fp64 mode, per configuration:",
+          {k: f"{v:.2e}" for k, v in worst.items()}, "; merges that are not the connected components:", differs, differs_big)
+    assert differs >= 3 and differs_big >= 1, (differs, differs_big)
+    assert any(s for n, s, _ in large if n == 257) and any(v for n, _, v in large if n == 257), large
+
+
+def test_family_weights_are_not_degenerate():
+    """each wrong statement moves the fp64 output by more than 100 TOL on the configuration that exists for it"""
+    va, vr, th = GS.graph_case("s1", "g13")
+    sd = GS.with_threshold("s1", th)
+    assert "baseline_model.st_gcns.0.residual.0.weight" not in sd   # S = 1: the first block's residual is the identity
+    assert GS.rel_err(GS.forward(sd, va, variant=("no_identity",))["out"], GS.forward(sd, va)["out"]) > 100 * GS.TOL
+    va, vr, th = GS.graph_case("j17", "g13")
+    sd = GS.with_threshold("j17", th)
+    assert GS.rel_err(GS.forward(sd, va, variant=("first_row",))["out"], GS.forward(sd, va)["out"]) > 100 * GS.TOL
+    for name in GS.CONFIGS:
+        for which in GS.ODD:
+            va, vr, th = GS.graph_case(name, which, True)
+            sd = GS.with_threshold(name, th)
+            assert not np.array_equal(va, vr)
+            assert GS.rel_err(GS.forward(sd, va)["out"], GS.forward(sd, va, v_rel=vr)["out"]) > 100 * GS.TOL, (name, which)
+
+
+def test_family_fixture_is_reproduced():
+    """G34 (tools/make_golden_gpgraph_stgcnn.py --family): the generated state is the recorded one (fp64 sums), the inputs
+    and thresholds are GS.graph_case's, the restatement's indices are the reference's, and fed the reference's recorded v'
+    and group means its output is within TOL of the recorded one"""
+    cases = sorted({k.rsplit(".", 1)[0] for k in Z34.files if k.endswith(".out")})
+    assert len(cases) == 4 * 6 + 2
+    for name in GS.CONFIGS:
+        sums = np.asarray([np.asarray(v, np.float64).sum() for v in GS.random_state(name).values()])
+        assert np.array_equal(sums, Z34[f"{name}.sums"]), name
+    for tag in cases:
+        name, which = tag.split(".")
+        odd = which.endswith("odd")
+        va, vr, th = GS.graph_case(name, which[:-3] if odd else which, odd)
+        assert np.array_equal(va, Z34[f"{tag}.v_abs"]) and np.array_equal(vr, Z34[f"{tag}.v_rel"]) and th == Z34[f"{tag}.th"]
+        assert odd == (not np.array_equal(va, vr))
+        sd = GS.with_threshold(name, th)
+        own = GS.forward(sd, va, v_rel=vr)
+        assert np.array_equal(own["indices"], Z34[f"{tag}.indices"]), tag
+        assert GS.rel_err(Z34[f"{tag}.dist"], own["dist"]) <= GS.TOL_D
+        r1, r2 = GS.check_inputs(vr, Z34[f"{tag}.v_intra"], Z34[f"{tag}.v_group"], Z34[f"{tag}.indices"])
+        assert r1 <= 1.0 and r2 <= 1.0, (tag, r1, r2)
+        res = GS.forward(sd, va, inputs=(Z34[f"{tag}.v_group"], Z34[f"{tag}.v_intra"]), indices=Z34[f"{tag}.indices"], v_rel=vr)
+        err = GS.rel_err(Z34[f"{tag}.out"], res["out"])
+        assert err <= GS.TOL, (tag, err)
+        if which == "g3":
+            assert float(Z34[f"{tag}.cond"]) <= GS.COND and bool(Z34[f"{tag}.ties_robust"]), tag

@@ -34,30 +34,36 @@ def net(dev, prefix="net."):
     return m.to(dev).eval()
 
 
-def run_graph(ops, m, dev, v):
-    """v (T, N) numpy -> the device's results: out (S, k, N), indices, dist, graph_inputs [v, group means, v']"""
+def run_graph(ops, m, dev, v, v_rel=None):
+    """v = v_abs (T, N) numpy, ``v_rel`` (T, N) or None: the same tensor, as the bridge hands it over -> the device's results:
+    out (S, k, N), indices, dist, graph_inputs [v_rel, group means, v']"""
     a = T(v[None, None], dev)
-    out, idx, det = ops.gpgraph_stgcnn_forward_graph(m, a, a, want_details=True)
-    plain, idx2 = m(a, a)  # forward is the graph form; asking for the details changes nothing; runs are bit-identical
+    r = a if v_rel is None else T(v_rel[None, None], dev)
+    out, idx, det = ops.gpgraph_stgcnn_forward_graph(m, a, r, want_details=True)
+    plain, idx2 = m(a, r)  # forward is the graph form; asking for the details changes nothing; runs are bit-identical
     assert torch.equal(plain, out) and torch.equal(idx2, idx) and idx.dtype == torch.int64
     assert det["n_groups"] == int(idx.max()) + 1
     return {"out": N_(out)[0], "indices": N_(idx), "dist": N_(det["dist"]), "gin": [N_(x) for x in det["graph_inputs"]]}
 
 
-def check(sd, v, got, th=None):
+def check(sd, v, got, th=None, v_rel=None):
     """the device's results against the restatement: distances, indices (no undecided pair -> equal), the fp32 bounds on the
-    inputs of passes 1 and 2, the output against the restatement fed THOSE inputs -> figures"""
+    inputs of passes 1 and 2, the output against the restatement fed THOSE inputs -> figures.  v = v_abs (the distances and
+    the decisions), ``v_rel`` (pass 0, v' and the group means; None: v_abs); every shape is the inputs' own (T = v.shape[0])"""
     rest = GN.split_state(sd)[1]
     th = GN.threshold(rest) if th is None else th
-    own = GS.forward(sd, v)
+    rel = v if v_rel is None else v_rel
+    own = GS.forward(sd, v, v_rel=v_rel)
     fig = {"n": v.shape[1], "dist_err": GS.rel_err(got["dist"], own["dist"]), "margin": GN.pair_margin(own["dist"], abs(th))}
     assert fig["dist_err"] <= GS.TOL_D, fig
     if fig["margin"] > GS.BAND_D:
         assert np.array_equal(got["indices"], own["indices"]), fig
-    assert np.array_equal(got["gin"][0], v)
-    fig["vprime"], fig["means"] = GS.check_inputs(v, got["gin"][2], got["gin"][1], got["indices"])
+    assert np.array_equal(got["gin"][0], rel)
+    g = int(np.max(got["indices"])) + 1
+    assert got["gin"][1].shape == (v.shape[0], g) and got["gin"][2].shape == v.shape
+    fig["vprime"], fig["means"] = GS.check_inputs(rel, got["gin"][2], got["gin"][1], got["indices"])
     assert fig["vprime"] <= 1.0 and fig["means"] <= 1.0, fig
-    ref = GS.forward(sd, v, inputs=(got["gin"][1], got["gin"][2]), indices=got["indices"])
+    ref = GS.forward(sd, v, inputs=(got["gin"][1], got["gin"][2]), indices=got["indices"], v_rel=v_rel)
     fig["out_err"] = GS.rel_err(got["out"], ref["out"])
     fig["n_groups"] = ref["n_groups"]
     print(f"gpgraph-stgcnn check: {fig}")
@@ -179,6 +185,8 @@ def test_scenes_form(dev, ops):
     assert Cc.shape == (6, n_all, 20) and Cc.is_contiguous()
     assert torch.equal(ops.gpgraph_stgcnn_forward_scenes(m, Cd, nd, scene_sizes=sizes), Cc)  # run to run, bit for bit
     Cc, gi, dist, gin = N_(Cc), N_(det["group_index"]), N_(det["dist"]), N_(det["graph_inputs"])
+    T_ = m.obs_seq_len  # graph_inputs is (3, T N): pass p of a scene is a (T, n_p) block at T (p N + first row)
+    assert gin.shape == (3, T_ * n_all)
     lo = sq = compared = 0
     for i, n in enumerate(sizes):
         # the graph form through the bridge
@@ -188,7 +196,7 @@ def test_scenes_form(dev, ops):
         assert np.array_equal(N_(idx), gi[lo:lo + n]), (lo, n)
         assert int(det["n_groups"][i]) == d["n_groups"]
         assert GS.rel_err(dist[sq:sq + n * n].reshape(n, n), N_(d["dist"])) <= GS.TOL_D
-        mine = [gin[p, 8 * lo:8 * (lo + nm)].reshape(8, nm) for p, nm in enumerate((n, d["n_groups"], n))]
+        mine = [gin[p, T_ * lo:T_ * (lo + nm)].reshape(T_, nm) for p, nm in enumerate((n, d["n_groups"], n))]
         if same_ties(mine, [N_(x) for x in d["graph_inputs"]]):
             compared += 1
             assert GS.rel_err(Cc[:, lo:lo + n], N_(ref)[0].transpose(1, 2, 0)) <= GS.TOL, (lo, n)

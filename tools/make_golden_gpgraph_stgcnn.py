@@ -4,6 +4,7 @@ get_GPGraph_STGCNN_model with the ET constructor arguments (utils/trainer.py:505
 out_dims=S), seeded, run on CPU.
 
     python tools/make_golden_gpgraph_stgcnn.py --ref <reference checkout> --out tests/golden
+    python tools/make_golden_gpgraph_stgcnn.py --family --ref <reference checkout>     # G34 only, see family(); G22 is left alone
 
 As in tools/make_golden_gpgraph_sgcn.py, `Tensor.cuda` / `Module.cuda` are the identity for the duration of this script, the
 reference's classes are constructed directly, and the arithmetic is the reference's own.  Every BatchNorm's running
@@ -139,13 +140,101 @@ def store_pick(out, tag, split, index, rec, th):
         out[f"{tag}.{key}"] = rec[key]
 
 
+def family(args):
+    """G34 (--family): the reference's GPGraph around its social_stgcnn at every member of tests/_gpgraph_stgcnn_np.py:
+    CONFIGS, under that configuration's seeded weights (GS.random_state, loaded with strict=True) and the case thresholds, on
+    the graph-form scenes of 3 and 13 pedestrians (GS.graph_case; `max`: 3 only) -- each with the bridge's v_rel = v_abs and
+    with the odd v_rel that no bridge builds.  Every case is run in fp32 and, the same modules converted with .double(), in
+    fp64.  Stored per case <name>.<g3|g13>[odd], data only:
+      .v_abs, .v_rel (T, n), .th, .dist (n, n), .indices, .v_group (T, G), .v_intra (T, n) (pass 0's input is .v_rel),
+      .out (S, k, n) fp32, .cond (the reference's own fp32-against-fp64 difference, of the largest entry), .ties_robust
+    and per configuration <name>.sums, the fp64 sum of every tensor of the generated state in the module's order: the weights
+    are not stored, the tests regenerate them from the seed, and a drifted generator shows here before any kernel is blamed.
+    Asserted before anything is written: v_abs, v_rel and th are GS.graph_case's, no pair is within 1e-5 th, and every case
+    of 3 pedestrians with the bridge's v_rel has cond <= GS.COND and robust ties."""
+    import json
+    from tests import _gpgraph_np as GN
+    from tests import _gpgraph_stgcnn_np as GS
+    sys.path.insert(0, args.ref)
+    os.chdir(args.ref)
+    torch.Tensor.cuda = lambda self, *a, **k: self
+    torch.nn.Module.cuda = lambda self, *a, **k: self
+    from baseline.gpgraphstgcnn.model_baseline import social_stgcnn
+    from baseline.gpgraphstgcnn.model_groupwrapper import GPGraph
+    torch.set_num_threads(1)
+    out, per_case = {}, {}
+    for name, (n_st, n_tp, S, k) in GS.CONFIGS.items():
+        sd = GS.random_state(name)
+        out[f"{name}.sums"] = np.asarray([np.asarray(v, np.float64).sum() for v in sd.values()], np.float64)
+        nets = []
+        for _ in range(2):  # (the identity residuals are lambdas: the fp64 copy is built afresh, not deep-copied)
+            base = social_stgcnn(n_stgcnn=n_st, n_txpcnn=n_tp, input_feat=1, output_feat=S, kernel_size=3, seq_len=k + 2,
+                                 pred_seq_len=k)
+            net = GPGraph(baseline_model=base, in_channels=1, out_channels=S, obs_seq_len=k + 2, pred_seq_len=k,
+                          d_type="learned_l2norm", d_th="learned", mix_type="mlp", group_type=(True, True, True),
+                          weight_share=True)
+            net.load_state_dict({key: torch.from_numpy(v) for key, v in sd.items()}, strict=True)
+            nets.append(net.eval())
+        caps = [Capture(nets[0]), Capture(nets[1].double())]
+        for which, odd in GS.graph_cases(name):
+            if which == "gL1" or (name == "max" and which != "g3"):  # (S k = 2048: the scene of 3 keeps the file small)
+                continue
+            v_abs, v_rel, th = GS.graph_case(name, which, odd)
+            recs = []
+            for cap, dt in zip(caps, (torch.float32, torch.float64)):
+                torch.set_default_dtype(dt)  # (the wrapper allocates its pooling buffers in the default dtype)
+                try:
+                    with torch.no_grad():
+                        cap.net.group_gen.th.fill_(float(th))
+                        cap.clear()
+                        o, idx = cap.net(torch.from_numpy(v_abs).to(dt)[None, None], torch.from_numpy(v_rel).to(dt)[None, None])
+                finally:
+                    torch.set_default_dtype(torch.float32)
+                assert len(cap.ins) == 3 and torch.equal(cap.ins[0][0, 0], torch.from_numpy(v_rel).to(dt))
+                recs.append({"out": o[0].numpy(), "indices": idx.numpy().astype(np.int64), "dist": cap.dist.numpy(),
+                             "v_group": cap.ins[1][0, 0].numpy(), "v_intra": cap.ins[2][0, 0].numpy()})
+            rec, r64 = recs
+            tag = f"{name}.{which}{'odd' if odd else ''}"
+            assert rec["out"].dtype == np.float32 and rec["out"].shape == (S, k, v_abs.shape[1]), tag
+            margin = GN.pair_margin(r64["dist"], float(th))
+            assert margin > GN.BAND_D and np.array_equal(rec["indices"], r64["indices"]), (tag, margin)
+            cond = GS.rel_err(rec["out"], r64["out"])
+            robust = GS.ties_robust(v_rel, rec["v_group"], rec["v_intra"])
+            if which == "g3" and not odd:
+                assert cond <= GS.COND and robust, (tag, cond, robust)
+            out[f"{tag}.v_abs"], out[f"{tag}.v_rel"], out[f"{tag}.th"] = v_abs, v_rel, np.float32(th)
+            for key in ("dist", "indices", "v_group", "v_intra", "out"):
+                out[f"{tag}.{key}"] = rec[key]
+            out[f"{tag}.cond"], out[f"{tag}.ties_robust"] = np.float64(cond), np.bool_(robust)
+            per_case[tag] = {"n": int(v_abs.shape[1]), "n_groups": int(rec["indices"].max()) + 1, "cond": cond,
+                             "ties_robust": bool(robust), "pair_margin": margin, "largest_entry": float(np.abs(rec["out"]).max())}
+            print(f"{tag}: n = {v_abs.shape[1]}, {per_case[tag]['n_groups']} groups, cond {cond:.2e}, ties_robust {robust}",
+                  flush=True)
+    path = os.path.join(args.out, "g34_gpgraph_stgcnn_family.npz")
+    np.savez_compressed(path, **out)
+    size = os.path.getsize(path)
+    assert size < 512 * 1024, size
+    manifest = {"g34_gpgraph_stgcnn_family": {
+        "cases": sorted(per_case), "state_seed": GS.STATE_SEED, "configs": {n: list(c) for n, c in GS.CONFIGS.items()},
+        "numpy": np.__version__, "torch": torch.__version__, "bytes": size, "per_case": per_case}}
+    with open(os.path.join(args.out, "MANIFEST_g34_gpgraph_stgcnn_family.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+        f.write("\n")
+    print("wrote", path, size)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", required=True, help="checkout of the reference project")
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
     ap.add_argument("--seed", type=int, default=1234, help="of the weights")
+    ap.add_argument("--family", action="store_true",
+                    help="write g34_gpgraph_stgcnn_family.npz (the members of tests/_gpgraph_stgcnn_np.py: CONFIGS) and leave "
+                         "g22 alone")
     args = ap.parse_args()
     args.out = os.path.abspath(args.out)
+    if args.family:
+        return family(args)
     from tests import _golden as G
     from tests import _gpgraph_np as GN
     from tests import _gpgraph_stgcnn_np as GS
