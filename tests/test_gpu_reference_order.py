@@ -1,6 +1,25 @@
 """GPU parity tests -- BatchKMeans(sums="reference-order"): ATen's own summation orders, whole reference runs bit for bit.
 HIP path (through the C ABI, via eigentrajectory_amd.ops) vs the CPU oracle and the golden vectors; needs a real MI355X:
-run with ``pytest -m gpu``."""
+run with ``pytest -m gpu``.
+
+Above 2^21 points three things change, each compared here with the reference (G7e) or the oracle: ATen's level step
+becomes 32 (from N = 2 097 156), the farthest-first point skip is on by default (N >= 2^21), and level 3 is folded in
+more than one staging round (more than 128 KiB / (16 (6 K + 8)) complete blocks).  Left out on purpose: N = 1e7 itself
+(the oracle takes about 6 s per iteration there plus its seeding; the staging-round cases run the only structurally new
+path of that size at a tenth of it) and level step 64 (N > 2^25).
+
+What the tests of this file notice: two variants of the kernels, each in bounds and wrong in numbers only, were run
+once with this file on the MI355X (66 tests; not committed).
+  * reforder_update_kernel2's level-3 loop stopping after its first staging round: 4 fail --
+    test_reference_order_level3_staging_rounds_vs_oracle (all three cases) and
+    test_reference_order_level_step_boundary_vs_oracle[2097155]; the other 62 pass, among them every test this file had
+    before those two were added (none of them has more complete blocks than a round holds).
+  * cascade_levels folding only the first 16 of a chain's 32 terms where lp = 5: 10 fail --
+    test_reference_order_l32_whole_runs_g7e (both), test_reference_order_l32_shards_g7e,
+    test_reference_order_level_step_boundary_vs_oracle[2097156], test_reference_order_l32_k_edges_vs_oracle (all four)
+    and, of the earlier tests, the two 4.3e6-point cases of test_reference_order_shards_equal_the_single_gpu_fit (the
+    shards and the single-GPU fit then differ from EACH OTHER; neither is compared with anything else there).  The other
+    56 pass: every comparison with the reference or the oracle this file had before ran at level step 16."""
 import os
 
 import numpy as np
@@ -160,6 +179,168 @@ def test_reference_order_kmeans_1e6_g7d(ops, dev, et_option, filter_lp):
         del x
     print(f"exact sums end with the reference's labels in {equal_exact} of {len(z['seeds'])} runs at N = 1e6")
     assert equal_exact == G7D_EXACT_EQUAL
+
+
+# ------------------------------------------------ above 2^21 points: level step 32, the point skip by default, staging rounds
+G7E_CASES = [(2097159, 300), (2101383, 301)]
+_ORACLE_RUNS = {}  # (n, K, seed, blobs, iterations) -> (x, c0, the oracle's fit): computed once, read only
+
+
+def _oracle_run(oracle, n, K, seed, blobs, iters):
+    """x = gaussian_points_np(6, n, seed, blobs), c0 = its first K points (no seeding: the oracle's takes seconds at these
+    sizes), the oracle's reference-order fit of `iters` iterations -- shared by the cases that differ in options only."""
+    from eigentrajectory_amd.synth import gaussian_points_np
+    key = (n, K, seed, blobs, iters)
+    if key not in _ORACLE_RUNS:
+        x = gaussian_points_np(6, n, seed=seed, n_blobs=blobs)
+        c0 = np.ascontiguousarray(x[:, :K])
+        _ORACLE_RUNS[key] = (x, c0, oracle.kmeans_fit(x, c0, iters, 1e-4, sums="reference-order"))
+    return _ORACLE_RUNS[key]
+
+
+def _same_as_oracle(r, ref, note):
+    assert r["n_iter"] == ref["n_iter"], note
+    assert np.array_equal(N_(r["labels"]), ref["labels"]), note
+    assert np.array_equal(N_(r["centroids"]), ref["centroids"]), note
+    assert np.array_equal(N_(r["trace"])[:, 0], ref["trace"][:, 0].astype(np.float32)), note
+    np.testing.assert_allclose(N_(r["trace"])[:, 1], ref["trace"][:, 1], rtol=1e-5)  # (the inertia: fp32 rounding of an fp64 sum)
+
+
+def _complete_blocks(n):
+    """ATen's level step for n points (N / 4 lane terms: 16 up to 2^19 of them, 32 up to 2^24) and the number of complete
+    level-2 blocks (4 L^3 points each) -- restated here, not asked of the library."""
+    L = 16 if n // 4 <= 1 << 19 else 32
+    assert n // 4 <= 1 << 24
+    return L, n // (4 * L ** 3)
+
+
+def _update_rows_cap(K):
+    """csrc/et_reforder_sharded.inl update_rows_cap, restated: rows of 16 (6 K + 8) bytes in 128 KiB."""
+    return (128 * 1024) // (16 * (6 * K + 8))
+
+
+@pytest.mark.parametrize("filter_lp", [9, 4])
+def test_reference_order_l32_whole_runs_g7e(ops, dev, et_option, filter_lp):
+    """Whole runs of the imported reference's BatchKMeans just above N = 2^21 (tests/golden/g7e,
+    tools/make_golden_batchkmeans_l32.py: farthest-first seeding + 4 Lloyd iterations): level step 32 in every cascade, and
+    the farthest-first point skip ON BY DEFAULT (reforder_init_skip_min = 2^21 <= N; nothing forces it here).  The
+    reference's initial centroids with the skip and without it; its iteration count, labels (sha256, counts), centroid
+    bits and the printed error of every iteration."""
+    import hashlib
+    from eigentrajectory_amd import _lib as L
+    from eigentrajectory_amd.synth import gaussian_points_np
+    assert int(L.get_option("reforder_init_skip_min")) == 1 << 21  # the default: the skip is on for both cases
+    et_option("reforder_filter_min_lp", filter_lp)  # 4: labels certified by the matrix-core filter from the second iteration on
+    z = G.load("g7e_batchkmeans_l32.npz")
+    K, max_iter, tol = int(z["K"]), int(z["max_iter"]), float(z["tol"])
+    assert (K, max_iter, tol) == (20, 4, 1e-4)
+    for n, seed in G7E_CASES:
+        tag = f"n{n}.s{seed}"
+        assert _complete_blocks(n) == (32, 16)
+        x = T(gaussian_points_np(6, n, seed=seed, n_blobs=int(z[f"{tag}.blobs"])), dev)
+        first = int(z[f"{tag}.first_index"])
+        c0 = ops.kmeans_init_farthest_reference_order(x, K, first)
+        assert np.array_equal(N_(c0), z[f"{tag}.c0"]), tag
+        r = ops.kmeans_fit_reference_order(x, c0, max_iter, tol)
+        lab = N_(r["labels"]).astype(np.uint8)
+        assert r["n_iter"] == int(z[f"{tag}.n_iter"]), tag
+        assert hashlib.sha256(lab.tobytes()).digest() == bytes(z[f"{tag}.labels_sha256"]), tag
+        assert np.array_equal(np.bincount(lab, minlength=K), z[f"{tag}.counts"]), tag
+        assert np.array_equal(N_(r["centroids"]), z[f"{tag}.centroids"]), tag
+        assert np.array_equal(N_(r["trace"])[:, 0], z[f"{tag}.trace"][:, 0].astype(np.float32)), tag
+        np.testing.assert_allclose(N_(r["trace"])[:, 1], z[f"{tag}.trace"][:, 1], rtol=1e-5)
+        et_option("reforder_init_skip_min", 1 << 40)  # the same picks with every point read at every step
+        plain = ops.kmeans_init_farthest_reference_order(x, K, first)
+        et_option("reforder_init_skip_min", 1 << 21)
+        assert np.array_equal(N_(plain), z[f"{tag}.c0"]), tag
+        del x
+
+
+def test_reference_order_l32_shards_g7e(dev):
+    """G7e's case B over two shards cut at level-2 blocks of 131 072 points: [8 blocks, the rest] and [16 blocks, the
+    rest] -- in the second the last rank holds nothing but the partial block, group and chunk (4 231 points).  Every shard
+    ends with the REFERENCE's centroid bits, iteration count and error trace; the shards' labels together hash to its
+    labels."""
+    import hashlib
+    from eigentrajectory_amd import _lib as L
+    from eigentrajectory_amd.synth import gaussian_points_np
+    z = G.load("g7e_batchkmeans_l32.npz")
+    n, seed = G7E_CASES[1]
+    tag = f"n{n}.s{seed}"
+    K, max_iter, tol = int(z["K"]), int(z["max_iter"]), float(z["tol"])
+    x = gaussian_points_np(6, n, seed=seed, n_blobs=int(z[f"{tag}.blobs"]))
+    block = int(L.lib().et_kmeans_reforder_shard_block(L.i64(n), 6, K))
+    assert block == 131072
+    for blocks in (8, 16):
+        sizes = [blocks * block, n - blocks * block]
+        assert blocks != 16 or sizes[1] == 4231
+        shards = _reference_order_shards_native(dev, x, z[f"{tag}.c0"], sizes, max_iter, tol)
+        for rank, sh in enumerate(shards):
+            assert np.array_equal(sh["centroids"], z[f"{tag}.centroids"]), (blocks, rank)
+            assert int(sh["state"].iter) == int(z[f"{tag}.n_iter"]), (blocks, rank)
+            assert np.array_equal(sh["trace"][:, 0], z[f"{tag}.trace"][:, 0].astype(np.float32)), (blocks, rank)
+            np.testing.assert_allclose(sh["trace"][:, 1], z[f"{tag}.trace"][:, 1], rtol=1e-5)
+        lab = np.concatenate([sh["labels"] for sh in shards]).astype(np.uint8)
+        assert len(lab) == n and hashlib.sha256(lab.tobytes()).digest() == bytes(z[f"{tag}.labels_sha256"]), blocks
+        assert np.array_equal(np.bincount(lab, minlength=K), z[f"{tag}.counts"]), blocks
+
+
+@pytest.mark.parametrize("n,block", [(2097155, 16384), (2097156, 131072)])
+def test_reference_order_level_step_boundary_vs_oracle(ops, dev, oracle, n, block):
+    """The last N with level step 16 and the first with 32 (N / 4 = 2^19 and 2^19 + 1 lane terms): predict and two
+    iterations against the oracle's literal restatement, every bit; the shard block tells that the two sizes sit on either
+    side of the change.  N = 2 097 155 is 128 complete blocks and 3 leftover points: at K = 20 level 3 is folded in two
+    FULL staging rounds of 64 rows (csrc/et_reforder_fast_update.inl)."""
+    from eigentrajectory_amd import _lib as L
+    K = 20
+    assert int(L.lib().et_kmeans_reforder_shard_block(L.i64(n), 6, K)) == block
+    step, complete = _complete_blocks(n)
+    assert block == 4 * step ** 3 and complete == (128 if n == 2097155 else 16)
+    assert n != 2097155 or complete == 2 * _update_rows_cap(K)
+    x, c0, ref = _oracle_run(oracle, n, K, 310, 7, 2)
+    lab_ref, ms_ref = oracle.kmeans_assign(x, c0, reference_order=True)
+    X = T(x, dev)
+    lab, ms = ops.kmeans_predict_reference_order(X, T(c0, dev))
+    assert np.array_equal(N_(lab), lab_ref) and np.array_equal(N_(ms), ms_ref)
+    _same_as_oracle(ops.kmeans_fit_reference_order(X, T(c0, dev), 2, 1e-4), ref, n)
+
+
+@pytest.mark.parametrize("n,K,complete", [(672839, 32, 41), (1066055, 20, 65), (2097155, 32, 128)])
+def test_reference_order_level3_staging_rounds_vs_oracle(ops, dev, oracle, n, K, complete):
+    """Level 3 of the cascade folded in MORE THAN ONE staging round (reforder_update_kernel2 stages at most
+    128 KiB / (16 (6 K + 8)) rows of complete blocks in LDS at a time: 40 at K = 32, 64 at K = 20) -- the smallest shapes
+    with a second round (40 + 1 and 64 + 1 rows; each with a partial block of one group, a partial group of one chunk, a
+    partial chunk and N mod 4 = 3) and four rounds with a short last one (40, 40, 40, 8).  Three iterations against the
+    oracle, every bit; the first size also as a batch of two problems, so that the joint stop crosses the rounds.  The
+    benchmark's N = 1e7 (76 complete blocks of 131 072, K = 20: 64 + 12) runs the same loop."""
+    assert _complete_blocks(n) == (16, complete) and n % 4 == 3
+    assert _update_rows_cap(K) == {20: 64, 32: 40}[K] and _update_rows_cap(K) < complete  # else the loop runs once
+    x, c0, ref = _oracle_run(oracle, n, K, 320, 5, 3)
+    _same_as_oracle(ops.kmeans_fit_reference_order(T(x, dev), T(c0, dev), 3, 1e-4), ref, (n, K))
+    if n == 672839:
+        x1, c1, _ = _oracle_run(oracle, n, K, 321, 0, 3)
+        xs, cs = np.stack([x, x1]), np.stack([c0, c1])
+        both = oracle.kmeans_fit_batch_reference_order(list(xs), list(cs), 3, 1e-4)
+        runs = ops.kmeans_fit_reference_order_batch(T(xs, dev), T(cs, dev), 3, 1e-4)
+        for b, r in enumerate(runs):
+            assert r["n_iter"] == both["n_iter"]
+            assert np.array_equal(N_(r["labels"]), both["labels"][b]), b
+            assert np.array_equal(N_(r["centroids"]), both["centroids"][b]), b
+            assert np.array_equal(N_(r["trace"])[:, 0], both["trace"][:, 0].astype(np.float32))
+            np.testing.assert_allclose(r["inertia"], both["inertia"][b], rtol=1e-5)
+
+
+@pytest.mark.parametrize("filter_lp", [9, 4])
+@pytest.mark.parametrize("K", [3, 32])
+def test_reference_order_l32_k_edges_vs_oracle(ops, dev, oracle, et_option, K, filter_lp):
+    """Level step 32 (G7e's case-B size: partial block, group, chunk, 3 leftover points) at K = 3 and at K = 32, the
+    largest accumulator region of the groups kernel's LDS: two iterations against the oracle, every bit, without and with
+    the matrix-core label certification."""
+    et_option("reforder_filter_min_lp", filter_lp)
+    n = 2101383
+    assert _complete_blocks(n) == (32, 16)
+    x, c0, ref = _oracle_run(oracle, n, K, 330, 9, 2)
+    _same_as_oracle(ops.kmeans_fit_reference_order(T(x, dev), T(c0, dev), 2, 1e-4), ref, (K, filter_lp))
 
 
 @pytest.mark.parametrize("n,d,K", [(1, 6, 1), (5, 6, 3), (37, 6, 7), (1003, 6, 20), (4099, 6, 33), (20000, 6, 20), (777, 9, 5),

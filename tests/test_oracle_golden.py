@@ -308,6 +308,47 @@ def test_reforder_arithmetic_equals_torch(oracle):
     for size in (1, 2, 3, 4, 5, 6, 7, 8, 9, 15, 16, 17, 31, 33, 120, 121, 127, 128, 255, 256, 1000, 6 * 255):
         v = (rng.standard_normal(size) ** 2).astype(f32)
         assert oracle.inner_sum(v) == torch.from_numpy(v).sum().item(), size
+    # ATen's level step on either side of its change (N / 4 > 2^19: 16 -> 32) and G7e's two sizes; K = 3 keeps the
+    # (1, 6, n, K) product at 150 MB
+    for n in (2097155, 2097156, 2097159, 2101383):
+        x = (rng.standard_normal((6, n)) * 3 + 1).astype(f32)
+        lab = rng.integers(0, 3, size=n)
+        xt, lt = torch.from_numpy(x)[None], torch.from_numpy(lab)[None]
+        mask = torch.stack([lt == i for i in range(3)], dim=-1)  # kmeans.py:180-182
+        want = (xt.unsqueeze(dim=-1) * mask.unsqueeze(dim=-3)).sum(dim=-2)[0].numpy()
+        assert np.array_equal(oracle.kmeans_reforder_sums(x, lab, 3), want), n
+
+
+G7E_CASES = [(2097159, 300), (2101383, 301)]
+
+
+@pytest.mark.parametrize("n,seed", G7E_CASES)
+def test_g7e_whole_runs_vs_reference(oracle, n, seed):
+    """Whole runs of the imported reference's BatchKMeans just above N = 2^21 (tests/golden/g7e,
+    tools/make_golden_batchkmeans_l32.py: farthest-first seeding + 4 Lloyd iterations), where ATen's cascade takes level
+    step 32.  The oracle's reference-order seeding and fit end on the reference's initial centroids, iteration count,
+    labels, counts, centroid BITS and the printed error of EVERY iteration; the exact-sum oracle from the same initial
+    centroids does not end on those labels, so the fixture tells the two modes apart."""
+    import hashlib
+    from eigentrajectory_amd.synth import gaussian_points_np
+    z = G.load("g7e_batchkmeans_l32.npz")
+    assert [int(v) for v in z["sizes"]] == [c[0] for c in G7E_CASES] and [int(v) for v in z["seeds"]] == [c[1] for c in G7E_CASES]
+    K, max_iter, tol = int(z["K"]), int(z["max_iter"]), float(z["tol"])
+    assert (K, max_iter, tol) == (20, 4, 1e-4)
+    tag = f"n{n}.s{seed}"
+    x = gaussian_points_np(6, n, seed=seed, n_blobs=int(z[f"{tag}.blobs"]))
+    c0, _ = oracle.kmeans_init_farthest(x, K, int(z[f"{tag}.first_index"]), reference_order=True)
+    assert np.array_equal(c0, z[f"{tag}.c0"])
+    r = oracle.kmeans_fit(x, c0, max_iter, tol, sums="reference-order")
+    lab = r["labels"].astype(np.uint8)
+    assert r["n_iter"] == int(z[f"{tag}.n_iter"]) == len(z[f"{tag}.trace"])
+    assert hashlib.sha256(lab.tobytes()).digest() == bytes(z[f"{tag}.labels_sha256"])
+    assert np.array_equal(np.bincount(lab, minlength=K), z[f"{tag}.counts"])
+    assert np.array_equal(r["centroids"], z[f"{tag}.centroids"])
+    assert np.array_equal(r["trace"][:, 0].astype(np.float32), z[f"{tag}.trace"][:, 0].astype(np.float32))  # torch's error, every bit
+    np.testing.assert_allclose(r["trace"][:, 1], z[f"{tag}.trace"][:, 1], rtol=1e-5)
+    e = oracle.kmeans_fit(x, c0, max_iter, tol)
+    assert hashlib.sha256(e["labels"].astype(np.uint8).tobytes()).digest() != bytes(z[f"{tag}.labels_sha256"])
 
 
 @pytest.mark.parametrize("n", [1000, 10000])
