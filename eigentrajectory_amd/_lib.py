@@ -163,6 +163,14 @@ SIGNATURES = {
     "et_graphtern_workspace_bytes": (_Z, [_P, _I64, _I64]),
     "et_graphtern_forward_graph": (_I, [_P, _P, _I64, _P, _P, _Z, _P]),
     "et_graphtern_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _Z, _P]),
+    # ---- Graph-TERN predictor, training
+    "et_graphtern_train_workspace_bytes": (_Z, [_P, _I64, _I]),
+    "et_graphtern_grad_floats": (_I64, [_P]),
+    "et_graphtern_train_layout": (_I, [_P, _I64, _I, _P, _I]),
+    "et_graphtern_train_forward_graph": (_I, [_P, _P, _I64, _P, _P, _P, _Z, _P]),
+    "et_graphtern_train_forward_scenes": (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _P, _Z, _P]),
+    "et_graphtern_backward_graph": (_I, [_P, _I64, _P, _P, _I64, _P, _Z, _P]),
+    "et_graphtern_backward_scenes": (_I, [_P, _I64, _P, _I, _P, _P, _I64, _P, _Z, _P]),
     # ---- fit
     "et_fit_gram_workspace_bytes": (_Z, [_I64, _I, _I]),
     "et_fit_gram": (_I, [_P, _P, _I64, _I, _I, _I, _F, _I, _P, _P, _P, _P, _Z, _P]),
@@ -427,6 +435,9 @@ class AgentFormerParams(C.Structure):
 
 GRAPHTERN_MAX_EPGCN = 4  # ET_GRAPHTERN_MAX_EPGCN
 GRAPHTERN_MAX_EPCNN = 8  # ET_GRAPHTERN_MAX_EPCNN
+GRAPHTERN_REL = 4        # relations per time row: [A_abs, A_rel, 1/A_abs, 1/A_rel]
+GRAPHTERN_TRAIN_MAX_N = 512          # ET_GRAPHTERN_TRAIN_MAX_N
+GRAPHTERN_TRAIN_LAYOUT_FIELDS = 16   # ET_GRAPHTERN_TRAIN_LAYOUT_FIELDS
 
 
 class GraphTERNLayer(C.Structure):

@@ -15,9 +15,20 @@ checkpoint's ``baseline_model.*`` keys load unchanged (``strict=True``), and the
 are read in place from this module's tensors (a ``load_state_dict``, a ``.to()`` or an in-place edit is seen by the next
 call, and by a captured graph's next replay).  ``tp_mrgcns.{i}.prelu`` is a parameter of the reference's state_dict that
 its forward never applies (``use_mdn``); it is kept for the checkpoint's sake and not applied here either.
-Training (drop_edge, dropout, the backward pass) is not implemented natively: a forward in training mode raises.  A whole
-split runs as one launch through :meth:`EigenTrajectory.evaluate_split` /
+A whole split runs as one launch through :meth:`EigenTrajectory.evaluate_split` /
 :func:`eigentrajectory_amd.ops.graphtern_forward_scenes`.
+A forward in training mode raises -- unless the instance was switched by
+``eigentrajectory_amd.enable_native_training(model)``.  Then a training-mode ``forward(S_obs, keep=None)`` is
+``et_graphtern_train_forward_graph`` (csrc/et_graphtern_train.hip, one launch), which is NOT the eval forward:
+MultiRelationalGCN applies ``drop_edge(A, 0.8)`` to the float tensor A (1, 4, T, N, N) before ``+ I`` and before the
+normalisation, so the degrees change with the mask and each normalised graph is no longer symmetric.  The draw is
+:meth:`GraphTERNLight.draw_keep` -- one ``torch.rand((1, 4, T, N, N))``, an entry kept where ``~(rand > 0.8)`` -- unless
+``keep`` (uint8, (4, T, N, N), indexed [r, t, w, v]) is given.  The output is differentiable with respect to every parameter
+the forward reads (``et_graphtern_backward_graph``, three launches; no input gradient; ``tp_mrgcns.0.prelu.weight.grad``
+stays None, as torch leaves it).  The switch is the plain attribute ``native_training`` (no parameter, no buffer, not in
+the ``state_dict``, default False).  Trained natively: the family below with ``n_epgcn = 1`` (the only depth ET builds; a
+deeper stack needs a gradient through the graph contraction), every ``Dropout.p = 0`` and scenes of at most 512
+pedestrians.
 Supported family: ``input_feat = 1``, ``seq_len = pred_seq_len + 2``, ``pred_seq_len <= 32``, ``1 <= n_smpl <= 64``,
 ``1 <= n_epgcn <= 4``, ``2 <= n_epcnn <= 8`` (the hidden width is the reference's constant 16); other shapes construct,
 but their forward raises.
@@ -28,10 +39,12 @@ by an ulp can move a scene's output by per cent ("Graph-TERN").
 """
 from __future__ import annotations
 
+import torch
 import torch.nn as nn
 
 from . import _lib as L
 from ._lib import _p
+from ._native_train import train_forward
 
 HIDDEN_FEAT = 16  # model.py:229
 KERNEL_SIZE = 3   # model.py:230
@@ -87,6 +100,12 @@ class GraphTERNLight(nn.Module):
     r"""baseline/graphtern/model.py's ``graph_tern_light`` (eval-mode inference on the GPU).  ``forward(S_obs)``: S_obs
     (1, 2, T, N, 1) = [abs, rel] as the graphtern bridge's pre-hook builds it -> (1, k, N, S); the post-hook squeezes it."""
 
+    native_training = False  # a plain attribute, set per instance by eigentrajectory_amd.enable_native_training
+    #: how enable_native_training ends its refusal of an instance outside the native family
+    trains_natively = ("LBEBM, PECNet, SocialImplicitLight, SGCN, SocialSTGCNN, SocialDMRGCN and a GraphTERNLight with "
+                       "n_epgcn = 1 and no dropout train natively")
+    drop_edge_percent = 0.8  # stmrgcn.py:22: drop_edge(A, 0.8, self.training) keeps an entry where ~(rand > 0.8)
+
     def __init__(self, n_epgcn=1, n_epcnn=6, input_feat=2, seq_len=8, pred_seq_len=12, n_smpl=20):
         super().__init__()
         self.n_epgcn, self.n_epcnn, self.n_smpl = n_epgcn, n_epcnn, n_smpl
@@ -125,7 +144,52 @@ class GraphTERNLight(nn.Module):
                 t.resc_w, t.resc_b = _p(blk.rescconv[0].weight), _p(blk.rescconv[0].bias)
         return p, dev
 
-    def forward(self, S_obs):
+    def outside_native_training(self):
+        """-> None, or the field that puts this instance outside the family that trains natively, as text"""
+        if self.n_epgcn != 1:
+            return (f"n_epgcn = {self.n_epgcn} (native: 1; a deeper stack sends a gradient through the graph contraction "
+                    "and is out of scope)")
+        for field, want in (("input_feat", 1), ("seq_len", self.pred_seq_len + 2)):
+            if getattr(self, field) != want:
+                return f"{field} = {getattr(self, field)} (native: {want})"
+        for field, lo, hi in (("n_epcnn", 2, L.GRAPHTERN_MAX_EPCNN), ("n_smpl", 1, 64), ("pred_seq_len", 1, L.MAX_K)):
+            if not lo <= getattr(self, field) <= hi:
+                return f"{field} = {getattr(self, field)} (native: {lo} to {hi})"
+        for name, m in self.named_modules():
+            if isinstance(m, nn.Dropout) and m.p != 0:
+                return f"{name}.p = {m.p} (native: 0)"
+        return None
+
+    def draw_keep(self, n, device, generator=None):
+        """The DropEdge draw of one training-mode forward on ``n`` pedestrians -> uint8 (4, T, n, n), indexed [r, t, w, v]:
+        one ``torch.rand((1, 4, T, n, n))``, as the reference's MultiRelationalGCN draws ``rand_like(A)``; an entry is kept
+        where ``~(rand > drop_edge_percent)``."""
+        draw = torch.rand((1, L.GRAPHTERN_REL, self.seq_len, n, n), device=device, generator=generator)
+        return (~(draw > self.drop_edge_percent))[0].to(torch.uint8)
+
+    native_parameters = nn.Module.parameters  # what :mod:`._native_train` differentiates: every parameter
+
+    def native_forward(self, et, S_obs, keep):
+        from . import ops
+        ws = ops.graphtern_train_workspace(self, S_obs.shape[3], et_params=et)
+        return ops.graphtern_train_forward_graph(self, S_obs, ws, keep=keep, et_params=et), (() if ws is None else (ws,))
+
+    def native_backward(self, et, kept, g_out):
+        from . import ops
+        ws = kept[0] if kept else None
+        views = ops.graphtern_grad_views(self, ops.graphtern_backward_graph(self, ws, g_out, et_params=et))
+        return [None if name == "tp_mrgcns.0.prelu.weight" else g for name, g in views.items()]  # never applied: no gradient
+
+    def forward(self, S_obs, keep=None):
+        if self.training and self.native_training and self.outside_native_training() is None:
+            if S_obs.requires_grad:
+                raise RuntimeError("GraphTERNLight: no input gradient is built (the graphtern bridge detaches S_obs); an "
+                                   "input requires one")
+            dev = L.module_device("GraphTERNLight", self)
+            S_obs = L.on_device(S_obs, dev)
+            if keep is None:
+                keep = self.draw_keep(S_obs.shape[3] if S_obs.dim() == 5 else 0, dev)
+            return train_forward(self, S_obs, keep)
         if self.training:
             raise RuntimeError("GraphTERNLight: only inference is native (no drop_edge, no dropout); training-mode forward "
                                "and backward are not implemented -- call .eval() first")

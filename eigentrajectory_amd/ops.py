@@ -1488,6 +1488,156 @@ def graphtern_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=F
     return (out, {"graph_inputs": gin}) if want_details else out
 
 
+# ------------------------------------------------------------------------------ Graph-TERN predictor (training)
+def _graphtern_train_params(who, model, et_params):
+    if et_params is not None:   # the training Function's calls: its forward() has looked at the family already
+        return et_params
+    why = model.outside_native_training()
+    if why is not None:
+        raise NotImplementedError(f"{who}: GraphTERNLight has no native backward pass outside its native family: {why}")
+    return model.et_params()
+
+
+def graphtern_train_workspace(model, n, n_scenes=1, et_params=None):
+    """A training workspace for ``n`` pedestrians in ``n_scenes`` scenes: :func:`graphtern_train_forward_graph` /
+    ``_scenes`` fill it, :func:`graphtern_backward_graph` / ``_scenes`` read it (None for ``n`` = 0)."""
+    params, dev = _graphtern_train_params("graphtern_train_workspace", model, et_params)
+    return _workspace("et_graphtern_train_workspace_bytes", dev, params, n, max(n_scenes, 1), required=n > 0)[0]
+
+
+def graphtern_train_forward_graph(model, S_obs, workspace, keep=None, et_params=None):
+    """``model`` in training mode on one scene as the graphtern bridge hands it over: S_obs (1, 2, T, N, 1) = [abs, rel],
+    ``keep`` uint8 (4, T, N, N) indexed [r, t, w, v] (:meth:`GraphTERNLight.draw_keep`; None keeps every edge) -> the raw
+    output (1, k, N, S).  What the backward reads stays in ``workspace`` (of :func:`graphtern_train_workspace`) for
+    :func:`graphtern_backward_graph`.  One launch."""
+    params, dev = _graphtern_train_params("graphtern_train_forward_graph", model, et_params)
+    T, k, S = params.seq_len, params.pred_seq_len, params.n_smpl
+    n = S_obs.shape[3] if S_obs.dim() == 5 else -1
+    if tuple(S_obs.shape) != (1, 2, T, n, 1):
+        raise ValueError(f"graphtern_train_forward_graph: S_obs {tuple(S_obs.shape)} is not (1,2,{T},N,1)")
+    if n > L.GRAPHTERN_TRAIN_MAX_N:
+        raise ValueError(f"graphtern_train_forward_graph: N = {n} exceeds the {L.GRAPHTERN_TRAIN_MAX_N} pedestrians a "
+                         "training scene may have")
+    (S_obs,) = _dev_args(dev, S_obs.detach())
+    keep = _dmrgcn_keep("graphtern_train_forward_graph", dev, keep, shape=(L.GRAPHTERN_REL, T, n, n))
+    out = torch.empty((1, k, n, S), device=dev)
+    if n:
+        _check_train_ws("graphtern_train_forward_graph", dev, workspace, "graphtern_train_workspace")
+    L.call("et_graphtern_train_forward_graph", C.byref(params), L.ptr(S_obs), n, L.ptr(keep), L.ptr(out), L.ptr(workspace),
+           _numel(workspace), L.stream(dev))
+    return out
+
+
+def graphtern_keep_offsets(scene_sizes, device=None):
+    """-> (int64 tensor (n_scenes + 1,): where each scene's (4, T, n, n) block of a packed keep mask starts, in units of
+    4 T entries (the running sum of n^2; a scene above the training cap takes no room), the total sum of n^2)"""
+    off = [0]
+    for s in scene_sizes:
+        off.append(off[-1] + (int(s) ** 2 if int(s) <= L.GRAPHTERN_TRAIN_MAX_N else 0))
+    t = torch.tensor(off, dtype=torch.int64)
+    return (t if device is None else t.to(device)), off[-1]
+
+
+def graphtern_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, keep=None, workspace=None):
+    """The graphtern bridge + ``model`` in training mode + the post-hook for every scene of a batch in ONE launch, one
+    workgroup per scene.  C_obs, nrm and ``scene_sizes`` as :func:`graphtern_forward_scenes`; ``keep``: uint8, every scene's
+    (4, T, n, n) block one after the other (:func:`graphtern_keep_offsets`), None keeps every edge -> (C_pred_refine
+    (k, N, S), workspace); the workspace (made here unless given) goes to :func:`graphtern_backward_scenes` with the same
+    ``scene_sizes``.  A scene of more than 512 pedestrians is not computed (NaN rows)."""
+    params, dev = _graphtern_train_params("graphtern_train_forward_scenes", model, None)
+    b = _scene_batch("graphtern_train_forward_scenes", dev, C_obs, nrm, params.pred_seq_len, scene_sizes)
+    if scene_sizes is None and b.n > L.GRAPHTERN_TRAIN_MAX_N:
+        raise ValueError(f"graphtern_train_forward_scenes: one unlisted scene of {b.n} pedestrians exceeds the "
+                         f"{L.GRAPHTERN_TRAIN_MAX_N} a training scene may have")
+    if workspace is None:
+        workspace = graphtern_train_workspace(model, b.n, len(b.sizes), et_params=(params, dev))
+    if b.n:
+        _check_train_ws("graphtern_train_forward_scenes", dev, workspace, "graphtern_train_workspace")
+    koff, total = graphtern_keep_offsets(b.sizes, dev if keep is not None else None)
+    keep = _dmrgcn_keep("graphtern_train_forward_scenes", dev, keep, numel=L.GRAPHTERN_REL * params.seq_len * total)
+    out = torch.empty((params.pred_seq_len, b.n, params.n_smpl), device=dev)
+    L.call("et_graphtern_train_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), b.n, L.ptr(b.off), b.n_scenes,
+           L.ptr(keep), L.ptr(koff if keep is not None else None), L.ptr(out), L.ptr(workspace), _numel(workspace),
+           L.stream(dev))
+    return out, workspace
+
+
+def graphtern_grad_views(model, grads):
+    """``grads``, the flat buffer of :func:`graphtern_backward_graph` / ``_scenes`` -> {state_dict key: a view of it shaped
+    like the parameter}, every parameter of ``model`` (state_dict order).  ``tp_mrgcns.0.prelu.weight``, which the forward
+    never applies, is always +0."""
+    return _grad_views("graphtern_grad_views", model, grads)
+
+
+def graphtern_backward_graph(model, workspace, d_out, et_params=None):
+    """The backward pass of :func:`graphtern_train_forward_graph` in three launches: ``workspace`` as that call filled it
+    (same weights), ``d_out`` (1, k, N, S) the gradient at its output -> the flat float32 gradient buffer
+    (:func:`graphtern_grad_views` names its parts)."""
+    params, dev = _graphtern_train_params("graphtern_backward_graph", model, et_params)
+    n = d_out.shape[2] if d_out.dim() == 4 else -1
+    d_out, grads = _backward_args("graphtern_backward_graph", "et_graphtern_grad_floats", params, dev, d_out,
+                                  (1, params.pred_seq_len, n, params.n_smpl))
+    if n:
+        _check_train_ws("graphtern_backward_graph", dev, workspace, "graphtern_train_workspace")
+    L.call("et_graphtern_backward_graph", C.byref(params), n, L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace),
+           _numel(workspace), L.stream(dev))
+    return grads
+
+
+def graphtern_backward_scenes(model, workspace, d_out, scene_sizes=None):
+    """The backward pass of :func:`graphtern_train_forward_scenes` in three launches whatever the number of scenes:
+    ``workspace`` as that call filled it, ``scene_sizes`` as given to it, ``d_out`` (k, N, S) -> the flat gradient buffer,
+    summed over the scenes in ascending order."""
+    params, dev = _graphtern_train_params("graphtern_backward_scenes", model, None)
+    n = d_out.shape[1] if d_out.dim() == 3 else -1
+    d_out, grads = _backward_args("graphtern_backward_scenes", "et_graphtern_grad_floats", params, dev, d_out,
+                                  (params.pred_seq_len, n, params.n_smpl))
+    _, off, n_scenes = _scene_sizes(scene_sizes, n, dev)
+    if n:
+        _check_train_ws("graphtern_backward_scenes", dev, workspace, "graphtern_train_workspace")
+    L.call("et_graphtern_backward_scenes", C.byref(params), n, L.ptr(off), n_scenes, L.ptr(d_out), L.ptr(grads),
+           grads.numel(), L.ptr(workspace), _numel(workspace), L.stream(dev))
+    return grads
+
+
+def graphtern_train_layout(model, n, n_scenes=1):
+    """-> the ``ET_GRAPHTERN_TRAIN_LAYOUT_FIELDS`` offsets of a training workspace, in floats (``et_graphtern_train_layout``;
+    include/eigentraj.h names the fields)"""
+    params, _ = model.et_params()
+    return _layout("et_graphtern_train_layout", L.GRAPHTERN_TRAIN_LAYOUT_FIELDS, params, n, n_scenes)
+
+
+def graphtern_train_views(model, workspace, n, n_scenes=1, lo=0, scene=0, scene_n=None):
+    """The values kept in ``workspace`` by name, as views, for scene number ``scene`` of ``scene_n`` pedestrians that starts
+    at row ``lo`` (one scene: the defaults).  Forward: ``u`` (T, n), ``d`` (4, T, n), ``P`` (4, 2, T, n) (the contracted
+    rows: j = 0 from u, j = 1 from the ones row), ``yp`` (16, T, n) the tcn PReLU's input, ``x0`` (T, 16, n) the st_mrgcn
+    block's output, and per epcnn block the lists ``c0`` / ``y`` (k, 16, n) and ``c1`` / ``o`` (k, C_out, n).  After a
+    backward call also ``d_o`` (k, C_out, n) and ``d_y`` (k, 16, n) per block, ``d_x0`` (T, 16, n), ``d_yt`` (16, T, n) the
+    gradient at PReLU(yp), and ``partial``, the scene's own flat gradient.  The offsets are the library's
+    (``et_graphtern_train_layout``)."""
+    params, _ = model.et_params()
+    T, k, S, H = params.seq_len, params.pred_seq_len, params.n_smpl, params.hidden_feat
+    m = n if scene_n is None else scene_n
+    f = workspace.view(torch.float32)
+    (o_u, o_d, o_p, o_yp, o_x0, o_tp, o_dtp, o_dx, o_dy, _, per, tp_stride, dtp_stride, o_part, G, _) = graphtern_train_layout(
+        model, n, n_scenes)
+    base = lo * per
+    fld = lambda off, *shape: f[base + off * m:base + off * m + math.prod(shape) * m].view(*shape, m)
+    kH, kC = k * H, k * max(H, S)
+    views = {"u": fld(o_u, T), "d": fld(o_d, L.GRAPHTERN_REL, T), "P": fld(o_p, L.GRAPHTERN_REL, 2, T), "yp": fld(o_yp, H, T),
+             "x0": fld(o_x0, T, H), "d_x0": fld(o_dx, T, H), "d_yt": fld(o_dy, H, T)}
+    blocks = range(params.n_epcnn)
+    cout = [S if j + 1 == params.n_epcnn else H for j in blocks]
+    views["c0"] = [fld(o_tp + j * tp_stride, k, H) for j in blocks]
+    views["y"] = [fld(o_tp + j * tp_stride + kH, k, H) for j in blocks]
+    views["c1"] = [fld(o_tp + j * tp_stride + 2 * kH, k, cout[j]) for j in blocks]
+    views["o"] = [fld(o_tp + j * tp_stride + 2 * kH + kC, k, cout[j]) for j in blocks]
+    views["d_o"] = [fld(o_dtp + j * dtp_stride, k, cout[j]) for j in blocks]
+    views["d_y"] = [fld(o_dtp + j * dtp_stride + kC, k, H) for j in blocks]
+    views["partial"] = f[o_part + scene * G:o_part + (scene + 1) * G]
+    return views
+
+
 # ------------------------------------------------------------------------------ PECNet / LBEBM predictors (inference)
 def _mlp_rows(who, dev, width, **tensors):
     """(N, width_i) float32 rows on ``dev``, all of one N"""

@@ -170,8 +170,10 @@ def enable_native_training(model, flag=True):
     ``SGCN(position_channel=True, dropout=0)``, or a ``SocialSTGCNN`` of its native family (``n_stgcnn = 1``, no per-time-row
     graph, affine BatchNorms that track running statistics with one float momentum, no dropout; its training-mode forward
     uses BatchNorm batch statistics and updates the running ones), or a ``SocialDMRGCN`` of its native family (``n_stgcn =
-    1``, every ``Dropout.p = 0``; its training-mode forward applies DropEdge through a keep mask it draws per call) (the
-    plain attribute ``native_training``); the other three predictors have no native backward pass and raise.  -> ``model``"""
+    1``, every ``Dropout.p = 0``; its training-mode forward applies DropEdge through a keep mask it draws per call), or a
+    ``GraphTERNLight`` of its native family (``n_epgcn = 1``, every ``Dropout.p = 0``; DropEdge on its float graphs through a
+    keep mask it draws per call) (the plain attribute ``native_training``); the other two predictors have no native backward
+    pass and raise.  -> ``model``"""
     from ._native_train import family_name
     from .gpgraph import GPGraph
     from .implicit import SocialImplicitLight
@@ -181,7 +183,7 @@ def enable_native_training(model, flag=True):
         net.enable_native_training(flag)
     elif isinstance(net, (PECNet, SocialImplicitLight)):
         net.native_training = bool(flag)
-    elif hasattr(net, "outside_native_training"):  # SGCN, GPGraph, SocialSTGCNN, SocialDMRGCN: a native family each
+    elif hasattr(net, "outside_native_training"):  # SGCN, GPGraph, SocialSTGCNN, SocialDMRGCN, GraphTERNLight: a family each
         why = net.outside_native_training()
         if why is not None:
             raise NotImplementedError(f"enable_native_training: {family_name(net)} has no native backward pass outside its "
@@ -189,6 +191,6 @@ def enable_native_training(model, flag=True):
         net.native_training = bool(flag)
     else:
         raise NotImplementedError(f"enable_native_training: {type(net).__name__} has no native backward pass; only LBEBM, "
-                                  "PECNet, SocialImplicitLight, SGCN, SocialSTGCNN and SocialDMRGCN, and GPGraph around SGCN, "
-                                  "train natively")
+                                  "PECNet, SocialImplicitLight, SGCN, SocialSTGCNN, SocialDMRGCN and GraphTERNLight, and GPGraph "
+                                  "around SGCN, train natively")
     return model

@@ -1176,6 +1176,73 @@ int et_graphtern_forward_scenes(const et_graphtern_params *params, const float *
                                 const int32_t *scene_offsets, int n_scenes, float *C_pred_refine, float *graph_inputs,
                                 void *workspace, size_t workspace_bytes, et_stream_t stream);
 
+/* ---- Graph-TERN predictor, training (graph_tern_light.forward in training mode + its backward pass) -------------------
+ * The training-mode forward is NOT the eval forward: MultiRelationalGCN applies drop_edge(A, 0.8) (stmrgcn.py:22) to the
+ * float tensor A (1,4,T,N,N) = [A_abs, A_rel, 1/A_abs, 1/A_rel] before + I and before the normalisation, one draw per
+ * st_mrgcn block.  The draw is the caller's: `keep`, uint8, (4,T,N,N) indexed [r,t,w,v] (graph form), entry != 0 keeps
+ * A_r[w,v]; scenes form: scene s's own (4,T,n,n) block starts at 4 T keep_offsets[s], keep_offsets (device, n_scenes + 1
+ * int64_t) the running sum of n^2 over the scenes (a scene above the cap takes no room); keep = NULL keeps everything.
+ * s[r,t,w] = sum_v (keep ? A_r[w,v] : 0) + [v==w], d = 1/sqrt(s) with inf set to 0, L[r,t,w,v] = (d_w ((keep ? A_r[w,v] :
+ * 0) + [v==w])) d_v with d_v the column pedestrian's own row degree: the degrees change with the mask and L is no longer
+ * symmetric.  A's diagonal is exactly 0, so the mask's diagonal has no effect.  Every other statement is
+ * et_graphtern_forward_*'s in its order, so with keep = NULL or all ones the output is bit-equal to the inference entry's.
+ * Trained natively: the inference family with n_epgcn = 1 (the only depth ET builds; a deeper stack needs a gradient
+ * through the contraction, L^T: ET_ERR_UNSUPPORTED) and scenes of at most ET_GRAPHTERN_TRAIN_MAX_N pedestrians (a larger
+ * scene of the scenes form is not computed: NaN outputs, no gradient; graph form: ET_ERR_INVALID_ARG).  The graphs are
+ * detached by the reference (model.py:244) and the bridge detaches the input: no gradient passes through a graph.
+ *   et_graphtern_train_workspace_bytes  the training workspace for N pedestrians in n_scenes scenes (graph form: 1): what
+ *                                       the forward keeps, the activation gradients, an arena for scenes that do not fit
+ *                                       LDS and the scenes' gradient partials.  0: outside the family, N <= 0 or
+ *                                       n_scenes < 1.
+ *   et_graphtern_train_forward_graph /  arguments as et_graphtern_forward_graph / _scenes (no graph_inputs) plus the mask.
+ *   et_graphtern_train_forward_scenes   ONE launch, one workgroup per scene, the live operands in the LDS arena when the
+ *                                       scene fits it (at S = 20, k = 6: up to 35 pedestrians), else in the workspace's
+ *                                       arena rows.
+ *   et_graphtern_backward_graph /       d_out laid out as the forward's output ((1,k,N,S) / (k,N,S)) and the workspace as
+ *   et_graphtern_backward_scenes        that forward left it (same parameters, N, scene_offsets) -> grads, grads_floats >=
+ *                                       et_graphtern_grad_floats floats: every parameter's gradient in state_dict order
+ *                                       (tp_mrgcns.0: prelu.weight, gcn.conv.weight, .bias, tcn.0.weight, tcn.1.weight,
+ *                                       .bias, residual.0.weight, .bias; tpcnns.j: tpcns.0.0.weight, .bias, tpcns.0.1.weight,
+ *                                       cpcns.0.0.weight, .bias, cpcns.0.1.weight, [rescconv.0.weight, .bias,]
+ *                                       [restconv.0.weight, .bias]).  tp_mrgcns.0.prelu.weight is never applied by the
+ *                                       forward: its slot is always +0 (torch leaves its .grad None).  THREE launches for
+ *                                       any N and any number of scenes: the activation gradients (one workgroup per scene,
+ *                                       the dependent chain in the arena), the parameter gradients (16 workgroups per
+ *                                       scene: every element is one wavefront's sum, the scene's 64 wavefronts take them
+ *                                       round robin), the reduction.
+ * The transposed 3x3 convolutions under replicate padding are gathers: an input cell sums the outputs whose clamped taps
+ * land on it, in a fixed order; the convolution weight gradients read the input through the same clamps.
+ * No gradient with respect to the input.  No atomics: a gradient element of a scene is one wavefront's sum over the
+ * element's positions (lane l adds positions l, l + 64, ... in ascending order, then the lanes by the xor butterfly 32, 16,
+ * ..., 1), and the scenes' partials are added in ascending order, the first one copied; results are bit-identical from run
+ * to run, and a one-scene scenes call equals the graph call.  Host-side checks answer ET_ERR_UNSUPPORTED /
+ * ET_ERR_INVALID_ARG / ET_ERR_WORKSPACE before any launch. */
+#define ET_GRAPHTERN_TRAIN_MAX_N 512
+size_t et_graphtern_train_workspace_bytes(const et_graphtern_params *params, int64_t N, int n_scenes);
+int64_t et_graphtern_grad_floats(const et_graphtern_params *params);
+/* where the training workspace keeps what (host only, no launch), in floats.  Per-pedestrian fields first (scene s's block
+ * starts at off[s] x [10]; field f of it at + offsets[f] x the scene's n): [0] u (T,n), [1] d (4,T,n) the D^-1/2 of the
+ * masked graphs, [2] P (4,2,T,n) the contracted rows (j = 0 from u, j = 1 from the ones row), [3] yp (16,T,n) the tcn
+ * PReLU's input, [4] x0 (T,16,n) the st_mrgcn block's output, [5] per epcnn block j at + j x [11]: c0, y (k,16,n each:
+ * tpcns.0's pre-activation and output), then c1, o (k,C,n each with C = max(16, S) floats of room, (k,C_out,n) used:
+ * cpcns.0's pre-activation, the block's output); block j's input is x0 (j = 0) or block j-1's o, [6] per epcnn block at +
+ * j x [12]: do (room (k,C,n), used (k,C_out,n)) the gradient at the block's output, dy (k,16,n) the gradient at y, [7] dx0
+ * (T,16,n), [8] dy (16,T,n) the gradient at PReLU(yp), [9] the arena; [10] floats per pedestrian; [13] the scenes'
+ * gradient partials, [14] = et_graphtern_grad_floats each; [15] the total. */
+#define ET_GRAPHTERN_TRAIN_LAYOUT_FIELDS 16
+int et_graphtern_train_layout(const et_graphtern_params *params, int64_t N, int n_scenes, int64_t *offsets, int n_offsets);
+int et_graphtern_train_forward_graph(const et_graphtern_params *params, const float *S_obs, int64_t N, const uint8_t *keep,
+                                     float *out, void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_graphtern_train_forward_scenes(const et_graphtern_params *params, const float *C_obs, const float *nrm, int64_t N,
+                                      const int32_t *scene_offsets, int n_scenes, const uint8_t *keep,
+                                      const int64_t *keep_offsets, float *C_pred_refine, void *workspace,
+                                      size_t workspace_bytes, et_stream_t stream);
+int et_graphtern_backward_graph(const et_graphtern_params *params, int64_t N, const float *d_out, float *grads,
+                                int64_t grads_floats, void *workspace, size_t workspace_bytes, et_stream_t stream);
+int et_graphtern_backward_scenes(const et_graphtern_params *params, int64_t N, const int32_t *scene_offsets, int n_scenes,
+                                 const float *d_out, float *grads, int64_t grads_floats, void *workspace,
+                                 size_t workspace_bytes, et_stream_t stream);
+
 /* ---- fit ----------------------------------------------------------------------------
  * Gram matrices of the normalised trajectories routed to descriptor `which`
  * (1 moving / 0 static) under `mode`:  G_obs (2T_obs,2T_obs), G_pred (2T_pred,2T_pred)
