@@ -265,6 +265,9 @@ class STGCNNParams(C.Structure):
 
 
 STGCNN_TRAIN_LAYOUT_FIELDS = 26  # ET_STGCNN_TRAIN_LAYOUT_FIELDS
+# ... by name, in the C enum's order (include/eigentraj.h names them in et_stgcnn_train_layout's comment)
+STGCNN_TRAIN_LAYOUT_NAMES = ("u", "d", "P", "g", "a1", "y", "t", "r", "s", "x", "tp", "dfin", "dtp", "dx", "ds", "dt", "dr", "dy",
+                             "da1", "dg", "per", "stats", "stat_stride", "partials", "grads", "total")
 
 
 class STGCNNTrain(C.Structure):
@@ -278,10 +281,16 @@ class STGCNNTrain(C.Structure):
 SGCN_MAX_LAYERS = 8  # ET_SGCN_MAX_LAYERS
 SGCN_MAX_N = 512     # ET_SGCN_MAX_N
 SGCN_TRAIN_LAYOUT_FIELDS = 24  # ET_SGCN_TRAIN_LAYOUT_FIELDS
+SGCN_TRAIN_LAYOUT_NAMES = ("v", "rows_s", "rows_t", "stack_s", "stack_s_stride", "stack_t", "stack_t_stride", "at", "f2", "f1",
+                           "ts", "keep", "keep_stride", "d_at", "d_f1", "d_ts", "d_f2", "rrec", "g_s", "g_t", "dir_s", "dir_t",
+                           "dd_s", "total")  # the C enum's order
 SGCN_BWD_CHUNK = 4     # ET_SGCN_BWD_CHUNK: pedestrians whose tail gradients one workgroup adds, in row order
 SGCN_BWD_ROWS = 1024   # ET_SGCN_BWD_ROWS: softmax rows per workgroup of the row kernels
 SGCN_BWD_ITEMS = 4096  # ET_SGCN_BWD_ITEMS: stack positions / entries per workgroup of the asym and fuse kernels
 GPGRAPH_SGCN_TRAIN_LAYOUT_FIELDS = 49  # ET_GPGRAPH_SGCN_TRAIN_LAYOUT_FIELDS
+GPGRAPH_SGCN_TRAIN_LAYOUT_NAMES = SGCN_TRAIN_LAYOUT_NAMES[:-1] + (  # SGCN's without its total, then the wrapper's
+    "vp", "vn", "gidx", "dax", "srec", "trec", "dacct", "dxas", "dxp", "dxv", "va", "feat", "dist", "sn", "po", "sig", "cs", "cnt",
+    "dmix", "dpo", "dvp", "dP", "dsig", "dd", "df", "total")
 GPGRAPH_BWD_ROWS = 64  # ET_GPGRAPH_BWD_ROWS: pedestrians per workgroup partial of the mix weights' gradients
 
 
@@ -328,6 +337,8 @@ DMRGCN_MAX_TPCNN = 8  # ET_DMRGCN_MAX_TPCNN
 DMRGCN_BINS = 5       # ET_DMRGCN_BINS
 DMRGCN_TRAIN_MAX_N = 512          # ET_DMRGCN_TRAIN_MAX_N
 DMRGCN_TRAIN_LAYOUT_FIELDS = 16   # ET_DMRGCN_TRAIN_LAYOUT_FIELDS
+DMRGCN_TRAIN_LAYOUT_NAMES = ("u", "P", "yp", "s", "x", "tp", "dtp", "dx", "dy", "arena", "per", "tp_stride", "dtp_stride",
+                             "partials", "grads", "total")  # the C enum's order
 
 
 class DMRGCNLayer(C.Structure):
@@ -438,6 +449,8 @@ GRAPHTERN_MAX_EPCNN = 8  # ET_GRAPHTERN_MAX_EPCNN
 GRAPHTERN_REL = 4        # relations per time row: [A_abs, A_rel, 1/A_abs, 1/A_rel]
 GRAPHTERN_TRAIN_MAX_N = 512          # ET_GRAPHTERN_TRAIN_MAX_N
 GRAPHTERN_TRAIN_LAYOUT_FIELDS = 16   # ET_GRAPHTERN_TRAIN_LAYOUT_FIELDS
+GRAPHTERN_TRAIN_LAYOUT_NAMES = ("u", "d", "P", "yp", "x0", "tp", "dtp", "dx0", "dy", "arena", "per", "tp_stride", "dtp_stride",
+                                "partials", "grads", "total")  # the C enum's order
 
 
 class GraphTERNLayer(C.Structure):

@@ -1,5 +1,6 @@
-"""The training-mode autograd Function of the scene-graph predictors (SocialSTGCNN, SGCN, GPGraph, SocialDMRGCN,
-SocialImplicitLight): one skeleton, three hooks on the model.
+"""The training-mode autograd Function of the six predictors whose kernels build no input gradient -- the five scene-graph
+ones (SocialSTGCNN, SGCN, GPGraph, SocialDMRGCN, GraphTERNLight) and SocialImplicitLight: one skeleton, three hooks on the
+model.
 
 ``native_parameters()``
     the parameters the kernels differentiate, in the order of the gradients

@@ -24,7 +24,7 @@
 //   2. dmrgcn_train_wgrad_kernel   grid (scenes, kDtChunks): every parameter-gradient element of a scene is one wavefront's
 //                                  sum; the scene's 64 wavefronts take the elements round robin -> the scene's partial
 //   3. scene_grad_reduce_kernel    grads[e] = the scenes' partials in ascending order, the first one copied
-//                                  (et_train_sums.inl, shared with et_stgcnn_train.hip)
+//                                  (et_train_sums.inl, which the three scene training units share)
 // Fixed orders (no atomics; two runs agree bit for bit, a one-scene scenes call equals the graph call): wave_sum of
 // et_train_sums.inl (lane l adds positions l, l + 64, ... ascending from +0, then the xor butterfly 32 .. 1); every other
 // sum is one lane's ascending fmaf chain.  Every PReLU branches on the kept fp32 word in both passes.
@@ -37,11 +37,6 @@ namespace {
 #include "et_scene_helpers.inl"
 #include "et_stgcnn_core.inl"
 #include "et_dmrgcn_core.inl"
-#include "et_train_sums.inl"
-
-constexpr int kDtMaxN = ET_DMRGCN_TRAIN_MAX_N;
-constexpr int kDtChunks = 16;                     // weight-gradient workgroups per scene
-constexpr int kDtWaves = kDtChunks * kTrWaves;    // ... and its wavefronts
 
 enum {
     F_U, F_P, F_YP, F_S, F_X, F_TP, F_DTP, F_DX, F_DY, F_ARENA, F_PER, F_TP_STRIDE, F_DTP_STRIDE, F_PARTIALS, F_GRADS, F_TOTAL,
@@ -49,9 +44,11 @@ enum {
 };
 static_assert(F_COUNT == ET_DMRGCN_TRAIN_LAYOUT_FIELDS, "et_dmrgcn_train_layout's field count");
 
-struct DtLayout {
-    int64_t o[F_COUNT];
-};
+#include "et_train_sums.inl"
+
+constexpr int kDtMaxN = ET_DMRGCN_TRAIN_MAX_N;
+constexpr int kDtChunks = 16;                     // weight-gradient workgroups per scene
+constexpr int kDtWaves = kDtChunks * kTrWaves;    // ... and its wavefronts
 
 // where every parameter's gradient starts in the flat buffer (state_dict order)
 struct DtGradOff {
@@ -88,8 +85,8 @@ __host__ __device__ inline DtGradOff dt_grad_off(const DmDims &D) {
 // the arena of both passes: dm_run_scene's, and room for the backward's two GTA rows behind its three buffers
 __host__ __device__ inline int64_t dt_arena_per_ped(const DmDims &D) { return dm_arena_per_ped(D) + 2 * D.S; }
 
-__host__ __device__ inline DtLayout dt_layout(const DmDims &D, int64_t N, int64_t n_scenes) {
-    DtLayout L{};
+__host__ __device__ inline TrainLayout dt_layout(const DmDims &D, int64_t N, int64_t n_scenes) {
+    TrainLayout L{};
     const int64_t SK = (int64_t)D.S * D.K, kS = (int64_t)D.k * D.S;
     int64_t at = 0;
     auto take = [&](int f, int64_t cnt) {
@@ -101,30 +98,17 @@ __host__ __device__ inline DtLayout dt_layout(const DmDims &D, int64_t N, int64_
     take(F_U, D.K), take(F_P, (int64_t)kDmRB * 2 * D.K), take(F_YP, SK), take(F_S, SK), take(F_X, SK);
     take(F_TP, D.n_tp * L.o[F_TP_STRIDE]), take(F_DTP, D.n_tp * L.o[F_DTP_STRIDE]);
     take(F_DX, SK), take(F_DY, SK), take(F_ARENA, dt_arena_per_ped(D));
-    L.o[F_PER] = at;
-    L.o[F_PARTIALS] = N * at;
-    L.o[F_GRADS] = dt_grad_off(D).total;
-    L.o[F_TOTAL] = L.o[F_PARTIALS] + n_scenes * L.o[F_GRADS];
+    layout_tail(L, at, N * at, dt_grad_off(D).total, n_scenes);
     return L;
 }
 
 // a scene's fields in the workspace
-struct DtScene {
-    float *f[F_PER];
-    float *part;
-    int n;
+struct DtScene : TrainScene {
     int64_t tp_stride, dtp_stride;  // x n: one tpcnn block's kept values / gradients
 };
 
-__device__ __forceinline__ DtScene dt_scene(float *ws, const DtLayout &L, int64_t b, int n, int scene) {
-    DtScene w;
-    float *base = ws + b * L.o[F_PER];
-    for (int i = 0; i < F_PER; ++i) w.f[i] = base + L.o[i] * n;
-    w.part = ws + L.o[F_PARTIALS] + scene * L.o[F_GRADS];
-    w.n = n;
-    w.tp_stride = L.o[F_TP_STRIDE] * n;
-    w.dtp_stride = L.o[F_DTP_STRIDE] * n;
-    return w;
+__device__ __forceinline__ DtScene dt_scene(float *ws, const TrainLayout &L, int64_t b, int n, int scene) {
+    return {train_scene(ws, L, b, n, scene), L.o[F_TP_STRIDE] * n, L.o[F_DTP_STRIDE] * n};
 }
 
 // block j's kept values: c0, y, c1, q, o (k,S,n each), z (S,n); its gradients: dq, dy (k,S,n), dg (S,n)
@@ -380,20 +364,15 @@ __global__ __launch_bounds__(kSgThreads) void dmrgcn_train_fwd_kernel(Src src, e
                                                                       const int32_t *__restrict__ off, int64_t N,
                                                                       const uint8_t *__restrict__ keep,
                                                                       const int64_t *__restrict__ keep_off, float *ws,
-                                                                      DtLayout L) {
+                                                                      TrainLayout L) {
     extern __shared__ float lds[];
     __shared__ float red[2 * kSgThreads / kWave];
-    const int64_t b = off ? off[blockIdx.x] : 0;
-    const int64_t e = off ? off[blockIdx.x + 1] : N;
-    if (e <= b) return;
+    const SceneRows R = scene_rows(off, N);
+    if (R.empty()) return;
     const DmDims D = dm_dims_of(p);
-    const int64_t n = e - b;
+    const int64_t b = R.b, n = R.n();
     if (n > kDtMaxN) {  // not computed: NaN
-        const float nan = __builtin_nanf("");
-        for (int64_t i = threadIdx.x; i < (int64_t)D.k * D.S * n; i += kSgThreads) {
-            const int w = (int)(i % n), ts = (int)(i / n);
-            src.store(ts / D.S, ts % D.S, w, D.k, D.S, (int)n, b, nan);
-        }
+        nan_scene(D.k, D.S, n, [&](int t, int s, int w, float nan) { src.store(t, s, w, D.k, D.S, (int)n, b, nan); });
         return;
     }
     const DtScene W = dt_scene(ws, L, b, (int)n, blockIdx.x);
@@ -406,14 +385,14 @@ __global__ __launch_bounds__(kSgThreads) void dmrgcn_train_fwd_kernel(Src src, e
 template <class Src>
 __global__ __launch_bounds__(kSgThreads) void dmrgcn_train_bwd_kernel(Src src, et_dmrgcn_params p,
                                                                       const int32_t *__restrict__ off, int64_t N, float *ws,
-                                                                      DtLayout L) {
+                                                                      TrainLayout L) {
     extern __shared__ float lds[];
-    const int64_t b = off ? off[blockIdx.x] : 0;
-    const int64_t e = off ? off[blockIdx.x + 1] : N;
-    if (e <= b || e - b > kDtMaxN) return;
+    const SceneRows R = scene_rows(off, N);
+    if (R.empty() || R.n() > kDtMaxN) return;
+    const int64_t b = R.b;
+    const int n = (int)R.n();
     const DmDims D = dm_dims_of(p);
     const int K = D.K, k = D.k, S = D.S, tid = threadIdx.x;
-    const int n = (int)(e - b);
     const DtScene W = dt_scene(ws, L, b, n, blockIdx.x);
     float *ar = dt_arena_per_ped(D) * n * 4 <= kSgLdsBytes ? lds : W.f[F_ARENA];
     float *A = ar, *Bf = A + (int64_t)D.qpp * n, *C = Bf + (int64_t)D.qpp * n;
@@ -506,21 +485,6 @@ __global__ __launch_bounds__(kSgThreads) void dmrgcn_train_bwd_kernel(Src src, e
     }
 }
 
-// the items of one segment of the gradient buffer, round robin over the scene's wavefronts: item g of the whole list goes to
-// wavefront g % kDtWaves
-template <class F>
-__device__ __forceinline__ void dt_segment(int &start, int count, int wv, F f) {
-    const int first = (wv - start % kDtWaves + kDtWaves) % kDtWaves;
-    for (int it = first; it < count; it += kDtWaves) f(it);
-    start += count;
-}
-
-template <class F>
-__device__ __forceinline__ void dt_sum(float *dst, int count, F f) {
-    const float s = wave_sum(count, f);
-    if ((threadIdx.x & (kWave - 1)) == 0) dst[0] = s;
-}
-
 // d W (Cout,Cin,3,3) of out = conv33(in) with d out = dsrc slope(pre): item oi = one (o, i) pair, its nine taps in one pass
 __device__ __forceinline__ void dt_conv33_dw(float *dst, int oi, const float *dsrc, const float *pre, const float *a,
                                              const float *in, int Cin, int S, int n) {
@@ -536,13 +500,13 @@ __device__ __forceinline__ void dt_conv33_dw(float *dst, int oi, const float *ds
 
 // launch 2 of the backward: the parameter gradients of one scene, grid (scenes, kDtChunks)
 __global__ __launch_bounds__(kSgThreads) void dmrgcn_train_wgrad_kernel(et_dmrgcn_params p, const int32_t *__restrict__ off,
-                                                                        int64_t N, float *ws, DtLayout L) {
-    const int64_t b = off ? off[blockIdx.x] : 0;
-    const int64_t e = off ? off[blockIdx.x + 1] : N;
-    if (e <= b || e - b > kDtMaxN) return;
+                                                                        int64_t N, float *ws, TrainLayout L) {
+    const SceneRows R = scene_rows(off, N);
+    if (R.empty() || R.n() > kDtMaxN) return;
+    const int64_t b = R.b;
+    const int n = (int)R.n();
     const DmDims D = dm_dims_of(p);
     const int K = D.K, k = D.k, S = D.S;
-    const int n = (int)(e - b);
     const DtScene W = dt_scene(ws, L, b, n, blockIdx.x);
     const int wv = blockIdx.y * kTrWaves + threadIdx.x / kWave;
     const int cnt = K * n, SKn = S * K * n, Sn = S * n, ko = k * S * n;
@@ -567,17 +531,17 @@ __global__ __launch_bounds__(kSgThreads) void dmrgcn_train_wgrad_kernel(et_dmrgc
     for (int r = 0; r < 2; ++r)
         for (int jj = 0; jj < 2; ++jj) {
             float *dst = take(kDmBins * S);
-            dt_segment(start, kDmBins * S, wv, [&](int o) {
+            segment<kDtWaves>(start, kDmBins * S, wv, [&](int o) {
                 const int bb = o / S, c = o - bb * S;
                 const float *Pr = Pk + ((int64_t)(r * kDmBins + bb) * 2 + jj) * cnt;
-                dt_sum(dst + o, cnt, [&](int pp) { return dyp(c, pp) * Pr[pp]; });
+                sum_to(dst + o, cnt, [&](int pp) { return dyp(c, pp) * Pr[pp]; });
             });
         }
     float *d_tcn_a = take(1), *d_tcn_w = take(S * S * 3), *d_tcn_b = take(S);
     float *d_res_w = S != 1 ? take(S) : nullptr, *d_res_b = S != 1 ? take(S) : nullptr;
     float *d_prelu = take(1);
-    dt_segment(start, 1, wv, [&](int) { dt_sum(d_tcn_a, SKn, [&](int pp) { return dy[pp] * neg_part(yp[pp]); }); });
-    dt_segment(start, S * S, wv, [&](int cc) {  // the (3,1) conv on y = prelu(yp)
+    segment<kDtWaves>(start, 1, wv, [&](int) { sum_to(d_tcn_a, SKn, [&](int pp) { return dy[pp] * neg_part(yp[pp]); }); });
+    segment<kDtWaves>(start, S * S, wv, [&](int cc) {  // the (3,1) conv on y = prelu(yp)
         const int ci = cc % S, c = cc / S;
         const float *yc = yp + (int64_t)ci * cnt;
         wave_sum_taps<3>(d_tcn_w + cc * 3, cnt, [&](int pp, int tap) {
@@ -586,13 +550,13 @@ __global__ __launch_bounds__(kSgThreads) void dmrgcn_train_wgrad_kernel(et_dmrgc
             return ds(c, pp) * prelu(yc[pp + (tap - 1) * n], Ly.tcn_prelu);
         });
     });
-    dt_segment(start, S, wv, [&](int c) { dt_sum(d_tcn_b + c, cnt, [&](int pp) { return ds(c, pp); }); });
+    segment<kDtWaves>(start, S, wv, [&](int c) { sum_to(d_tcn_b + c, cnt, [&](int pp) { return ds(c, pp); }); });
     if (S != 1) {  // the residual 1x1 conv from u
-        dt_segment(start, S, wv, [&](int c) { dt_sum(d_res_w + c, cnt, [&](int pp) { return ds(c, pp) * u[pp]; }); });
-        dt_segment(start, S, wv, [&](int c) { dt_sum(d_res_b + c, cnt, [&](int pp) { return ds(c, pp); }); });
+        segment<kDtWaves>(start, S, wv, [&](int c) { sum_to(d_res_w + c, cnt, [&](int pp) { return ds(c, pp) * u[pp]; }); });
+        segment<kDtWaves>(start, S, wv, [&](int c) { sum_to(d_res_b + c, cnt, [&](int pp) { return ds(c, pp); }); });
     }
-    dt_segment(start, 1, wv, [&](int) {
-        dt_sum(d_prelu, SKn, [&](int pp) {
+    segment<kDtWaves>(start, 1, wv, [&](int) {
+        sum_to(d_prelu, SKn, [&](int pp) {
             const int w = pp % n, ct = pp / n;
             const int c = ct / K, t = ct - c * K;
             return dx[(t * S + c) * n + w] * neg_part(sk[pp]);
@@ -608,30 +572,32 @@ __global__ __launch_bounds__(kSgThreads) void dmrgcn_train_wgrad_kernel(et_dmrgc
             const float *a = Tp.conv_a[m];
             const int Ci = m ? k : Cin;
             float *d_w = take(k * Ci * 9), *d_b = take(k), *d_a = take(1);
-            dt_segment(start, k * Ci, wv, [&](int oi) { dt_conv33_dw(d_w, oi, dsrc, pre, a, in, Ci, S, n); });
-            dt_segment(start, k, wv, [&](int o) {
-                dt_sum(d_b + o, Sn, [&](int pp) { return dsrc[(int64_t)o * Sn + pp] * slope(pre[(int64_t)o * Sn + pp], a); });
+            segment<kDtWaves>(start, k * Ci, wv, [&](int oi) { dt_conv33_dw(d_w, oi, dsrc, pre, a, in, Ci, S, n); });
+            segment<kDtWaves>(start, k, wv, [&](int o) {
+                sum_to(d_b + o, Sn, [&](int pp) { return dsrc[(int64_t)o * Sn + pp] * slope(pre[(int64_t)o * Sn + pp], a); });
             });
-            dt_segment(start, 1, wv, [&](int) { dt_sum(d_a, ko, [&](int pp) { return dsrc[pp] * neg_part(pre[pp]); }); });
+            segment<kDtWaves>(start, 1, wv,
+                              [&](int) { sum_to(d_a, ko, [&](int pp) { return dsrc[pp] * neg_part(pre[pp]); }); });
         }
         float *d_gw = take(S * S * k), *d_gb = take(S), *d_ga = take(1);
-        dt_segment(start, S * S * k, wv, [&](int el) {  // d Wg[so,s,t] = sum_w d z[so,w] q[t,s,w]
+        segment<kDtWaves>(start, S * S * k, wv, [&](int el) {  // d Wg[so,s,t] = sum_w d z[so,w] q[t,s,w]
             const int t = el % k, ss = el / k;
             const int s = ss % S, so = ss / S;
             const float *dgo = B.dg + (int64_t)so * n, *zo = B.z + (int64_t)so * n, *qr = B.q + (int64_t)(t * S + s) * n;
-            dt_sum(d_gw + el, n, [&](int w) { return (dgo[w] * slope(zo[w], Tp.gta_a)) * qr[w]; });
+            sum_to(d_gw + el, n, [&](int w) { return (dgo[w] * slope(zo[w], Tp.gta_a)) * qr[w]; });
         });
-        dt_segment(start, S, wv, [&](int so) {
-            dt_sum(d_gb + so, n, [&](int w) { return B.dg[(int64_t)so * n + w] * slope(B.z[(int64_t)so * n + w], Tp.gta_a); });
+        segment<kDtWaves>(start, S, wv, [&](int so) {
+            sum_to(d_gb + so, n, [&](int w) { return B.dg[(int64_t)so * n + w] * slope(B.z[(int64_t)so * n + w], Tp.gta_a); });
         });
-        dt_segment(start, 1, wv, [&](int) { dt_sum(d_ga, Sn, [&](int pp) { return B.dg[pp] * neg_part(B.z[pp]); }); });
+        segment<kDtWaves>(start, 1, wv, [&](int) { sum_to(d_ga, Sn, [&](int pp) { return B.dg[pp] * neg_part(B.z[pp]); }); });
         if (j == 0) {  // the residual 1x1 conv (K -> k) sees d y
             float *d_rw = take(k * K), *d_rb = take(k);
-            dt_segment(start, k * K, wv, [&](int oi) {
+            segment<kDtWaves>(start, k * K, wv, [&](int oi) {
                 const int i = oi % K, o = oi / K;
-                dt_sum(d_rw + oi, Sn, [&](int pp) { return B.dy[(int64_t)o * Sn + pp] * xin[(int64_t)i * Sn + pp]; });
+                sum_to(d_rw + oi, Sn, [&](int pp) { return B.dy[(int64_t)o * Sn + pp] * xin[(int64_t)i * Sn + pp]; });
             });
-            dt_segment(start, k, wv, [&](int o) { dt_sum(d_rb + o, Sn, [&](int pp) { return B.dy[(int64_t)o * Sn + pp]; }); });
+            segment<kDtWaves>(start, k, wv,
+                              [&](int o) { sum_to(d_rb + o, Sn, [&](int pp) { return B.dy[(int64_t)o * Sn + pp]; }); });
         }
     }
 }
@@ -644,7 +610,7 @@ static int dt_check_params(const et_dmrgcn_params *p) {
 
 template <class Src>
 static int dt_forward(const Src &src, const et_dmrgcn_params *p, const int32_t *off, int ns, int64_t N, const uint8_t *keep,
-                      const int64_t *keep_off, void *workspace, const DtLayout &L, et_stream_t stream) {
+                      const int64_t *keep_off, void *workspace, const TrainLayout &L, et_stream_t stream) {
     hipLaunchKernelGGL((dmrgcn_train_fwd_kernel<Src>), dim3((unsigned)ns), dim3(kSgThreads), kSgLdsBytes, (hipStream_t)stream,
                        src, *p, off, N, keep, keep_off, (float *)workspace, L);
     ET_LAUNCH_CHECK();
@@ -653,7 +619,7 @@ static int dt_forward(const Src &src, const et_dmrgcn_params *p, const int32_t *
 
 template <class Src>
 static int dt_backward(const Src &src, const et_dmrgcn_params *p, const int32_t *off, int ns, int64_t N, float *grads,
-                       void *workspace, const DtLayout &L, et_stream_t stream) {
+                       void *workspace, const TrainLayout &L, et_stream_t stream) {
     if (N > 0) {
         hipLaunchKernelGGL((dmrgcn_train_bwd_kernel<Src>), dim3((unsigned)ns), dim3(kSgThreads), kSgLdsBytes,
                            (hipStream_t)stream, src, *p, off, N, (float *)workspace, L);
@@ -684,10 +650,7 @@ extern "C" int et_dmrgcn_train_layout(const et_dmrgcn_params *params, int64_t N,
                                       int n_offsets) {
     const int rc = dt_check_params(params);
     if (rc != ET_OK) return rc;
-    if (N < 0 || n_scenes < 1 || !offsets || n_offsets != ET_DMRGCN_TRAIN_LAYOUT_FIELDS) return ET_ERR_INVALID_ARG;
-    const DtLayout L = dt_layout(dm_dims_of(*params), N, n_scenes);
-    for (int i = 0; i < F_COUNT; ++i) offsets[i] = L.o[i];
-    return ET_OK;
+    return layout_out(N, n_scenes, offsets, n_offsets, [&] { return dt_layout(dm_dims_of(*params), N, n_scenes); });
 }
 
 extern "C" int et_dmrgcn_train_forward_scenes(const et_dmrgcn_params *params, const float *C_obs, const float *nrm, int64_t N,
@@ -701,7 +664,7 @@ extern "C" int et_dmrgcn_train_forward_scenes(const et_dmrgcn_params *params, co
     if (!C_obs || !nrm || !C_pred_refine) return ET_ERR_INVALID_ARG;
     if (keep && scene_offsets && !keep_offsets) return ET_ERR_INVALID_ARG;  // where each scene's block of the mask starts
     const int ns = scene_offsets ? n_scenes : 1;
-    const DtLayout L = dt_layout(dm_dims_of(*params), N, ns);
+    const TrainLayout L = dt_layout(dm_dims_of(*params), N, ns);
     if (!train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return dt_forward(TrainScenesSrc{{C_obs, nrm, N, C_pred_refine}, nullptr}, params, scene_offsets, ns, N, keep,
                       scene_offsets ? keep_offsets : nullptr, workspace, L, stream);
@@ -715,7 +678,7 @@ extern "C" int et_dmrgcn_train_forward_graph(const et_dmrgcn_params *params, con
     if (N < 0 || N > kDtMaxN) return ET_ERR_INVALID_ARG;
     if (N == 0) return ET_OK;
     if (!v || !a || !out) return ET_ERR_INVALID_ARG;
-    const DtLayout L = dt_layout(dm_dims_of(*params), N, 1);
+    const TrainLayout L = dt_layout(dm_dims_of(*params), N, 1);
     if (!train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return dt_forward(TrainGraphSrc{{v, a, out}, nullptr}, params, nullptr, 1, N, keep, nullptr, workspace, L, stream);
 }
@@ -729,7 +692,7 @@ extern "C" int et_dmrgcn_backward_scenes(const et_dmrgcn_params *params, int64_t
     rc = backward_args_status(N, scene_offsets, n_scenes, kDtMaxN, d_out, grads, grads_floats, dt_grad_off(D).total);
     if (rc != ET_OK) return rc;
     const int ns = scene_offsets ? n_scenes : 1;
-    const DtLayout L = dt_layout(D, N, ns);
+    const TrainLayout L = dt_layout(D, N, ns);
     if (N > 0 && !train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return dt_backward(TrainScenesSrc{{nullptr, nullptr, N, nullptr}, d_out}, params, scene_offsets, ns, N, grads, workspace, L,
                        stream);
@@ -742,7 +705,7 @@ extern "C" int et_dmrgcn_backward_graph(const et_dmrgcn_params *params, int64_t 
     const DmDims D = dm_dims_of(*params);
     rc = backward_args_status(N, nullptr, 0, kDtMaxN, d_out, grads, grads_floats, dt_grad_off(D).total);
     if (rc != ET_OK) return rc;
-    const DtLayout L = dt_layout(D, N, 1);
+    const TrainLayout L = dt_layout(D, N, 1);
     if (N > 0 && !train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return dt_backward(TrainGraphSrc{{nullptr, nullptr, nullptr}, d_out}, params, nullptr, 1, N, grads, workspace, L, stream);
 }

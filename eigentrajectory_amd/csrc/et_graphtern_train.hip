@@ -27,7 +27,7 @@
 //   2. graphtern_train_wgrad_kernel  grid (scenes, kGttChunks): every parameter-gradient element of a scene is one wavefront's
 //                                    sum; the scene's 64 wavefronts take the elements round robin -> the scene's partial
 //   3. scene_grad_reduce_kernel      grads[e] = the scenes' partials in ascending order, the first one copied
-//                                    (et_train_sums.inl, shared with et_stgcnn_train.hip and et_dmrgcn_train.hip)
+//                                    (et_train_sums.inl, which the three scene training units share)
 // The transposed 3x3 convolution under REPLICATE padding is written in gather form (conv33_replicate_dx): an input cell sums
 // the outputs whose clamped taps land on it -- exactly three (output row, row tap) pairs and three (output column, column
 // tap) pairs for every cell and every plane size (at n = 1 all three column taps of output column 0, at n = 2 two taps of the
@@ -46,11 +46,6 @@ namespace {
 #include "et_scene_helpers.inl"
 #include "et_stgcnn_core.inl"
 #include "et_graphtern_core.inl"
-#include "et_train_sums.inl"
-
-constexpr int kGttMaxN = ET_GRAPHTERN_TRAIN_MAX_N;
-constexpr int kGttChunks = 16;                     // weight-gradient workgroups per scene
-constexpr int kGttWaves = kGttChunks * kTrWaves;   // ... and its wavefronts
 
 enum {
     F_U, F_D, F_P, F_YP, F_X0, F_TP, F_DTP, F_DX0, F_DY, F_ARENA, F_PER, F_TP_STRIDE, F_DTP_STRIDE, F_PARTIALS, F_GRADS, F_TOTAL,
@@ -58,9 +53,11 @@ enum {
 };
 static_assert(F_COUNT == ET_GRAPHTERN_TRAIN_LAYOUT_FIELDS, "et_graphtern_train_layout's field count");
 
-struct GttLayout {
-    int64_t o[F_COUNT];
-};
+#include "et_train_sums.inl"
+
+constexpr int kGttMaxN = ET_GRAPHTERN_TRAIN_MAX_N;
+constexpr int kGttChunks = 16;                     // weight-gradient workgroups per scene
+constexpr int kGttWaves = kGttChunks * kTrWaves;   // ... and its wavefronts
 
 __host__ __device__ inline int gtt_cmax(const GtDims &D) { return D.S > kGtHidden ? D.S : kGtHidden; }
 
@@ -78,8 +75,8 @@ __host__ __device__ inline int gtt_grad_total(const GtDims &D) {
     return at;
 }
 
-__host__ __device__ inline GttLayout gtt_layout(const GtDims &D, int64_t N, int64_t n_scenes) {
-    GttLayout L{};
+__host__ __device__ inline TrainLayout gtt_layout(const GtDims &D, int64_t N, int64_t n_scenes) {
+    TrainLayout L{};
     const int64_t HT = (int64_t)kGtHidden * D.T, kH = (int64_t)D.k * kGtHidden, kC = (int64_t)D.k * gtt_cmax(D);
     int64_t at = 0;
     auto take = [&](int f, int64_t cnt) {
@@ -91,30 +88,17 @@ __host__ __device__ inline GttLayout gtt_layout(const GtDims &D, int64_t N, int6
     take(F_U, D.T), take(F_D, (int64_t)kGtRel * D.T), take(F_P, (int64_t)kGtRel * 2 * D.T), take(F_YP, HT), take(F_X0, HT);
     take(F_TP, D.n_cnn * L.o[F_TP_STRIDE]), take(F_DTP, D.n_cnn * L.o[F_DTP_STRIDE]);
     take(F_DX0, HT), take(F_DY, HT), take(F_ARENA, gt_arena_per_ped(D));
-    L.o[F_PER] = at;
-    L.o[F_PARTIALS] = N * at;
-    L.o[F_GRADS] = gtt_grad_total(D);
-    L.o[F_TOTAL] = L.o[F_PARTIALS] + n_scenes * L.o[F_GRADS];
+    layout_tail(L, at, N * at, gtt_grad_total(D), n_scenes);
     return L;
 }
 
 // a scene's fields in the workspace
-struct GttScene {
-    float *f[F_PER];
-    float *part;
-    int n;
+struct GttScene : TrainScene {
     int64_t tp_stride, dtp_stride;  // x n: one epcnn block's kept values / gradients
 };
 
-__device__ __forceinline__ GttScene gtt_scene(float *ws, const GttLayout &L, int64_t b, int n, int scene) {
-    GttScene w;
-    float *base = ws + b * L.o[F_PER];
-    for (int i = 0; i < F_PER; ++i) w.f[i] = base + L.o[i] * n;
-    w.part = ws + L.o[F_PARTIALS] + scene * L.o[F_GRADS];
-    w.n = n;
-    w.tp_stride = L.o[F_TP_STRIDE] * n;
-    w.dtp_stride = L.o[F_DTP_STRIDE] * n;
-    return w;
+__device__ __forceinline__ GttScene gtt_scene(float *ws, const TrainLayout &L, int64_t b, int n, int scene) {
+    return {train_scene(ws, L, b, n, scene), L.o[F_TP_STRIDE] * n, L.o[F_DTP_STRIDE] * n};
 }
 
 // block j's kept values: c0, y (k,16,n), c1, o (k,C_out,n); its gradients: d_o (k,C_out,n) at the block's output, dy (k,16,n)
@@ -310,15 +294,14 @@ __global__ __launch_bounds__(kSgThreads) void graphtern_train_fwd_kernel(Src src
                                                                          const int32_t *__restrict__ off, int64_t N,
                                                                          const uint8_t *__restrict__ keep,
                                                                          const int64_t *__restrict__ keep_off, float *out,
-                                                                         float *ws, GttLayout L) {
+                                                                         float *ws, TrainLayout L) {
     extern __shared__ float lds[];
     __shared__ float red[2 * kSgThreads / kWave];
-    const int64_t b = off ? off[blockIdx.x] : 0;
-    const int64_t e = off ? off[blockIdx.x + 1] : N;
-    if (e <= b) return;
+    const SceneRows R = scene_rows(off, N);
+    if (R.empty()) return;
     const GtDims D = gt_dims_of(p);
-    const int64_t n = e - b;
-    if (n > kGttMaxN) {  // not computed: NaN
+    const int64_t b = R.b, n = R.n();
+    if (n > kGttMaxN) {  // not computed: NaN, the scene's n S floats of every output row at a stretch
         const float nan = __builtin_nanf("");
         for (int64_t t = 0; t < D.k; ++t)
             for (int64_t i = threadIdx.x; i < n * D.S; i += kSgThreads) out[(t * N + b) * D.S + i] = nan;
@@ -357,14 +340,14 @@ __device__ __forceinline__ float conv33_replicate_dx(const float *dY, int Cout, 
 __global__ __launch_bounds__(kSgThreads) void graphtern_train_bwd_kernel(et_graphtern_params p,
                                                                          const int32_t *__restrict__ off, int64_t N,
                                                                          const float *__restrict__ d_out, float *ws,
-                                                                         GttLayout L) {
+                                                                         TrainLayout L) {
     extern __shared__ float lds[];
-    const int64_t b = off ? off[blockIdx.x] : 0;
-    const int64_t e = off ? off[blockIdx.x + 1] : N;
-    if (e <= b || e - b > kGttMaxN) return;
+    const SceneRows R = scene_rows(off, N);
+    if (R.empty() || R.n() > kGttMaxN) return;
+    const int64_t b = R.b;
+    const int n = (int)R.n();
     const GtDims D = gt_dims_of(p);
     const int T = D.T, k = D.k, S = D.S, H = kGtHidden, tid = threadIdx.x;
-    const int n = (int)(e - b);
     const GttScene W = gtt_scene(ws, L, b, n, blockIdx.x);
     float *ar = gt_arena_per_ped(D) * n * 4 <= kSgLdsBytes ? lds : W.f[F_ARENA];
     float *A = ar, *Bf = A + (int64_t)D.qpp * n, *C = Bf + (int64_t)D.qpp * n;
@@ -434,21 +417,6 @@ __global__ __launch_bounds__(kSgThreads) void graphtern_train_bwd_kernel(et_grap
     }
 }
 
-// the items of one segment of the gradient buffer, round robin over the scene's wavefronts: item g of the whole list goes to
-// wavefront g % kGttWaves
-template <class F>
-__device__ __forceinline__ void gtt_segment(int &start, int count, int wv, F f) {
-    const int first = (wv - start % kGttWaves + kGttWaves) % kGttWaves;
-    for (int it = first; it < count; it += kGttWaves) f(it);
-    start += count;
-}
-
-template <class F>
-__device__ __forceinline__ void gtt_sum(float *dst, int count, F f) {
-    const float s = wave_sum(count, f);
-    if ((threadIdx.x & (kWave - 1)) == 0) dst[0] = s;
-}
-
 // d W (Cout,Cin,3,3) of out = conv33_replicate(in) with d out = dsrc slope(pre): item oi = one (o, i) pair, its nine taps in
 // one pass over the R n output positions, the input read through the forward's clamps.  Entry (o, h, w) of dsrc / pre is at
 // [(o co + h ho) n + w], entry (i, h, w) of in at [(i ci + h ch) n + w]
@@ -466,13 +434,13 @@ __device__ __forceinline__ void gtt_conv33_dw(float *dst, int oi, const float *d
 // launch 2 of the backward: the parameter gradients of one scene, grid (scenes, kGttChunks)
 __global__ __launch_bounds__(kSgThreads) void graphtern_train_wgrad_kernel(et_graphtern_params p,
                                                                            const int32_t *__restrict__ off, int64_t N,
-                                                                           float *ws, GttLayout L) {
-    const int64_t b = off ? off[blockIdx.x] : 0;
-    const int64_t e = off ? off[blockIdx.x + 1] : N;
-    if (e <= b || e - b > kGttMaxN) return;
+                                                                           float *ws, TrainLayout L) {
+    const SceneRows R = scene_rows(off, N);
+    if (R.empty() || R.n() > kGttMaxN) return;
+    const int64_t b = R.b;
+    const int n = (int)R.n();
     const GtDims D = gt_dims_of(p);
     const int T = D.T, k = D.k, S = D.S, H = kGtHidden;
-    const int n = (int)(e - b);
     const GttScene W = gtt_scene(ws, L, b, n, blockIdx.x);
     const int wv = blockIdx.y * kTrWaves + threadIdx.x / kWave;
     const int cnt = T * n, HTn = H * T * n, Hn = H * n, kn = k * n;
@@ -494,21 +462,21 @@ __global__ __launch_bounds__(kSgThreads) void graphtern_train_wgrad_kernel(et_gr
     };
     auto dyp = [&](int c, int pp) { return dy[(int64_t)c * cnt + pp] * slope(yp[(int64_t)c * cnt + pp], Ly.tcn_prelu); };
     float *d_prelu = take(1);  // never applied by the forward: +0
-    gtt_segment(start, 1, wv, [&](int) {
+    segment<kGttWaves>(start, 1, wv, [&](int) {
         if ((threadIdx.x & (kWave - 1)) == 0) d_prelu[0] = 0.f;
     });
     // the gcn through the kept contracted rows: channel o = r 16 + c reads P[r,0] (weight) and P[r,1] (bias)
     for (int jj = 0; jj < 2; ++jj) {
         float *dst = take(kGtRel * H);
-        gtt_segment(start, kGtRel * H, wv, [&](int o) {
+        segment<kGttWaves>(start, kGtRel * H, wv, [&](int o) {
             const int r = o / H, c = o - r * H;
             const float *Pr = Pk + (int64_t)(r * 2 + jj) * cnt;
-            gtt_sum(dst + o, cnt, [&](int pp) { return dyp(c, pp) * Pr[pp]; });
+            sum_to(dst + o, cnt, [&](int pp) { return dyp(c, pp) * Pr[pp]; });
         });
     }
     float *d_tcn_a = take(1), *d_tcn_w = take(H * H * 3), *d_tcn_b = take(H), *d_res_w = take(H), *d_res_b = take(H);
-    gtt_segment(start, 1, wv, [&](int) { gtt_sum(d_tcn_a, HTn, [&](int pp) { return dy[pp] * neg_part(yp[pp]); }); });
-    gtt_segment(start, H * H, wv, [&](int cc) {  // the (3,1) conv on y = prelu(yp)
+    segment<kGttWaves>(start, 1, wv, [&](int) { sum_to(d_tcn_a, HTn, [&](int pp) { return dy[pp] * neg_part(yp[pp]); }); });
+    segment<kGttWaves>(start, H * H, wv, [&](int cc) {  // the (3,1) conv on y = prelu(yp)
         const int ci = cc % H, c = cc / H;
         const float *yc = yp + (int64_t)ci * cnt;
         wave_sum_taps<3>(d_tcn_w + cc * 3, cnt, [&](int pp, int tap) {
@@ -517,10 +485,10 @@ __global__ __launch_bounds__(kSgThreads) void graphtern_train_wgrad_kernel(et_gr
             return ds(c, pp) * prelu(yc[pp + (tap - 1) * n], Ly.tcn_prelu);
         });
     });
-    gtt_segment(start, H, wv, [&](int c) { gtt_sum(d_tcn_b + c, cnt, [&](int pp) { return ds(c, pp); }); });
+    segment<kGttWaves>(start, H, wv, [&](int c) { sum_to(d_tcn_b + c, cnt, [&](int pp) { return ds(c, pp); }); });
     // the residual 1x1 conv from u
-    gtt_segment(start, H, wv, [&](int c) { gtt_sum(d_res_w + c, cnt, [&](int pp) { return ds(c, pp) * u[pp]; }); });
-    gtt_segment(start, H, wv, [&](int c) { gtt_sum(d_res_b + c, cnt, [&](int pp) { return ds(c, pp); }); });
+    segment<kGttWaves>(start, H, wv, [&](int c) { sum_to(d_res_w + c, cnt, [&](int pp) { return ds(c, pp) * u[pp]; }); });
+    segment<kGttWaves>(start, H, wv, [&](int c) { sum_to(d_res_b + c, cnt, [&](int pp) { return ds(c, pp); }); });
     for (int j = 0; j < D.n_cnn; ++j) {
         const et_graphtern_epcnn &Ep = p.tpcnns[j];
         const GttBlock B = gtt_block(W, D, j);
@@ -529,40 +497,41 @@ __global__ __launch_bounds__(kSgThreads) void graphtern_train_wgrad_kernel(et_gr
         const float *xin = j == 0 ? xk : gtt_block(W, D, j - 1).o;
         {  // tpcns.0: d c0 = d y slope(c0); output (o,h,w) at (o 16 + h) n + w over the (16, n) plane, input (i,h,w) likewise
             float *d_w = take(k * Rin * 9), *d_b = take(k), *d_a = take(1);
-            gtt_segment(start, k * Rin, wv,
+            segment<kGttWaves>(start, k * Rin, wv,
                         [&](int oi) { gtt_conv33_dw(d_w, oi, B.dy, B.c0, Ep.tpcn_a, H, 1, xin, Rin, H, 1, H, n); });
-            gtt_segment(start, k, wv, [&](int o) {
-                gtt_sum(d_b + o, Hn, [&](int pp) {
+            segment<kGttWaves>(start, k, wv, [&](int o) {
+                sum_to(d_b + o, Hn, [&](int pp) {
                     return B.dy[(int64_t)o * Hn + pp] * slope(B.c0[(int64_t)o * Hn + pp], Ep.tpcn_a);
                 });
             });
-            gtt_segment(start, 1, wv, [&](int) { gtt_sum(d_a, k * Hn, [&](int pp) { return B.dy[pp] * neg_part(B.c0[pp]); }); });
+            segment<kGttWaves>(start, 1, wv,
+                               [&](int) { sum_to(d_a, k * Hn, [&](int pp) { return B.dy[pp] * neg_part(B.c0[pp]); }); });
         }
         {  // cpcns.0: d c1 = d o slope(c1); output (o,t,w) at (t C_out + o) n + w over the (k, n) plane, input (c,t,w) at (t 16 + c) n + w
             float *d_w = take(Cout * H * 9), *d_b = take(Cout), *d_a = take(1);
-            gtt_segment(start, Cout * H, wv,
+            segment<kGttWaves>(start, Cout * H, wv,
                         [&](int oi) { gtt_conv33_dw(d_w, oi, B.d_o, B.c1, Ep.cpcn_a, 1, Cout, B.y, H, 1, H, k, n); });
-            gtt_segment(start, Cout, wv, [&](int o) {
-                gtt_sum(d_b + o, kn, [&](int pp) {
+            segment<kGttWaves>(start, Cout, wv, [&](int o) {
+                sum_to(d_b + o, kn, [&](int pp) {
                     const int t = pp / n, w = pp - t * n;
                     const int64_t idx = ((int64_t)t * Cout + o) * n + w;
                     return B.d_o[idx] * slope(B.c1[idx], Ep.cpcn_a);
                 });
             });
-            gtt_segment(start, 1, wv,
-                        [&](int) { gtt_sum(d_a, k * Cout * n, [&](int pp) { return B.d_o[pp] * neg_part(B.c1[pp]); }); });
+            segment<kGttWaves>(start, 1, wv,
+                        [&](int) { sum_to(d_a, k * Cout * n, [&](int pp) { return B.d_o[pp] * neg_part(B.c1[pp]); }); });
         }
         if (last && S != H) {  // rescconv: the residual 1x1 conv over the channels sees d o
             float *d_rw = take(S * H), *d_rb = take(S);
-            gtt_segment(start, S * H, wv, [&](int oc) {
+            segment<kGttWaves>(start, S * H, wv, [&](int oc) {
                 const int c = oc % H, o = oc / H;
-                gtt_sum(d_rw + oc, kn, [&](int pp) {
+                sum_to(d_rw + oc, kn, [&](int pp) {
                     const int t = pp / n, w = pp - t * n;
                     return B.d_o[((int64_t)t * S + o) * n + w] * xin[((int64_t)t * H + c) * n + w];
                 });
             });
-            gtt_segment(start, S, wv, [&](int o) {
-                gtt_sum(d_rb + o, kn, [&](int pp) {
+            segment<kGttWaves>(start, S, wv, [&](int o) {
+                sum_to(d_rb + o, kn, [&](int pp) {
                     const int t = pp / n, w = pp - t * n;
                     return B.d_o[((int64_t)t * S + o) * n + w];
                 });
@@ -570,11 +539,12 @@ __global__ __launch_bounds__(kSgThreads) void graphtern_train_wgrad_kernel(et_gr
         }
         if (j == 0) {  // restconv: the residual 1x1 conv over the rows (T -> k) sees d o (k,16,n)
             float *d_rw = take(k * T), *d_rb = take(k);
-            gtt_segment(start, k * T, wv, [&](int ti) {
+            segment<kGttWaves>(start, k * T, wv, [&](int ti) {
                 const int i = ti % T, t = ti / T;
-                gtt_sum(d_rw + ti, Hn, [&](int pp) { return B.d_o[(int64_t)t * Hn + pp] * xin[(int64_t)i * Hn + pp]; });
+                sum_to(d_rw + ti, Hn, [&](int pp) { return B.d_o[(int64_t)t * Hn + pp] * xin[(int64_t)i * Hn + pp]; });
             });
-            gtt_segment(start, k, wv, [&](int t) { gtt_sum(d_rb + t, Hn, [&](int pp) { return B.d_o[(int64_t)t * Hn + pp]; }); });
+            segment<kGttWaves>(start, k, wv,
+                               [&](int t) { sum_to(d_rb + t, Hn, [&](int pp) { return B.d_o[(int64_t)t * Hn + pp]; }); });
         }
     }
 }
@@ -587,7 +557,7 @@ static int gtt_check_params(const et_graphtern_params *p) {
 
 template <class Src>
 static int gtt_forward(const Src &src, const et_graphtern_params *p, const int32_t *off, int ns, int64_t N,
-                       const uint8_t *keep, const int64_t *keep_off, float *out, void *workspace, const GttLayout &L,
+                       const uint8_t *keep, const int64_t *keep_off, float *out, void *workspace, const TrainLayout &L,
                        et_stream_t stream) {
     hipLaunchKernelGGL((graphtern_train_fwd_kernel<Src>), dim3((unsigned)ns), dim3(kSgThreads), kSgLdsBytes,
                        (hipStream_t)stream, src, *p, off, N, keep, keep_off, out, (float *)workspace, L);
@@ -596,7 +566,7 @@ static int gtt_forward(const Src &src, const et_graphtern_params *p, const int32
 }
 
 static int gtt_backward(const et_graphtern_params *p, const int32_t *off, int ns, int64_t N, const float *d_out, float *grads,
-                        void *workspace, const GttLayout &L, et_stream_t stream) {
+                        void *workspace, const TrainLayout &L, et_stream_t stream) {
     if (N > 0) {
         hipLaunchKernelGGL(graphtern_train_bwd_kernel, dim3((unsigned)ns), dim3(kSgThreads), kSgLdsBytes, (hipStream_t)stream,
                            *p, off, N, d_out, (float *)workspace, L);
@@ -627,10 +597,7 @@ extern "C" int et_graphtern_train_layout(const et_graphtern_params *params, int6
                                          int n_offsets) {
     const int rc = gtt_check_params(params);
     if (rc != ET_OK) return rc;
-    if (N < 0 || n_scenes < 1 || !offsets || n_offsets != ET_GRAPHTERN_TRAIN_LAYOUT_FIELDS) return ET_ERR_INVALID_ARG;
-    const GttLayout L = gtt_layout(gt_dims_of(*params), N, n_scenes);
-    for (int i = 0; i < F_COUNT; ++i) offsets[i] = L.o[i];
-    return ET_OK;
+    return layout_out(N, n_scenes, offsets, n_offsets, [&] { return gtt_layout(gt_dims_of(*params), N, n_scenes); });
 }
 
 extern "C" int et_graphtern_train_forward_scenes(const et_graphtern_params *params, const float *C_obs, const float *nrm,
@@ -644,7 +611,7 @@ extern "C" int et_graphtern_train_forward_scenes(const et_graphtern_params *para
     if (!C_obs || !nrm || !C_pred_refine) return ET_ERR_INVALID_ARG;
     if (keep && scene_offsets && !keep_offsets) return ET_ERR_INVALID_ARG;  // where each scene's block of the mask starts
     const int ns = scene_offsets ? n_scenes : 1;
-    const GttLayout L = gtt_layout(gt_dims_of(*params), N, ns);
+    const TrainLayout L = gtt_layout(gt_dims_of(*params), N, ns);
     if (!train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return gtt_forward(ScenesSrc{C_obs, nrm, N}, params, scene_offsets, ns, N, keep, scene_offsets ? keep_offsets : nullptr,
                        C_pred_refine, workspace, L, stream);
@@ -658,7 +625,7 @@ extern "C" int et_graphtern_train_forward_graph(const et_graphtern_params *param
     if (N < 0 || N > kGttMaxN) return ET_ERR_INVALID_ARG;
     if (N == 0) return ET_OK;
     if (!S_obs || !out) return ET_ERR_INVALID_ARG;
-    const GttLayout L = gtt_layout(gt_dims_of(*params), N, 1);
+    const TrainLayout L = gtt_layout(gt_dims_of(*params), N, 1);
     if (!train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return gtt_forward(GraphSrc{S_obs}, params, nullptr, 1, N, keep, nullptr, out, workspace, L, stream);
 }
@@ -672,7 +639,7 @@ extern "C" int et_graphtern_backward_scenes(const et_graphtern_params *params, i
     rc = backward_args_status(N, scene_offsets, n_scenes, kGttMaxN, d_out, grads, grads_floats, gtt_grad_total(D));
     if (rc != ET_OK) return rc;
     const int ns = scene_offsets ? n_scenes : 1;
-    const GttLayout L = gtt_layout(D, N, ns);
+    const TrainLayout L = gtt_layout(D, N, ns);
     if (N > 0 && !train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return gtt_backward(params, scene_offsets, ns, N, d_out, grads, workspace, L, stream);
 }
@@ -684,7 +651,7 @@ extern "C" int et_graphtern_backward_graph(const et_graphtern_params *params, in
     const GtDims D = gt_dims_of(*params);
     rc = backward_args_status(N, nullptr, 0, kGttMaxN, d_out, grads, grads_floats, gtt_grad_total(D));
     if (rc != ET_OK) return rc;
-    const GttLayout L = gtt_layout(D, N, 1);
+    const TrainLayout L = gtt_layout(D, N, 1);
     if (N > 0 && !train_ws_fits(L.o[F_TOTAL], workspace, workspace_bytes)) return ET_ERR_WORKSPACE;
     return gtt_backward(params, nullptr, 1, N, d_out, grads, workspace, L, stream);
 }

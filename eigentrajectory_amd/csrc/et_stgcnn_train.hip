@@ -49,9 +49,7 @@ enum {
 };
 static_assert(F_COUNT == ET_STGCNN_TRAIN_LAYOUT_FIELDS, "et_stgcnn_train_layout's field count");
 
-struct TrainLayout {
-    int64_t o[F_COUNT];
-};
+#include "et_train_sums.inl"
 
 // where every parameter's gradient starts in the flat buffer (state_dict order)
 struct GradOff {
@@ -96,16 +94,11 @@ __host__ __device__ inline TrainLayout train_layout(const Dims &D, int64_t N, in
     take(F_G, SK), take(F_A1, SK), take(F_Y, SK), take(F_T, SK), take(F_R, SK), take(F_S, SK), take(F_X, SK);
     take(F_TP, tp), take(F_DFIN, kS), take(F_DTP, tp);
     take(F_DX, SK), take(F_DS, SK), take(F_DT, SK), take(F_DR, SK), take(F_DY, SK), take(F_DA1, SK), take(F_DG, SK);
-    L.o[F_PER] = at;
     L.o[F_STATS] = N * at;
     L.o[F_STAT_STRIDE] = 15 * D.S;
-    L.o[F_PARTIALS] = L.o[F_STATS] + n_scenes * L.o[F_STAT_STRIDE];
-    L.o[F_GRADS] = grad_off(D).total;
-    L.o[F_TOTAL] = L.o[F_PARTIALS] + n_scenes * L.o[F_GRADS];
+    layout_tail(L, at, L.o[F_STATS] + n_scenes * L.o[F_STAT_STRIDE], grad_off(D).total, n_scenes);
     return L;
 }
-
-#include "et_train_sums.inl"  // wave_sum, wave_sums, wave_sum_taps, slope, neg_part, conv33_dx
 
 // one scene as the bridge hands it over: v (1,1,K,N), L (K,N,N) given; out / d_out (1,S,k,N) = the output conv's (o,h,w)
 struct TrainGraphSrc {
@@ -149,8 +142,7 @@ struct SceneWs {
 
 __device__ __forceinline__ SceneWs scene_ws(float *ws, const TrainLayout &L, int64_t b, int n, int scene) {
     SceneWs w;
-    float *base = ws + b * L.o[F_PER];
-    for (int i = 0; i < F_PER; ++i) w.f[i] = base + L.o[i] * n;
+    scene_fields(w.f, ws, L, b, n);
     w.stat = ws + L.o[F_STATS] + scene * L.o[F_STAT_STRIDE];
     w.part = ws + L.o[F_PARTIALS] + scene * L.o[F_GRADS];
     return w;
@@ -223,20 +215,16 @@ __global__ __launch_bounds__(kSgThreads) void stgcnn_train_fwd_kernel(Src src, e
                                                                       const int32_t *__restrict__ off, int64_t N, float *ws,
                                                                       TrainLayout L) {
     __shared__ float red[2 * kSgThreads / kWave];
-    const int64_t b = off ? off[blockIdx.x] : 0;
-    const int64_t e = off ? off[blockIdx.x + 1] : N;
-    if (e <= b) return;
+    const SceneRows R = scene_rows(off, N);
+    if (R.empty()) return;
     const Dims D = dims_of(p);
     const int K = D.K, k = D.k, S = D.S, tid = threadIdx.x;
-    if (e - b > ET_SCENE_MAX_N) {  // not computed: NaN (et_stgcnn_forward_scenes' rule)
-        const float nan = __builtin_nanf("");
-        for (int64_t i = tid; i < (int64_t)k * S * (e - b); i += kSgThreads) {
-            const int w = (int)(i % (e - b)), oh = (int)(i / (e - b));
-            src.out[src.at(oh / S, oh % S, w, k, S, (int)(e - b), b)] = nan;
-        }
+    const int64_t b = R.b, rows = R.n();
+    if (rows > ET_SCENE_MAX_N) {  // not computed: NaN (et_stgcnn_forward_scenes' rule)
+        nan_scene(k, S, rows, [&](int o, int h, int w, float nan) { src.out[src.at(o, h, w, k, S, (int)rows, b)] = nan; });
         return;
     }
-    const int n = (int)(e - b);
+    const int n = (int)rows;
     const SceneWs W = scene_ws(ws, L, b, n, blockIdx.x);
     const et_stgcnn_layer &Ly = p.st_gcns[0];
     float *u = W.f[F_U], *d = W.f[F_D], *q = W.f[F_P], *g = W.f[F_G], *a1 = W.f[F_A1], *y = W.f[F_Y], *t1 = W.f[F_T];
@@ -395,13 +383,13 @@ template <class Src>
 __global__ __launch_bounds__(kSgThreads) void stgcnn_train_bwd_kernel(Src src, et_stgcnn_params p,
                                                                       const int32_t *__restrict__ off, int64_t N, float *ws,
                                                                       TrainLayout L) {
-    const int64_t b = off ? off[blockIdx.x] : 0;
-    const int64_t e = off ? off[blockIdx.x + 1] : N;
-    if (e <= b || e - b > ET_SCENE_MAX_N) return;
+    const SceneRows R = scene_rows(off, N);
+    if (R.empty() || R.n() > ET_SCENE_MAX_N) return;
     const Dims D = dims_of(p);
     const GradOff G = grad_off(D);
     const int K = D.K, k = D.k, S = D.S, tid = threadIdx.x;
-    const int n = (int)(e - b);
+    const int64_t b = R.b;
+    const int n = (int)R.n();
     const SceneWs W = scene_ws(ws, L, b, n, blockIdx.x);
     const et_stgcnn_layer &Ly = p.st_gcns[0];
     const int cnt = K * n, SKn = S * K * n, ko = k * S * n, A = applied_tpcnns(D);
@@ -579,10 +567,7 @@ extern "C" int et_stgcnn_train_layout(const et_stgcnn_params *params, int64_t N,
                                       int n_offsets) {
     const int rc = check_train_params(params);
     if (rc != ET_OK) return rc;
-    if (N < 0 || n_scenes < 1 || !offsets || n_offsets != ET_STGCNN_TRAIN_LAYOUT_FIELDS) return ET_ERR_INVALID_ARG;
-    const TrainLayout L = train_layout(dims_of(*params), N, n_scenes);
-    for (int i = 0; i < F_COUNT; ++i) offsets[i] = L.o[i];
-    return ET_OK;
+    return layout_out(N, n_scenes, offsets, n_offsets, [&] { return train_layout(dims_of(*params), N, n_scenes); });
 }
 
 extern "C" int et_stgcnn_train_forward_scenes(const et_stgcnn_params *params, const et_stgcnn_train *train,

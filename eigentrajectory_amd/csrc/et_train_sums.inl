@@ -1,7 +1,11 @@
-// et_train_sums.inl -- the fixed-order sums, the small backward pieces and the tail (the scenes' gradient reduce, the
-// backward entries' argument check) that the scene training units share (et_stgcnn_train.hip, et_dmrgcn_train.hip),
-// #included inside their anonymous namespaces after et_stgcnn_core.inl (kSgThreads).  The statements are
-// et_stgcnn_train.hip's, moved here unchanged; its header comment ("wave_sum") gives the order of every sum.
+// et_train_sums.inl -- what the three scene training units hold once (et_stgcnn_train.hip, et_dmrgcn_train.hip,
+// et_graphtern_train.hip): the fixed-order sums and the small backward pieces, the skeleton of a training workspace (the
+// layout array and its tail, a scene's fields, the et_*_train_layout copy-out), the preamble of a scene kernel (its row range,
+// the NaN rows of a scene over the cap), the weight-gradient kernels' round robin (DMRGCN, Graph-TERN) and the tail of a
+// backward pass (the scenes' gradient reduce, the backward entries' argument check).  #included inside the unit's anonymous
+// namespace after et_stgcnn_core.inl (kSgThreads) and after the unit's own field enum, whose F_PER (= the number of
+// per-pedestrian fields, which come first), F_PARTIALS, F_GRADS, F_TOTAL and F_COUNT this file reads.  The statements are
+// the units', moved here unchanged; et_stgcnn_train.hip's header comment ("wave_sum") gives the order of every sum.
 constexpr int kTrWaves = kSgThreads / kWave;
 
 // header comment: "wave_sum".  Called by all 64 lanes of a wavefront with the same count; every lane gets the sum.
@@ -21,6 +25,22 @@ __device__ __forceinline__ void wave_sums(float *dst, int E, int count, F f) {
         const float s = wave_sum(count, [&](int p) { return f(e, p); });
         if (lane == 0) dst[e] = s;
     }
+}
+
+// dst[0] = wave_sum(count, f): one wavefront, lane 0 writes
+template <class F>
+__device__ __forceinline__ void sum_to(float *dst, int count, F f) {
+    const float s = wave_sum(count, f);
+    if ((threadIdx.x & (kWave - 1)) == 0) dst[0] = s;
+}
+
+// the items of one segment of the gradient buffer, round robin over a scene's Waves weight-gradient wavefronts: item g of
+// the whole list (start = the items of the segments before) goes to wavefront g % Waves; f(it) for this wavefront's (wv)
+template <int Waves, class F>
+__device__ __forceinline__ void segment(int &start, int count, int wv, F f) {
+    const int first = (wv - start % Waves + Waves) % Waves;
+    for (int it = first; it < count; it += Waves) f(it);
+    start += count;
 }
 
 __device__ __forceinline__ float slope(float x, const float *a) { return x > 0.f ? 1.f : a[0]; }
@@ -64,6 +84,75 @@ __device__ __forceinline__ void wave_sum_taps(float *dst, int count, F f) {
         float v = s[t];
         for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
         if ((threadIdx.x & (kWave - 1)) == 0) dst[t] = v;
+    }
+}
+
+// a training workspace's offsets in floats, as et_*_train_layout hands them out: the unit's field enum indexes them
+struct TrainLayout {
+    int64_t o[F_COUNT];
+};
+
+// the tail of every layout: `per` floats per pedestrian, the scenes' gradient partials (G floats each) from `partials` on
+__host__ __device__ inline void layout_tail(TrainLayout &L, int64_t per, int64_t partials, int64_t G, int64_t n_scenes) {
+    L.o[F_PER] = per;
+    L.o[F_PARTIALS] = partials;
+    L.o[F_GRADS] = G;
+    L.o[F_TOTAL] = L.o[F_PARTIALS] + n_scenes * L.o[F_GRADS];
+}
+
+// the body of an et_*_train_layout entry point once its parameters have passed; make() -> the TrainLayout
+template <class Make>
+static inline int layout_out(int64_t N, int n_scenes, int64_t *offsets, int n_offsets, Make make) {
+    if (N < 0 || n_scenes < 1 || !offsets || n_offsets != F_COUNT) return ET_ERR_INVALID_ARG;
+    const TrainLayout L = make();
+    for (int i = 0; i < F_COUNT; ++i) offsets[i] = L.o[i];
+    return ET_OK;
+}
+
+// a scene's fields in the workspace (n pedestrians from row b on) and its gradient partial: DMRGCN's and Graph-TERN's
+// scene structs start with these.  et_stgcnn_train.hip takes scene_fields alone: it places its statistics before the
+// partial, and in the other order its kernels compile to other code
+struct TrainScene {
+    float *f[F_PER];
+    float *part;
+    int n;
+};
+
+__device__ __forceinline__ void scene_fields(float *(&f)[F_PER], float *ws, const TrainLayout &L, int64_t b, int n) {
+    float *base = ws + b * L.o[F_PER];
+    for (int i = 0; i < F_PER; ++i) f[i] = base + L.o[i] * n;
+}
+
+__device__ __forceinline__ TrainScene train_scene(float *ws, const TrainLayout &L, int64_t b, int n, int scene) {
+    TrainScene w;
+    scene_fields(w.f, ws, L, b, n);
+    w.part = ws + L.o[F_PARTIALS] + scene * L.o[F_GRADS];
+    w.n = n;
+    return w;
+}
+
+// a scene kernel's preamble: workgroup blockIdx.x's scene is rows [b, e) (the graph form, off = NULL: all N rows).  A kernel
+// returns on empty(), which it touches nothing of, and on n() over its cap (the forward after nan_scene); it spells the
+// two tests in its own `if`: folded into one bool here they compile to other code
+struct SceneRows {
+    int64_t b, e;
+    __device__ __forceinline__ int64_t n() const { return e - b; }
+    __device__ __forceinline__ bool empty() const { return e <= b; }
+};
+
+__device__ __forceinline__ SceneRows scene_rows(const int32_t *off, int64_t N) {
+    const int64_t b = off ? off[blockIdx.x] : 0;
+    const int64_t e = off ? off[blockIdx.x + 1] : N;
+    return {b, e};
+}
+
+// a scene over the cap is not computed: store(r, s, w, NaN) for every entry (r, s, w) of its (rows, S, n) output
+template <class Store>
+__device__ __forceinline__ void nan_scene(int rows, int S, int64_t n, Store store) {
+    const float nan = __builtin_nanf("");
+    for (int64_t i = threadIdx.x; i < (int64_t)rows * S * n; i += kSgThreads) {
+        const int w = (int)(i % n), rs = (int)(i / n);
+        store(rs / S, rs % S, w, nan);
     }
 }
 

@@ -10,11 +10,13 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from types import SimpleNamespace
 from typing import NamedTuple
 
 import torch
 
 from . import _lib as L
+from ._native_train import family_name
 from ._lib import MODE_IDENTITY, MODE_MOVING, MODE_SPLIT, MODE_STATIC  # noqa: F401  (re-exported)
 
 
@@ -336,7 +338,9 @@ def _read_in_place(who, dev, tensors):
                              f"contiguous={t.is_contiguous()})")
 
 
-# ------------------------------------------------------ what the four scene-graph predictors' training wrappers share
+# ------------------------------------------------------ what the five scene-graph predictors' training wrappers share
+# (SocialSTGCNN, SGCN, GPGraph around SGCN, SocialDMRGCN, GraphTERNLight: ``prefix`` below is stgcnn, sgcn, gpgraph_sgcn,
+# dmrgcn or graphtern, the middle of their entry points' and wrappers' names)
 def _numel(t):
     return 0 if t is None else t.numel()
 
@@ -372,11 +376,79 @@ def _grad_views(who, model, grads):
     return out
 
 
-def _layout(entry, n_fields, params, *args):
-    """-> the ``n_fields`` offsets of a training workspace as ``entry``, an ``et_*_train_layout``, gives them for ``args``"""
-    o = (C.c_int64 * n_fields)()
-    L.call(entry, C.byref(params), *args, o, n_fields)
-    return [int(x) for x in o]
+def _layout(entry, names, params, *args):
+    """-> the offsets of a training workspace as ``entry``, an ``et_*_train_layout``, gives them for ``args``, by the
+    ``names`` of ``_lib.*_TRAIN_LAYOUT_NAMES`` (the C enum's order)"""
+    o = (C.c_int64 * len(names))()
+    L.call(entry, C.byref(params), *args, o, len(names))
+    return SimpleNamespace(**{name: int(x) for name, x in zip(names, o)})
+
+
+def _train_params(who, model, et_params):
+    """-> (params, device) of ``model`` for the training wrapper ``who``; ``et_params``: what the caller holds already"""
+    if et_params is not None:   # the training Function's calls: its forward() has looked at the family already
+        return et_params
+    why = model.outside_native_training()
+    if why is not None:
+        raise NotImplementedError(f"{who}: {family_name(model)} has no native backward pass outside its native family: {why}")
+    return model.et_params()
+
+
+def _train_workspace(prefix, model, et_params, n, *sizes):
+    """the body of ``{prefix}_train_workspace``: ``sizes`` are the entry point's arguments after ``n``"""
+    params, dev = _train_params(f"{prefix}_train_workspace", model, et_params)
+    return _workspace(f"et_{prefix}_train_workspace_bytes", dev, params, n, *sizes, required=n > 0)[0]
+
+
+def _backward_graph(prefix, model, workspace, d_out, et_params, n_axis, shape):
+    """the body of ``{prefix}_backward_graph``: ``d_out`` is 4-d with N on ``n_axis``, ``shape(params, n)`` what it must be"""
+    who = f"{prefix}_backward_graph"
+    params, dev = _train_params(who, model, et_params)
+    n = d_out.shape[n_axis] if d_out.dim() == 4 else -1
+    d_out, grads = _backward_args(who, f"et_{prefix}_grad_floats", params, dev, d_out, shape(params, n))
+    if n:
+        _check_train_ws(who, dev, workspace, f"{prefix}_train_workspace")
+    L.call(f"et_{prefix}_backward_graph", C.byref(params), n, L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace),
+           _numel(workspace), L.stream(dev))
+    return grads
+
+
+def _backward_scenes(prefix, model, workspace, d_out, scene_sizes, k_S, packed=False, cap=None):
+    """the body of ``{prefix}_backward_scenes``: ``d_out`` is (k, N, S) with ``k_S(params)`` = (k, S).  ``packed``: the entry
+    point also takes the sum of n^2 over the scenes (of at most ``cap`` pedestrians, if given) and the largest scene"""
+    who = f"{prefix}_backward_scenes"
+    params, dev = _train_params(who, model, None)
+    n = d_out.shape[1] if d_out.dim() == 3 else -1
+    k, S = k_S(params)
+    d_out, grads = _backward_args(who, f"et_{prefix}_grad_floats", params, dev, d_out, (k, n, S))
+    sizes, off, n_scenes = _scene_sizes(scene_sizes, n, dev)
+    if n:
+        _check_train_ws(who, dev, workspace, f"{prefix}_train_workspace")
+    sums = (sum(s * s for s in sizes if cap is None or s <= cap), max(sizes, default=0)) if packed else ()
+    L.call(f"et_{prefix}_backward_scenes", C.byref(params), n, L.ptr(off), n_scenes, *sums, L.ptr(d_out), L.ptr(grads),
+           grads.numel(), L.ptr(workspace), _numel(workspace), L.stream(dev))
+    return grads
+
+
+def _keep_mask(who, dev, keep, shape=None, numel=None):
+    """the keep mask as the kernel reads it: contiguous uint8 on ``dev`` of ``shape`` (or of ``numel`` entries); None stays"""
+    if keep is None:
+        return None
+    if keep.dtype != torch.uint8 or (shape is not None and tuple(keep.shape) != shape) or \
+            (numel is not None and keep.numel() != numel):
+        raise ValueError(f"{who}: keep {tuple(keep.shape)} {keep.dtype} is not uint8 "
+                         f"{shape if shape is not None else f'of {numel} entries'}")
+    return keep.to(dev).contiguous()
+
+
+def _keep_offsets(scene_sizes, cap, device):
+    """-> (int64 tensor (n_scenes + 1,): the running sum of n^2, a scene of more than ``cap`` pedestrians taking no room; the
+    total)"""
+    off = [0]
+    for s in scene_sizes:
+        off.append(off[-1] + (int(s) ** 2 if int(s) <= cap else 0))
+    t = torch.tensor(off, dtype=torch.int64)
+    return (t if device is None else t.to(device)), off[-1]
 
 
 # ------------------------------------------------------------------------ Social-STGCNN predictor (inference)
@@ -420,20 +492,10 @@ def stgcnn_forward_scenes(model, C_obs, nrm, scene_sizes=None):
 
 
 # ------------------------------------------------------------------------ Social-STGCNN predictor (training)
-def _stgcnn_train_params(who, model, et_params):
-    if et_params is not None:   # the training Function's calls: its forward() has looked at the family already
-        return et_params
-    why = model.outside_native_training()
-    if why is not None:
-        raise NotImplementedError(f"{who}: SocialSTGCNN has no native backward pass outside its native family: {why}")
-    return model.et_params()
-
-
 def stgcnn_train_workspace(model, n, n_scenes=1, et_params=None):
     """A training workspace for ``n`` pedestrians in ``n_scenes`` scenes: :func:`stgcnn_train_forward_graph` / ``_scenes``
     fill it, :func:`stgcnn_backward_graph` / ``_scenes`` read it."""
-    params, dev = _stgcnn_train_params("stgcnn_train_workspace", model, et_params)
-    return _workspace("et_stgcnn_train_workspace_bytes", dev, params, n, max(n_scenes, 1), required=n > 0)[0]
+    return _train_workspace("stgcnn", model, et_params, n, max(n_scenes, 1))
 
 
 def stgcnn_train_forward_graph(model, v, a, workspace, et_params=None):
@@ -441,7 +503,7 @@ def stgcnn_train_forward_graph(model, v, a, workspace, et_params=None):
     output (1, S, k, N).  The three BatchNorms use the scene's batch statistics, and their running statistics and
     ``num_batches_tracked`` are updated in place; every intermediate stays in ``workspace`` (of
     :func:`stgcnn_train_workspace`) for :func:`stgcnn_backward_graph`.  Two launches."""
-    params, dev = _stgcnn_train_params("stgcnn_train_forward_graph", model, et_params)
+    params, dev = _train_params("stgcnn_train_forward_graph", model, et_params)
     v, a, n = _stgcnn_graph_args("stgcnn_train_forward_graph", params, dev, v, a)
     out = torch.empty((1, params.output_feat, params.pred_seq_len, n), device=dev)
     if n:
@@ -458,7 +520,7 @@ def stgcnn_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, workspace=N
     consecutive single-scene calls in row order (an empty scene is no batch).  C_obs, nrm and ``scene_sizes`` as
     :func:`stgcnn_forward_scenes` -> (C_pred_refine (k, N, S), workspace); the workspace (made here unless given) goes to
     :func:`stgcnn_backward_scenes` with the same ``scene_sizes``."""
-    params, dev = _stgcnn_train_params("stgcnn_train_forward_scenes", model, None)
+    params, dev = _train_params("stgcnn_train_forward_scenes", model, None)
     b = _scene_batch("stgcnn_train_forward_scenes", dev, C_obs, nrm, params.pred_seq_len, scene_sizes)
     if workspace is None:
         workspace = stgcnn_train_workspace(model, b.n, len(b.sizes), et_params=(params, dev))
@@ -482,31 +544,15 @@ def stgcnn_backward_graph(model, workspace, d_out, et_params=None):
     """The backward pass of :func:`stgcnn_train_forward_graph` in two launches: ``workspace`` as that call filled it (same
     weights), ``d_out`` (1, S, k, N) the gradient at its output -> the flat float32 gradient buffer
     (:func:`stgcnn_grad_views` names its parts)."""
-    params, dev = _stgcnn_train_params("stgcnn_backward_graph", model, et_params)
-    n = d_out.shape[-1] if d_out.dim() == 4 else -1
-    d_out, grads = _backward_args("stgcnn_backward_graph", "et_stgcnn_grad_floats", params, dev, d_out,
-                                  (1, params.output_feat, params.pred_seq_len, n))
-    if n:
-        _check_train_ws("stgcnn_backward_graph", dev, workspace, "stgcnn_train_workspace")
-    L.call("et_stgcnn_backward_graph", C.byref(params), n, L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace),
-           _numel(workspace), L.stream(dev))
-    return grads
+    return _backward_graph("stgcnn", model, workspace, d_out, et_params, -1,
+                           lambda p, n: (1, p.output_feat, p.pred_seq_len, n))
 
 
 def stgcnn_backward_scenes(model, workspace, d_out, scene_sizes=None):
     """The backward pass of :func:`stgcnn_train_forward_scenes` in two launches whatever the number of scenes:
     ``workspace`` as that call filled it, ``scene_sizes`` as given to it, ``d_out`` (k, N, S) -> the flat gradient buffer,
     summed over the scenes in ascending order."""
-    params, dev = _stgcnn_train_params("stgcnn_backward_scenes", model, None)
-    n = d_out.shape[1] if d_out.dim() == 3 else -1
-    d_out, grads = _backward_args("stgcnn_backward_scenes", "et_stgcnn_grad_floats", params, dev, d_out,
-                                  (params.pred_seq_len, n, params.output_feat))
-    _, off, n_scenes = _scene_sizes(scene_sizes, n, dev)
-    if n:
-        _check_train_ws("stgcnn_backward_scenes", dev, workspace, "stgcnn_train_workspace")
-    L.call("et_stgcnn_backward_scenes", C.byref(params), n, L.ptr(off), n_scenes, L.ptr(d_out), L.ptr(grads), grads.numel(),
-           L.ptr(workspace), _numel(workspace), L.stream(dev))
-    return grads
+    return _backward_scenes("stgcnn", model, workspace, d_out, scene_sizes, lambda p: (p.pred_seq_len, p.output_feat))
 
 
 def stgcnn_train_views(model, workspace, n, n_scenes=1, lo=0, scene=0, scene_n=None):
@@ -522,22 +568,22 @@ def stgcnn_train_views(model, workspace, n, n_scenes=1, lo=0, scene=0, scene_n=N
     K, k, S = params.seq_len, params.pred_seq_len, params.output_feat
     m = n if scene_n is None else scene_n
     f = workspace.view(torch.float32)
-    (o_u, o_d, o_p, o_g, o_a1, o_y, o_t, o_r, o_s, o_x, o_tp, o_dfin, o_dtp, o_dx, o_ds, o_dt, o_dr, o_dy, o_da1, o_dg, per,
-     o_stats, stat_stride, o_part, G, _) = _layout("et_stgcnn_train_layout", L.STGCNN_TRAIN_LAYOUT_FIELDS, params, n, n_scenes)
-    base = lo * per
+    lay = _layout("et_stgcnn_train_layout", L.STGCNN_TRAIN_LAYOUT_NAMES, params, n, n_scenes)
+    base = lo * lay.per
     fld = lambda off, *shape: f[base + off * m:base + off * m + math.prod(shape) * m].view(*shape, m)
     A = max(1, params.n_txpcnn - 1)
-    views = {"u": fld(o_u, K), "d": fld(o_d, K), "P": fld(o_p, K, K + 1)}
-    for name, off in (("g", o_g), ("a1", o_a1), ("y", o_y), ("t", o_t), ("r", o_r), ("s", o_s), ("x", o_x), ("d_x", o_dx),
-                      ("d_s", o_ds), ("d_t", o_dt), ("d_r", o_dr), ("d_y", o_dy), ("d_a1", o_da1), ("d_g", o_dg)):
-        views[name] = fld(off, S, K)
-    views["tp_pre"] = [fld(o_tp + 2 * j * k * S, k, S) for j in range(A)]
-    views["tp_out"] = [fld(o_tp + (2 * j + 1) * k * S, k, S) for j in range(A)]
-    views["d_tp_pre"] = [fld(o_dtp + 2 * j * k * S, k, S) for j in range(A)]
-    views["d_tp_out"] = [fld(o_dtp + (2 * j + 1) * k * S, k, S) for j in range(A)]
-    views["d_fin"] = fld(o_dfin, k, S)
-    views["stats"] = f[o_stats + scene * stat_stride:o_stats + (scene + 1) * stat_stride].view(3, 5, S)
-    views["partial"] = f[o_part + scene * G:o_part + (scene + 1) * G]
+    views = {"u": fld(lay.u, K), "d": fld(lay.d, K), "P": fld(lay.P, K, K + 1)}
+    for name in ("g", "a1", "y", "t", "r", "s", "x"):
+        views[name] = fld(getattr(lay, name), S, K)
+    for name in ("dx", "ds", "dt", "dr", "dy", "da1", "dg"):
+        views["d_" + name[1:]] = fld(getattr(lay, name), S, K)
+    views["tp_pre"] = [fld(lay.tp + 2 * j * k * S, k, S) for j in range(A)]
+    views["tp_out"] = [fld(lay.tp + (2 * j + 1) * k * S, k, S) for j in range(A)]
+    views["d_tp_pre"] = [fld(lay.dtp + 2 * j * k * S, k, S) for j in range(A)]
+    views["d_tp_out"] = [fld(lay.dtp + (2 * j + 1) * k * S, k, S) for j in range(A)]
+    views["d_fin"] = fld(lay.dfin, k, S)
+    views["stats"] = f[lay.stats + scene * lay.stat_stride:lay.stats + (scene + 1) * lay.stat_stride].view(3, 5, S)
+    views["partial"] = f[lay.partials + scene * lay.grads:lay.partials + (scene + 1) * lay.grads]
     return views
 
 
@@ -607,29 +653,17 @@ def sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_logits=False):
 
 
 # ------------------------------------------------------------------------------ SGCN predictor (training)
-def _sgcn_train_params(who, model, et_params):
-    if et_params is not None:   # the training Function's calls: its forward() has looked at the family already
-        return et_params
-    if getattr(model, "position_channel", False):
-        raise NotImplementedError(f"{who}: a two-channel SGCN (position_channel=True) has no native backward pass")
-    if model.dropout != 0:
-        raise RuntimeError(f"{who}: dropout = {model.dropout} is not implemented natively; construct with dropout=0")
-    return model.et_params()
-
-
 def sgcn_train_workspace(model, n, sum_n2=None, n_scenes=1, et_params=None):
     """A training workspace for ``n`` pedestrians in ``n_scenes`` scenes whose squared sizes sum to ``sum_n2`` (one scene:
     n * n): :func:`sgcn_train_forward_graph` / ``_scenes`` fill it, :func:`sgcn_backward_graph` / ``_scenes`` read it."""
-    params, dev = _sgcn_train_params("sgcn_train_workspace", model, et_params)
-    return _workspace("et_sgcn_train_workspace_bytes", dev, params, n, n * n if sum_n2 is None else sum_n2, n_scenes,
-                      required=n > 0)[0]
+    return _train_workspace("sgcn", model, et_params, n, n * n if sum_n2 is None else sum_n2, n_scenes)
 
 
 def sgcn_train_forward_graph(model, v, identity, workspace, want_logits=False, et_params=None):
     """:func:`sgcn_forward_graph` with the kept layout (the same kernels; the output is bit-equal): every asymmetric layer's
     input, the softmax row records, A_t, f1, f2, ts and the tail's activations stay in ``workspace`` (of
     :func:`sgcn_train_workspace`) for :func:`sgcn_backward_graph`."""
-    params, dev = _sgcn_train_params("sgcn_train_forward_graph", model, et_params)
+    params, dev = _train_params("sgcn_train_forward_graph", model, et_params)
     T, k, S = params.obs_len, params.pred_len, params.out_dims
     id_s, id_t, n = _sgcn_graph_args("sgcn_train_forward_graph", params, dev, v, identity)
     _check_train_ws("sgcn_train_forward_graph", dev, workspace, "sgcn_train_workspace")
@@ -646,7 +680,7 @@ def sgcn_train_forward_graph(model, v, identity, workspace, want_logits=False, e
 def sgcn_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_logits=False, workspace=None):
     """:func:`sgcn_forward_scenes` with the kept layout -> (C_pred_refine (k, N, S)[, logit_s, logit_t], workspace); the
     workspace (made here unless given) goes to :func:`sgcn_backward_scenes` with the same ``scene_sizes``."""
-    params, dev = _sgcn_train_params("sgcn_train_forward_scenes", model, None)
+    params, dev = _train_params("sgcn_train_forward_scenes", model, None)
     b = _scene_batch("sgcn_train_forward_scenes", dev, C_obs, nrm, params.pred_len, scene_sizes)
     n = b.n
     if b.max_n > L.SGCN_MAX_N:
@@ -674,7 +708,7 @@ def sgcn_backward_graph(model, identity, workspace, d_out, et_params=None):
     """The backward pass of :func:`sgcn_train_forward_graph` in ``number_asymmetric_conv_layer + 8`` launches: ``identity``
     and ``workspace`` as that call read / filled them (same weights), ``d_out`` (pred_len, N, out_dims) the gradient at its
     output -> the flat float32 gradient buffer (:func:`sgcn_grad_views` names its parts)."""
-    params, dev = _sgcn_train_params("sgcn_backward_graph", model, et_params)
+    params, dev = _train_params("sgcn_backward_graph", model, et_params)
     id_s, id_t = identity
     n = id_s.shape[-1]
     _read_in_place("sgcn_backward_graph", dev, {"identity[0]": id_s, "identity[1]": id_t})
@@ -691,17 +725,7 @@ def sgcn_backward_scenes(model, workspace, d_out, scene_sizes=None):
     """The backward pass of :func:`sgcn_train_forward_scenes`, the same number of launches whatever the number of scenes:
     ``workspace`` as that call filled it, ``scene_sizes`` as given to it, ``d_out`` (k, N, S) -> the flat gradient buffer,
     summed over the scenes in ascending order."""
-    params, dev = _sgcn_train_params("sgcn_backward_scenes", model, None)
-    n = d_out.shape[1] if d_out.dim() == 3 else -1
-    d_out, grads = _backward_args("sgcn_backward_scenes", "et_sgcn_grad_floats", params, dev, d_out,
-                                  (params.pred_len, n, params.out_dims))
-    sizes, off, n_scenes = _scene_sizes(scene_sizes, n, dev)
-    if n:
-        _check_train_ws("sgcn_backward_scenes", dev, workspace, "sgcn_train_workspace")
-    L.call("et_sgcn_backward_scenes", C.byref(params), n, L.ptr(off), n_scenes, sum(s * s for s in sizes),
-           max(sizes, default=0), L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace), _numel(workspace),
-           L.stream(dev))
-    return grads
+    return _backward_scenes("sgcn", model, workspace, d_out, scene_sizes, lambda p: (p.pred_len, p.out_dims), packed=True)
 
 
 def sgcn_train_views(model, workspace, n, sum_n2=None, n_scenes=1, lo=0, sq=0, scene_n=None):
@@ -720,28 +744,27 @@ def sgcn_train_views(model, workspace, n, sum_n2=None, n_scenes=1, lo=0, sq=0, s
     N, n2 = n, n * n if sum_n2 is None else sum_n2
     m = N if scene_n is None else scene_n
     f = workspace.view(torch.float32)
-    (o_v, o_rs, o_rt, o_xs, xs_stride, o_xt, xt_stride, o_at, o_f2, o_f1, o_ts, o_keep, KS, o_dat, o_df1, o_dts, o_df2, o_rrec,
-     o_gs, o_gt, o_dirs, o_dirt, o_dds, _) = _layout("et_sgcn_train_layout", L.SGCN_TRAIN_LAYOUT_FIELDS, params, N, n2, n_scenes)
+    lay = _layout("et_sgcn_train_layout", L.SGCN_TRAIN_LAYOUT_NAMES, params, N, n2, n_scenes)
     sl = lambda off, cnt, *shape: f[off:off + cnt].view(*shape)
     rows = lambda off: sl(off + lo * 4 * T * T, m * 4 * T * T, m, 4, T, T)          # (n, 4, T, T) blocks
     feat = lambda off, *shape: sl(off + lo * 4 * T * 16, m * 4 * T * 16, *shape)     # 64 T floats per pedestrian
     dense = lambda off: sl(off + 4 * T * sq, 4 * T * m * m, T, 4, m, m)              # (T, 4, n, n) blocks
-    keep = sl(o_keep + lo * KS, m * KS, m, 2 * T + 2 * nt * k, 64)
+    keep = sl(lay.keep + lo * lay.keep_stride, m * lay.keep_stride, m, 2 * T + 2 * nt * k, 64)
     return {
-        "v": sl(o_v + T * lo, T * m, T, m),
-        "stack_s": [dense(o_xs + j * xs_stride) for j in range(na + 1)],
-        "stack_t": [rows(o_xt + j * xt_stride) for j in range(na + 1)],
-        "rows_s": sl(o_rs + 2 * T * 4 * lo, 2 * T * 4 * m, T, 4, m, 2),
-        "rows_t": sl(o_rt + 2 * T * 4 * lo, 2 * T * 4 * m, m, 4, T, 2),
-        "at": rows(o_at), "f1": feat(o_f1, T, 4, m, 16), "f2": feat(o_f2, m, 4, T, 16), "ts": feat(o_ts, m, 4, T, 16),
+        "v": sl(lay.v + T * lo, T * m, T, m),
+        "stack_s": [dense(lay.stack_s + j * lay.stack_s_stride) for j in range(na + 1)],
+        "stack_t": [rows(lay.stack_t + j * lay.stack_t_stride) for j in range(na + 1)],
+        "rows_s": sl(lay.rows_s + 2 * T * 4 * lo, 2 * T * 4 * m, T, 4, m, 2),
+        "rows_t": sl(lay.rows_t + 2 * T * 4 * lo, 2 * T * 4 * m, m, 4, T, 2),
+        "at": rows(lay.at), "f1": feat(lay.f1, T, 4, m, 16), "f2": feat(lay.f2, m, 4, T, 16), "ts": feat(lay.ts, m, 4, T, 16),
         "st_pre": keep[:, :T], "rep": keep[:, T:2 * T],
         "tcn_pre": [keep[:, 2 * T + 2 * j * k:2 * T + (2 * j + 1) * k] for j in range(nt)],
         "tcn_out": [keep[:, 2 * T + (2 * j + 1) * k:2 * T + (2 * j + 2) * k] for j in range(nt)],
-        "d_ts": feat(o_dts, m, 4, T, 16), "d_f2": feat(o_df2, m, 4, T, 16), "d_f1": feat(o_df1, T, 4, m, 16), "d_at": rows(o_dat),
-        "d_accn": sl(o_rrec + 4 * T * lo * 17, 4 * T * m * 17, T, 4, m, 17)[..., 1:],
-        "g_s": [dense(o_gs + j * xs_stride) for j in range(na + 1)],
-        "g_t": [rows(o_gt + j * xt_stride) for j in range(na + 1)],
-        "dir_s": dense(o_dirs), "dir_t": rows(o_dirt), "dd_s": dense(o_dds),
+        "d_ts": feat(lay.d_ts, m, 4, T, 16), "d_f2": feat(lay.d_f2, m, 4, T, 16), "d_f1": feat(lay.d_f1, T, 4, m, 16),
+        "d_at": rows(lay.d_at), "d_accn": sl(lay.rrec + 4 * T * lo * 17, 4 * T * m * 17, T, 4, m, 17)[..., 1:],
+        "g_s": [dense(lay.g_s + j * lay.stack_s_stride) for j in range(na + 1)],
+        "g_t": [rows(lay.g_t + j * lay.stack_t_stride) for j in range(na + 1)],
+        "dir_s": dense(lay.dir_s), "dir_t": rows(lay.dir_t), "dd_s": dense(lay.dd_s),
     }
 
 
@@ -822,25 +845,11 @@ def gpgraph_sgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_detail
 
 
 # ------------------------------------------------------------------------ GP-Graph-SGCN predictor (training)
-def _gpgraph_train_params(who, model, et_params):
-    if et_params is not None:   # the training Function's calls: its forward() has looked at the family already
-        return et_params
-    if model.stgcnn_base:
-        raise NotImplementedError(f"{who}: GP-Graph around SocialSTGCNN has no native backward pass (its per-time-row "
-                                  "base with BatchNorm batch statistics has none)")
-    if model.baseline_model.dropout != 0:
-        raise RuntimeError(f"{who}: dropout = {model.baseline_model.dropout} is not implemented natively; construct the base "
-                           "with dropout=0")
-    return model.et_params()
-
-
 def gpgraph_sgcn_train_workspace(model, n, sum_n2=None, n_scenes=1, et_params=None):
     """A training workspace for ``n`` pedestrians in ``n_scenes`` scenes whose squared sizes sum to ``sum_n2`` (one scene:
     n * n): :func:`gpgraph_sgcn_train_forward_graph` / ``_scenes`` fill it, :func:`gpgraph_sgcn_backward_graph` / ``_scenes``
     read it."""
-    params, dev = _gpgraph_train_params("gpgraph_sgcn_train_workspace", model, et_params)
-    return _workspace("et_gpgraph_sgcn_train_workspace_bytes", dev, params, n, n * n if sum_n2 is None else sum_n2, n_scenes,
-                      required=n > 0)[0]
+    return _train_workspace("gpgraph_sgcn", model, et_params, n, n * n if sum_n2 is None else sum_n2, n_scenes)
 
 
 def _gpgraph_details(want, T, n, sum_n2, dev):
@@ -856,7 +865,7 @@ def gpgraph_sgcn_train_forward_graph(model, v_abs, v_rel, workspace, want_detail
     backward pass reads stays in ``workspace`` (of :func:`gpgraph_sgcn_train_workspace`) for
     :func:`gpgraph_sgcn_backward_graph`."""
     who = "gpgraph_sgcn_train_forward_graph"
-    params, dev = _gpgraph_train_params(who, model, et_params)
+    params, dev = _train_params(who, model, et_params)
     T, k, S = params.base.obs_len, params.base.pred_len, params.base.out_dims
     n = v_abs.shape[3] if v_abs.dim() == 4 else -1
     if tuple(v_abs.shape) != (1, 1, T, n) or tuple(v_rel.shape) != (1, 2, T, n) or n < 1:
@@ -885,7 +894,7 @@ def gpgraph_sgcn_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_
     """:func:`gpgraph_sgcn_forward_scenes` with the kept layout -> (C_pred_refine (k, N, S)[, details], workspace); the
     workspace (made here unless given) goes to :func:`gpgraph_sgcn_backward_scenes` with the same ``scene_sizes``."""
     who = "gpgraph_sgcn_train_forward_scenes"
-    params, dev = _gpgraph_train_params(who, model, None)
+    params, dev = _train_params(who, model, None)
     b = _scene_batch(who, dev, C_obs, nrm, params.base.pred_len, scene_sizes)
     n = b.n
     if b.off is None and n > L.SGCN_MAX_N:
@@ -917,7 +926,7 @@ def gpgraph_sgcn_backward_graph(model, workspace, d_out, et_params=None):
     ``workspace`` as that call filled it (same weights), ``d_out`` (1, S, k, N) the gradient at its output -> the flat float32
     gradient buffer (:func:`gpgraph_sgcn_grad_views` names its parts)."""
     who = "gpgraph_sgcn_backward_graph"
-    params, dev = _gpgraph_train_params(who, model, et_params)
+    params, dev = _train_params(who, model, et_params)
     n = d_out.shape[3] if d_out.dim() == 4 else -1
     _check_train_ws(who, dev, workspace, "gpgraph_sgcn_train_workspace")
     d_out, grads = _backward_args(who, "et_gpgraph_sgcn_grad_floats", params, dev, d_out,
@@ -931,18 +940,8 @@ def gpgraph_sgcn_backward_scenes(model, workspace, d_out, scene_sizes=None):
     """The backward pass of :func:`gpgraph_sgcn_train_forward_scenes`, the same number of launches whatever the number of
     scenes: ``workspace`` as that call filled it, ``scene_sizes`` as given to it, ``d_out`` (k, N, S) -> the flat gradient
     buffer, summed over the scenes in ascending order."""
-    who = "gpgraph_sgcn_backward_scenes"
-    params, dev = _gpgraph_train_params(who, model, None)
-    n = d_out.shape[1] if d_out.dim() == 3 else -1
-    d_out, grads = _backward_args(who, "et_gpgraph_sgcn_grad_floats", params, dev, d_out,
-                                  (params.base.pred_len, n, params.base.out_dims))
-    sizes, off, n_scenes = _scene_sizes(scene_sizes, n, dev)
-    if n:
-        _check_train_ws(who, dev, workspace, "gpgraph_sgcn_train_workspace")
-    L.call("et_gpgraph_sgcn_backward_scenes", C.byref(params), n, L.ptr(off), n_scenes,
-           sum(s * s for s in sizes if s <= L.SGCN_MAX_N), max(sizes, default=0), L.ptr(d_out), L.ptr(grads), grads.numel(),
-           L.ptr(workspace), _numel(workspace), L.stream(dev))
-    return grads
+    return _backward_scenes("gpgraph_sgcn", model, workspace, d_out, scene_sizes,
+                            lambda p: (p.base.pred_len, p.base.out_dims), packed=True, cap=L.SGCN_MAX_N)
 
 
 def gpgraph_sgcn_train_views(model, workspace, n, sum_n2=None, n_scenes=1, lo=0, sq=0, scene_n=None, scene=0):
@@ -962,51 +961,50 @@ def gpgraph_sgcn_train_views(model, workspace, n, sum_n2=None, n_scenes=1, lo=0,
     m0 = N if scene_n is None else scene_n
     f = workspace.view(torch.float32)
     i32 = workspace.view(torch.int32)
-    (o_v, o_rs, o_rt, o_xs, xs_stride, o_xt, xt_stride, o_at, o_f2, o_f1, o_ts, o_keep, KS, o_dat, o_df1, o_dts, o_df2, o_rrec,
-     o_gs, o_gt, o_dirs, o_dirt, o_dds, o_vp, o_vn, o_gidx, o_dax, o_srec, o_trec, o_dacct, o_dxas, o_dxp, o_dxv, o_va, o_feat,
-     o_dist, o_sn, o_po, o_sig, o_cs, o_cnt, o_dmix, o_dpo, o_dvp, o_dP, o_dsig, o_dd, o_df, _) = _layout(
-         "et_gpgraph_sgcn_train_layout", L.GPGRAPH_SGCN_TRAIN_LAYOUT_FIELDS, params, N, n2, n_scenes)
+    lay = _layout("et_gpgraph_sgcn_train_layout", L.GPGRAPH_SGCN_TRAIN_LAYOUT_NAMES, params, N, n2, n_scenes)
     sl = lambda off, cnt, *shape: f[off:off + cnt].view(*shape)
-    G = int(i32[o_vn + n_scenes + scene])
+    G = int(i32[lay.vn + n_scenes + scene])
     passes = []
     for p_, m in enumerate((m0, G, m0)):
         r0, q0 = p_ * N + lo, p_ * n2 + sq     # the virtual scene's first row and packed offset
         rows = lambda off: sl(off + r0 * 4 * T * T, m * 4 * T * T, m, 4, T, T)
         feat = lambda off, *shape: sl(off + r0 * 4 * T * 16, m * 4 * T * 16, *shape)
         dense = lambda off: sl(off + 4 * T * q0, 4 * T * m * m, T, 4, m, m)
-        keep = sl(o_keep + r0 * KS, m * KS, m, 2 * T + 2 * nt * k, 64)
+        keep = sl(lay.keep + r0 * lay.keep_stride, m * lay.keep_stride, m, 2 * T + 2 * nt * k, 64)
         po = lambda off: f[off:off + k * 3 * N * S].view(k, 3 * N, S)[:, r0:r0 + m]
         passes.append({
-            "v": sl(o_v + T * r0, T * m, T, m), "vp": sl(o_vp + T * r0, T * m, T, m),
-            "stack_s": [dense(o_xs + j * xs_stride) for j in range(na + 1)],
-            "stack_t": [rows(o_xt + j * xt_stride) for j in range(na + 1)],
-            "rows_s": sl(o_rs + 2 * T * 4 * r0, 2 * T * 4 * m, T, 4, m, 2),
-            "rows_t": sl(o_rt + 2 * T * 4 * r0, 2 * T * 4 * m, m, 4, T, 2),
-            "at": rows(o_at), "f1": feat(o_f1, T, 4, m, 16), "f2": feat(o_f2, m, 4, T, 16), "ts": feat(o_ts, m, 4, T, 16),
+            "v": sl(lay.v + T * r0, T * m, T, m), "vp": sl(lay.vp + T * r0, T * m, T, m),
+            "stack_s": [dense(lay.stack_s + j * lay.stack_s_stride) for j in range(na + 1)],
+            "stack_t": [rows(lay.stack_t + j * lay.stack_t_stride) for j in range(na + 1)],
+            "rows_s": sl(lay.rows_s + 2 * T * 4 * r0, 2 * T * 4 * m, T, 4, m, 2),
+            "rows_t": sl(lay.rows_t + 2 * T * 4 * r0, 2 * T * 4 * m, m, 4, T, 2),
+            "at": rows(lay.at), "f1": feat(lay.f1, T, 4, m, 16), "f2": feat(lay.f2, m, 4, T, 16), "ts": feat(lay.ts, m, 4, T, 16),
             "st_pre": keep[:, :T], "rep": keep[:, T:2 * T],
             "tcn_pre": [keep[:, 2 * T + 2 * j * k:2 * T + (2 * j + 1) * k] for j in range(nt)],
             "tcn_out": [keep[:, 2 * T + (2 * j + 1) * k:2 * T + (2 * j + 2) * k] for j in range(nt)],
-            "out": po(o_po), "d_out": po(o_dpo),
-            "d_ts": feat(o_dts, m, 4, T, 16), "d_f2": feat(o_df2, m, 4, T, 16), "d_f1": feat(o_df1, T, 4, m, 16),
-            "d_at": rows(o_dat), "d_accn": sl(o_rrec + 4 * T * r0 * 17, 4 * T * m * 17, T, 4, m, 17)[..., 1:],
-            "g_s": [dense(o_gs + j * xs_stride) for j in range(na + 1)],
-            "g_t": [rows(o_gt + j * xt_stride) for j in range(na + 1)],
-            "dir_s": dense(o_dirs), "dir_t": rows(o_dirt), "dd_s": dense(o_dds),
-            "d_ax": sl(o_dax + 4 * T * r0, 4 * T * m, T, 4, m), "srec": sl(o_srec + 8 * T * r0, 8 * T * m, T, 4, m, 2),
-            "trec": sl(o_trec + 12 * T * r0, 12 * T * m, m, 4, T, 3), "d_acc_t": sl(o_dacct + 4 * T * r0, 4 * T * m, m, 4, T),
-            "dx_as": sl(o_dxas + 4 * T * r0, 4 * T * m, m, 4, T),
-            "dx": torch.stack([sl(o_dxp + T * r0, T * m, T, m), sl(o_dxv + T * r0, T * m, T, m)]),
+            "out": po(lay.po), "d_out": po(lay.dpo),
+            "d_ts": feat(lay.d_ts, m, 4, T, 16), "d_f2": feat(lay.d_f2, m, 4, T, 16), "d_f1": feat(lay.d_f1, T, 4, m, 16),
+            "d_at": rows(lay.d_at), "d_accn": sl(lay.rrec + 4 * T * r0 * 17, 4 * T * m * 17, T, 4, m, 17)[..., 1:],
+            "g_s": [dense(lay.g_s + j * lay.stack_s_stride) for j in range(na + 1)],
+            "g_t": [rows(lay.g_t + j * lay.stack_t_stride) for j in range(na + 1)],
+            "dir_s": dense(lay.dir_s), "dir_t": rows(lay.dir_t), "dd_s": dense(lay.dd_s),
+            "d_ax": sl(lay.dax + 4 * T * r0, 4 * T * m, T, 4, m), "srec": sl(lay.srec + 8 * T * r0, 8 * T * m, T, 4, m, 2),
+            "trec": sl(lay.trec + 12 * T * r0, 12 * T * m, m, 4, T, 3), "d_acc_t": sl(lay.dacct + 4 * T * r0, 4 * T * m, m, 4, T),
+            "dx_as": sl(lay.dxas + 4 * T * r0, 4 * T * m, m, 4, T),
+            "dx": torch.stack([sl(lay.dxp + T * r0, T * m, T, m), sl(lay.dxv + T * r0, T * m, T, m)]),
         })
     m = m0
-    dmix = f[o_dmix:o_dmix + k * 3 * N * S].view(k, 3 * N, S)
+    dmix = f[lay.dmix:lay.dmix + k * 3 * N * S].view(k, 3 * N, S)
     return {
         "n_groups": G, "passes": passes,
-        "v_abs": sl(o_va + T * lo, T * m, T, m), "f": sl(o_feat + 8 * T * lo, 8 * T * m, 8, T, m),
-        "dist": sl(o_dist + sq, m * m, m, m), "sn": sl(o_sn + sq, m * m, m, m), "sig": sl(o_sig + sq, m * m, m, m),
-        "colsum": sl(o_cs + lo, m, m), "group_index": i32[o_gidx + lo:o_gidx + lo + m], "group_size": i32[o_cnt + lo:o_cnt + lo + G],
+        "v_abs": sl(lay.va + T * lo, T * m, T, m), "f": sl(lay.feat + 8 * T * lo, 8 * T * m, 8, T, m),
+        "dist": sl(lay.dist + sq, m * m, m, m), "sn": sl(lay.sn + sq, m * m, m, m), "sig": sl(lay.sig + sq, m * m, m, m),
+        "colsum": sl(lay.cs + lo, m, m), "group_index": i32[lay.gidx + lo:lay.gidx + lo + m],
+        "group_size": i32[lay.cnt + lo:lay.cnt + lo + G],
         "d_o": [dmix[:, p_ * N + lo:p_ * N + lo + m] for p_ in range(3)],
-        "d_vp": sl(o_dvp + 2 * T * lo, 2 * T * m, 2, T, m), "d_P": sl(o_dP + sq, m * m, m, m),
-        "d_sig": sl(o_dsig + sq, m * m, m, m), "d_d": sl(o_dd + sq, m * m, m, m), "d_f": sl(o_df + 8 * T * lo, 8 * T * m, 8, T, m),
+        "d_vp": sl(lay.dvp + 2 * T * lo, 2 * T * m, 2, T, m), "d_P": sl(lay.dP + sq, m * m, m, m),
+        "d_sig": sl(lay.dsig + sq, m * m, m, m), "d_d": sl(lay.dd + sq, m * m, m, m),
+        "d_f": sl(lay.df + 8 * T * lo, 8 * T * m, 8, T, m),
     }
 
 
@@ -1129,31 +1127,10 @@ def dmrgcn_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=Fals
 
 
 # ------------------------------------------------------------------------------ DMRGCN predictor (training)
-def _dmrgcn_train_params(who, model, et_params):
-    if et_params is not None:   # the training Function's calls: its forward() has looked at the family already
-        return et_params
-    why = model.outside_native_training()
-    if why is not None:
-        raise NotImplementedError(f"{who}: SocialDMRGCN has no native backward pass outside its native family: {why}")
-    return model.et_params()
-
-
 def dmrgcn_train_workspace(model, n, n_scenes=1, et_params=None):
     """A training workspace for ``n`` pedestrians in ``n_scenes`` scenes: :func:`dmrgcn_train_forward_graph` / ``_scenes``
     fill it, :func:`dmrgcn_backward_graph` / ``_scenes`` read it (None for ``n`` = 0)."""
-    params, dev = _dmrgcn_train_params("dmrgcn_train_workspace", model, et_params)
-    return _workspace("et_dmrgcn_train_workspace_bytes", dev, params, n, max(n_scenes, 1), required=n > 0)[0]
-
-
-def _dmrgcn_keep(who, dev, keep, shape=None, numel=None):
-    """the keep mask as the kernel reads it: contiguous uint8 on ``dev`` of ``shape`` (or of ``numel`` entries); None stays"""
-    if keep is None:
-        return None
-    if keep.dtype != torch.uint8 or (shape is not None and tuple(keep.shape) != shape) or \
-            (numel is not None and keep.numel() != numel):
-        raise ValueError(f"{who}: keep {tuple(keep.shape)} {keep.dtype} is not uint8 "
-                         f"{shape if shape is not None else f'of {numel} entries'}")
-    return keep.to(dev).contiguous()
+    return _train_workspace("dmrgcn", model, et_params, n, max(n_scenes, 1))
 
 
 def dmrgcn_train_forward_graph(model, v, a, workspace, keep=None, et_params=None):
@@ -1161,7 +1138,7 @@ def dmrgcn_train_forward_graph(model, v, a, workspace, keep=None, et_params=None
     ``keep`` uint8 (2, 5, K, N, N) indexed [r, b, t, w, v] (:meth:`SocialDMRGCN.draw_keep`; None keeps every edge) -> the
     raw output (1, S, k, N).  What the backward reads stays in ``workspace`` (of :func:`dmrgcn_train_workspace`) for
     :func:`dmrgcn_backward_graph`.  One launch."""
-    params, dev = _dmrgcn_train_params("dmrgcn_train_forward_graph", model, et_params)
+    params, dev = _train_params("dmrgcn_train_forward_graph", model, et_params)
     K, k, S = params.seq_len, params.pred_seq_len, params.output_feat
     n = v.shape[-1]
     if tuple(v.shape) != (1, 1, K, n) or tuple(a.shape) != (1, 2, K, n, n):
@@ -1171,7 +1148,7 @@ def dmrgcn_train_forward_graph(model, v, a, workspace, keep=None, et_params=None
         raise ValueError(f"dmrgcn_train_forward_graph: N = {n} exceeds the {L.DMRGCN_TRAIN_MAX_N} pedestrians a training scene "
                          "may have")
     v, a = _dev_args(dev, v.detach(), a.detach())
-    keep = _dmrgcn_keep("dmrgcn_train_forward_graph", dev, keep, shape=(2, L.DMRGCN_BINS, K, n, n))
+    keep = _keep_mask("dmrgcn_train_forward_graph", dev, keep, shape=(2, L.DMRGCN_BINS, K, n, n))
     out = torch.empty((1, S, k, n), device=dev)
     if n:
         _check_train_ws("dmrgcn_train_forward_graph", dev, workspace, "dmrgcn_train_workspace")
@@ -1183,11 +1160,7 @@ def dmrgcn_train_forward_graph(model, v, a, workspace, keep=None, et_params=None
 def dmrgcn_keep_offsets(scene_sizes, device=None):
     """-> (int64 tensor (n_scenes + 1,): where each scene's (2, 5, K, n, n) block of a packed keep mask starts, in units of
     10 K entries (the running sum of n^2; a scene above the training cap takes no room), the total sum of n^2)"""
-    off = [0]
-    for s in scene_sizes:
-        off.append(off[-1] + (int(s) ** 2 if int(s) <= L.DMRGCN_TRAIN_MAX_N else 0))
-    t = torch.tensor(off, dtype=torch.int64)
-    return (t if device is None else t.to(device)), off[-1]
+    return _keep_offsets(scene_sizes, L.DMRGCN_TRAIN_MAX_N, device)
 
 
 def dmrgcn_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, keep=None, workspace=None):
@@ -1196,7 +1169,7 @@ def dmrgcn_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, keep=None, 
     (2, 5, K, n, n) block one after the other (:func:`dmrgcn_keep_offsets`), None keeps every edge -> (C_pred_refine
     (k, N, S), workspace); the workspace (made here unless given) goes to :func:`dmrgcn_backward_scenes` with the same
     ``scene_sizes``.  A scene of more than 512 pedestrians is not computed (NaN rows)."""
-    params, dev = _dmrgcn_train_params("dmrgcn_train_forward_scenes", model, None)
+    params, dev = _train_params("dmrgcn_train_forward_scenes", model, None)
     b = _scene_batch("dmrgcn_train_forward_scenes", dev, C_obs, nrm, params.pred_seq_len, scene_sizes)
     if scene_sizes is None and b.n > L.DMRGCN_TRAIN_MAX_N:
         raise ValueError(f"dmrgcn_train_forward_scenes: one unlisted scene of {b.n} pedestrians exceeds the "
@@ -1206,7 +1179,7 @@ def dmrgcn_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, keep=None, 
     if b.n:
         _check_train_ws("dmrgcn_train_forward_scenes", dev, workspace, "dmrgcn_train_workspace")
     koff, total = dmrgcn_keep_offsets(b.sizes, dev if keep is not None else None)
-    keep = _dmrgcn_keep("dmrgcn_train_forward_scenes", dev, keep, numel=2 * L.DMRGCN_BINS * params.seq_len * total)
+    keep = _keep_mask("dmrgcn_train_forward_scenes", dev, keep, numel=2 * L.DMRGCN_BINS * params.seq_len * total)
     out = torch.empty((params.pred_seq_len, b.n, params.output_feat), device=dev)
     L.call("et_dmrgcn_train_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), b.n, L.ptr(b.off), b.n_scenes,
            L.ptr(keep), L.ptr(koff if keep is not None else None), L.ptr(out), L.ptr(workspace), _numel(workspace),
@@ -1224,31 +1197,15 @@ def dmrgcn_backward_graph(model, workspace, d_out, et_params=None):
     """The backward pass of :func:`dmrgcn_train_forward_graph` in three launches: ``workspace`` as that call filled it (same
     weights), ``d_out`` (1, S, k, N) the gradient at its output -> the flat float32 gradient buffer
     (:func:`dmrgcn_grad_views` names its parts)."""
-    params, dev = _dmrgcn_train_params("dmrgcn_backward_graph", model, et_params)
-    n = d_out.shape[-1] if d_out.dim() == 4 else -1
-    d_out, grads = _backward_args("dmrgcn_backward_graph", "et_dmrgcn_grad_floats", params, dev, d_out,
-                                  (1, params.output_feat, params.pred_seq_len, n))
-    if n:
-        _check_train_ws("dmrgcn_backward_graph", dev, workspace, "dmrgcn_train_workspace")
-    L.call("et_dmrgcn_backward_graph", C.byref(params), n, L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace),
-           _numel(workspace), L.stream(dev))
-    return grads
+    return _backward_graph("dmrgcn", model, workspace, d_out, et_params, -1,
+                           lambda p, n: (1, p.output_feat, p.pred_seq_len, n))
 
 
 def dmrgcn_backward_scenes(model, workspace, d_out, scene_sizes=None):
     """The backward pass of :func:`dmrgcn_train_forward_scenes` in three launches whatever the number of scenes:
     ``workspace`` as that call filled it, ``scene_sizes`` as given to it, ``d_out`` (k, N, S) -> the flat gradient buffer,
     summed over the scenes in ascending order."""
-    params, dev = _dmrgcn_train_params("dmrgcn_backward_scenes", model, None)
-    n = d_out.shape[1] if d_out.dim() == 3 else -1
-    d_out, grads = _backward_args("dmrgcn_backward_scenes", "et_dmrgcn_grad_floats", params, dev, d_out,
-                                  (params.pred_seq_len, n, params.output_feat))
-    _, off, n_scenes = _scene_sizes(scene_sizes, n, dev)
-    if n:
-        _check_train_ws("dmrgcn_backward_scenes", dev, workspace, "dmrgcn_train_workspace")
-    L.call("et_dmrgcn_backward_scenes", C.byref(params), n, L.ptr(off), n_scenes, L.ptr(d_out), L.ptr(grads), grads.numel(),
-           L.ptr(workspace), _numel(workspace), L.stream(dev))
-    return grads
+    return _backward_scenes("dmrgcn", model, workspace, d_out, scene_sizes, lambda p: (p.pred_seq_len, p.output_feat))
 
 
 def dmrgcn_train_views(model, workspace, n, n_scenes=1, lo=0, scene=0, scene_n=None):
@@ -1263,21 +1220,20 @@ def dmrgcn_train_views(model, workspace, n, n_scenes=1, lo=0, scene=0, scene_n=N
     K, k, S = params.seq_len, params.pred_seq_len, params.output_feat
     m = n if scene_n is None else scene_n
     f = workspace.view(torch.float32)
-    (o_u, o_p, o_yp, o_s, o_x, o_tp, o_dtp, o_dx, o_dy, _, per, tp_stride, dtp_stride, o_part, G, _) = _layout(
-        "et_dmrgcn_train_layout", L.DMRGCN_TRAIN_LAYOUT_FIELDS, params, n, n_scenes)
-    base = lo * per
+    lay = _layout("et_dmrgcn_train_layout", L.DMRGCN_TRAIN_LAYOUT_NAMES, params, n, n_scenes)
+    base = lo * lay.per
     fld = lambda off, *shape: f[base + off * m:base + off * m + math.prod(shape) * m].view(*shape, m)
     kS = k * S
-    views = {"u": fld(o_u, K), "P": fld(o_p, 2, L.DMRGCN_BINS, 2, K), "yp": fld(o_yp, S, K), "s": fld(o_s, S, K),
-             "x": fld(o_x, K, S), "d_x": fld(o_dx, K, S), "d_yt": fld(o_dy, S, K)}
+    views = {"u": fld(lay.u, K), "P": fld(lay.P, 2, L.DMRGCN_BINS, 2, K), "yp": fld(lay.yp, S, K), "s": fld(lay.s, S, K),
+             "x": fld(lay.x, K, S), "d_x": fld(lay.dx, K, S), "d_yt": fld(lay.dy, S, K)}
     blocks = range(params.n_tpcnn)
     for q, name in enumerate(("c0", "y", "c1", "q", "o")):
-        views[name] = [fld(o_tp + j * tp_stride + q * kS, k, S) for j in blocks]
-    views["z"] = [fld(o_tp + j * tp_stride + 5 * kS, S) for j in blocks]
-    views["d_q"] = [fld(o_dtp + j * dtp_stride, k, S) for j in blocks]
-    views["d_y"] = [fld(o_dtp + j * dtp_stride + kS, k, S) for j in blocks]
-    views["d_g"] = [fld(o_dtp + j * dtp_stride + 2 * kS, S) for j in blocks]
-    views["partial"] = f[o_part + scene * G:o_part + (scene + 1) * G]
+        views[name] = [fld(lay.tp + j * lay.tp_stride + q * kS, k, S) for j in blocks]
+    views["z"] = [fld(lay.tp + j * lay.tp_stride + 5 * kS, S) for j in blocks]
+    views["d_q"] = [fld(lay.dtp + j * lay.dtp_stride, k, S) for j in blocks]
+    views["d_y"] = [fld(lay.dtp + j * lay.dtp_stride + kS, k, S) for j in blocks]
+    views["d_g"] = [fld(lay.dtp + j * lay.dtp_stride + 2 * kS, S) for j in blocks]
+    views["partial"] = f[lay.partials + scene * lay.grads:lay.partials + (scene + 1) * lay.grads]
     return views
 
 
@@ -1489,20 +1445,10 @@ def graphtern_forward_scenes(model, C_obs, nrm, scene_sizes=None, want_details=F
 
 
 # ------------------------------------------------------------------------------ Graph-TERN predictor (training)
-def _graphtern_train_params(who, model, et_params):
-    if et_params is not None:   # the training Function's calls: its forward() has looked at the family already
-        return et_params
-    why = model.outside_native_training()
-    if why is not None:
-        raise NotImplementedError(f"{who}: GraphTERNLight has no native backward pass outside its native family: {why}")
-    return model.et_params()
-
-
 def graphtern_train_workspace(model, n, n_scenes=1, et_params=None):
     """A training workspace for ``n`` pedestrians in ``n_scenes`` scenes: :func:`graphtern_train_forward_graph` /
     ``_scenes`` fill it, :func:`graphtern_backward_graph` / ``_scenes`` read it (None for ``n`` = 0)."""
-    params, dev = _graphtern_train_params("graphtern_train_workspace", model, et_params)
-    return _workspace("et_graphtern_train_workspace_bytes", dev, params, n, max(n_scenes, 1), required=n > 0)[0]
+    return _train_workspace("graphtern", model, et_params, n, max(n_scenes, 1))
 
 
 def graphtern_train_forward_graph(model, S_obs, workspace, keep=None, et_params=None):
@@ -1510,7 +1456,7 @@ def graphtern_train_forward_graph(model, S_obs, workspace, keep=None, et_params=
     ``keep`` uint8 (4, T, N, N) indexed [r, t, w, v] (:meth:`GraphTERNLight.draw_keep`; None keeps every edge) -> the raw
     output (1, k, N, S).  What the backward reads stays in ``workspace`` (of :func:`graphtern_train_workspace`) for
     :func:`graphtern_backward_graph`.  One launch."""
-    params, dev = _graphtern_train_params("graphtern_train_forward_graph", model, et_params)
+    params, dev = _train_params("graphtern_train_forward_graph", model, et_params)
     T, k, S = params.seq_len, params.pred_seq_len, params.n_smpl
     n = S_obs.shape[3] if S_obs.dim() == 5 else -1
     if tuple(S_obs.shape) != (1, 2, T, n, 1):
@@ -1519,7 +1465,7 @@ def graphtern_train_forward_graph(model, S_obs, workspace, keep=None, et_params=
         raise ValueError(f"graphtern_train_forward_graph: N = {n} exceeds the {L.GRAPHTERN_TRAIN_MAX_N} pedestrians a "
                          "training scene may have")
     (S_obs,) = _dev_args(dev, S_obs.detach())
-    keep = _dmrgcn_keep("graphtern_train_forward_graph", dev, keep, shape=(L.GRAPHTERN_REL, T, n, n))
+    keep = _keep_mask("graphtern_train_forward_graph", dev, keep, shape=(L.GRAPHTERN_REL, T, n, n))
     out = torch.empty((1, k, n, S), device=dev)
     if n:
         _check_train_ws("graphtern_train_forward_graph", dev, workspace, "graphtern_train_workspace")
@@ -1531,11 +1477,7 @@ def graphtern_train_forward_graph(model, S_obs, workspace, keep=None, et_params=
 def graphtern_keep_offsets(scene_sizes, device=None):
     """-> (int64 tensor (n_scenes + 1,): where each scene's (4, T, n, n) block of a packed keep mask starts, in units of
     4 T entries (the running sum of n^2; a scene above the training cap takes no room), the total sum of n^2)"""
-    off = [0]
-    for s in scene_sizes:
-        off.append(off[-1] + (int(s) ** 2 if int(s) <= L.GRAPHTERN_TRAIN_MAX_N else 0))
-    t = torch.tensor(off, dtype=torch.int64)
-    return (t if device is None else t.to(device)), off[-1]
+    return _keep_offsets(scene_sizes, L.GRAPHTERN_TRAIN_MAX_N, device)
 
 
 def graphtern_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, keep=None, workspace=None):
@@ -1544,7 +1486,7 @@ def graphtern_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, keep=Non
     (4, T, n, n) block one after the other (:func:`graphtern_keep_offsets`), None keeps every edge -> (C_pred_refine
     (k, N, S), workspace); the workspace (made here unless given) goes to :func:`graphtern_backward_scenes` with the same
     ``scene_sizes``.  A scene of more than 512 pedestrians is not computed (NaN rows)."""
-    params, dev = _graphtern_train_params("graphtern_train_forward_scenes", model, None)
+    params, dev = _train_params("graphtern_train_forward_scenes", model, None)
     b = _scene_batch("graphtern_train_forward_scenes", dev, C_obs, nrm, params.pred_seq_len, scene_sizes)
     if scene_sizes is None and b.n > L.GRAPHTERN_TRAIN_MAX_N:
         raise ValueError(f"graphtern_train_forward_scenes: one unlisted scene of {b.n} pedestrians exceeds the "
@@ -1554,7 +1496,7 @@ def graphtern_train_forward_scenes(model, C_obs, nrm, scene_sizes=None, keep=Non
     if b.n:
         _check_train_ws("graphtern_train_forward_scenes", dev, workspace, "graphtern_train_workspace")
     koff, total = graphtern_keep_offsets(b.sizes, dev if keep is not None else None)
-    keep = _dmrgcn_keep("graphtern_train_forward_scenes", dev, keep, numel=L.GRAPHTERN_REL * params.seq_len * total)
+    keep = _keep_mask("graphtern_train_forward_scenes", dev, keep, numel=L.GRAPHTERN_REL * params.seq_len * total)
     out = torch.empty((params.pred_seq_len, b.n, params.n_smpl), device=dev)
     L.call("et_graphtern_train_forward_scenes", C.byref(params), L.ptr(b.C_obs), L.ptr(b.nrm), b.n, L.ptr(b.off), b.n_scenes,
            L.ptr(keep), L.ptr(koff if keep is not None else None), L.ptr(out), L.ptr(workspace), _numel(workspace),
@@ -1573,38 +1515,25 @@ def graphtern_backward_graph(model, workspace, d_out, et_params=None):
     """The backward pass of :func:`graphtern_train_forward_graph` in three launches: ``workspace`` as that call filled it
     (same weights), ``d_out`` (1, k, N, S) the gradient at its output -> the flat float32 gradient buffer
     (:func:`graphtern_grad_views` names its parts)."""
-    params, dev = _graphtern_train_params("graphtern_backward_graph", model, et_params)
-    n = d_out.shape[2] if d_out.dim() == 4 else -1
-    d_out, grads = _backward_args("graphtern_backward_graph", "et_graphtern_grad_floats", params, dev, d_out,
-                                  (1, params.pred_seq_len, n, params.n_smpl))
-    if n:
-        _check_train_ws("graphtern_backward_graph", dev, workspace, "graphtern_train_workspace")
-    L.call("et_graphtern_backward_graph", C.byref(params), n, L.ptr(d_out), L.ptr(grads), grads.numel(), L.ptr(workspace),
-           _numel(workspace), L.stream(dev))
-    return grads
+    return _backward_graph("graphtern", model, workspace, d_out, et_params, 2,
+                           lambda p, n: (1, p.pred_seq_len, n, p.n_smpl))
 
 
 def graphtern_backward_scenes(model, workspace, d_out, scene_sizes=None):
     """The backward pass of :func:`graphtern_train_forward_scenes` in three launches whatever the number of scenes:
     ``workspace`` as that call filled it, ``scene_sizes`` as given to it, ``d_out`` (k, N, S) -> the flat gradient buffer,
     summed over the scenes in ascending order."""
-    params, dev = _graphtern_train_params("graphtern_backward_scenes", model, None)
-    n = d_out.shape[1] if d_out.dim() == 3 else -1
-    d_out, grads = _backward_args("graphtern_backward_scenes", "et_graphtern_grad_floats", params, dev, d_out,
-                                  (params.pred_seq_len, n, params.n_smpl))
-    _, off, n_scenes = _scene_sizes(scene_sizes, n, dev)
-    if n:
-        _check_train_ws("graphtern_backward_scenes", dev, workspace, "graphtern_train_workspace")
-    L.call("et_graphtern_backward_scenes", C.byref(params), n, L.ptr(off), n_scenes, L.ptr(d_out), L.ptr(grads),
-           grads.numel(), L.ptr(workspace), _numel(workspace), L.stream(dev))
-    return grads
+    return _backward_scenes("graphtern", model, workspace, d_out, scene_sizes, lambda p: (p.pred_seq_len, p.n_smpl))
 
 
 def graphtern_train_layout(model, n, n_scenes=1):
     """-> the ``ET_GRAPHTERN_TRAIN_LAYOUT_FIELDS`` offsets of a training workspace, in floats (``et_graphtern_train_layout``;
     include/eigentraj.h names the fields)"""
-    params, _ = model.et_params()
-    return _layout("et_graphtern_train_layout", L.GRAPHTERN_TRAIN_LAYOUT_FIELDS, params, n, n_scenes)
+    return list(vars(_graphtern_layout(model.et_params()[0], n, n_scenes)).values())
+
+
+def _graphtern_layout(params, n, n_scenes):
+    return _layout("et_graphtern_train_layout", L.GRAPHTERN_TRAIN_LAYOUT_NAMES, params, n, n_scenes)
 
 
 def graphtern_train_views(model, workspace, n, n_scenes=1, lo=0, scene=0, scene_n=None):
@@ -1619,22 +1548,21 @@ def graphtern_train_views(model, workspace, n, n_scenes=1, lo=0, scene=0, scene_
     T, k, S, H = params.seq_len, params.pred_seq_len, params.n_smpl, params.hidden_feat
     m = n if scene_n is None else scene_n
     f = workspace.view(torch.float32)
-    (o_u, o_d, o_p, o_yp, o_x0, o_tp, o_dtp, o_dx, o_dy, _, per, tp_stride, dtp_stride, o_part, G, _) = graphtern_train_layout(
-        model, n, n_scenes)
-    base = lo * per
+    lay = _graphtern_layout(params, n, n_scenes)
+    base = lo * lay.per
     fld = lambda off, *shape: f[base + off * m:base + off * m + math.prod(shape) * m].view(*shape, m)
     kH, kC = k * H, k * max(H, S)
-    views = {"u": fld(o_u, T), "d": fld(o_d, L.GRAPHTERN_REL, T), "P": fld(o_p, L.GRAPHTERN_REL, 2, T), "yp": fld(o_yp, H, T),
-             "x0": fld(o_x0, T, H), "d_x0": fld(o_dx, T, H), "d_yt": fld(o_dy, H, T)}
+    views = {"u": fld(lay.u, T), "d": fld(lay.d, L.GRAPHTERN_REL, T), "P": fld(lay.P, L.GRAPHTERN_REL, 2, T),
+             "yp": fld(lay.yp, H, T), "x0": fld(lay.x0, T, H), "d_x0": fld(lay.dx0, T, H), "d_yt": fld(lay.dy, H, T)}
     blocks = range(params.n_epcnn)
     cout = [S if j + 1 == params.n_epcnn else H for j in blocks]
-    views["c0"] = [fld(o_tp + j * tp_stride, k, H) for j in blocks]
-    views["y"] = [fld(o_tp + j * tp_stride + kH, k, H) for j in blocks]
-    views["c1"] = [fld(o_tp + j * tp_stride + 2 * kH, k, cout[j]) for j in blocks]
-    views["o"] = [fld(o_tp + j * tp_stride + 2 * kH + kC, k, cout[j]) for j in blocks]
-    views["d_o"] = [fld(o_dtp + j * dtp_stride, k, cout[j]) for j in blocks]
-    views["d_y"] = [fld(o_dtp + j * dtp_stride + kC, k, H) for j in blocks]
-    views["partial"] = f[o_part + scene * G:o_part + (scene + 1) * G]
+    views["c0"] = [fld(lay.tp + j * lay.tp_stride, k, H) for j in blocks]
+    views["y"] = [fld(lay.tp + j * lay.tp_stride + kH, k, H) for j in blocks]
+    views["c1"] = [fld(lay.tp + j * lay.tp_stride + 2 * kH, k, cout[j]) for j in blocks]
+    views["o"] = [fld(lay.tp + j * lay.tp_stride + 2 * kH + kC, k, cout[j]) for j in blocks]
+    views["d_o"] = [fld(lay.dtp + j * lay.dtp_stride, k, cout[j]) for j in blocks]
+    views["d_y"] = [fld(lay.dtp + j * lay.dtp_stride + kC, k, H) for j in blocks]
+    views["partial"] = f[lay.partials + scene * lay.grads:lay.partials + (scene + 1) * lay.grads]
     return views
 
 

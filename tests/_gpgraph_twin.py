@@ -2,7 +2,7 @@
 restatement of what csrc/et_gpgraph.hip computes (tests/_gpgraph_np.py is the numpy form), with the attentions un-collapsed,
 the learned distance through ``norm`` (whose backward is 0 at 0), the straight-through soft assignment written with
 ``detach`` and the pooling with ``index_add``.  Used by tests/test_gpgraph_train_cpu.py as the autograd reference of
-tests/_gpgraph_train_np.py and by tools/time_gpgraph_sgcn_train.py as the stock-torch network.  Not a test module itself."""
+tests/_gpgraph_train_np.py and by tools/time_train.py --predictor gpgraph_sgcn as the stock-torch network.  Not a test module itself."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -114,7 +114,7 @@ def gradients(sd, v_abs, v_rel, d_out, dtype=torch.float64, device="cpu", **kw):
 
 class Twin(torch.nn.Module):
     """``forward(v_abs, v_rel)`` of an :class:`eigentrajectory_amd.gpgraph.GPGraph` in the stock operators above, on that
-    module's own parameters (``net``), under torch autograd: what tools/time_gpgraph_sgcn_train.py times the native path
+    module's own parameters (``net``), under torch autograd: what tools/time_train.py --predictor gpgraph_sgcn times the native path
     against"""
 
     def __init__(self, net):

@@ -134,3 +134,22 @@ def pack_bits(keep):
 
 def unpack_bits(bits, shape):
     return np.unpackbits(np.asarray(bits, np.uint8))[:int(np.prod(shape))].reshape(shape)
+
+
+def host_params(S=20, k=6, n_cnn=6, **kw):
+    """et_graphtern_params whose every pointer is a (never dereferenced) non-NULL host address"""
+    from eigentrajectory_amd import _lib
+    p = _lib.GraphTERNParams()
+    p.n_epgcn, p.n_epcnn, p.input_feat, p.hidden_feat, p.seq_len, p.pred_seq_len, p.n_smpl = 1, n_cnn, 1, 16, k + 2, k, S
+    ly = p.tp_mrgcns[0]
+    ly.gcn_w = ly.gcn_b = ly.tcn_prelu = ly.tcn_w = ly.tcn_b = ly.res_w = ly.res_b = ly.prelu = 8
+    for j in range(min(n_cnn, _lib.GRAPHTERN_MAX_EPCNN)):
+        t = p.tpcnns[j]
+        t.tpcn_w = t.tpcn_b = t.tpcn_a = t.cpcn_w = t.cpcn_b = t.cpcn_a = 8
+        if j == 0:
+            t.rest_w = t.rest_b = 8
+        if j + 1 == n_cnn and S != 16:
+            t.resc_w = t.resc_b = 8
+    for key, val in kw.items():
+        setattr(p, key, val)
+    return p

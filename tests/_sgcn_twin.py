@@ -1,7 +1,7 @@
 """SGCN's forward (in_dims = 1, dropout = 0) in stock torch operators, differentiable by autograd: our own restatement of
 what csrc/et_sgcn.hip computes (tests/_sgcn_np.py is the numpy form), with the attention un-collapsed (embedding, query, key
 as three linear layers).  Used by tests/test_sgcn_train_cpu.py as the autograd reference of tests/_sgcn_train_np.py and by
-tools/time_sgcn_train.py as the stock-torch network.  Not a test module itself."""
+tools/time_train.py --predictor sgcn as the stock-torch network.  Not a test module itself."""
 import torch
 import torch.nn.functional as F
 
@@ -91,7 +91,7 @@ def gradients(sd, v, identity_s, identity_t, d_out, dtype=torch.float64, decisio
 
 class Twin(torch.nn.Module):
     """``forward(graph, identity)`` of an :class:`eigentrajectory_amd.sgcn.SGCN` in the stock operators above, on that
-    module's own parameters (``net``), under torch autograd: what tools/time_sgcn_train.py times the native path against"""
+    module's own parameters (``net``), under torch autograd: what tools/time_train.py --predictor sgcn times the native path against"""
 
     def __init__(self, net):
         super().__init__()

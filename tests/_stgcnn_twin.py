@@ -1,7 +1,7 @@
 """Social-STGCNN's forward (n_stgcnn = 1, input_feat = 1) in stock torch functions over a module's own tensors,
 ``F.batch_norm(training=True)`` included, differentiable by autograd: our own restatement of what
 csrc/et_stgcnn_train.hip computes (tests/_stgcnn_train_np.py is the numpy form).  Used by tests/test_stgcnn_train_cpu.py as
-the autograd reference, by tests/test_gpu_stgcnn_train.py as the fp32 network and by tools/time_stgcnn_train.py as the
+the autograd reference, by tests/test_gpu_stgcnn_train.py as the fp32 network and by tools/time_train.py --predictor stgcnn as the
 stock-torch network.  Not a test module itself."""
 import copy
 

@@ -199,30 +199,7 @@ def test_enable_native_training_contract():
         ET.enable_native_training(torch.nn.Linear(2, 2))
 
 
-def _params(S=20, k=6, n_tp=4, **kw):
-    """et_dmrgcn_params whose every pointer is a (never dereferenced) non-NULL host address"""
-    from eigentrajectory_amd import _lib
-    p = _lib.DMRGCNParams()
-    p.n_stgcn, p.n_tpcnn, p.input_feat, p.output_feat, p.seq_len, p.pred_seq_len, p.kernel_size = 1, n_tp, 1, S, k + 2, k, 3
-    for r in range(2):
-        for b, val in enumerate(DN.SPLIT[r]):
-            p.split[r][b] = val
-    ly = p.st_dmrgcns[0]
-    for r in range(2):
-        ly.gcn_w[r] = ly.gcn_b[r] = 8
-    ly.tcn_prelu = ly.tcn_w = ly.tcn_b = ly.prelu = 8
-    if S != 1:
-        ly.res_w = ly.res_b = 8
-    for j in range(min(n_tp, _lib.DMRGCN_MAX_TPCNN)):
-        t = p.tpcnns[j]
-        for m in range(2):
-            t.conv_w[m] = t.conv_b[m] = t.conv_a[m] = 8
-        t.gta_w = t.gta_b = t.gta_a = 8
-        if j == 0:
-            t.res_w = t.res_b = 8
-    for key, val in kw.items():
-        setattr(p, key, val)
-    return p
+_params = CS.host_params
 
 
 def test_arguments_are_validated_on_the_host():
